@@ -11,7 +11,10 @@ Workload at N=1: BASELINE.json configs[1] = random sparse QP n=10000 m=20000, NN
 uniform random pattern: SURVEY.md §8d).  N>1: one independent problem per GPU (different seed),
 no data-path collective; RCCL only for the start/stop barrier + max-over-ranks time.
 
-One JSON line on rank 0 (see DESIGN.md §6 for the roofline / cpu_baseline definitions).
+One JSON line on rank 0 (see DESIGN.md §6 for the roofline / cpu_baseline definitions).  A plain run sets up, warms up, times the
+steps and prints the headline figures; `--full` adds everything that takes runs of its own: the end-to-end solves, the roofline /
+per-kernel profiling passes, the CPU baseline + parity and the box probe.  `--dump-outputs DIR` writes what the last timed step
+computed to DIR/<name>.npy (float64).
 """
 import argparse
 import json
@@ -41,6 +44,25 @@ def make_problem(cfg, seed_shift=0):
     if cfg == "5":
         return problems.sdp_blocks(seed=5 + seed_shift), "SDP 20 x PSDTriangle(50), n=1000 (cfg 5)"
     raise SystemExit(f"unknown config {cfg}")
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, rank, arrays):
+    """DIR/<name>.npy in float64 for every array (rank r > 0: DIR/rank<r>/); an array above its share of DUMP_LIMIT_BYTES is
+    replaced by a fixed, seeded sample of its flattened entries (same positions in every run: DIR/<name>_sample_index.npy)"""
+    if rank > 0:
+        path = os.path.join(path, f"rank{rank}")
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // (2 * max(1, len(arrays)))
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // 8, replace=False))
+            np.save(os.path.join(path, f"{name}_sample_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, f"{name}.npy"), a)
 
 
 def kernel_sources_hash():
@@ -199,7 +221,14 @@ def bench_batch(args, cl, torch, dist, rank, world, local):
     total_bytes = batch.gather_counts(int(sum(r[4] for r in res)), dist, dev)
     cpu_baseline = None
     parity = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.dump_outputs:
+        # what the callers of the timed step received, per problem of this rank in seed order: iterations, status (1 = SOLVED),
+        # objective, primal and dual residual
+        done = sorted(res, key=lambda r: r[0])
+        dump_outputs(args.dump_outputs, rank, {
+            "seeds": [r[0] for r in done], "iterations": [r[1] for r in done], "solved": [r[2] == "SOLVED" for r in done],
+            "objective": [r[3] for r in done], "r_prim": [r[6] for r in done], "r_dual": [r[7] for r in done]})
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # all-cores CPU baseline: the same problems, one per core, oracle KKT solver, bounded sample
         import multiprocessing as mp
 
@@ -327,9 +356,18 @@ def main():
     ap.add_argument("--workers", type=int, default=6, help="cfg 4: host processes per GPU, each with its own HIP context")
     ap.add_argument("--device-scaling", action="store_true", help="also solve once end to end with N1 on (update_scaling!/get_Hs! on the device) and report it under end_to_end")
     ap.add_argument("--sequential-solves", action="store_true", help="three separate solve calls per unit instead of 2 concurrent + 1")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: end-to-end solves, roofline / per-kernel profiling passes, CPU baseline + "
+                         "parity, box probe (a plain run times the steps and prints the headline figures only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64, at most 64 MB in all)")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 0 if args.config == "4" else 20
+    if args.config != "4" and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.device_scaling and not args.full:
+        ap.error("--device-scaling adds to the end-to-end figures of --full")
 
     import torch
 
@@ -403,18 +441,19 @@ def main():
     # N2 hook on (reduced-system algebra of kkt_solve! by the plugin: what julia/clarabel_l1_seam.patch wires), (c) with N2 + N4 on
     # (residuals_update! by the plugin too: NOT wired on the Julia side -- solver.jl / residuals.jl stay untouched, INTEGRATION.md
     # section 5).  The headline is (b); three runs each, the MEDIAN counts.
-    e2e_runs = {}
-    for tag, kw in (("l1_contract_only", {}), ("n2_hook", {"device_reduced": True}), ("n2_n4_hooks", {"device_reduced": True, "device_residuals": True})):
-        rates = []
-        for _rep in range(3):     # (wall time of a 0.1-0.2 s host loop: three runs, all reported, the median counts)
-            s_ = cl.Solver(P, q, A, b, cones, cl.Settings(device_id=local, **kw), kktsolver_factory=lambda *a: HipKKTSolver(*a, **optkw))
-            sol_ = s_.solve()
-            rates.append(round(sol_.iterations / s_.info.timers["IP iteration"], 4))
-            e2e_runs[tag] = {"status": sol_.status, "ipm_iterations": sol_.iterations, "iterations_per_s": float(np.median(rates)), "iterations_per_s_runs": list(rates),
-                             "objective_rel_diff_vs_recording_run": float(abs(sol_.obj_val - sol.obj_val) / max(1.0, abs(sol.obj_val)))}
-            del s_
-    e2e_iters = e2e_runs["n2_hook"]["ipm_iterations"]
-    e2e_rate = e2e_runs["n2_hook"]["iterations_per_s"]
+    if args.full:
+        e2e_runs = {}
+        for tag, kw in (("l1_contract_only", {}), ("n2_hook", {"device_reduced": True}), ("n2_n4_hooks", {"device_reduced": True, "device_residuals": True})):
+            rates = []
+            for _rep in range(3):     # (wall time of a 0.1-0.2 s host loop: three runs, all reported, the median counts)
+                s_ = cl.Solver(P, q, A, b, cones, cl.Settings(device_id=local, **kw), kktsolver_factory=lambda *a: HipKKTSolver(*a, **optkw))
+                sol_ = s_.solve()
+                rates.append(round(sol_.iterations / s_.info.timers["IP iteration"], 4))
+                e2e_runs[tag] = {"status": sol_.status, "ipm_iterations": sol_.iterations, "iterations_per_s": float(np.median(rates)), "iterations_per_s_runs": list(rates),
+                                 "objective_rel_diff_vs_recording_run": float(abs(sol_.obj_val - sol.obj_val) / max(1.0, abs(sol.obj_val)))}
+                del s_
+        e2e_iters = e2e_runs["n2_hook"]["ipm_iterations"]
+        e2e_rate = e2e_runs["n2_hook"]["iterations_per_s"]
     tm = h.timing()
     # keep iterations that carry the regular 3 solves (the initial factorisation has 2 or 3)
     units = [t for t in trace if len(t["rhs"]) == 3]
@@ -435,25 +474,29 @@ def main():
         t["rhs_d"] = [t["rhs_all_d"][k] for k in range(3)]
     out_d = torch.zeros(h.n + h.m, dtype=torch.float64, device=dev)
     out2_d = torch.zeros(2, h.n + h.m, dtype=torch.float64, device=dev)
+    out3_d = torch.zeros(3, h.n + h.m, dtype=torch.float64, device=dev) if args.sequential_solves else None
     torch.cuda.synchronize()
     ir = dict(ir_enable=st.iterative_refinement_enable, reltol=st.iterative_refinement_reltol,
               abstol=st.iterative_refinement_abstol, max_iter=st.iterative_refinement_max_iter,
               stop_ratio=st.iterative_refinement_stop_ratio)
     has_soc = ks._soc_total > 0
     ir_steps_total = [0]
+    last = {}                             # what the caller received in the latest step besides the solutions (--dump-outputs)
 
     def step(i):
         t = units[i % len(units)]
         h.set_hs_dev(t["hs_d"].data_ptr(), h.nHs)
         if has_soc:
             h.set_soc_batch(t["eta2"], t["u"], t["v"])
-        ok, _, _ = h.refactor(st.static_regularization_enable, st.static_regularization_constant,
-                              st.static_regularization_proportional)
+        ok, eps, nreg = h.refactor(st.static_regularization_enable, st.static_regularization_constant,
+                                   st.static_regularization_proportional)
         if args.sequential_solves:
-            for r in t["rhs_d"]:
+            ir_steps = []
+            for k, r in enumerate(t["rhs_d"]):
                 h.setrhs_dev(r.data_ptr())
-                ok2, steps = h.solve_dev(out_d.data_ptr(), **ir)
+                ok2, steps = h.solve_dev(out3_d[k].data_ptr(), **ir)
                 ir_steps_total[0] += steps
+                ir_steps.append(steps)
                 ok = ok and ok2
         else:
             # what the batching caller does (julia_standin/ipm.py KKTSystem): [-q; b] and the affine
@@ -462,7 +505,9 @@ def main():
             h.setrhs_dev(t["rhs_d"][2].data_ptr())
             ok3, steps3 = h.solve_dev(out_d.data_ptr(), **ir)
             ir_steps_total[0] += int(steps2.sum()) + steps3
+            ir_steps = [*steps2, steps3]
             ok = ok and ok2 and ok3
+        last.update(eps=eps, nreg=nreg, ir_steps=ir_steps)
         if not ok:
             raise SystemExit("numerical failure inside the timed region")
 
@@ -476,165 +521,174 @@ def main():
     factor_ms = tm["acc_factor_ms"] / max(1, tm["n_factor"])
     solve_ms = tm["acc_solve_ms"] / max(1, tm["n_solve_calls"])
     ldl_per_unit = tm["n_ldl_solves"] / max(1, args.steps)
+    if args.dump_outputs:
+        # what the caller of the timed path received in the last timed step: the three refined solutions [constant rhs, affine,
+        # combined] of the KKT system, their refinement step counts, the static regularisation's eps and count of regularised pivots
+        sols = out3_d if args.sequential_solves else torch.cat([out2_d, out_d[None]])
+        dump_outputs(args.dump_outputs, rank, {
+            "solutions": sols.cpu().numpy(),
+            "refinement_steps": np.asarray(last["ir_steps"], dtype=np.float64),
+            "regularisation": np.asarray([last["eps"], last["nreg"]], dtype=np.float64)})
 
-    # ---- 3. roofline of the dominant kernel (k_update_stage, FP64 MFMA): live HIP-event timing of
-    #         every update launch on the handle's stream, in a profiling pass over the same inputs
-    cm = h.cost_model()
-    h.set_profiling(True)
-    upd_ms, d4 = [], []
-    for i in range(3):
-        t = units[i % len(units)]
-        h.set_hs_dev(t["hs_d"].data_ptr(), h.nHs)
-        h.refactor(st.static_regularization_enable, st.static_regularization_constant,
-                   st.static_regularization_proportional)
-        upd_ms.append(h.timing()["last_update_ms"])
-        d4.append(h.profile())
-        launches = h.profile_launches()
-    # the same launches with every far tile kept in its stage's own launch (none riding in the next k_front_block launch): what the
-    # dominant kernel's launches looked like before round 3's extra workgroups, for comparison
-    h.set_profiling(2)
-    d4n = []
-    for i in range(3):
-        t = units[i % len(units)]
-        h.set_hs_dev(t["hs_d"].data_ptr(), h.nHs)
-        h.refactor(st.static_regularization_enable, st.static_regularization_constant, st.static_regularization_proportional)
-        d4n.append(h.profile())
-    p4n = sorted(d4n, key=lambda p: p["dense4_ms"])[len(d4n) // 2]
-    h.set_profiling(False)
-    upd = float(np.median(upd_ms))
-    p4 = sorted(d4, key=lambda p: p["dense4_ms"])[len(d4) // 2]
-    # the just-in-time updates inside a front's update batches run inside k_front_block, not in the timed update kernels
-    # ... and so does the partial last round of a front batch's far updates (extra workgroups of the NEXT k_front_block launch)
-    flops_upd_kernels = cm["flops_update"] - p4.get("front_block_update_flops", 0.0) - p4.get("front_block_extra_flops", 0.0)
-    agg = flops_upd_kernels / (upd * 1e-3) / 1e12 if upd > 0 else 0.0
-    if p4["dense4_launches"] > 0 and p4["dense4_ms"] > 0:
-        # dominant kernel alone: k_update_dense<4,4> (one wavefront per 64x64 tile), HIP events around each launch
-        achieved = p4["dense4_flops"] / (p4["dense4_ms"] * 1e-3) / 1e12
-        kern = "k_update_dense<4,4>"
-        per_launch = dict(launches_per_refactor=p4["dense4_launches"],
-                          avg_launch_us=round(1e3 * p4["dense4_ms"] / p4["dense4_launches"], 2),
-                          flops_per_launch=p4["dense4_flops"] / p4["dense4_launches"])
-    else:   # small problems never reach the large-launch variant: report the aggregate of all update kernels
-        achieved, kern, per_launch = agg, "all Schur-update kernels", {}
-    lms, lfl, ltl = launches
-    if len(lms):
-        # the launches one by one: flops per target tile tells the K = 320 passes over the front (2 * 64 * 64 * 320 = 2.6e6 per
-        # tile) from the pass that carries the sparse part of the tree into it (many narrow sources per tile, a fraction of that)
-        per_launch["launches"] = [dict(tiles=int(t), us=round(1e3 * m, 1), tflops=round(f / (m * 1e-3) / 1e12, 2), mflop_per_tile=round(f / t / 1e6, 3))
-                                  for m, f, t in zip(lms, lfl, ltl)]
-        dense = [(m, f) for m, f, t in zip(lms, lfl, ltl) if f / t >= 2.0e6]
-        if dense:
-            per_launch["full_K_launches"] = dict(count=len(dense), achieved=round(sum(f for _, f in dense) / (sum(m for m, _ in dense) * 1e-3) / 1e12, 3),
-                                                 frac=round(sum(f for _, f in dense) / (sum(m for m, _ in dense) * 1e-3) / 1e12 / F64_MFMA_PEAK_TFLOPS, 4))
-    if p4.get("front_block_launches", 0) > 0:
-        # the other big time block of a refactorisation: the front-batch kernels are bound by the pivot chain (64 sequential pivots
-        # per 64-column panel), not by a throughput roofline -- reported as time per panel on that chain
-        per_launch["critical_path_kernel"] = dict(
-            kernel="k_front_block", bound="dependency latency (pivot chain)", launches_per_refactor=p4["front_block_launches"],
-            panels=p4["front_block_panels"], ms_per_refactor=round(p4["front_block_ms"], 4),
-            us_per_panel=round(1e3 * p4["front_block_ms"] / max(1, p4["front_block_panels"]), 2),
-            floor_note="one diagonal workgroup's 64 pivots + the next one finishing the last streamed record behind them; the per-phase "
-                       "stamps of the committed code are under profiles/ (<round>_*_cfg2a_front_block_stamps.txt, tools/fb2_trace.py) and in "
-                       "DESIGN.md section 7 -- this line carries no numbers of its own",
-            extra_update_tiles=p4.get("front_block_extra_tiles", 0), extra_update_flops=p4.get("front_block_extra_flops", 0.0),
-            extra_note="dense update tiles of the partial last rounds of the far stages, executed by extra workgroups of these launches on compute "
-                       "units the panel chain leaves idle; their flops are NOT in roofline.achieved / all_update_kernels (those time the update "
-                       "kernels' own launches)")
-    # algorithmic HBM bytes of one big dense-update launch, from the plan (every target tile read and written
-    # once, every source panel row once): T tiles of 64 x 64 doubles; a launch over T = R (R + 1) / 2 tiles of a front touches R
-    # row blocks of its K source columns (K = flops per tile / (2 * 64 * 64))
-    alg_bytes = None
-    if len(lms):
-        per = []
-        for m_, f_, t_ in zip(lms, lfl, ltl):
-            K_ = f_ / t_ / (2.0 * 64 * 64)
-            R_ = (np.sqrt(8.0 * t_ + 1.0) - 1.0) / 2.0
-            per.append(2.0 * t_ * 64 * 64 * 8 + R_ * 64 * K_ * 8)
-        alg_bytes = float(np.mean(per))
-    ctr, why = pmc_counters(args.config)
-    traffic = None
-    if ctr is not None:
-        traffic = dict(bytes_per_launch=ctr["bytes_per_launch"], read_x2_MB=ctr["read_x2_MB"], write_MB=ctr["write_MB"],
-                       launches_in_trace=ctr["launches_in_trace"], source=ctr["source"], kernel_sources_sha1=ctr["kernel_sources_sha1"],
-                       algorithmic_bytes_per_launch=None if alg_bytes is None else round(alg_bytes),
-                       ratio_to_algorithmic=None if not alg_bytes else round(ctr["bytes_per_launch"] / alg_bytes, 2),
-                       note="fabric-side bytes (L2 misses; Infinity-Cache hits are counted): FETCH_SIZE x2 (calibrated on this access shape, "
-                            "profiles/r03_a_traffic_calibration.txt) + WRITE_SIZE per launch")
-    # the refactorisation as a whole, from the same counter passes: what a latency-regime workload (cfg 1 / 2b: the big dense-update
-    # launches never run, `launches_in_trace` 0) quotes as `traffic` -- against B_factor of SURVEY section 8(d)
-    whole_traffic = None
-    if ctr is not None and ctr.get("whole_refactor"):
-        wr_ = ctr["whole_refactor"]
-        whole_traffic = dict(bytes_per_refactor=wr_["bytes_per_refactor"], read_x2_MB=wr_["read_x2_MB"], write_MB=wr_["write_MB"],
-                             dispatches_per_refactor=wr_.get("dispatches_per_refactor"), algorithmic_bytes_per_refactor=round(cm["bytes_factor"]),
-                             ratio_to_algorithmic=round(wr_["bytes_per_refactor"] / cm["bytes_factor"], 2) if cm["bytes_factor"] else None,
-                             source=ctr["source"], note=wr_.get("note"))
-    big_launches = ctr is not None and ctr.get("launches_in_trace", 0) > 0
-    if ctr is not None and not big_launches:
+    if args.full:
+        # ---- 3. roofline of the dominant kernel (k_update_stage, FP64 MFMA): live HIP-event timing of
+        #         every update launch on the handle's stream, in a profiling pass over the same inputs
+        cm = h.cost_model()
+        h.set_profiling(True)
+        upd_ms, d4 = [], []
+        for i in range(3):
+            t = units[i % len(units)]
+            h.set_hs_dev(t["hs_d"].data_ptr(), h.nHs)
+            h.refactor(st.static_regularization_enable, st.static_regularization_constant,
+                       st.static_regularization_proportional)
+            upd_ms.append(h.timing()["last_update_ms"])
+            d4.append(h.profile())
+            launches = h.profile_launches()
+        # the same launches with every far tile kept in its stage's own launch (none riding in the next k_front_block launch): what the
+        # dominant kernel's launches looked like before round 3's extra workgroups, for comparison
+        h.set_profiling(2)
+        d4n = []
+        for i in range(3):
+            t = units[i % len(units)]
+            h.set_hs_dev(t["hs_d"].data_ptr(), h.nHs)
+            h.refactor(st.static_regularization_enable, st.static_regularization_constant, st.static_regularization_proportional)
+            d4n.append(h.profile())
+        p4n = sorted(d4n, key=lambda p: p["dense4_ms"])[len(d4n) // 2]
+        h.set_profiling(False)
+        upd = float(np.median(upd_ms))
+        p4 = sorted(d4, key=lambda p: p["dense4_ms"])[len(d4) // 2]
+        # the just-in-time updates inside a front's update batches run inside k_front_block, not in the timed update kernels
+        # ... and so does the partial last round of a front batch's far updates (extra workgroups of the NEXT k_front_block launch)
+        flops_upd_kernels = cm["flops_update"] - p4.get("front_block_update_flops", 0.0) - p4.get("front_block_extra_flops", 0.0)
+        agg = flops_upd_kernels / (upd * 1e-3) / 1e12 if upd > 0 else 0.0
+        if p4["dense4_launches"] > 0 and p4["dense4_ms"] > 0:
+            # dominant kernel alone: k_update_dense<4,4> (one wavefront per 64x64 tile), HIP events around each launch
+            achieved = p4["dense4_flops"] / (p4["dense4_ms"] * 1e-3) / 1e12
+            kern = "k_update_dense<4,4>"
+            per_launch = dict(launches_per_refactor=p4["dense4_launches"],
+                              avg_launch_us=round(1e3 * p4["dense4_ms"] / p4["dense4_launches"], 2),
+                              flops_per_launch=p4["dense4_flops"] / p4["dense4_launches"])
+        else:   # small problems never reach the large-launch variant: report the aggregate of all update kernels
+            achieved, kern, per_launch = agg, "all Schur-update kernels", {}
+        lms, lfl, ltl = launches
+        if len(lms):
+            # the launches one by one: flops per target tile tells the K = 320 passes over the front (2 * 64 * 64 * 320 = 2.6e6 per
+            # tile) from the pass that carries the sparse part of the tree into it (many narrow sources per tile, a fraction of that)
+            per_launch["launches"] = [dict(tiles=int(t), us=round(1e3 * m, 1), tflops=round(f / (m * 1e-3) / 1e12, 2), mflop_per_tile=round(f / t / 1e6, 3))
+                                      for m, f, t in zip(lms, lfl, ltl)]
+            dense = [(m, f) for m, f, t in zip(lms, lfl, ltl) if f / t >= 2.0e6]
+            if dense:
+                per_launch["full_K_launches"] = dict(count=len(dense), achieved=round(sum(f for _, f in dense) / (sum(m for m, _ in dense) * 1e-3) / 1e12, 3),
+                                                     frac=round(sum(f for _, f in dense) / (sum(m for m, _ in dense) * 1e-3) / 1e12 / F64_MFMA_PEAK_TFLOPS, 4))
+        if p4.get("front_block_launches", 0) > 0:
+            # the other big time block of a refactorisation: the front-batch kernels are bound by the pivot chain (64 sequential pivots
+            # per 64-column panel), not by a throughput roofline -- reported as time per panel on that chain
+            per_launch["critical_path_kernel"] = dict(
+                kernel="k_front_block", bound="dependency latency (pivot chain)", launches_per_refactor=p4["front_block_launches"],
+                panels=p4["front_block_panels"], ms_per_refactor=round(p4["front_block_ms"], 4),
+                us_per_panel=round(1e3 * p4["front_block_ms"] / max(1, p4["front_block_panels"]), 2),
+                floor_note="one diagonal workgroup's 64 pivots + the next one finishing the last streamed record behind them; the per-phase "
+                           "stamps of the committed code are under profiles/ (<round>_*_cfg2a_front_block_stamps.txt, tools/fb2_trace.py) and in "
+                           "DESIGN.md section 7 -- this line carries no numbers of its own",
+                extra_update_tiles=p4.get("front_block_extra_tiles", 0), extra_update_flops=p4.get("front_block_extra_flops", 0.0),
+                extra_note="dense update tiles of the partial last rounds of the far stages, executed by extra workgroups of these launches on compute "
+                           "units the panel chain leaves idle; their flops are NOT in roofline.achieved / all_update_kernels (those time the update "
+                           "kernels' own launches)")
+        # algorithmic HBM bytes of one big dense-update launch, from the plan (every target tile read and written
+        # once, every source panel row once): T tiles of 64 x 64 doubles; a launch over T = R (R + 1) / 2 tiles of a front touches R
+        # row blocks of its K source columns (K = flops per tile / (2 * 64 * 64))
+        alg_bytes = None
+        if len(lms):
+            per = []
+            for m_, f_, t_ in zip(lms, lfl, ltl):
+                K_ = f_ / t_ / (2.0 * 64 * 64)
+                R_ = (np.sqrt(8.0 * t_ + 1.0) - 1.0) / 2.0
+                per.append(2.0 * t_ * 64 * 64 * 8 + R_ * 64 * K_ * 8)
+            alg_bytes = float(np.mean(per))
+        ctr, why = pmc_counters(args.config)
         traffic = None
-    cm_f = cm["flops_factor"]
-    whole = cm_f / (factor_ms * 1e-3) / 1e12
-    # per-kernel table underneath the headline: the dense-update family (throughput-bound), the front-batch kernel (latency-bound; its
-    # matrix-core flops -- in-batch updates + the far tiles riding in its launches -- from the counter file), all update kernels
-    fbk = None
-    if p4.get("front_block_launches", 0) > 0:
-        cfb = (ctr or {}).get("front_block") or {}
-        hwf = cfb.get("hw_flops_per_refactor")
-        fbk = dict(kernel="k_front_block", bound="dependency latency (pivot chain of the front's diagonal tiles)",
-                   ms_per_refactor=round(p4["front_block_ms"], 4), launches_per_refactor=p4["front_block_launches"],
-                   share_of_factor_time=round(p4["front_block_ms"] / factor_ms, 3) if factor_ms > 0 else None,
-                   hw_flops_per_refactor=hwf, achieved=None if not hwf else round(hwf / (p4["front_block_ms"] * 1e-3) / 1e12, 3),
-                   frac=None if not hwf else round(hwf / (p4["front_block_ms"] * 1e-3) / 1e12 / F64_MFMA_PEAK_TFLOPS, 4),
-                   mfma_busy_pct=cfb.get("mfma_busy_pct"),
-                   flops_note="SQ_INSTS_VALU_MFMA_MOPS_F64 x 512 per refactorisation (counter file; null when it is stale): executed matrix-core flops of the "
-                              "panel batches and of the dense update tiles that ride in these launches as extra workgroups")
-    dense_k = dict(kernel=kern, bound="mfma", achieved=round(achieved, 3), frac=round(achieved / F64_MFMA_PEAK_TFLOPS, 4),
-                   mfma_busy_pct=None if ctr is None else ctr.get("mfma_busy_pct"), traffic=traffic, traffic_unavailable=why,
-                   share_of_factor_time=round(p4["dense4_ms"] / factor_ms, 3) if factor_ms > 0 and p4["dense4_ms"] > 0 else None,
-                   note=("algorithmic flops of the k_update_dense<4,4> / k_update_dense_tail launches / their HIP-event time.  The far tiles that would form a "
-                         "stage's partial last rounds ride in the next k_front_block launch instead (critical_path_kernel.extra_update_*): the launches "
-                         "that remain are whole rounds plus the sparse-tree launch; `all_tiles_in_own_launches` = the same refactorisation with that off"),
-                   all_tiles_in_own_launches=(None if not (p4n["dense4_launches"] > 0 and p4n["dense4_ms"] > 0) else dict(
-                       achieved=round(p4n["dense4_flops"] / (p4n["dense4_ms"] * 1e-3) / 1e12, 3),
-                       frac=round(p4n["dense4_flops"] / (p4n["dense4_ms"] * 1e-3) / 1e12 / F64_MFMA_PEAK_TFLOPS, 4),
-                       launches_per_refactor=p4n["dense4_launches"], ms_per_refactor=round(p4n["dense4_ms"], 4),
-                       front_block_ms_per_refactor=round(p4n["front_block_ms"], 4))),
-                   **per_launch)
-    # the solves: HBM-bound by their algorithmic bytes (B_solve = 2 (8 + 4) nnz(L) + 40 N per LDL solve, + B_spmv per
-    # refinement SpMV), in fact bound by the hand-off chain of the sweeps -- the fraction says how far
-    n_ldl = tm["n_ldl_solves"]
-    solve_bytes = n_ldl * (cm["bytes_solve"] + cm["bytes_spmv"])       # every LDL solve of a refined solve is followed by one residual SpMV
-    solve_s = tm["acc_solve_ms"] * 1e-3
-    hbm_solve = dict(bound="hbm", kernel="LDL solves + refinement SpMVs (k_front_fwd_sb / k_front_bwd_sb, k_fwd_seg / k_bwd_seg, k_spmv_residual, ...)",
-                     achieved=round(solve_bytes / solve_s / 1e9, 1) if solve_s > 0 else None, peak=8000.0, unit="GB/s",
-                     frac=round(solve_bytes / solve_s / 1e9 / 8000.0, 4) if solve_s > 0 else None,
-                     frac_of_measured_peak_6300=round(solve_bytes / solve_s / 1e9 / 6300.0, 4) if solve_s > 0 else None,
-                     ldl_solves=n_ldl, bytes_per_ldl_solve=cm["bytes_solve"], bytes_per_spmv=cm["bytes_spmv"], device_ms=round(tm["acc_solve_ms"], 3),
-                     note="algorithmic bytes of the timed steps' solves / their HIP-event time (two concurrent solves of a pair are charged their common "
-                          "span); the sweeps are latency-bound: ~22 hand-offs per front sweep, DESIGN.md section 5")
-    roofline = dict(bound="mfma", achieved=round(whole, 3), peak=F64_MFMA_PEAK_TFLOPS, unit="TFLOP/s",
-                    frac=round(whole / F64_MFMA_PEAK_TFLOPS, 4),
-                    kernel="numeric LDL^T factorisation, all kernels (k_front_block, k_update_dense<4,4>, k_update_dense<1,2>, k_update_gather, k_factor_panel, ...)",
-                    what="SURVEY section 8(d): F_factor / t_factor with F_factor = sum_j (c_j^2 + 3 c_j) from the symbolic factor in use and t_factor = the "
-                         "mean HIP-event time of hipkkt_refactor over the timed steps",
-                    flops=cm_f, ms=round(factor_ms, 4),
-                    traffic=(traffic["bytes_per_launch"] if traffic is not None else
-                             (whole_traffic["bytes_per_refactor"] if (whole_traffic is not None and not big_launches) else None)),
-                    traffic_of=("kernels.dense_update (per launch of the dominant throughput kernel)" if (traffic is not None or whole_traffic is None) else
-                                "whole_refactor (every kernel of one refactorisation: this workload never reaches the big dense-update launches)"),
-                    traffic_unavailable=why, whole_refactor=whole_traffic,
-                    kernels=dict(dense_update=dense_k, front_block=fbk,
-                                 all_update_kernels=dict(achieved=round(agg, 3), frac=round(agg / F64_MFMA_PEAK_TFLOPS, 4), ms_per_refactor=round(upd, 4),
-                                                         flops_per_refactor=flops_upd_kernels)),
-                    solves=hbm_solve,
-                    peak_source="MI355X datasheet FP64 matrix (the figure every frac here is priced against)",
-                    sustained_matrix_rate=dict(two_wavefronts_per_simd_tflops=67.0, one_wavefront_per_simd_tflops=50.2,
-                                               frac_of_peak=round(67.0 / F64_MFMA_PEAK_TFLOPS, 3),
-                                               source="profiles/r06_b_ubench_mfma_occupancy_and_dense_tile_fit.txt (tools/ubench_mfma_mix.hip, tools/ubench_macro.hip)",
-                                               note="v_mfma_f64_16x16x4_f64 back to back on all 1024 SIMDs, measured in round 6: 67 TFLOP/s with two wavefronts "
-                                                    "per SIMD (what the dense update kernel runs), 50 with one (what the update tiles riding in a front-batch launch "
-                                                    "run).  The dense update's tile core: 1.22 us per k-step against 1.0 us of pure matrix work (82 %), plus ~35 us "
-                                                    "per launch in which every wavefront reads / writes its 32 KB tile at the same time"))
+        if ctr is not None:
+            traffic = dict(bytes_per_launch=ctr["bytes_per_launch"], read_x2_MB=ctr["read_x2_MB"], write_MB=ctr["write_MB"],
+                           launches_in_trace=ctr["launches_in_trace"], source=ctr["source"], kernel_sources_sha1=ctr["kernel_sources_sha1"],
+                           algorithmic_bytes_per_launch=None if alg_bytes is None else round(alg_bytes),
+                           ratio_to_algorithmic=None if not alg_bytes else round(ctr["bytes_per_launch"] / alg_bytes, 2),
+                           note="fabric-side bytes (L2 misses; Infinity-Cache hits are counted): FETCH_SIZE x2 (calibrated on this access shape, "
+                                "profiles/r03_a_traffic_calibration.txt) + WRITE_SIZE per launch")
+        # the refactorisation as a whole, from the same counter passes: what a latency-regime workload (cfg 1 / 2b: the big dense-update
+        # launches never run, `launches_in_trace` 0) quotes as `traffic` -- against B_factor of SURVEY section 8(d)
+        whole_traffic = None
+        if ctr is not None and ctr.get("whole_refactor"):
+            wr_ = ctr["whole_refactor"]
+            whole_traffic = dict(bytes_per_refactor=wr_["bytes_per_refactor"], read_x2_MB=wr_["read_x2_MB"], write_MB=wr_["write_MB"],
+                                 dispatches_per_refactor=wr_.get("dispatches_per_refactor"), algorithmic_bytes_per_refactor=round(cm["bytes_factor"]),
+                                 ratio_to_algorithmic=round(wr_["bytes_per_refactor"] / cm["bytes_factor"], 2) if cm["bytes_factor"] else None,
+                                 source=ctr["source"], note=wr_.get("note"))
+        big_launches = ctr is not None and ctr.get("launches_in_trace", 0) > 0
+        if ctr is not None and not big_launches:
+            traffic = None
+        cm_f = cm["flops_factor"]
+        whole = cm_f / (factor_ms * 1e-3) / 1e12
+        # per-kernel table underneath the headline: the dense-update family (throughput-bound), the front-batch kernel (latency-bound; its
+        # matrix-core flops -- in-batch updates + the far tiles riding in its launches -- from the counter file), all update kernels
+        fbk = None
+        if p4.get("front_block_launches", 0) > 0:
+            cfb = (ctr or {}).get("front_block") or {}
+            hwf = cfb.get("hw_flops_per_refactor")
+            fbk = dict(kernel="k_front_block", bound="dependency latency (pivot chain of the front's diagonal tiles)",
+                       ms_per_refactor=round(p4["front_block_ms"], 4), launches_per_refactor=p4["front_block_launches"],
+                       share_of_factor_time=round(p4["front_block_ms"] / factor_ms, 3) if factor_ms > 0 else None,
+                       hw_flops_per_refactor=hwf, achieved=None if not hwf else round(hwf / (p4["front_block_ms"] * 1e-3) / 1e12, 3),
+                       frac=None if not hwf else round(hwf / (p4["front_block_ms"] * 1e-3) / 1e12 / F64_MFMA_PEAK_TFLOPS, 4),
+                       mfma_busy_pct=cfb.get("mfma_busy_pct"),
+                       flops_note="SQ_INSTS_VALU_MFMA_MOPS_F64 x 512 per refactorisation (counter file; null when it is stale): executed matrix-core flops of the "
+                                  "panel batches and of the dense update tiles that ride in these launches as extra workgroups")
+        dense_k = dict(kernel=kern, bound="mfma", achieved=round(achieved, 3), frac=round(achieved / F64_MFMA_PEAK_TFLOPS, 4),
+                       mfma_busy_pct=None if ctr is None else ctr.get("mfma_busy_pct"), traffic=traffic, traffic_unavailable=why,
+                       share_of_factor_time=round(p4["dense4_ms"] / factor_ms, 3) if factor_ms > 0 and p4["dense4_ms"] > 0 else None,
+                       note=("algorithmic flops of the k_update_dense<4,4> / k_update_dense_tail launches / their HIP-event time.  The far tiles that would form a "
+                             "stage's partial last rounds ride in the next k_front_block launch instead (critical_path_kernel.extra_update_*): the launches "
+                             "that remain are whole rounds plus the sparse-tree launch; `all_tiles_in_own_launches` = the same refactorisation with that off"),
+                       all_tiles_in_own_launches=(None if not (p4n["dense4_launches"] > 0 and p4n["dense4_ms"] > 0) else dict(
+                           achieved=round(p4n["dense4_flops"] / (p4n["dense4_ms"] * 1e-3) / 1e12, 3),
+                           frac=round(p4n["dense4_flops"] / (p4n["dense4_ms"] * 1e-3) / 1e12 / F64_MFMA_PEAK_TFLOPS, 4),
+                           launches_per_refactor=p4n["dense4_launches"], ms_per_refactor=round(p4n["dense4_ms"], 4),
+                           front_block_ms_per_refactor=round(p4n["front_block_ms"], 4))),
+                       **per_launch)
+        # the solves: HBM-bound by their algorithmic bytes (B_solve = 2 (8 + 4) nnz(L) + 40 N per LDL solve, + B_spmv per
+        # refinement SpMV), in fact bound by the hand-off chain of the sweeps -- the fraction says how far
+        n_ldl = tm["n_ldl_solves"]
+        solve_bytes = n_ldl * (cm["bytes_solve"] + cm["bytes_spmv"])       # every LDL solve of a refined solve is followed by one residual SpMV
+        solve_s = tm["acc_solve_ms"] * 1e-3
+        hbm_solve = dict(bound="hbm", kernel="LDL solves + refinement SpMVs (k_front_fwd_sb / k_front_bwd_sb, k_fwd_seg / k_bwd_seg, k_spmv_residual, ...)",
+                         achieved=round(solve_bytes / solve_s / 1e9, 1) if solve_s > 0 else None, peak=8000.0, unit="GB/s",
+                         frac=round(solve_bytes / solve_s / 1e9 / 8000.0, 4) if solve_s > 0 else None,
+                         frac_of_measured_peak_6300=round(solve_bytes / solve_s / 1e9 / 6300.0, 4) if solve_s > 0 else None,
+                         ldl_solves=n_ldl, bytes_per_ldl_solve=cm["bytes_solve"], bytes_per_spmv=cm["bytes_spmv"], device_ms=round(tm["acc_solve_ms"], 3),
+                         note="algorithmic bytes of the timed steps' solves / their HIP-event time (two concurrent solves of a pair are charged their common "
+                              "span); the sweeps are latency-bound: ~22 hand-offs per front sweep, DESIGN.md section 5")
+        roofline = dict(bound="mfma", achieved=round(whole, 3), peak=F64_MFMA_PEAK_TFLOPS, unit="TFLOP/s",
+                        frac=round(whole / F64_MFMA_PEAK_TFLOPS, 4),
+                        kernel="numeric LDL^T factorisation, all kernels (k_front_block, k_update_dense<4,4>, k_update_dense<1,2>, k_update_gather, k_factor_panel, ...)",
+                        what="SURVEY section 8(d): F_factor / t_factor with F_factor = sum_j (c_j^2 + 3 c_j) from the symbolic factor in use and t_factor = the "
+                             "mean HIP-event time of hipkkt_refactor over the timed steps",
+                        flops=cm_f, ms=round(factor_ms, 4),
+                        traffic=(traffic["bytes_per_launch"] if traffic is not None else
+                                 (whole_traffic["bytes_per_refactor"] if (whole_traffic is not None and not big_launches) else None)),
+                        traffic_of=("kernels.dense_update (per launch of the dominant throughput kernel)" if (traffic is not None or whole_traffic is None) else
+                                    "whole_refactor (every kernel of one refactorisation: this workload never reaches the big dense-update launches)"),
+                        traffic_unavailable=why, whole_refactor=whole_traffic,
+                        kernels=dict(dense_update=dense_k, front_block=fbk,
+                                     all_update_kernels=dict(achieved=round(agg, 3), frac=round(agg / F64_MFMA_PEAK_TFLOPS, 4), ms_per_refactor=round(upd, 4),
+                                                             flops_per_refactor=flops_upd_kernels)),
+                        solves=hbm_solve,
+                        peak_source="MI355X datasheet FP64 matrix (the figure every frac here is priced against)",
+                        sustained_matrix_rate=dict(two_wavefronts_per_simd_tflops=67.0, one_wavefront_per_simd_tflops=50.2,
+                                                   frac_of_peak=round(67.0 / F64_MFMA_PEAK_TFLOPS, 3),
+                                                   source="profiles/r06_b_ubench_mfma_occupancy_and_dense_tile_fit.txt (tools/ubench_mfma_mix.hip, tools/ubench_macro.hip)",
+                                                   note="v_mfma_f64_16x16x4_f64 back to back on all 1024 SIMDs, measured in round 6: 67 TFLOP/s with two wavefronts "
+                                                        "per SIMD (what the dense update kernel runs), 50 with one (what the update tiles riding in a front-batch launch "
+                                                        "run).  The dense update's tile core: 1.22 us per k-step against 1.0 us of pure matrix work (82 %), plus ~35 us "
+                                                        "per launch in which every wavefront reads / writes its 32 KB tile at the same time"))
 
     result = {
         "metric": "IPM iterations/sec + KKT factor+solve ms, 10k-var sparse QP, 1/2/4/8 GPU",
@@ -646,28 +700,31 @@ def main():
         "dtype": "f64", "data": "synthetic",
         "config": {"workload": workload, "N": h.N, "nnzK": h.nnzK, "nnzL": h.nnzL, "supernodes": h.nsuper,
                    "levels": h.nlevels, "ordering": ["minimum degree", "cone rows first, variables last", "user", "nested dissection"][h.ordering], "parallelism": f"{world} independent problem(s), one per GPU"},
-        "ipm_iterations_per_s_end_to_end": e2e_rate,
-        "value_is": "replayed KKT iteration units per second with every input resident in HBM (tier rule for `value`); "
-                    "`ipm_iterations_per_s_end_to_end` is SURVEY section 8(d)'s rate: iterations / wall time of the whole IPM loop "
-                    "incl. the host cone algebra and the PCIe transfers -- of the numpy stand-in of the Julia caller (no Julia has run), with the N2 hook "
-                    "of julia/clarabel_l1_seam.patch on; median of three runs (end_to_end.runs)",
         "kkt_factor_ms": round(factor_ms, 4), "kkt_solve_ms_per_call": round(solve_ms, 4),
         "kkt_solve_calls_per_step": round(tm["n_solve_calls"] / max(1, args.steps), 2),
         "kkt_factor_plus_solves_ms": round(factor_ms + solve_ms * tm["n_solve_calls"] / max(1, args.steps), 4),
         "ldl_solves_per_step": round(ldl_per_unit, 2),
-        "refined_block_solves": {"factorisations_with_some": int(h.counters()["accurate_factorisations"]), "blocks_last_factorisation": int(h.profile()["refined_blocks"]),
-                                 "threshold": 64.0, "note": "wide diagonal blocks (> 16 columns, regular supernodes) whose explicit inverse has an entry above the "
-                                 "threshold: their solves take one refinement step against the factored block (kernels.hip k_invert_diag_wide; hipkkt_get_profile out[10..11])"},
-        "end_to_end": {"ipm_iterations": e2e_iters, "status": e2e_runs["n2_hook"]["status"], "iterations_per_s": e2e_rate,
-                       "caller": "julia_standin/ipm.py (numpy stand-in of the untouched Julia IPM loop); no Julia has run",
-                       "note": "headline = median of three runs with the N2 hook (reduced-system algebra by the plugin: wired by julia/clarabel_l1_seam.patch); "
-                               "`runs` holds it next to the L1-contract-only run and the N2 + N4 run (N4 is NOT wired on the Julia side)",
-                       "runs": e2e_runs,
-                       "recording_run": {"ipm_iterations": rec_iters, "iterations_per_s": round(rec_iters / rec_time, 4), "status": sol.status,
-                                         "note": "the run the replayed trace was recorded from (copies every Hs / rhs on the host)"},
-                       "setup_s": round(t_setup, 3)},
-        "roofline": roofline,
     }
+    if args.full:
+        result.update({
+            "ipm_iterations_per_s_end_to_end": e2e_rate,
+            "value_is": "replayed KKT iteration units per second with every input resident in HBM (tier rule for `value`); "
+                        "`ipm_iterations_per_s_end_to_end` is SURVEY section 8(d)'s rate: iterations / wall time of the whole IPM loop "
+                        "incl. the host cone algebra and the PCIe transfers -- of the numpy stand-in of the Julia caller (no Julia has run), with the N2 hook "
+                        "of julia/clarabel_l1_seam.patch on; median of three runs (end_to_end.runs)",
+            "refined_block_solves": {"factorisations_with_some": int(h.counters()["accurate_factorisations"]), "blocks_last_factorisation": int(h.profile()["refined_blocks"]),
+                                     "threshold": 64.0, "note": "wide diagonal blocks (> 16 columns, regular supernodes) whose explicit inverse has an entry above the "
+                                     "threshold: their solves take one refinement step against the factored block (kernels.hip k_invert_diag_wide; hipkkt_get_profile out[10..11])"},
+            "end_to_end": {"ipm_iterations": e2e_iters, "status": e2e_runs["n2_hook"]["status"], "iterations_per_s": e2e_rate,
+                           "caller": "julia_standin/ipm.py (numpy stand-in of the untouched Julia IPM loop); no Julia has run",
+                           "note": "headline = median of three runs with the N2 hook (reduced-system algebra by the plugin: wired by julia/clarabel_l1_seam.patch); "
+                                   "`runs` holds it next to the L1-contract-only run and the N2 + N4 run (N4 is NOT wired on the Julia side)",
+                           "runs": e2e_runs,
+                           "recording_run": {"ipm_iterations": rec_iters, "iterations_per_s": round(rec_iters / rec_time, 4), "status": sol.status,
+                                             "note": "the run the replayed trace was recorded from (copies every Hs / rhs on the host)"},
+                           "setup_s": round(t_setup, 3)},
+            "roofline": roofline,
+        })
     if args.device_scaling and rank == 0:
         # SURVEY section 8(f) row N1 end to end: the same solve with update_scaling! / get_Hs! formed by the plugin from (s, z)
         # (hipkkt_update_scaling): no Hs vector, no SOC (u, v, eta) and no PSD block crosses PCIe
@@ -682,7 +739,7 @@ def main():
 
     # ---- 4. CPU baseline + parity: the oracle (C restatement of the reference's :qdldl path), 1 thread, same
     #         permutation, KKT iteration units of the same trace; its solutions are compared with the HIP path's
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         import ctypes as C
 
         from oracle.kkt_oracle import OracleKKTSolver
@@ -762,16 +819,17 @@ def main():
         result["parity"] = par
 
     if rank == 0:
-        # what the latency-bound kernels (front batches, panel kernels, sweeps) depend on and the matrix-core / memory-bound ones do
-        # not: a slow line names its cause (1.6x between two boxes of the pool on exactly those kernels)
-        try:
-            from clarabel_jl_amd import hipkkt as _hk
-            result["box_probe"] = _hk.box_probe(local)
-            result["box_probe"]["note"] = ("hipkkt_box_probe: shader clock one busy wavefront gets (shader cycles / 100 MHz constant clock), round trip of a "
-                                           "flag between two workgroups on the same / on different XCDs (relaxed agent-scope atomics); reference box of "
-                                           "profiles/r05_a_box_probe.txt: 2.39 GHz, 1000 / 1085 ns")
-        except Exception as e:      # the probe never fails the bench
-            result["box_probe"] = {"error": str(e)}
+        if args.full:
+            # what the latency-bound kernels (front batches, panel kernels, sweeps) depend on and the matrix-core / memory-bound ones do
+            # not: a slow line names its cause (1.6x between two boxes of the pool on exactly those kernels)
+            try:
+                from clarabel_jl_amd import hipkkt as _hk
+                result["box_probe"] = _hk.box_probe(local)
+                result["box_probe"]["note"] = ("hipkkt_box_probe: shader clock one busy wavefront gets (shader cycles / 100 MHz constant clock), round trip of a "
+                                               "flag between two workgroups on the same / on different XCDs (relaxed agent-scope atomics); reference box of "
+                                               "profiles/r05_a_box_probe.txt: 2.39 GHz, 1000 / 1085 ns")
+            except Exception as e:      # the probe never fails the bench
+                result["box_probe"] = {"error": str(e)}
         print(json.dumps(result))
     if dist is not None:
         dist.destroy_process_group()

@@ -3,11 +3,12 @@ image, so what can be checked without executing them is checked here: every `cca
 names a function declared in include/hipkkt.h, with the declared number of parameters, a matching return type and matching parameter
 type classes (Ptr{Float64} <-> double*, Int64 <-> int64_t, Ptr{Cvoid} <-> hipkkt_handle, ...); the `HipKKTOpts` struct mirrors
 `hipkkt_opts` field for field; INTEGRATION.md refers to the files instead of carrying copies of them; and the core patch of seam L1
-is a REAL patch: it applies to the reference checkout (`patch --dry-run`, when /root/reference is there), never mentions the extension
+is a REAL patch: it applies to the reference checkout exactly where its hunks say (held against tests/golden/reference_checkout_facts.json,
+written from a checkout by tests/golden/make_reference_facts.py), never mentions the extension
 module (the core must not import what imports it), and every kktsolver_* function it calls is defined by the patch itself (generic
 default) and extended by the extension."""
-import shutil
-import subprocess
+import hashlib
+import json
 import os
 import re
 
@@ -202,39 +203,60 @@ def test_core_patch_defines_what_it_calls_and_the_extension_extends_it():
     assert 'ClarabelHipKKTExt = "AMDGPU"' in added
 
 
-@pytest.mark.skipif(not (os.path.isdir("/root/reference/src") and shutil.which("patch")), reason="needs the reference checkout and patch(1)")
+def _reference_facts():
+    with open(os.path.join(ROOT, "tests", "golden", "reference_checkout_facts.json")) as fh:
+        return json.load(fh)
+
+
+def _patch_old_lines():
+    """{file: {old line number: line}}: every line the patch's hunks read from the reference (context and removed lines)"""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("make_reference_facts", os.path.join(ROOT, "tests", "golden", "make_reference_facts.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod.patch_old_lines(open(PATCH).read())
+
+
 def test_core_patch_applies_to_the_reference():
-    r = subprocess.run(["patch", "-p1", "--dry-run", "-d", "/root/reference", "-i", PATCH], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
+    """every line a hunk reads is the reference's line at the position the hunk gives (no offset, no fuzz): sha256 of the patch's
+    own context / removed lines against the reference's, recorded by tests/golden/make_reference_facts.py"""
+    facts = _reference_facts()["patch_context"]
+    old = _patch_old_lines()
     for f in ("src/kktsolvers/kktsolver_defaults.jl", "src/kktsystem.jl", "src/data_updating.jl", "src/kktsolvers/direct-ldl/directldl_auto.jl", "Project.toml"):
-        assert f in r.stdout, r.stdout
+        assert f in old, f
+    for f, lines in old.items():
+        assert f in facts, f"{f}: not a file of the recorded reference checkout"
+        assert lines, f
+        for ln, text in lines.items():
+            assert ln <= facts[f]["lines"], f"{f}:{ln}: past the end of the reference's file"
+            assert hashlib.sha256(text.encode("utf-8")).hexdigest() == facts[f]["sha256"].get(str(ln)), f"{f}:{ln}: {text!r} is not the reference's line"
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/src"), reason="needs the reference checkout")
 def test_reference_test_kit_uses_only_names_that_exist():
     """julia/run_reference_tests_hip.jl (the reference's own acceptance tests with the plugin's tokens, for the day a Julia box exists)
-    cannot be executed here; what can be checked: every Clarabel name it uses is defined by the reference or by the patch, every
-    extension name by julia/ext, every test file it reads exists and contains the text it substitutes."""
+    cannot be executed here; what can be checked: every Clarabel name it uses is defined by the reference (the names recorded from a
+    checkout by tests/golden/make_reference_facts.py) or by the patch, every extension name by julia/ext, every test file it reads
+    exists in the reference and contains the text it substitutes."""
+    facts = _reference_facts()
     kit = open(os.path.join(ROOT, "julia", "run_reference_tests_hip.jl")).read()
-    ref_src = ""
-    for dp, _, files in os.walk("/root/reference/src"):
-        for f in files:
-            if f.endswith(".jl"):
-                ref_src += open(os.path.join(dp, f)).read() + "\n"
-    patched = ref_src + "\n".join(_patch_added_lines())
+    added = "\n".join(_patch_added_lines())
     for name in sorted(set(re.findall(r"\bClarabel\.([A-Za-z_]\w*!?)", kit))):
-        assert re.search(r"\b" + re.escape(name) + r"\b", patched), f"Clarabel.{name} is not defined by the (patched) reference"
+        assert name in facts["kit_names"] or re.search(r"\b" + re.escape(name) + r"\b", added), \
+            f"Clarabel.{name} is not defined by the (patched) reference"
     ext = "".join(open(os.path.join(JL_DIR, f)).read() for f in os.listdir(JL_DIR) if f.endswith(".jl"))
     for name in sorted(set(re.findall(r"\bClarabelHipKKTExt\.([A-Za-z_]\w*!?)", kit)) - {"jl"}):     # ("ClarabelHipKKTExt.jl" is the file)
         assert re.search(r"(function\s+|struct\s+|^)" + re.escape(name) + r"\b", ext, flags=re.M), f"ClarabelHipKKTExt.{name}"
-    tests_dir = "/root/reference/test/OptTests"
-    for f in re.findall(r'"((?:basic_\w+|linear_solvers)\.jl)"', kit):
-        txt = open(os.path.join(tests_dir, f)).read()
+    files = re.findall(r'"((?:basic_\w+|linear_solvers)\.jl)"', kit)
+    assert files
+    for f in files:
+        assert f in facts["kit_files"], f"test/OptTests/{f} is not a file of the recorded reference checkout"
+        feat = facts["kit_files"][f]
         if f == "linear_solvers.jl":
-            assert re.search(r"SolverTypes\s*=\s*\[[^\]]*\]", txt)        # the list the kit replaces (linear_solvers.jl:11)
-            assert "direct_solve_method = SolverType" in txt
+            assert feat["solver_types_list"]                   # the list the kit replaces (linear_solvers.jl:11)
+            assert feat["direct_solve_method_from_list"]
         else:
-            assert "Clarabel.Solver(" in txt and "UnitTestFloats" in txt   # the constructor calls the kit redirects; the float list it pins
+            assert feat["constructs_solver"] and feat["unit_test_floats"]   # the constructor calls the kit redirects; the float list it pins
     assert "get_auto_ldl_solver() === :hip" in kit
 
 

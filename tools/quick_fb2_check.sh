@@ -6,7 +6,7 @@ mkdir -p gpurun_out; cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 (timeout 400 python -m pytest tests/test_gpu_fullsize.py -x -q -m gpu -k "second_form" > gpurun_out/${tag}_pytest_v2.txt 2>&1; echo "pytest rc=$?" >> gpurun_out/${tag}_pytest_v2.txt); tail -2 gpurun_out/${tag}_pytest_v2.txt
 timeout 300 python tools/fb2_trace.py > gpurun_out/${tag}_fb2trace.txt 2>&1; grep -A20 "batch 8" gpurun_out/${tag}_fb2trace.txt | grep -E "chain|first record|total" | cut -c1-220; tail -1 gpurun_out/${tag}_fb2trace.txt
 for e in "HIPKKT_VERBOSE=0" "HIPKKT_FB_EXTRA_PW=1,10,28"; do
-env $e timeout 400 python bench.py --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
+env $e timeout 400 python bench.py --full --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); fb = d['roofline']['kernels']['front_block']
 print('$e', d['value'], 'factor', d['kkt_factor_ms'], 'fb us/launch', round(1e3 * fb['ms_per_refactor'] / 17, 1), 'frac', d['roofline']['frac'])"
