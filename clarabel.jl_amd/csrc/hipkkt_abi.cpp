@@ -652,7 +652,7 @@ int32_t hipkkt_get_counters(hipkkt_handle h, int64_t *out, int64_t cap) {
 // developer diagnostic (not part of the plugin contract): internal vectors of the last LDL solve / plan tables as doubles.
 // what: 0 = the permuted right-hand side, 1 = z (forward result / D), 2 = x (permuted), 3 = ubuf, 4 = the unregularised KKT values,
 // 5 = D and 6 = 1/D of the last factorisation (permuted order), 7 / 8 = u / v of the sparse second-order cones (concatenated), 10 = sn_first, 11 = sn_level,
-// 12 = rows per supernode, 13 = sn_parent, 14 = persistent-sweep membership (1 = item of a segment launch)
+// 12 = rows per supernode, 13 = sn_parent, 14 = persistent-sweep membership (1 = item of a segment launch), 22 = the fronts (4 values each)
 int32_t hipkkt_debug_dump(hipkkt_handle h, int32_t what, double *out, int64_t cap, int64_t *len) {
     HK_ENTER(h)
     const HostPlan &P = S->plan;
@@ -719,6 +719,16 @@ int32_t hipkkt_debug_dump(hipkkt_handle h, int32_t what, double *out, int64_t ca
                 const double rec[5] = {(double)P.sn_level[s], (double)(P.sn_first[s + 1] - P.sn_first[s]), (double)(b - a), (double)mx,
                                        (double)(P.g_ptr[b] - P.g_ptr[a]) / (double)std::max<int64_t>(b - a, 1)};
                 v.insert(v.end(), rec, rec + 5);
+            }
+            host((int64_t)v.size(), [&](int64_t i) { return v[i]; });
+            break;
+        }
+        case 22: {   // per front of the plan, 4 values: first panel (supernode id), panels, rows, panels per super-block of its sweeps (0 = one
+                     // hop per panel, k_front_fwd / k_front_bwd; > 0 = k_front_fwd_sb / k_front_bwd_sb)
+            std::vector<double> v;
+            for (const FrontDesc &F : P.fronts) {
+                const double rec[4] = {(double)F.s0, (double)F.np, (double)F.rF, (double)F.sb_g};
+                v.insert(v.end(), rec, rec + 4);
             }
             host((int64_t)v.size(), [&](int64_t i) { return v[i]; });
             break;

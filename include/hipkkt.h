@@ -319,7 +319,10 @@ int32_t hipkkt_get_counters(hipkkt_handle h, int64_t *out, int64_t cap);
  * the last SpMV on solve context 0 (original ordering), 19 the number of dense triangles of K outside the symmetric view, 20 six values per
  * dense update tile of the plan: stage, tasks, sum of source widths, tasks through a tile map, full-tile flag, sum of rows x columns x
  * width; 21 five values per supernode of the persistent segment sweeps: level, width, rows, longest and mean gather list of its row
- * slots -- tools/dense_stage_stats.py); *len receives the length, nothing is copied when cap is too small */
+ * slots -- tools/dense_stage_stats.py; 22 four values per front, written on the host: its first panel (supernode id), panels, rows,
+ * and the panels per super-block of its solve sweeps, 0 = one hop per panel through that panel's inverse (k_front_fwd / k_front_bwd),
+ * > 0 = products with the super-blocks' inverses (k_front_fwd_sb / k_front_bwd_sb)); *len receives the length, nothing is copied
+ * when cap is too small */
 int32_t hipkkt_debug_dump(hipkkt_handle h, int32_t what, double *out, int64_t cap, int64_t *len);
 /* developer diagnostic, host logic only (no device needed): how many of the `nd` dense tiles of a front batch's far stage -- the
  * first `ncrit` of them belong to the next batch's columns -- ride in the next k_front_block launch, which has `next_blk` workgroups

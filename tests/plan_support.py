@@ -37,7 +37,7 @@ def symmetric_product(N, colptr, rowval, nzval, x, first_col=-1, min_dim=128):
 
 STAT_NAMES = ["nsuper", "nlevels", "nnzL", "panel_doubles", "ntasks", "ngroups", "etree_height",
               "flops_colcount", "flops_update", "flops_exec", "nreg", "max_group_tasks",
-              "nfronts", "ngather_entries", "ndense_groups", "nmapped_tasks"]
+              "nfronts", "ngather_entries", "ndense_groups", "nmapped_tasks", "nsb_fronts", "max_front_panels"]
 
 
 def run(N, colptr, rowval, nzval, dsigns, b=None, perm=None, max_width=64, relax=1, policy=0,
@@ -45,7 +45,7 @@ def run(N, colptr, rowval, nzval, dsigns, b=None, perm=None, max_width=64, relax
     L = lib()
     x = np.zeros(N)
     perm_out = np.zeros(N, dtype=np.int64)
-    stats = np.zeros(16)
+    stats = np.zeros(len(STAT_NAMES))
     if b is None:
         b = np.zeros(N)
     pp = None

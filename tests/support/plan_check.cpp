@@ -203,8 +203,9 @@ int plan_check_symmetric_product(int64_t N, const int64_t *Ap, const int64_t *Ai
     return 0;
 }
 
-// stats: [0] nsuper [1] nlevels [2] nnzL [3] panel_doubles [4] ntasks [5] ngroups [6] etree_height
-//        [7] flops_colcount [8] flops_update [9] flops_exec [10] nreg [11] max group tasks
+// stats (18 doubles): [0] nsuper [1] nlevels [2] nnzL [3] panel_doubles [4] ntasks [5] ngroups [6] etree_height
+//        [7] flops_colcount [8] flops_update [9] flops_exec [10] nreg [11] max group tasks [12] fronts [13] gather entries
+//        [14] dense update groups [15] tasks through a tile map [16] fronts swept super-block by super-block [17] most panels of a front
 int plan_check_run(int64_t N, const int64_t *Ap, const int64_t *Ai, const double *Ax, const int64_t *dsigns,
                    const int64_t *user_perm, int max_width, int relax, int policy, double reg_eps,
                    double reg_delta, const double *b, double *x, int64_t *perm_out, double *stats,
@@ -226,10 +227,11 @@ int plan_check_run(int64_t N, const int64_t *Ap, const int64_t *Ai, const double
         size_t nmapped = 0, ndense = 0;
         for (auto &t : P.upd_tasks) nmapped += (t.geom >> 17) & 1;
         for (auto &g : P.upd_groups) ndense += g.dense == 1;
-        int nsbf = 0;
-        for (auto &F : P.fronts) nsbf += F.sb_g > 0;
+        int nsbf = 0, maxnp = 0;
+        for (auto &F : P.fronts) { nsbf += F.sb_g > 0; maxnp = std::max(maxnp, F.np); }
         if (getenv("PLANCHECK_VERBOSE")) fprintf(stderr, "plan_check: %zu fronts, %d with super-block sweeps\n", P.fronts.size(), nsbf);
         stats[12] = (double)P.fronts.size(); stats[13] = (double)P.gath_tgt.size(); stats[14] = (double)ndense; stats[15] = (double)nmapped;
+        stats[16] = (double)nsbf; stats[17] = (double)maxnp;
     }
     if (symbolic_only) return 0;
 
@@ -357,9 +359,15 @@ int plan_check_run(int64_t N, const int64_t *Ap, const int64_t *Ai, const double
     int64_t nflag = 0;
     const int xwmax = getenv("PLANCHECK_INV_WMAX") ? atoi(getenv("PLANCHECK_INV_WMAX")) : 1 << 30;   // refine only blocks up to this width
     const int xwmin = getenv("PLANCHECK_INV_WMIN") ? atoi(getenv("PLANCHECK_INV_WMIN")) : 0;         // ... and from this width
+    // PLANCHECK_FRONT_REFINE=0: never refine the panels of a front (the kernels' front sweeps k_front_fwd / k_front_bwd do not)
+    const bool front_refine = getenv("PLANCHECK_FRONT_REFINE") ? atoi(getenv("PLANCHECK_FRONT_REFINE")) != 0 : true;
+    // PLANCHECK_SB_SUBST=1: the fronts swept super-block by super-block are solved panel by panel like the other fronts instead
+    // (substitution, or with PLANCHECK_EXPLICIT_INV the panels' own inverses), not through the super-block inverses of SbEmu
+    const bool sb_subst = getenv("PLANCHECK_SB_SUBST") ? atoi(getenv("PLANCHECK_SB_SUBST")) != 0 : false;
     auto flagged = [&](int s_, int w_) {
         if (xmode < 2) return false;
         if (w_ > xwmax || w_ < xwmin) return false;
+        if (!front_refine && P.sn_front[s_] >= 0) return false;
         double mx = 0;
         const double *li = &sbe.Linv[P.sn_diag[s_]];
         for (int q = 0; q < w_ * w_; q++) mx = std::max(mx, std::fabs(li[q]));
@@ -419,7 +427,7 @@ int plan_check_run(int64_t N, const int64_t *Ap, const int64_t *Ai, const double
         // fronts that end at this level: the persistent sweep (external gathers + panel-ordered accumulation)
         for (const FrontDesc &F : P.fronts) {
             if (F.level_last != lvl) continue;
-            if (F.sb_g > 0) { sbe.invert_super(F); sbe.fwd(F, y, ub); continue; }   // front_sweep.hip
+            if (F.sb_g > 0 && !sb_subst) { sbe.invert_super(F); sbe.fwd(F, y, ub); continue; }   // front_sweep.hip
             const FrontPanel *fp = &P.front_panels[F.fp_off];
             std::vector<double> acc(F.rF, 0.0);
             for (int i = 0; i < F.rF; i++)
@@ -446,10 +454,10 @@ int plan_check_run(int64_t N, const int64_t *Ap, const int64_t *Ai, const double
     for (int k = 0; k < N; k++) y[k] *= Dinv[k];
     for (int lvl = P.nlevels - 1; lvl >= 0; lvl--) {
         for (const FrontDesc &F : P.fronts)
-            if (F.sb_g > 0 && F.level_last == lvl) { const std::vector<double> zc(y); sbe.bwd(F, zc, y); }   // k_front_bwd_sb
+            if (F.sb_g > 0 && !sb_subst && F.level_last == lvl) { const std::vector<double> zc(y); sbe.bwd(F, zc, y); }   // k_front_bwd_sb
         for (int q = P.lvl_ptr[lvl]; q < P.lvl_ptr[lvl + 1]; q++) {
             int s = P.lvl_sn[q], w = W(s), r = R(s), f = P.sn_first[s];
-            if (P.sn_front[s] >= 0 && P.fronts[P.sn_front[s]].sb_g > 0) continue;
+            if (P.sn_front[s] >= 0 && P.fronts[P.sn_front[s]].sb_g > 0 && !sb_subst) continue;
             const double *pan = &Lx[P.sn_panel[s]];
             const double *ld = &Ld[P.sn_diag[s]];
             const int *rows = &P.sn_rows[P.sn_rowptr[s]];
