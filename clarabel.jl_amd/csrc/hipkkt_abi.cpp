@@ -387,11 +387,21 @@ int32_t hipkkt_set_hs_psd(hipkkt_handle h, int64_t npsd, const int64_t *hs_off, 
 // ---- N1: update_scaling! + get_Hs! of the symmetric cones on the device (scaling.hip) ---------------------------------
 // kinds[c]: 0 ZeroCone, 1 NonnegativeCone, 2 SecondOrderCone, 3 PSDTriangleCone, anything else = a cone whose block the
 // caller keeps setting through hipkkt_set_hs / hipkkt_set_genpow (ref: the SupportedCone types of cone_types.jl / cone_api.py)
-int32_t hipkkt_set_cone_types(hipkkt_handle h, int64_t ncones, const int32_t *kinds) {
+// ex: hipkkt_set_cone_types_ex -- kinds 4 Exponential, 5 Power, 6 GenPower are checked and get their tables (scaling.hip); alpha = the
+// exponents of the Power / GenPower cones concatenated in cone order
+static int32_t set_cone_types_impl(hipkkt_handle h, int64_t ncones, const int32_t *kinds, bool ex, int64_t nalpha, const double *alpha) {
     HK_ENTER(h)
     if (!S->l1 || ncones != (int64_t)S->cone_numel.size() || (ncones && !kinds)) { S->err = "set_cone_types: not an L1 handle / wrong number of cones"; return HIPKKT_ERR_ARGUMENT; }
+    if (ex && (nalpha < 0 || (nalpha && !alpha))) { S->err = "set_cone_types_ex: null alpha"; return HIPKKT_ERR_ARGUMENT; }
     const int64_t m = S->img.m;
     S->sc_ready = false;          // until this call has validated and uploaded its tables
+    S->ns_active = false;
+    // the non-symmetric cones: three-row cones in two lists (joined [Exponential | Power] below), GenPower descriptors of 8 values
+    struct Row3 { int64_t row0, hs0, out0; double alpha; };
+    std::vector<Row3> exp3, pow3;
+    std::vector<int64_t> gpdesc, gpidx;
+    std::vector<double> gpalpha;
+    int64_t aoff = 0, ns_out = 0;
     std::vector<signed char> kind((size_t)std::max<int64_t>(m, 1), 2);
     std::vector<int64_t> rowhs((size_t)std::max<int64_t>(m, 1), 0), socdesc;
     S->sc_psd_hs.clear(); S->sc_psd_n.clear(); S->sc_psd_total = 0; S->sc_nsoc = 0;
@@ -424,12 +434,38 @@ int32_t hipkkt_set_cone_types(hipkkt_handle h, int64_t ncones, const int32_t *ki
             S->sc_psd_hs.push_back(hs);
             S->sc_psd_n.push_back(n);
             S->sc_psd_total += n * n;
+        } else if (ex && (kinds[c] == HIPKKT_CONE_EXP || kinds[c] == HIPKKT_CONE_POW)) {
+            if (numel != 3 || !dense || sk != 0) { S->err = "set_cone_types_ex: an Exponential / Power cone has three rows, a dense Hs block and no expansion"; return HIPKKT_ERR_ARGUMENT; }
+            double a = 0.0;
+            if (kinds[c] == HIPKKT_CONE_POW) {
+                if (aoff >= nalpha) { S->err = "set_cone_types_ex: alpha is shorter than the Power / GenPower cones need"; return HIPKKT_ERR_ARGUMENT; }
+                a = alpha[aoff++];
+                if (!(a > 0.0 && a < 1.0)) { S->err = "set_cone_types_ex: the exponent of a Power cone lies in (0, 1)"; return HIPKKT_ERR_ARGUMENT; }
+            }
+            (kinds[c] == HIPKKT_CONE_EXP ? exp3 : pow3).push_back({row, hs, ns_out, a});
+            ns_out += 15;
+        } else if (ex && kinds[c] == HIPKKT_CONE_GENPOW) {
+            if (sk != HIPKKT_SPARSE_GENPOW || dense || S->img.smaps[sparse_idx].kind != 2) { S->err = "set_cone_types_ex: a GenPower cone has a diagonal Hs block and a GenPow expansion map"; return HIPKKT_ERR_ARGUMENT; }
+            const SparseMap &sm = S->img.smaps[sparse_idx];
+            const int64_t d1 = (int64_t)sm.vec[0].size(), d2 = (int64_t)sm.vec[1].size();
+            if (d1 < 1 || d1 + d2 != numel || (int64_t)sm.vec[2].size() != numel) { S->err = "set_cone_types_ex: GenPower cone does not match its expansion map"; return HIPKKT_ERR_ARGUMENT; }
+            if (aoff + d1 > nalpha) { S->err = "set_cone_types_ex: alpha is shorter than the Power / GenPower cones need"; return HIPKKT_ERR_ARGUMENT; }
+            for (int64_t i = 0; i < d1; i++)
+                if (!(alpha[aoff + i] > 0.0 && alpha[aoff + i] < 1.0)) { S->err = "set_cone_types_ex: the exponents of a GenPower cone lie in (0, 1)"; return HIPKKT_ERR_ARGUMENT; }
+            const int64_t d8[8] = {row, d1, d2, hs, ns_out, (int64_t)gpalpha.size(), (int64_t)gpidx.size(), 0};
+            gpdesc.insert(gpdesc.end(), d8, d8 + 8);
+            gpalpha.insert(gpalpha.end(), alpha + aoff, alpha + aoff + d1);
+            for (int t = 0; t < 3; t++) gpidx.insert(gpidx.end(), sm.vec[t].begin(), sm.vec[t].end());
+            gpidx.insert(gpidx.end(), sm.D, sm.D + 3);
+            aoff += d1;
+            ns_out += 3 * numel + d1 + 1;
         }
         if (sk != 0) sparse_idx++;
         row += numel;
         hs += blk;
     }
     if (row != m || hs != S->img.nHs) { S->sc_ready = false; S->err = "set_cone_types: cone sizes do not add up to m / the Hs vector"; return HIPKKT_ERR_ARGUMENT; }
+    if (ex && aoff != nalpha) { S->err = "set_cone_types_ex: alpha is longer than the Power / GenPower cones need"; return HIPKKT_ERR_ARGUMENT; }
     if (socdesc.empty()) socdesc.assign(5, 0);
     // device buffers: allocated on the first call; a later call (same cone sizes, possibly other kinds) re-uses them when they are
     // large enough -- slab memory is only returned when the handle is destroyed, so repeated calls must not allocate again
@@ -450,17 +486,67 @@ int32_t hipkkt_set_cone_types(hipkkt_handle h, int64_t ncones, const int32_t *ki
     copy_sync(S->stream, S->d_sc_kind, kind.data(), kind.size() * sizeof(signed char), hipMemcpyHostToDevice);
     copy_sync(S->stream, S->d_sc_rowhs, rowhs.data(), rowhs.size() * sizeof(int64_t), hipMemcpyHostToDevice);
     copy_sync(S->stream, S->d_sc_socdesc, socdesc.data(), socdesc.size() * sizeof(int64_t), hipMemcpyHostToDevice);
+    const int64_t n3 = (int64_t)(exp3.size() + pow3.size()), ngp = (int64_t)gpdesc.size() / 8;
+    if (n3 + ngp > 0) {
+        if (n3 > 0x7fffffff || ngp > 0x7fffffff) { S->err = "set_cone_types_ex: too many cones"; return HIPKKT_ERR_ARGUMENT; }
+        // same rule as above: allocated on the first call, re-used while large enough
+        if (n3 > S->ns_cap3) {
+            S->d_ns_row0 = S->dalloc<int64_t>(n3); S->d_ns_hs0 = S->dalloc<int64_t>(n3); S->d_ns_out0 = S->dalloc<int64_t>(n3);
+            S->d_ns_alpha = S->dalloc<double>(n3); S->d_ns_trips = S->dalloc<int>(n3);
+            S->ns_cap3 = n3;
+        }
+        if (ngp > S->ns_cap_gp) { S->d_ns_gpdesc = S->dalloc<int64_t>(8 * ngp); S->ns_cap_gp = ngp; }
+        if ((int64_t)gpalpha.size() > S->ns_cap_gpalpha) { S->d_ns_gpalpha = S->dalloc<double>(gpalpha.size()); S->ns_cap_gpalpha = (int64_t)gpalpha.size(); }
+        if ((int64_t)gpidx.size() > S->ns_cap_gpidx) { S->d_ns_gpidx = S->dalloc<int64_t>(gpidx.size()); S->ns_cap_gpidx = (int64_t)gpidx.size(); }
+        if (ns_out > S->ns_cap_out) { S->d_ns_out = S->dalloc<double>(ns_out); S->ns_cap_out = ns_out; }
+        if (n3) {
+            std::vector<int64_t> t_row((size_t)n3), t_hs((size_t)n3), t_out((size_t)n3);
+            std::vector<double> t_a((size_t)n3);
+            size_t k = 0;
+            for (const std::vector<Row3> *v : {&exp3, &pow3})
+                for (const Row3 &r : *v) { t_row[k] = r.row0; t_hs[k] = r.hs0; t_out[k] = r.out0; t_a[k] = r.alpha; k++; }
+            copy_sync(S->stream, S->d_ns_row0, t_row.data(), t_row.size() * sizeof(int64_t), hipMemcpyHostToDevice);
+            copy_sync(S->stream, S->d_ns_hs0, t_hs.data(), t_hs.size() * sizeof(int64_t), hipMemcpyHostToDevice);
+            copy_sync(S->stream, S->d_ns_out0, t_out.data(), t_out.size() * sizeof(int64_t), hipMemcpyHostToDevice);
+            copy_sync(S->stream, S->d_ns_alpha, t_a.data(), t_a.size() * sizeof(double), hipMemcpyHostToDevice);
+            fill_async(S->stream, S->d_ns_trips, 0, (size_t)n3 * sizeof(int));
+        }
+        if (ngp) {
+            copy_sync(S->stream, S->d_ns_gpdesc, gpdesc.data(), gpdesc.size() * sizeof(int64_t), hipMemcpyHostToDevice);
+            copy_sync(S->stream, S->d_ns_gpalpha, gpalpha.data(), gpalpha.size() * sizeof(double), hipMemcpyHostToDevice);
+            copy_sync(S->stream, S->d_ns_gpidx, gpidx.data(), gpidx.size() * sizeof(int64_t), hipMemcpyHostToDevice);
+        }
+        S->ns_nexp = (int)exp3.size(); S->ns_npow = (int)pow3.size(); S->ns_ngenpow = (int)ngp;
+        S->ns_out_len = ns_out;
+        S->ns_active = true;
+    }
     S->sc_ready = true;
     return HIPKKT_OK;
     HK_LEAVE
 }
+int32_t hipkkt_set_cone_types(hipkkt_handle h, int64_t ncones, const int32_t *kinds) {
+    return set_cone_types_impl(h, ncones, kinds, false, 0, nullptr);
+}
+int32_t hipkkt_set_cone_types_ex(hipkkt_handle h, int64_t ncones, const int32_t *kinds, int64_t nalpha, const double *alpha) {
+    return set_cone_types_impl(h, ncones, kinds, true, nalpha, alpha);
+}
+int32_t hipkkt_get_nonsym_len(hipkkt_handle h, int64_t *len) {
+    if (!h || !len) return HIPKKT_ERR_ARGUMENT;
+    *len = h->ns_active ? h->ns_out_len : 0;
+    return HIPKKT_OK;
+}
 
 // s, z (length m), psd_R (concatenated n x n column-major R factors, NULL = leave the PSD blocks to hipkkt_set_hs_psd) and the three
 // outputs (w and lambda of length m, eta per second-order cone; any may be NULL) are host pointers, or device pointers when `dev`
+// ex: hipkkt_update_scaling_ex[_dev] -- the same launches in the same order, then the non-symmetric cones of the registration with
+// (mu, strategy); nonsym_out (may be NULL) receives their output vector.  One host synchronisation per call, whatever the cone count.
 static int32_t update_scaling_impl(hipkkt_handle h, const double *s, const double *z, const double *psd_R, double *w_out,
-                                   double *lambda_out, double *soc_eta_out, int32_t *scaling_ok, bool dev) {
+                                   double *lambda_out, double *soc_eta_out, int32_t *scaling_ok, bool dev, bool ex = false,
+                                   double mu = 0.0, int32_t strategy = 0, double *nonsym_out = nullptr) {
     HK_ENTER(h)
     if (!S->sc_ready) { S->err = "update_scaling: call hipkkt_set_cone_types first"; return HIPKKT_ERR_ARGUMENT; }
+    if (!ex && S->ns_active) { S->err = "update_scaling: the cone set has Exponential / Power / GenPower cones, which need mu: call hipkkt_update_scaling_ex"; return HIPKKT_ERR_ARGUMENT; }
+    if (ex && strategy != 0 && strategy != 1) { S->err = "update_scaling_ex: strategy is 0 (PrimalDual) or 1 (Dual)"; return HIPKKT_ERR_ARGUMENT; }
     const int64_t m = S->img.m;
     if (m && (!s || !z)) { S->err = "update_scaling: null s / z"; return HIPKKT_ERR_ARGUMENT; }
     const double *ds = s, *dz = z, *dR = psd_R;
@@ -492,7 +578,15 @@ static int32_t update_scaling_impl(hipkkt_handle h, const double *s, const doubl
             off += (int64_t)n * n;
         }
     }
+    if (ex && S->ns_active) {
+        launch_scaling_cone3(S->stream, S->ns_nexp, S->ns_npow, S->d_ns_row0, S->d_ns_hs0, S->d_ns_out0, S->d_ns_alpha, S->d_mapHs, ds, dz,
+                             mu, strategy, S->dp.kval, S->d_ns_out, S->d_ns_trips, S->d_sc_fail);
+        launch_scaling_genpow(S->stream, S->ns_ngenpow, S->d_ns_gpdesc, S->d_ns_gpalpha, S->d_ns_gpidx, S->d_mapHs, dz, mu, std::sqrt(mu),
+                              S->dp.kval, S->d_ns_out, S->d_sc_fail);
+    }
     const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (ex && S->ns_active && nonsym_out && S->ns_out_len)
+        HK_CHECK(hipMemcpyAsync(nonsym_out, S->d_ns_out, (size_t)S->ns_out_len * sizeof(double), kind, S->stream));
     if (w_out && m) HK_CHECK(hipMemcpyAsync(w_out, dw, m * sizeof(double), kind, S->stream));
     if (lambda_out && m) HK_CHECK(hipMemcpyAsync(lambda_out, dl, m * sizeof(double), kind, S->stream));
     if (soc_eta_out && S->sc_nsoc) HK_CHECK(hipMemcpyAsync(soc_eta_out, S->d_sc_eta, S->sc_nsoc * sizeof(double), kind, S->stream));
@@ -509,6 +603,16 @@ int32_t hipkkt_update_scaling(hipkkt_handle h, const double *s, const double *z,
 int32_t hipkkt_update_scaling_dev(hipkkt_handle h, const double *s_dev, const double *z_dev, const double *psd_R_dev, double *w_out_dev,
                                   double *lambda_out_dev, double *soc_eta_out_dev, int32_t *scaling_ok) {
     return update_scaling_impl(h, s_dev, z_dev, psd_R_dev, w_out_dev, lambda_out_dev, soc_eta_out_dev, scaling_ok, true);
+}
+int32_t hipkkt_update_scaling_ex(hipkkt_handle h, const double *s, const double *z, const double *psd_R, double mu, int32_t strategy,
+                                 double *w_out, double *lambda_out, double *soc_eta_out, double *nonsym_out, int32_t *scaling_ok) {
+    return update_scaling_impl(h, s, z, psd_R, w_out, lambda_out, soc_eta_out, scaling_ok, false, true, mu, strategy, nonsym_out);
+}
+int32_t hipkkt_update_scaling_ex_dev(hipkkt_handle h, const double *s_dev, const double *z_dev, const double *psd_R_dev, double mu,
+                                     int32_t strategy, double *w_out_dev, double *lambda_out_dev, double *soc_eta_out_dev,
+                                     double *nonsym_out_dev, int32_t *scaling_ok) {
+    return update_scaling_impl(h, s_dev, z_dev, psd_R_dev, w_out_dev, lambda_out_dev, soc_eta_out_dev, scaling_ok, true, true, mu, strategy,
+                               nonsym_out_dev);
 }
 
 int32_t hipkkt_set_soc_batch(hipkkt_handle h, int64_t nsoc, const double *eta2, const double *u_all, const double *v_all,
@@ -731,6 +835,13 @@ int32_t hipkkt_debug_dump(hipkkt_handle h, int32_t what, double *out, int64_t ca
                 v.insert(v.end(), rec, rec + 4);
             }
             host((int64_t)v.size(), [&](int64_t i) { return v[i]; });
+            break;
+        }
+        case 23: {   // Newton steps of the last hipkkt_update_scaling_ex per Power cone, in cone order (0 = Dual scaling or s3 = 0)
+            if (!S->ns_active) return HIPKKT_ERR_ARGUMENT;
+            std::vector<int> v((size_t)std::max(S->ns_npow, 1), 0);
+            if (S->ns_npow) copy_sync(S->stream, v.data(), S->d_ns_trips + S->ns_nexp, (size_t)S->ns_npow * sizeof(int), hipMemcpyDeviceToHost);
+            host(S->ns_npow, [&](int64_t i) { return v[i]; });
             break;
         }
         case 7: dev(S->d_soc_u, S->soc_total); break;

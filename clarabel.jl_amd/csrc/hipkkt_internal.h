@@ -240,6 +240,16 @@ struct hipkkt_solver {
     int64_t *d_sc_rowhs = nullptr, *d_sc_socdesc = nullptr;
     double *d_sc_sz = nullptr, *d_sc_wl = nullptr, *d_sc_eta = nullptr, *d_sc_R = nullptr, *d_sc_W = nullptr;
     int *d_sc_fail = nullptr;
+    // N1, the non-symmetric cones (hipkkt_set_cone_types_ex + hipkkt_update_scaling_ex): tables built once per registration
+    bool ns_active = false;                                // the last registration named an Exponential / Power / GenPower cone
+    int ns_nexp = 0, ns_npow = 0, ns_ngenpow = 0;
+    int64_t ns_out_len = 0;                                // doubles of the output vector (hipkkt_get_nonsym_len)
+    int64_t ns_cap3 = 0, ns_cap_gp = 0, ns_cap_gpalpha = 0, ns_cap_gpidx = 0, ns_cap_out = 0;   // capacities, as sc_cap_*
+    int64_t *d_ns_row0 = nullptr, *d_ns_hs0 = nullptr, *d_ns_out0 = nullptr;                   // three-row cones, [Exponential | Power]
+    double *d_ns_alpha = nullptr;
+    int *d_ns_trips = nullptr;                             // Newton steps of the last update per table entry (debug_dump 23)
+    int64_t *d_ns_gpdesc = nullptr, *d_ns_gpidx = nullptr; // GenPower cones: 8 values per cone; [map.q | map.r | map.p | map.D] per cone
+    double *d_ns_gpalpha = nullptr, *d_ns_out = nullptr;
 
     // vectors
     double *d_b = nullptr, *d_x = nullptr, *d_dx = nullptr, *d_e = nullptr;

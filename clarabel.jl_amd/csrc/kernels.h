@@ -40,6 +40,15 @@ void launch_scaling_soc(hipStream_t st, int nsoc, const int64_t *desc, const int
                         double *w, double *lam, double *eta_out, double *soc_u, double *soc_v, double *soc_eta2, double *kval,
                         int *fail);
 void launch_psd_rrt(hipStream_t st, const double *R, double *W, int n);
+// scaling.hip, the non-symmetric cones (hipkkt_update_scaling_ex).  Three-row cones: SoA tables ordered by kind, the first nexp
+// entries Exponential, the next npow Power (one launch per kind: a wavefront never mixes the two bodies); strategy 0 PrimalDual,
+// 1 Dual; trips (may be NULL) receives the Newton steps per table entry.  Generalized Power: one wavefront per cone, desc = 8 int64 per
+// cone, idx = the resident [map.q | map.r | map.p | map.D] tables concatenated.
+void launch_scaling_cone3(hipStream_t st, int nexp, int npow, const int64_t *row0, const int64_t *hs0, const int64_t *out0,
+                          const double *alpha, const int64_t *map_hs, const double *s, const double *z, double mu, int strategy,
+                          double *kval, double *out, int *trips, int *fail);
+void launch_scaling_genpow(hipStream_t st, int ngenpow, const int64_t *desc, const double *alpha, const int64_t *idx,
+                           const int64_t *map_hs, const double *z, double mu, double sqrtmu, double *kval, double *out, int *fail);
 void launch_block_products(hipStream_t st, const DevPlan &P, const double *x, const double *z, double *Px, double *ATz,
                            double *Ax, int n, int m);
 void launch_zero_words(hipStream_t st, void *p, int nwords);

@@ -129,6 +129,369 @@ k_psd_rrt(const double *__restrict__ R, double *__restrict__ W, int n) {
     W[e] = acc;
 }
 
+// ---- the non-symmetric cones (hipkkt_update_scaling_ex) ------------------------------------------------------------------------
+//   Exponential   coneops_expcone.jl:63-83 (update_scaling!), :284-297 (gradient_primal), :370-467 (update_dual_grad_H, Wright omega)
+//   Power         coneops_powcone.jl:65-85, :288-317, :408-478 (one-sided Newton-Raphson, at most 100 steps)
+//   both          coneops_nonsymmetric_common.jl:50-192 (Dual: Hs = mu H*, PrimalDual: the BFGS form or the central-path fallback)
+//   GenPower      coneops_genpowcone.jl:64-108, :343-396 and _csc_update_sparsecone, directldl_datamaps.jl:146-167
+// A cone whose z is not strictly inside the dual cone, whose s is not strictly inside the primal cone (PrimalDual), or whose result is
+// not finite sets the fail word, fills its slot of the output vector with NaN and leaves its entries of K alone: no assert, no trap.
+// Every loop is bounded (the Newton iteration by the reference's 100 steps) and every index comes from the tables of the handle.
+
+__device__ __forceinline__ double logsafe(double v) {      // mathutils.jl:12-18
+    if (v < 0.0) return -1.7976931348623157e308;
+    if (v == 0.0) return -__builtin_huge_val();
+    return log(v);
+}
+__device__ __forceinline__ bool finite3(double a, double b, double c) { return isfinite(a) && isfinite(b) && isfinite(c); }
+
+// coneops_expcone.jl:412-467; the caller has checked z >= 0
+__device__ double wright_omega(double z) {
+    double w;
+    if (z < 1.0 + 3.141592653589793) {
+        const double zm1 = z - 1.0;
+        double p = zm1;
+        w = 1.0 + 0.5 * p;
+        p *= zm1;
+        w += (1.0 / 16.0) * p;
+        p *= zm1;
+        w -= (1.0 / 192.0) * p;
+        p *= zm1;
+        w -= (1.0 / 3072.0) * p;
+        p *= zm1;
+        w += (13.0 / 61440.0) * p;
+    } else {
+        const double logz = logsafe(z), zinv = 1.0 / z;
+        w = z - logz;
+        double q = logz * zinv;
+        w += q;
+        q *= zinv;
+        w += q * (logz / 2.0 - 1.0);
+        w += q * (logz * logz / 3.0 - (3.0 / 2.0) * logz + 1.0);      // (:451 does not store q * zinv)
+    }
+    double r = z - w - logsafe(w);
+    for (int k = 0; k < 2; k++) {
+        const double wp1 = w + 1.0;
+        const double t = wp1 * (wp1 + (2.0 * r) / 3.0);
+        w *= 1.0 + (r / wp1) * (t - 0.5 * r) / (t - r);
+        r = (2.0 * w * w - 8.0 * w - 1.0) / (72.0 * (wp1 * wp1 * wp1 * wp1 * wp1 * wp1)) * r * r * r * r;
+    }
+    return w;
+}
+
+// H = the dual Hessian in pack_triu order {00, 01, 11, 02, 12, 22}
+struct Cone3 { double g[3], H[6]; };
+
+__device__ __forceinline__ bool exp_dual_grad_H(const double z[3], Cone3 &K) {      // coneops_expcone.jl:269-281, :370-400
+    if (!(z[2] > 0.0 && z[0] < 0.0)) return false;
+    const double l = logsafe(-z[2] / z[0]);
+    if (!(z[1] - z[0] - z[0] * l > 0.0)) return false;
+    const double r = -z[0] * l - z[0] + z[1];
+    const double c2 = 1.0 / r;
+    K.g[0] = c2 * l - 1.0 / z[0];
+    K.g[1] = -c2;
+    K.g[2] = (c2 * z[0] - 1.0) / z[2];
+    K.H[0] = (r * r - z[0] * r + l * l * z[0] * z[0]) / (r * z[0] * z[0] * r);
+    K.H[1] = -l / (r * r);
+    K.H[2] = 1.0 / (r * r);
+    K.H[3] = (z[1] - z[0]) / (r * r * z[2]);
+    K.H[4] = -z[0] / (r * r * z[2]);
+    K.H[5] = (r * r - z[0] * r + z[0] * z[0]) / (r * r * z[2] * z[2]);
+    return true;
+}
+__device__ __forceinline__ bool exp_gradient_primal(const double s[3], double g[3]) {      // coneops_expcone.jl:253-266, :284-297
+    if (!(s[2] > 0.0 && s[1] > 0.0)) return false;
+    if (!(s[1] * logsafe(s[2] / s[1]) - s[0] > 0.0)) return false;
+    const double arg = 1.0 - s[0] / s[1] - logsafe(s[1] / s[2]);
+    if (!(arg >= 0.0)) return false;                       // (:415 throws)
+    const double om = wright_omega(arg);
+    g[0] = 1.0 / ((om - 1.0) * s[1]);
+    g[1] = g[0] + g[0] * logsafe(om * s[1] / s[2]) - 1.0 / s[1];
+    g[2] = om / ((1.0 - om) * s[2]);
+    return true;
+}
+
+__device__ __forceinline__ bool pow_dual_grad_H(const double z[3], double a, Cone3 &K) {      // coneops_powcone.jl:272-285, :408-442
+    if (!(z[0] > 0.0 && z[1] > 0.0)) return false;
+    if (!(exp(2.0 * a * logsafe(z[0] / a) + 2.0 * (1.0 - a) * logsafe(z[1] / (1.0 - a))) - z[2] * z[2] > 0.0)) return false;
+    const double phi = pow(z[0] / a, 2.0 * a) * pow(z[1] / (1.0 - a), 2.0 - 2.0 * a);
+    const double psi = phi - z[2] * z[2];
+    const double gp0 = 2.0 * a * phi / (z[0] * psi), gp1 = 2.0 * (1.0 - a) * phi / (z[1] * psi), gp2 = -2.0 * z[2] / psi;
+    K.H[0] = gp0 * gp0 - 2.0 * a * (2.0 * a - 1.0) * phi / (z[0] * z[0] * psi) + (1.0 - a) / (z[0] * z[0]);
+    K.H[1] = gp0 * gp1 - 4.0 * a * (1.0 - a) * phi / (z[0] * z[1] * psi);
+    K.H[2] = gp1 * gp1 - 2.0 * (1.0 - a) * (1.0 - 2.0 * a) * phi / (z[1] * z[1] * psi) + a / (z[1] * z[1]);
+    K.H[3] = gp0 * gp2;
+    K.H[4] = gp1 * gp2;
+    K.H[5] = gp2 * gp2 + 2.0 / psi;
+    K.g[0] = -2.0 * a * phi / (z[0] * psi) - (1.0 - a) / z[0];
+    K.g[1] = -2.0 * (1.0 - a) * phi / (z[1] * psi) - a / z[1];
+    K.g[2] = 2.0 * z[2] / psi;
+    return true;
+}
+// coneops_powcone.jl:449-478 with _newton_raphson_onesided, coneops_nonsymmetric_common.jl:170-192 (at most 100 steps)
+__device__ double pow_newton_raphson(double s3, double phi, double a, int *trips) {
+    const double eps = 2.220446049250313e-16, sqrt_eps = 1.4901161193847656e-08;
+    double x = -1.0 / s3 + (2.0 * s3 + sqrt(phi * phi / s3 / s3 + 3.0 * phi)) / (phi - s3 * s3);
+    const double t0 = -2.0 * a * logsafe(a) - 2.0 * (1.0 - a) * logsafe(1.0 - a);
+    int it = 0;
+    while (it < 100) {
+        it++;
+        const double t1 = x * x;
+        const double t2 = 2.0 * x / s3, t2d = x * 2.0 / s3;
+        const double dfdx = 2.0 * a * a / (a * x + (1.0 + a) / s3) + 2.0 * (1.0 - a) * (1.0 - a) / ((1.0 - a) * x + (2.0 - a) / s3) -
+                            2.0 * (x + 1.0 / s3) / (t1 + t2d);
+        const double f = 2.0 * a * logsafe(2.0 * a * t1 + (1.0 + a) * t2) + 2.0 * (1.0 - a) * logsafe(2.0 * (1.0 - a) * t1 + (2.0 - a) * t2) -
+                         logsafe(phi) - logsafe(t1 + t2) - 2.0 * logsafe(t2) + t0;
+        const double dx = -f / dfdx;
+        if (dx < eps || fabs(dx / x) < sqrt_eps || fabs(dfdx) < eps) break;
+        x += dx;
+    }
+    *trips = it;
+    return x;
+}
+__device__ __forceinline__ bool pow_gradient_primal(const double s[3], double a, double g[3], int *trips) {   // :256-269, :288-317
+    if (!(s[0] > 0.0 && s[1] > 0.0)) return false;
+    if (!(exp(2.0 * a * logsafe(s[0]) + 2.0 * (1.0 - a) * logsafe(s[1])) - s[2] * s[2] > 0.0)) return false;
+    const double phi = pow(s[0], 2.0 * a) * pow(s[1], 2.0 - 2.0 * a);
+    const double abs_s = fabs(s[2]);
+    if (abs_s > 2.220446049250313e-16) {
+        g[2] = pow_newton_raphson(abs_s, phi, a, trips);
+        if (s[2] < 0.0) g[2] = -g[2];
+        g[0] = -(a * g[2] * s[2] + 1.0 + a) / s[0];
+        g[1] = -((1.0 - a) * g[2] * s[2] + 2.0 - a) / s[1];
+    } else {
+        g[2] = 0.0;
+        g[0] = -(1.0 + a) / s[0];
+        g[1] = -(2.0 - a) / s[1];
+    }
+    return true;
+}
+
+// use_primal_dual_scaling, coneops_nonsymmetric_common.jl:82-164: st = K.g, zt = -f'(s); Hs in pack_triu order
+__device__ bool primal_dual_hs(const Cone3 &K, const double s[3], const double z[3], const double zt[3], double Hs[6]) {
+    const double eps = 2.220446049250313e-16, sqrt_eps = 1.4901161193847656e-08;
+    const double *st = K.g, *H = K.H;
+    const double Hf[3][3] = {{H[0], H[1], H[3]}, {H[1], H[2], H[4]}, {H[3], H[4], H[5]}};
+    const double dot_sz = z[0] * s[0] + z[1] * s[1] + z[2] * s[2];
+    const double mu = dot_sz / 3.0;
+    const double mut = (zt[0] * st[0] + zt[1] * st[1] + zt[2] * st[2]) / 3.0;
+    double ds[3], dz[3];
+    for (int i = 0; i < 3; i++) { ds[i] = s[i] + mu * st[i]; dz[i] = z[i] + mu * zt[i]; }
+    const double dot_dsz = ds[0] * dz[0] + ds[1] * dz[1] + ds[2] * dz[2];
+    const double de1 = mu * mut - 1.0;
+    double Hz[3];
+    for (int i = 0; i < 3; i++) Hz[i] = Hf[i][0] * zt[0] + Hf[i][1] * zt[1] + Hf[i][2] * zt[2];
+    const double de2 = (zt[0] * Hz[0] + zt[1] * Hz[1] + zt[2] * Hz[2]) - 3.0 * mut * mut;
+    if (fabs(de1) > sqrt_eps && fabs(de2) > eps && dot_sz > 0.0 && dot_dsz > 0.0) {
+        double tmp[3];
+        for (int i = 0; i < 3; i++) tmp[i] = mut * st[i] - Hf[i][0] * zt[0] - Hf[i][1] * zt[1] - Hf[i][2] * zt[2];
+        double nrm2 = 0.0;
+        for (int j = 0; j < 3; j++)
+            for (int i = 0; i < 3; i++) {
+                const double e = Hf[i][j] - (st[i] * st[j] / 3.0 + tmp[i] * tmp[j] / de2);
+                nrm2 += e * e;
+            }
+        const double t = mu * sqrt(nrm2);      // Frobenius norm
+        if (!(t > 0.0)) return false;          // (:135 asserts)
+        double ax[3] = {z[1] * zt[2] - z[2] * zt[1], z[2] * zt[0] - z[0] * zt[2], z[0] * zt[1] - z[1] * zt[0]};
+        const double inv = 1.0 / sqrt(ax[0] * ax[0] + ax[1] * ax[1] + ax[2] * ax[2]);
+        for (int i = 0; i < 3; i++) ax[i] *= inv;
+        int h = 0;
+        for (int j = 0; j < 3; j++)
+            for (int i = 0; i <= j; i++) Hs[h++] = s[i] * s[j] / dot_sz + ds[i] * ds[j] / dot_dsz + t * ax[i] * ax[j];
+    } else {
+        for (int i = 0; i < 6; i++) Hs[i] = mu * H[i];      // on the central path: the LOCAL mu = <s, z> / 3 (:159)
+    }
+    return true;
+}
+
+// cholesky_3x3_explicit_factor!, mathutils.jl:427-451, on a pack_triu matrix: does the factorisation go through?
+__device__ __forceinline__ bool chol3_ok(const double A[6]) {
+    double t = A[0];
+    if (!(t > 0.0)) return false;
+    const double l11 = sqrt(t), l21 = A[1] / l11;
+    t = A[2] - l21 * l21;
+    if (!(t > 0.0)) return false;
+    const double l22 = sqrt(t), l31 = A[3] / l11, l32 = (A[4] - l21 * l31) / l22;
+    t = A[5] - l31 * l31 - l32 * l32;
+    return t > 0.0;
+}
+// On late iterates Hs, positive definite in exact arithmetic, reaches condition numbers of 1e16 .. 4e18 and the 3 x 3 Cholesky of the
+// rounded block can break down (on the reference's own host values as well).  Such a block gets the smallest shift
+// 2^k eps max(diag) on its diagonal, k = 1 .. 8, with which the factorisation goes through -- a change in the last one or two bits of the
+// diagonal (k = 1 on every block met so far), far below what one ulp of (s, z) moves such a block by.  A block that needs more is
+// left as the reference's formulas give it.  Blocks whose Cholesky goes through are never touched.
+__device__ __forceinline__ void keep_positive_definite(double Hs[6]) {
+    if (chol3_ok(Hs)) return;
+    const double dmax = fmax(Hs[0], fmax(Hs[2], Hs[5]));
+    double delta = 2.220446049250313e-16 * dmax;
+    for (int k = 1; k <= 8; k++) {
+        delta *= 2.0;
+        double T[6] = {Hs[0] + delta, Hs[1], Hs[2] + delta, Hs[3], Hs[4], Hs[5] + delta};
+        if (chol3_ok(T)) {
+            for (int i = 0; i < 6; i++) Hs[i] = T[i];
+            return;
+        }
+    }
+}
+
+// One lane per three-row cone; a launch holds cones of one kind only (POW = false Exponential, true Power): the tables are ordered
+// by kind, this launch takes the `count` cones from `first` on.  strategy 0 PrimalDual, 1 Dual (types.jl:73-76).
+// Per cone: Hs (6) negated through map_hs into kval; Hs (6), H_dual (6), grad (3) into out[out0 ..).  trips (may be NULL) receives the
+// steps of the Newton iteration.
+template <bool POW>
+__global__ void __launch_bounds__(256)
+k_scaling_cone3(int first, int count, const int64_t *__restrict__ row0_t, const int64_t *__restrict__ hs0_t,
+                const int64_t *__restrict__ out0_t, const double *__restrict__ alpha_t, const int64_t *__restrict__ map_hs,
+                const double *__restrict__ s_all, const double *__restrict__ z_all, double mu, int strategy,
+                double *__restrict__ kval, double *__restrict__ out, int *__restrict__ trips_out, int *__restrict__ fail) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= count) return;
+    const int c = first + k;
+    const int64_t row0 = row0_t[c], hs0 = hs0_t[c], out0 = out0_t[c];
+    const double a = POW ? alpha_t[c] : 0.0;
+    const double s[3] = {s_all[row0], s_all[row0 + 1], s_all[row0 + 2]};
+    const double z[3] = {z_all[row0], z_all[row0 + 1], z_all[row0 + 2]};
+    Cone3 K;
+    double Hs[6];
+    int trips = 0;
+    bool ok = POW ? pow_dual_grad_H(z, a, K) : exp_dual_grad_H(z, K);
+    if (ok) {
+        if (strategy == 1) {
+            for (int i = 0; i < 6; i++) Hs[i] = mu * K.H[i];      // use_dual_scaling, coneops_nonsymmetric_common.jl:71-78
+        } else {
+            double zt[3];
+            ok = POW ? pow_gradient_primal(s, a, zt, &trips) : exp_gradient_primal(s, zt);
+            ok = ok && finite3(zt[0], zt[1], zt[2]) && primal_dual_hs(K, s, z, zt, Hs);
+        }
+    }
+    if (ok) {
+        ok = finite3(K.g[0], K.g[1], K.g[2]);
+        for (int i = 0; i < 6; i++) ok = ok && isfinite(Hs[i]) && isfinite(K.H[i]);
+    }
+    if (ok) keep_positive_definite(Hs);
+    double *o = out + out0;
+    if (trips_out) trips_out[c] = trips;
+    if (!ok) {
+        atomicOr(fail, 1);
+        for (int i = 0; i < 15; i++) o[i] = __builtin_nan("");
+        return;
+    }
+    for (int i = 0; i < 6; i++) {
+        kval[map_hs[hs0 + i]] = -Hs[i];
+        o[i] = Hs[i];
+        o[6 + i] = K.H[i];
+    }
+    for (int i = 0; i < 3; i++) o[12 + i] = K.g[i];
+}
+
+__device__ __forceinline__ double wave_sum(double v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+__device__ __forceinline__ double wave_prod(double v) {
+    for (int o = 32; o > 0; o >>= 1) v *= __shfl_xor(v, o);
+    return v;
+}
+__device__ __forceinline__ int wave_or(int v) {
+    for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o);
+    return v;
+}
+
+// One wavefront (= one workgroup of 64) per Generalized Power cone.  desc[8 c ..] = {first row, dim1, dim2, first Hs entry, offset of
+// the cone's slot in `out`, offset of its exponents in alpha_all, offset of its index table in idx_all, unused}; the index table is
+// [map.q (dim1) | map.r (dim2) | map.p (dim) | map.D (3)] of the cone's GenPowExpansionMap (directldl_datamaps.jl:81-99), resident.
+// The cone always takes the Dual scaling with the caller's mu (coneops_genpowcone.jl:21, :64-80).  Products and sums over the cone
+// are butterfly reductions: every lane holds the same phi, |w|^2.
+// out slot: grad (dim) | d1 (dim1) | d2 | p (dim) | q (dim1) | r (dim2).
+__global__ void __launch_bounds__(64)
+k_scaling_genpow(const int64_t *__restrict__ desc, const double *__restrict__ alpha_all, const int64_t *__restrict__ idx_all,
+                 const int64_t *__restrict__ map_hs, const double *__restrict__ z_all, double mu, double sqrtmu,
+                 double *__restrict__ kval, double *__restrict__ out, int *__restrict__ fail) {
+    const int c = blockIdx.x, t = threadIdx.x;
+    const int64_t *d = desc + 8 * (int64_t)c;
+    const int64_t row0 = d[0], dim1 = d[1], dim2 = d[2], hs0 = d[3], dim = dim1 + dim2;
+    const double *z = z_all + row0, *a = alpha_all + d[5];
+    const int64_t *qi = idx_all + d[6], *ri = qi + dim1, *pi = ri + dim2, *Di = pi + dim;
+    double *g = out + d[4], *od1 = g + dim, *od2 = od1 + dim1, *op = od2 + 1, *oq = op + dim, *orr = oq + dim1;
+    // update_dual_grad_H, :343-396
+    double phi = 1.0, n2 = 0.0;
+    int bad = 0;
+    for (int64_t i = t; i < dim1; i += 64) {
+        if (!(z[i] > 0.0)) bad = 1;
+        phi *= pow(z[i] / a[i], 2.0 * a[i]);
+    }
+    for (int64_t i = t; i < dim2; i += 64) n2 += z[dim1 + i] * z[dim1 + i];
+    phi = wave_prod(phi);
+    const double norm2w = wave_sum(n2);
+    const double zeta = phi - norm2w;
+    bad = wave_or(bad);
+    if (!bad && !(zeta > 0.0 && isfinite(phi))) bad = 1;      // (:357 asserts); uniform over the wavefront
+    const double p0 = sqrt(phi * (phi + norm2w) / 2.0), p1 = -2.0 * phi / p0, q0 = sqrt(zeta * phi / 2.0);
+    const double r1 = 2.0 * sqrt(zeta / (phi + norm2w)), d2 = 2.0 / zeta;
+    // two passes with the same expressions: the first only looks for a non-finite result, so that a failing cone writes nothing
+    for (int pass = 0; pass < 2; pass++) {
+        if (pass == 1) {
+            bad = wave_or(bad);
+            if (bad) {
+                if (t == 0) atomicOr(fail, 1);
+                for (int64_t i = t; i < 3 * dim + dim1 + 1; i += 64) g[i] = __builtin_nan("");
+                return;
+            }
+        } else if (bad) {
+            continue;
+        }
+        for (int64_t i = t; i < dim1; i += 64) {
+            const double tau = 2.0 * a[i] / z[i];
+            const double gi = -tau * phi / zeta - (1.0 - a[i]) / z[i];
+            const double d1 = tau * phi / (zeta * z[i]) + (1.0 - a[i]) / (z[i] * z[i]);
+            const double p = p0 * tau / zeta, q = tau * (q0 / zeta);
+            if (pass == 0) {
+                if (!(finite3(gi, d1, p) && isfinite(q) && isfinite(mu * d1) && d1 > 0.0)) bad = 1;
+            } else {
+                g[i] = gi; od1[i] = d1; op[i] = p; oq[i] = q;
+                kval[map_hs[hs0 + i]] = -(mu * d1);                       // get_Hs!, :91-108
+                kval[qi[i]] = q * -sqrtmu;                                // directldl_datamaps.jl:157-162
+                kval[pi[i]] = p * -sqrtmu;
+            }
+        }
+        for (int64_t i = t; i < dim2; i += 64) {
+            const double w = z[dim1 + i];
+            const double gi = 2.0 * w / zeta, p = p1 * w / zeta, r = r1 * w / zeta;
+            if (pass == 0) {
+                if (!finite3(gi, p, r)) bad = 1;
+            } else {
+                g[dim1 + i] = gi; op[dim1 + i] = p; orr[i] = r;
+                kval[map_hs[hs0 + dim1 + i]] = -(mu * d2);
+                kval[ri[i]] = r * -sqrtmu;
+                kval[pi[dim1 + i]] = p * -sqrtmu;
+            }
+        }
+        if (pass == 0) {
+            if (!(finite3(d2, mu * d2, sqrtmu) && d2 > 0.0)) bad = 1;
+        } else if (t == 0) {
+            od2[0] = d2;
+            kval[Di[0]] = -1.0; kval[Di[1]] = -1.0; kval[Di[2]] = 1.0;      // :165
+        }
+    }
+}
+
+void launch_scaling_cone3(hipStream_t st, int nexp, int npow, const int64_t *row0, const int64_t *hs0, const int64_t *out0,
+                          const double *alpha, const int64_t *map_hs, const double *s, const double *z, double mu, int strategy,
+                          double *kval, double *out, int *trips, int *fail) {
+    if (nexp > 0)
+        hipLaunchKernelGGL(k_scaling_cone3<false>, dim3((unsigned)((nexp + 255) / 256)), dim3(256), 0, st, 0, nexp, row0, hs0, out0,
+                           alpha, map_hs, s, z, mu, strategy, kval, out, trips, fail);
+    if (npow > 0)
+        hipLaunchKernelGGL(k_scaling_cone3<true>, dim3((unsigned)((npow + 255) / 256)), dim3(256), 0, st, nexp, npow, row0, hs0, out0,
+                           alpha, map_hs, s, z, mu, strategy, kval, out, trips, fail);
+}
+void launch_scaling_genpow(hipStream_t st, int ngenpow, const int64_t *desc, const double *alpha, const int64_t *idx,
+                           const int64_t *map_hs, const double *z, double mu, double sqrtmu, double *kval, double *out, int *fail) {
+    if (ngenpow > 0)
+        hipLaunchKernelGGL(k_scaling_genpow, dim3(ngenpow), dim3(64), 0, st, desc, alpha, idx, map_hs, z, mu, sqrtmu, kval, out, fail);
+}
+
 void launch_scaling_diag(hipStream_t st, const signed char *row_kind, const int64_t *row_hs, const int64_t *map_hs, const double *s,
                          const double *z, double *w, double *lam, double *kval, int64_t m) {
     if (m > 0)

@@ -26,14 +26,14 @@ _i64p = np.ctypeslib.ndpointer(dtype=np.int64, flags="C_CONTIGUOUS")
 _i32p = np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")
 _f64p = np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
 
-ABI_VERSION = 4   # include/hipkkt.h HIPKKT_ABI_VERSION (checked when the library is loaded)
+ABI_VERSION = 5   # include/hipkkt.h HIPKKT_ABI_VERSION (checked when the library is loaded)
 
 # every symbol include/hipkkt.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
     "hipkkt_default_opts", "hipkkt_is_available", "hipkkt_abi_version", "hipkkt_trim_cache", "hipkkt_create", "hipkkt_create_from_parts", "hipkkt_destroy",
     "hipkkt_get_dims", "hipkkt_info", "hipkkt_get_cost_model", "hipkkt_get_kkt", "hipkkt_get_perm",
     "hipkkt_get_dsigns", "hipkkt_get_map", "hipkkt_get_sparse_map", "hipkkt_update_values", "hipkkt_scale_values",
-    "hipkkt_set_hs", "hipkkt_set_hs_dev", "hipkkt_set_hs_psd", "hipkkt_set_cone_types", "hipkkt_update_scaling", "hipkkt_update_scaling_dev", "hipkkt_block_products", "hipkkt_set_soc", "hipkkt_set_soc_batch", "hipkkt_set_genpow",
+    "hipkkt_set_hs", "hipkkt_set_hs_dev", "hipkkt_set_hs_psd", "hipkkt_set_cone_types", "hipkkt_update_scaling", "hipkkt_update_scaling_dev", "hipkkt_set_cone_types_ex", "hipkkt_get_nonsym_len", "hipkkt_update_scaling_ex", "hipkkt_update_scaling_ex_dev", "hipkkt_block_products", "hipkkt_set_soc", "hipkkt_set_soc_batch", "hipkkt_set_genpow",
     "hipkkt_update_P", "hipkkt_update_A", "hipkkt_refactor", "hipkkt_setrhs", "hipkkt_setrhs_dev", "hipkkt_solve",
     "hipkkt_solve_dev", "hipkkt_solve_multi", "hipkkt_solve_multi_dev", "hipkkt_kkt_solve_reduced", "hipkkt_kkt_solve_reduced_dev", "hipkkt_ldl_solve", "hipkkt_get_timing", "hipkkt_reset_timing", "hipkkt_get_profile", "hipkkt_get_profile_launches", "hipkkt_set_profiling",
     "hipkkt_get_counters", "hipkkt_debug_dump", "hipkkt_debug_extra_tiles", "hipkkt_debug_set", "hipkkt_debug_is_testing_build", "hipkkt_set_qb", "hipkkt_residuals", "hipkkt_residuals_dev",
@@ -95,6 +95,10 @@ def lib():
     L.hipkkt_set_cone_types.argtypes = [vp, i64, _i32p]
     L.hipkkt_update_scaling.argtypes = [vp, _f64p, _f64p, vp, vp, vp, vp, C.POINTER(i32)]
     L.hipkkt_update_scaling_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.POINTER(i32)]
+    L.hipkkt_set_cone_types_ex.argtypes = [vp, i64, _i32p, i64, _f64p]
+    L.hipkkt_get_nonsym_len.argtypes = [vp, C.POINTER(i64)]
+    L.hipkkt_update_scaling_ex.argtypes = [vp, _f64p, _f64p, vp, f64, i32, vp, vp, vp, vp, C.POINTER(i32)]
+    L.hipkkt_update_scaling_ex_dev.argtypes = [vp, vp, vp, vp, f64, i32, vp, vp, vp, vp, C.POINTER(i32)]
     L.hipkkt_block_products.argtypes = [vp, _f64p, _f64p, _f64p, _f64p, _f64p]
     L.hipkkt_set_soc.argtypes = [vp, i64, f64, _f64p, _f64p, i64]
     L.hipkkt_set_soc_batch.argtypes = [vp, i64, _f64p, _f64p, _f64p, i64]
@@ -362,6 +366,62 @@ class Handle:
     def update_scaling_dev(self, s_ptr, z_ptr, R_ptr=None, w_ptr=None, lam_ptr=None, eta_ptr=None):
         ok = C.c_int32(0)
         self._chk(self.L.hipkkt_update_scaling_dev(self.h, s_ptr, z_ptr, R_ptr, w_ptr, lam_ptr, eta_ptr, C.byref(ok)), "update_scaling_dev")
+        return bool(ok.value)
+
+    # ---- N1 with the non-symmetric cones (include/hipkkt.h hipkkt_update_scaling_ex): kinds 4 Exponential, 5 Power, 6 GenPower
+    def _set_kind_lengths(self, kinds):
+        self._n_soc_all = int(np.sum(kinds == 2))
+        nel = getattr(self, "_cone_numel", np.zeros(0, dtype=np.int64))[kinds == 3]
+        nn = ((np.sqrt(8.0 * nel + 1.0) - 1.0) / 2.0 + 0.5).astype(np.int64)
+        self._psd_r_len = int(np.sum(nn * nn))
+
+    def set_cone_types_ex(self, kinds, alpha=()):
+        """kinds 0..6 per cone, alpha = the exponents of the Power / GenPower cones concatenated in cone order"""
+        kinds = np.ascontiguousarray(kinds, dtype=np.int32)
+        alpha = np.ascontiguousarray(alpha, dtype=np.float64).ravel()
+        a = alpha if alpha.size else np.zeros(1)
+        rc = self.L.hipkkt_set_cone_types_ex(self.h, len(kinds), kinds, alpha.size, a)
+        if rc == -1:      # HIPKKT_ERR_ARGUMENT
+            raise ValueError(f"set_cone_types_ex: {self.L.hipkkt_last_error(self.h).decode()}")
+        self._chk(rc, "set_cone_types_ex")
+        self._set_kind_lengths(kinds)
+
+    def nonsym_len(self):
+        """doubles of the non-symmetric output vector: 15 per three-row cone, 3 dim + dim1 + 1 per GenPower cone, in cone order"""
+        ln = C.c_int64(0)
+        self._chk(self.L.hipkkt_get_nonsym_len(self.h, C.byref(ln)), "get_nonsym_len")
+        return int(ln.value)
+
+    def update_scaling_ex(self, s, z, mu, strategy, psd_R=None, want_outputs=True):
+        """-> (ok, w, lam, soc_eta, nonsym): update_scaling plus the Exponential / Power / GenPower cones; strategy 0 PrimalDual, 1 Dual"""
+        s = np.ascontiguousarray(s, dtype=np.float64)
+        z = np.ascontiguousarray(z, dtype=np.float64)
+        if len(s) != self.m or len(z) != self.m:
+            raise ValueError("update_scaling_ex: s and z must have length m")
+        if strategy not in (0, 1):
+            raise ValueError("update_scaling_ex: strategy is 0 (PrimalDual) or 1 (Dual)")
+        R = None if psd_R is None else np.ascontiguousarray(psd_R, dtype=np.float64)
+        if R is not None and R.size != self._psd_r_len:
+            raise ValueError(f"update_scaling_ex: psd_R must hold {self._psd_r_len} doubles (the n x n factors of the PSD cones), got {R.size}")
+        nlen = self.nonsym_len()
+        w = np.zeros(max(self.m, 1)) if want_outputs else None
+        lam = np.zeros(max(self.m, 1)) if want_outputs else None
+        eta = np.zeros(max(self._n_soc_all, 1)) if want_outputs else None
+        ns = np.zeros(max(nlen, 1)) if want_outputs else None
+        ok = C.c_int32(0)
+        p = lambda a: None if a is None else a.ctypes.data
+        self._chk(self.L.hipkkt_update_scaling_ex(self.h, s, z, p(R), float(mu), int(strategy), p(w), p(lam), p(eta), p(ns), C.byref(ok)),
+                  "update_scaling_ex")
+        if not want_outputs:
+            return bool(ok.value), None, None, None, None
+        return bool(ok.value), w[: self.m], lam[: self.m], eta[: self._n_soc_all], ns[:nlen]
+
+    def update_scaling_ex_dev(self, s_ptr, z_ptr, mu, strategy, R_ptr=None, w_ptr=None, lam_ptr=None, eta_ptr=None, nonsym_ptr=None):
+        if strategy not in (0, 1):
+            raise ValueError("update_scaling_ex_dev: strategy is 0 (PrimalDual) or 1 (Dual)")
+        ok = C.c_int32(0)
+        self._chk(self.L.hipkkt_update_scaling_ex_dev(self.h, s_ptr, z_ptr, R_ptr, float(mu), int(strategy), w_ptr, lam_ptr, eta_ptr,
+                                                      nonsym_ptr, C.byref(ok)), "update_scaling_ex_dev")
         return bool(ok.value)
 
     def set_soc(self, i, eta2, u, v):

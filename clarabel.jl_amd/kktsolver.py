@@ -46,11 +46,19 @@ class HipKKTSolver:
         self._psd_dim = np.array([c.n for c, _ in self._psd], dtype=np.int64)
         self._psd_cones = tuple(c for c, _ in self._psd)
         # N1: cone types for the on-device update_scaling! / get_Hs! (hipkkt_set_cone_types); optional in the cones object
-        # (the on-device scaling knows the symmetric cones only: include/hipkkt.h hipkkt_set_cone_types)
+        # (hipkkt_set_cone_types knows the symmetric cones; a cones object that also offers kkt_cone_kinds_ex() -> (kinds 0..6, alpha)
+        # and has an Exponential / Power / GenPower member is registered through hipkkt_set_cone_types_ex)
         kinds = cones.kkt_cone_kinds() if hasattr(cones, "kkt_cone_kinds") else None
         self._has_cone_kinds = kinds is not None and bool(np.all(np.asarray(kinds) >= 0))
-        if self._has_cone_kinds:
+        self.scales_nonsymmetric = False
+        kinds_ex, alpha = cones.kkt_cone_kinds_ex() if hasattr(cones, "kkt_cone_kinds_ex") else (None, None)
+        if kinds_ex is not None and bool(np.any(np.asarray(kinds_ex) >= 4)) and bool(np.all(np.asarray(kinds_ex) >= 0)):
+            self.h.set_cone_types_ex(kinds_ex, alpha)
+            self._kinds_ex = [int(k) for k in kinds_ex]
+            self._has_cone_kinds = self.scales_nonsymmetric = True
+        elif self._has_cone_kinds:
             self.h.set_cone_types(kinds)
+        self.scaling_nonsym = None
         self.scaling_w = self.scaling_lambda = self.scaling_soc_eta = None
         self.diagonal_regularizer = 0.0
         self.last_ir_steps = 0
@@ -93,10 +101,38 @@ class HipKKTSolver:
     # kktsolver_update! fed with the iterate instead of the cones' scaling -- update_scaling! + get_Hs! of
     # the Zero / Nonnegative / SecondOrder cones and skron(R R^T) of the PSD cones run on the device (hipkkt_update_scaling); nothing
     # but (s, z) and the PSD cones' R factors crosses PCIe.  The device's (w, lambda, eta) are kept for the caller.
-    def kktsolver_update_scaled(self, cones, s, z) -> bool:
+    # With Exponential / Power / GenPower members (hipkkt_update_scaling_ex) the call needs mu and the scaling strategy
+    # ("primal_dual" / "dual" or 0 / 1; None = what the cone set allows, solver.jl:222); every such cone then ADOPTS the device's values
+    # from its slot of the output vector (cone.adopt_scaling(slot, z, mu)), so that the matrix and the caller's mul_Hs! /
+    # combined_ds_shift! use the same numbers.
+    def kktsolver_update_scaled(self, cones, s, z, mu=None, strategy=None) -> bool:
         if not self._has_cone_kinds:
             raise hipkkt.HipKKTError("kktsolver_update_scaled: the cones object does not provide kkt_cone_kinds()")
         R = np.concatenate([c.R.ravel(order="F") for c in self._psd_cones]) if self._psd_cones else None
+        if self.scales_nonsymmetric:
+            if mu is None:
+                raise ValueError("kktsolver_update_scaled: a cone set with Exponential / Power / GenPower cones needs mu")
+            if strategy is None:
+                strategy = 0 if cones.allows_primal_dual_scaling() else 1
+            strategy = {"primal_dual": 0, "dual": 1}.get(strategy, strategy)
+            ok, self.scaling_w, self.scaling_lambda, self.scaling_soc_eta, self.scaling_nonsym = \
+                self.h.update_scaling_ex(s, z, mu, strategy, R)
+            if not ok:
+                return False
+            # (a second-order cone that offers adopt_symmetric_scaling takes the device's w, lambda, eta as well: on the late iterates
+            # of these problems a host copy that differs from the matrix in the last bits makes the primal residual grow again)
+            off, soc = 0, 0
+            for c, r, kind in zip(cones.cones, cones.rng_cones, self._kinds_ex):
+                if hasattr(c, "adopt_scaling"):
+                    k = c.scaling_slot_len
+                    c.adopt_scaling(self.scaling_nonsym[off:off + k], np.asarray(z)[r], float(mu))
+                    off += k
+                elif kind == 2:
+                    if hasattr(c, "adopt_symmetric_scaling"):
+                        c.adopt_symmetric_scaling(self.scaling_w[r], self.scaling_lambda[r], self.scaling_soc_eta[soc])
+                    soc += 1
+            assert off == len(self.scaling_nonsym)
+            return self._refactor()
         ok, self.scaling_w, self.scaling_lambda, self.scaling_soc_eta = self.h.update_scaling(s, z, R)
         if not ok:
             return False

@@ -70,8 +70,9 @@ void hipkkt_default_opts(hipkkt_opts *opts);
 int32_t hipkkt_is_available(void);
 /* Version of THIS interface.  A binding compares it with the HIPKKT_ABI_VERSION it was written against when it loads the library
  * and refuses a mismatch (the Julia glue and the ctypes mirror do): signatures may change between versions, never within one.
- * 4: hipkkt_get_profile / hipkkt_get_counters take the capacity of the caller's buffer (they wrote a fixed, growing number of values). */
-#define HIPKKT_ABI_VERSION 4
+ * 4: hipkkt_get_profile / hipkkt_get_counters take the capacity of the caller's buffer (they wrote a fixed, growing number of values).
+ * 5: hipkkt_set_cone_types_ex / hipkkt_get_nonsym_len / hipkkt_update_scaling_ex[_dev] (the bindings bind them when they load). */
+#define HIPKKT_ABI_VERSION 5
 int32_t hipkkt_abi_version(void);
 /* releases the process-wide cache of device memory blocks the library keeps between handles (not in the reference: an embedding
  * host under memory pressure may call it at any time; live handles are unaffected) */
@@ -182,6 +183,46 @@ int32_t hipkkt_update_scaling(hipkkt_handle h, const double *s, const double *z,
                               double *lambda_out, double *soc_eta_out, int32_t *scaling_ok);
 int32_t hipkkt_update_scaling_dev(hipkkt_handle h, const double *s_dev, const double *z_dev, const double *psd_R_dev,
                                   double *w_out_dev, double *lambda_out_dev, double *soc_eta_out_dev, int32_t *scaling_ok);
+
+/* N1 for the NON-SYMMETRIC cones: update_scaling! + get_Hs! + _csc_update_sparsecone of Exponential, Power and Generalized Power cones
+ * on the device, next to the symmetric ones.  The two calls above keep their behaviour: hipkkt_set_cone_types treats any kind outside
+ * 0..3 as the caller's, hipkkt_update_scaling[_dev] never touches such a cone.
+ *   three-row cones, one lane per cone: update_dual_grad_H(z) -> grad, H_dual (coneops_expcone.jl:370-400, coneops_powcone.jl:408-442);
+ *     Dual: Hs = mu H_dual (coneops_nonsymmetric_common.jl:71-78); PrimalDual: gradient_primal(s) by Wright omega
+ *     (coneops_expcone.jl:284-297, 412-467) resp. the one-sided Newton-Raphson iteration of at most 100 steps (coneops_powcone.jl:288-317,
+ *     449-478, coneops_nonsymmetric_common.jl:170-192), then the BFGS form or, on the central path, Hs = (<s, z> / 3) H_dual
+ *     (coneops_nonsymmetric_common.jl:82-164).  pack_triu(Hs) goes negated through map.Hsblocks like hipkkt_set_hs.
+ *     A block whose 3 x 3 Cholesky (mathutils.jl:427-451) breaks down in rounding -- late iterates, condition numbers beyond 1e16 --
+ *     gets the smallest shift 2^k eps max(diag), k = 1 .. 8, on its diagonal with which it goes through (K and the output vector hold
+ *     the shifted block); every other block is exactly what the reference's expressions give.
+ *   GenPower cones, one wavefront per cone: update_dual_grad_H(z) -> grad, d1, d2, p, q, r (coneops_genpowcone.jl:343-396); the block
+ *     -mu d1, -mu d2 (:91-108), the q, r, p columns times -sqrt(mu) and the diagonals (-1, -1, +1) of the expansion
+ *     (directldl_datamaps.jl:146-167) through index tables made resident by hipkkt_set_cone_types_ex: no upload and no host
+ *     synchronisation per cone.  These cones always take Dual with the caller's mu (coneops_genpowcone.jl:21, 64-80).
+ *   Failure: a cone whose z is not strictly inside the dual cone, whose s is not strictly inside the primal cone (PrimalDual), whose
+ *     Wright-omega argument is negative or whose result is not finite gives *scaling_ok = 0 (the reference asserts / throws); its slot of
+ *     the output vector is filled with NaN, its entries of K are not written; what hipkkt_update_scaling says about the state after
+ *     *scaling_ok = 0 holds here too.  The return value stays HIPKKT_OK. */
+#define HIPKKT_CONE_EXP 4      /* ExponentialCone,  cone_types.jl */
+#define HIPKKT_CONE_POW 5      /* PowerCone(alpha): 1 entry of `alpha` */
+#define HIPKKT_CONE_GENPOW 6   /* GenPowerCone(alpha, dim2): dim1 entries of `alpha` */
+/* kinds 0..3 as hipkkt_set_cone_types; alpha = the exponents of the Power / GenPow cones concatenated in cone order.  Checked
+ * against (numel, hs_dense, sparse_kind, dim1) of the handle: 4 / 5 = numel 3, dense block, no expansion; 6 = sparse_kind
+ * HIPKKT_SPARSE_GENPOW, diagonal block, dim1 = its share of alpha, every alpha in (0, 1). */
+int32_t hipkkt_set_cone_types_ex(hipkkt_handle h, int64_t ncones, const int32_t *kinds, int64_t nalpha, const double *alpha);
+/* doubles in the non-symmetric output vector: 15 per three-row cone (Hs 6, H_dual 6, grad 3; the 3 x 3 matrices in pack_triu order),
+ * 3 dim + dim1 + 1 per GenPow cone (grad dim, d1 dim1, d2 1, p dim, q dim1, r dim2), cones in cone order; 0 without such cones */
+int32_t hipkkt_get_nonsym_len(hipkkt_handle h, int64_t *len);
+/* hipkkt_update_scaling + the cones above.  strategy: 0 PrimalDual, 1 Dual (types.jl:73-76); GenPow cones always take Dual with
+ * the caller's mu.  nonsym_out may be NULL.  On a handle without kinds 4..6 the resident K is bit-identical to hipkkt_update_scaling's.
+ * hipkkt_update_scaling[_dev] on a handle whose last registration named a kind 4..6 returns HIPKKT_ERR_ARGUMENT (it has no mu). */
+int32_t hipkkt_update_scaling_ex(hipkkt_handle h, const double *s, const double *z, const double *psd_R, double mu,
+                                 int32_t strategy, double *w_out, double *lambda_out, double *soc_eta_out, double *nonsym_out,
+                                 int32_t *scaling_ok);
+/* the same with every pointer except scaling_ok in device memory */
+int32_t hipkkt_update_scaling_ex_dev(hipkkt_handle h, const double *s_dev, const double *z_dev, const double *psd_R_dev, double mu,
+                                     int32_t strategy, double *w_out_dev, double *lambda_out_dev, double *soc_eta_out_dev,
+                                     double *nonsym_out_dev, int32_t *scaling_ok);
 /* ref: _csc_update_sparsecone(::SecondOrderCone,...), directldl_datamaps.jl:61-79 */
 int32_t hipkkt_set_soc(hipkkt_handle h, int64_t sparse_idx, double eta2, const double *u, const double *v,
                        int64_t dim);
@@ -321,7 +362,8 @@ int32_t hipkkt_get_counters(hipkkt_handle h, int64_t *out, int64_t cap);
  * width; 21 five values per supernode of the persistent segment sweeps: level, width, rows, longest and mean gather list of its row
  * slots -- tools/dense_stage_stats.py; 22 four values per front, written on the host: its first panel (supernode id), panels, rows,
  * and the panels per super-block of its solve sweeps, 0 = one hop per panel through that panel's inverse (k_front_fwd / k_front_bwd),
- * > 0 = products with the super-blocks' inverses (k_front_fwd_sb / k_front_bwd_sb)); *len receives the length, nothing is copied
+ * > 0 = products with the super-blocks' inverses (k_front_fwd_sb / k_front_bwd_sb), 23 the Newton steps of the last hipkkt_update_scaling_ex per
+ * Power cone in cone order); *len receives the length, nothing is copied
  * when cap is too small */
 int32_t hipkkt_debug_dump(hipkkt_handle h, int32_t what, double *out, int64_t cap, int64_t *len);
 /* developer diagnostic, host logic only (no device needed): how many of the `nd` dense tiles of a front batch's far stage -- the

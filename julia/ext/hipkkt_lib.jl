@@ -30,7 +30,7 @@ hip_last_error(handle::Ptr{Cvoid} = C_NULL) =
     unsafe_string(ccall((:hipkkt_last_error, libhipkkt), Cstring, (Ptr{Cvoid},), handle))
 
 # include/hipkkt.h HIPKKT_ABI_VERSION this file was written against: signatures may change between versions, never within one
-const HIPKKT_ABI_VERSION = Int32(4)
+const HIPKKT_ABI_VERSION = Int32(5)
 function hip_check_abi()
     v = ccall((:hipkkt_abi_version, libhipkkt), Int32, ())
     v == HIPKKT_ABI_VERSION || error("libclarabel_hipkkt implements ABI version $v, this extension was written against $HIPKKT_ABI_VERSION")

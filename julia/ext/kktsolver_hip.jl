@@ -6,11 +6,13 @@
 # capabilities with defaults in kktsolver_defaults.jl -- all extended from THIS file; the core never refers to the extension.
 #
 # Beyond the six contract methods, the rows SURVEY.md section 8(f) widens:
-#   N1  kktsolver_update_scaled!      update_scaling! + get_Hs! of Zero / Nonnegative / SecondOrder / PSD cones formed from (s, z)
+#   N1  kktsolver_update_scaled!      update_scaling! + get_Hs! of Zero / Nonnegative / SecondOrder / PSD cones formed from (s, z);
+#                                     with μ and the scaling strategy also of Exponential / Power / GenPower cones
 #   N2  kktsolver_solve_multi!        two right-hand sides on one factorisation, concurrently
 #       kktsolver_kkt_solve_reduced!  kkt_solve! between the cone algebra and mul_Hs!: dtau dots, quad_form, dx, dz on the device
 #   N4  kktsolver_residuals!          residuals_update! from the resident P, A, q, b
 import Clarabel: AbstractKKTSolver, CompositeCone, SecondOrderCone, GenPowerCone, ZeroCone, NonnegativeCone, PSDTriangleCone
+import Clarabel: ExponentialCone, PowerCone, ScalingStrategy
 import Clarabel: get_Hs!, Hs_is_diagonal, is_sparse_expandable, numel
 import Clarabel: kktsolver_update!, kktsolver_setrhs!, kktsolver_solve!
 import Clarabel: kktsolver_update_P!, kktsolver_update_A!, kktsolver_linear_solver_info
@@ -23,6 +25,7 @@ mutable struct HipKKTSolver{T} <: AbstractKKTSolver{T}
     soc_u::Vector{T}; soc_v::Vector{T}; soc_eta2::Vector{T}
     w::Vector{T}; λ::Vector{T}; η::Vector{T}      # N1: the device's scaling, in cone order (what mul_Hs! etc. read)
     psd_cones::Vector{Any}
+    nonsym::Vector{T}               # N1: output vector of the Exponential / Power / GenPower cones (hipkkt_get_nonsym_len), empty without
     diagonal_regularizer::T
     has_qb::Bool
 
@@ -49,11 +52,27 @@ mutable struct HipKKTSolver{T} <: AbstractKKTSolver{T}
         nsoc_all = count(c -> c isa SecondOrderCone, cones)
         s = new(h[], m, n, settings, zeros(T, dims[6]), zeros(T, nsocrows), zeros(T, nsocrows),
                 zeros(T, count(==(1), ckind)), zeros(T, m), zeros(T, m), zeros(T, nsoc_all),
-                Any[c for c in cones if c isa PSDTriangleCone], zero(T), false)
+                Any[c for c in cones if c isa PSDTriangleCone], T[], zero(T), false)
         finalizer(hip_destroy!, s)
-        # N1: cone kinds for hipkkt_update_scaling (0 Zero, 1 Nonnegative, 2 SecondOrder, 3 PSDTriangle, -1 = stays with set_hs / set_genpow)
-        kinds = Int32[c isa ZeroCone ? 0 : c isa NonnegativeCone ? 1 : c isa SecondOrderCone ? 2 : c isa PSDTriangleCone ? 3 : -1 for c in cones]
-        ccall((:hipkkt_set_cone_types, libhipkkt), Int32, (Ptr{Cvoid}, Int64, Ptr{Int32}), s.handle, length(kinds), kinds)
+        # N1: cone kinds for hipkkt_update_scaling (0 Zero, 1 Nonnegative, 2 SecondOrder, 3 PSDTriangle) and, through
+        # hipkkt_set_cone_types_ex, 4 Exponential, 5 Power, 6 GenPower with their exponents concatenated in cone order
+        kinds = Int32[c isa ZeroCone ? 0 : c isa NonnegativeCone ? 1 : c isa SecondOrderCone ? 2 : c isa PSDTriangleCone ? 3 :
+                      c isa ExponentialCone ? 4 : c isa PowerCone ? 5 : c isa GenPowerCone ? 6 : -1 for c in cones]
+        if any(k -> k >= 4, kinds)
+            alpha = Float64[]
+            for c in cones
+                c isa PowerCone && push!(alpha, c.α)
+                c isa GenPowerCone && append!(alpha, c.α)
+            end
+            rc = ccall((:hipkkt_set_cone_types_ex, libhipkkt), Int32, (Ptr{Cvoid}, Int64, Ptr{Int32}, Int64, Ptr{Float64}),
+                       s.handle, length(kinds), kinds, length(alpha), alpha)
+            rc == 0 || error("hipkkt_set_cone_types_ex failed ($rc): " * hip_last_error(s.handle))
+            len = Ref{Int64}(0)
+            ccall((:hipkkt_get_nonsym_len, libhipkkt), Int32, (Ptr{Cvoid}, Ref{Int64}), s.handle, len)
+            s.nonsym = zeros(T, len[])
+        else
+            ccall((:hipkkt_set_cone_types, libhipkkt), Int32, (Ptr{Cvoid}, Int64, Ptr{Int32}), s.handle, length(kinds), kinds)
+        end
         return s
     end
 end
@@ -107,12 +126,54 @@ end
 # Cholesky / SVD stay in Julia, only their n x n factor R (column-major = Julia's layout, concatenated) goes down.
 # w, λ (length m, cone order) and η (one per second-order cone) come back for mul_Hs! / affine_ds! / combined_ds_shift!.
 function kktsolver_update_scaled!(ks::HipKKTSolver{T}, cones, s::Vector{T}, z::Vector{T}) where {T}
+    isempty(ks.nonsym) || error("this cone set has Exponential / Power / GenPower cones: pass μ and the scaling strategy")
     R = isempty(ks.psd_cones) ? C_NULL : reduce(vcat, (vec(K.data.R) for K in ks.psd_cones))
     ok = Ref{Int32}(0)
     rc = ccall((:hipkkt_update_scaling, libhipkkt), Int32,
                (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Int32}),
                ks.handle, s, z, R, ks.w, ks.λ, ks.η, ok)
     (rc == 0 && ok[] == 1) || return false           # ok == 0 <=> update_scaling! would return false (SOC s or z not interior)
+    return _hip_refactor!(ks)
+end
+
+# N1 with the non-symmetric cones: the same from (s, z, μ, strategy) through hipkkt_update_scaling_ex.  The plugin forms
+# update_dual_grad_H, gradient_primal and the Hs of Exponential / Power cones (coneops_expcone.jl:63-83, coneops_powcone.jl:65-85,
+# coneops_nonsymmetric_common.jl:50-192) and the (grad, d1, d2, p, q, r) of GenPower cones (coneops_genpowcone.jl:64-108, 343-396)
+# and writes them into K; every such cone then takes the device's values from its slot of the output vector, so that mul_Hs! /
+# combined_ds_shift! use the numbers the matrix holds.  The caller skips update_scaling! of these cones.
+function _hip_unpack_triu3!(M, v, o)      # pack_triu order, mathutils.jl:402-412
+    M[1,1] = v[o+1]; M[1,2] = v[o+2]; M[2,2] = v[o+3]; M[1,3] = v[o+4]; M[2,3] = v[o+5]; M[3,3] = v[o+6]
+    M[2,1] = M[1,2]; M[3,1] = M[1,3]; M[3,2] = M[2,3]
+    return nothing
+end
+function kktsolver_update_scaled!(ks::HipKKTSolver{T}, cones, s::Vector{T}, z::Vector{T}, μ::T, strategy::ScalingStrategy) where {T}
+    isempty(ks.nonsym) && return kktsolver_update_scaled!(ks, cones, s, z)
+    R = isempty(ks.psd_cones) ? C_NULL : reduce(vcat, (vec(K.data.R) for K in ks.psd_cones))
+    ok = Ref{Int32}(0)
+    rc = ccall((:hipkkt_update_scaling_ex, libhipkkt), Int32,
+               (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Float64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                Ptr{Float64}, Ref{Int32}),
+               ks.handle, s, z, R, μ, Int32(strategy), ks.w, ks.λ, ks.η, ks.nonsym, ok)
+    (rc == 0 && ok[] == 1) || return false           # ok == 0 <=> the reference would assert / throw / return false
+    v = ks.nonsym; o = 0
+    for (K, rng) in zip(cones, cones.rng_cones)
+        if K isa ExponentialCone || K isa PowerCone
+            _hip_unpack_triu3!(K.Hs, v, o); _hip_unpack_triu3!(K.H_dual, v, o + 6)
+            K.grad .= view(v, o+13:o+15)
+            K.z .= view(z, rng)
+            o += 15
+        elseif K isa GenPowerCone
+            dat = K.data; d1 = length(K.α); d2 = K.dim2; d = d1 + d2
+            dat.grad .= view(v, o+1:o+d);            o += d
+            dat.d1   .= view(v, o+1:o+d1);           o += d1
+            dat.d2    = v[o+1];                      o += 1
+            dat.p    .= view(v, o+1:o+d);            o += d
+            dat.q    .= view(v, o+1:o+d1);           o += d1
+            dat.r    .= view(v, o+1:o+d2);           o += d2
+            dat.μ = μ
+            dat.z .= view(z, rng)
+        end
+    end
     return _hip_refactor!(ks)
 end
 

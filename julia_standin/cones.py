@@ -258,6 +258,24 @@ class SecondOrderCone:
             self.v[1:] = v1 * w[1:]
         return True
 
+    def adopt_symmetric_scaling(self, w, lam, eta):
+        """take over the plugin's on-device scaling of this cone (hipkkt_update_scaling[_ex]: w, lambda, eta), so that mul_Hs! uses the
+        numbers the matrix holds; the sparse terms follow from w as in update_scaling (:125-153)"""
+        self.w[:] = w
+        self.lam[:] = lam
+        self.eta = float(eta)
+        if self.is_sparse_expandable:
+            w = self.w
+            w1sq = float(np.dot(w[1:], w[1:]))
+            wsq = w[0] * w[0] + w1sq
+            wsqinv = 1.0 / wsq
+            self.d = wsqinv / 2.0
+            u0 = math.sqrt(wsq - self.d)
+            self.u[0] = u0
+            self.u[1:] = (2.0 * w[0] / u0) * w[1:]
+            self.v[0] = 0.0
+            self.v[1:] = math.sqrt(2.0 * (2.0 + wsqinv) / (2.0 * wsq - wsqinv)) * w[1:]
+
     def get_Hs(self, block):  # :159-192
         eta2 = self.eta * self.eta
         if self.is_sparse_expandable:
@@ -649,10 +667,14 @@ class CompositeCone:
         for c in self.cones:
             c.set_identity_scaling()
 
-    def update_scaling(self, s, z, mu, strategy="primal_dual"):  # :103-120
+    def update_scaling(self, s, z, mu, strategy="primal_dual", host_nonsymmetric=True):  # :103-120
+        """host_nonsymmetric=False: the non-symmetric cones are left alone -- the plugin scales them on the device and they adopt its
+        values (kkt_cone_kinds_ex / adopt_scaling)"""
         for c, r in zip(self.cones, self.rng_cones):
             if getattr(c, "is_symmetric", True):
                 ok = c.update_scaling(s[r], z[r], mu)
+            elif not host_nonsymmetric:
+                continue
             else:
                 ok = c.update_scaling(s[r], z[r], mu, strategy)
             if not ok:
@@ -706,3 +728,10 @@ class CompositeCone:
     def kkt_cone_kinds(self):
         """cone type codes for the plugin's on-device scaling"""
         return np.array([c.kind_code for c in self.cones], dtype=np.int32)
+
+    def kkt_cone_kinds_ex(self):
+        """(kinds, alpha) for hipkkt_set_cone_types_ex: kinds 0..3 as kkt_cone_kinds(), 4 Exponential, 5 Power, 6 GenPower; alpha = the
+        exponents of the Power / GenPower cones concatenated in cone order"""
+        kinds = np.array([getattr(c, "kind_code_ex", c.kind_code) for c in self.cones], dtype=np.int32)
+        alpha = [np.atleast_1d(np.asarray(c.alpha, dtype=np.float64)) for c in self.cones if getattr(c, "kind_code_ex", -1) in (5, 6)]
+        return kinds, (np.concatenate(alpha) if alpha else np.zeros(0))

@@ -128,6 +128,7 @@ class _Cone3:
     is_symmetric = False
     allows_primal_dual_scaling = True
     kind_code = -1          # no on-device scaling for these (include/hipkkt.h hipkkt_set_cone_types knows 0..3)
+    scaling_slot_len = 15   # doubles of this cone in the output vector of hipkkt_update_scaling_ex: Hs 6, H_dual 6, grad 3
     dim = 3
     numel = 3
     degree = 3
@@ -159,6 +160,15 @@ class _Cone3:
             self._use_primal_dual_scaling(s, z)
         self.z[:] = z
         return True
+
+    def adopt_scaling(self, slot, z, mu=None):
+        """take over what the plugin's on-device update_scaling! computed for this cone (include/hipkkt.h hipkkt_update_scaling_ex):
+        slot = [pack_triu(Hs) | pack_triu(H_dual) | grad].  The matrix in K and mul_Hs! / combined_ds_shift! then use the SAME numbers."""
+        for M, t in ((self.Hs, slot[0:6]), (self.H_dual, slot[6:12])):
+            M[0, 0], M[0, 1], M[1, 1], M[0, 2], M[1, 2], M[2, 2] = t
+            M[1, 0], M[2, 0], M[2, 1] = M[0, 1], M[0, 2], M[1, 2]
+        self.grad[:] = slot[12:15]
+        self.z[:] = z
 
     def _use_dual_scaling(self, mu):  # :71-79
         self.Hs[:] = mu * self.H_dual
@@ -233,6 +243,8 @@ class _Cone3:
 class ExponentialCone(_Cone3):
     """coneops_expcone.jl.  Primal: s3 >= s2 exp(s1 / s2), s2, s3 > 0; dual: z3 >= -z1 exp(z2 / z1 - 1), z3 > 0, z1 < 0;
     dual barrier f*(z) = -log(z2 - z1 - z1 log(z3 / -z1)) - log(-z1) - log(z3)."""
+
+    kind_code_ex = 4        # include/hipkkt.h HIPKKT_CONE_EXP
 
     def unit_initialization(self, z, s):  # :36-52
         s[0] = -1.051383945322714
@@ -311,6 +323,8 @@ class ExponentialCone(_Cone3):
 class PowerCone(_Cone3):
     """coneops_powcone.jl.  Primal: s1^a s2^(1-a) >= |s3|, s1, s2 >= 0; dual: (z1/a)^a (z2/(1-a))^(1-a) >= |z3|;
     dual barrier f*(z) = -log((z1/a)^2a (z2/(1-a))^(2-2a) - z3^2) - (1-a) log z1 - a log z2."""
+
+    kind_code_ex = 5        # include/hipkkt.h HIPKKT_CONE_POW
 
     def __init__(self, alpha):
         super().__init__()
@@ -438,6 +452,7 @@ class GenPowerCone:
     is_symmetric = False
     allows_primal_dual_scaling = False   # :21
     kind_code = -1
+    kind_code_ex = 6                     # include/hipkkt.h HIPKKT_CONE_GENPOW
     sparse_kind = 2                      # include/hipkkt.h HIPKKT_SPARSE_GENPOW
 
     def __init__(self, alpha, dim2):
@@ -481,6 +496,23 @@ class GenPowerCone:
         self.mu = mu
         self.z[:] = z
         return True
+
+    @property
+    def scaling_slot_len(self):          # grad dim, d1 dim1, d2 1, p dim, q dim1, r dim2 (hipkkt_get_nonsym_len)
+        return 3 * self.dim + self.dim1 + 1
+
+    def adopt_scaling(self, slot, z, mu):
+        """take over the on-device update_scaling! of this cone: slot = [grad | d1 | d2 | p | q | r] (hipkkt_update_scaling_ex)"""
+        d, d1 = self.dim, self.dim1
+        o = 0
+        for name, k in (("grad", d), ("d1", d1), ("d2", 1), ("p", d), ("q", d1), ("r", self.dim2)):
+            if name == "d2":
+                self.d2 = float(slot[o])
+            else:
+                getattr(self, name)[:] = slot[o:o + k]
+            o += k
+        self.mu = mu
+        self.z[:] = z
 
     def get_Hs(self, block):  # :91-108: the diagonal D only; the three extra entries belong to the expansion
         block[: self.dim1] = self.mu * self.d1

@@ -262,10 +262,13 @@ class KKTSystem:
         self._rx2, self._rz2 = np.zeros((2, n)), np.zeros((2, m))
         self._lx2, self._lz2 = np.zeros((2, n)), np.zeros((2, m))
 
-    def kkt_update(self, data, cones, sz=None):  # :62-78
+    def kkt_update(self, data, cones, sz=None, mu=None, strategy=None):  # :62-78
         if sz is not None and self._device_scaling:
             # the plugin forms the Hs blocks / sparse-cone terms of K from the iterate (s, z) itself
-            ok = self.kktsolver.kktsolver_update_scaled(cones, sz[0], sz[1])
+            if cones.is_symmetric():
+                ok = self.kktsolver.kktsolver_update_scaled(cones, sz[0], sz[1])
+            else:      # Exponential / Power / GenPower members need mu and the strategy and adopt the device's values
+                ok = self.kktsolver.kktsolver_update_scaled(cones, sz[0], sz[1], mu=mu, strategy=strategy)
         else:
             ok = self.kktsolver.kktsolver_update(cones)
         if not ok:
@@ -640,14 +643,18 @@ class Solver:
                         continue
                 break
             t0 = time.perf_counter()
-            ok_scaling = cones.update_scaling(v.s, v.z, mu, scaling) if nonsym else cones.update_scaling(v.s, v.z, mu)
+            if nonsym:     # (device-scaling mode: the plugin scales the non-symmetric cones in kkt_update below, they adopt its values)
+                on_device = self.kktsystem._device_scaling and getattr(self.kktsystem.kktsolver, "scales_nonsymmetric", False)
+                ok_scaling = cones.update_scaling(v.s, v.z, mu, scaling, host_nonsymmetric=not on_device)
+            else:
+                ok_scaling = cones.update_scaling(v.s, v.z, mu)
             tm["scale cones"] += time.perf_counter() - t0
             if not ok_scaling:
                 info.status = NUMERICAL_ERROR
                 break
             it += 1
             t0 = time.perf_counter()
-            ok = self.kktsystem.kkt_update(data, cones, sz=(v.s, v.z))
+            ok = self.kktsystem.kkt_update(data, cones, sz=(v.s, v.z), mu=mu, strategy=scaling)
             tm["kkt update"] += time.perf_counter() - t0
             # variables_affine_step_rhs!, variables.jl:107-121
             rhs.x[:] = r.rx
