@@ -8,7 +8,7 @@ cd "$(dirname "$0")"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-result $HIPKKT_EXTRA_FLAGS"   # (development: e.g. -DHIPKKT_SWEEP_TRACE)
 mkdir -p ../../build/obj ../../build/obj_testing
-HOSTSRC="hipkkt_abi.cpp hipkkt_setup.cpp hipkkt_factor.cpp hipkkt_solve.cpp symbolic.cpp ordering.cpp assemble.cpp"
+HOSTSRC="hipkkt_abi.cpp hipkkt_setup.cpp hipkkt_factor.cpp hipkkt_solve.cpp hipkkt_step.cpp symbolic.cpp ordering.cpp assemble.cpp"
 # kernels are identical in both builds (nothing in a .hip file depends on HIPKKT_TESTING): compiled once
 KSRC="kernels.hip assemble_dev.hip front_sweep.hip front_block2.hip probe.hip"
 OBJ=../../build/obj
@@ -27,8 +27,10 @@ done
 $HIPCC $FLAGS -c front_block.hip -o $OBJT/front_block.o & pids+=($!)
 # scaling.hip mirrors the reference's cone formulas operation by operation: no FMA contraction
 $HIPCC $FLAGS -ffp-contract=off -c scaling.hip -o $OBJ/scaling.o & pids+=($!)
+# step.hip does the same for the cone algebra of an interior-point step
+$HIPCC $FLAGS -ffp-contract=off -c step.hip -o $OBJ/step.o & pids+=($!)
 for p in "${pids[@]}"; do wait $p; done
-COMMON="$OBJ/hipkkt_solve.o $OBJ/symbolic.o $OBJ/ordering.o $OBJ/assemble.o $OBJ/assemble_dev.o $OBJ/scaling.o $OBJ/front_block2.o $OBJ/front_sweep.o $OBJ/probe.o $OBJ/kernels.o"
+COMMON="$OBJ/hipkkt_solve.o $OBJ/hipkkt_step.o $OBJ/symbolic.o $OBJ/ordering.o $OBJ/assemble.o $OBJ/assemble_dev.o $OBJ/scaling.o $OBJ/step.o $OBJ/front_block2.o $OBJ/front_sweep.o $OBJ/probe.o $OBJ/kernels.o"
 $HIPCC --offload-arch=gfx950 -shared -fPIC -o ../libclarabel_hipkkt.so $OBJ/hipkkt_abi.o $OBJ/hipkkt_setup.o $OBJ/hipkkt_factor.o $COMMON
 $HIPCC --offload-arch=gfx950 -shared -fPIC -o ../libclarabel_hipkkt_testing.so $OBJT/hipkkt_abi.o $OBJT/hipkkt_setup.o $OBJT/hipkkt_factor.o $OBJT/front_block.o $COMMON
 echo "built $(readlink -f ../libclarabel_hipkkt.so) and $(readlink -f ../libclarabel_hipkkt_testing.so)"

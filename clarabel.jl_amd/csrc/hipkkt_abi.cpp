@@ -396,6 +396,9 @@ static int32_t set_cone_types_impl(hipkkt_handle h, int64_t ncones, const int32_
     const int64_t m = S->img.m;
     S->sc_ready = false;          // until this call has validated and uploaded its tables
     S->ns_active = false;
+    S->sc_scaled = false;
+    S->sc_step_kinds = true;
+    for (int64_t c = 0; c < ncones; c++) S->sc_step_kinds = S->sc_step_kinds && kinds[c] >= 0 && kinds[c] <= 2;
     // the non-symmetric cones: three-row cones in two lists (joined [Exponential | Power] below), GenPower descriptors of 8 values
     struct Row3 { int64_t row0, hs0, out0; double alpha; };
     std::vector<Row3> exp3, pow3;
@@ -560,6 +563,9 @@ static int32_t update_scaling_impl(hipkkt_handle h, const double *s, const doubl
             HK_CHECK(hipMemcpyAsync(S->d_sc_R, psd_R, (size_t)S->sc_psd_total * sizeof(double), hipMemcpyHostToDevice, S->stream));
             dR = S->d_sc_R;
         }
+    } else if (m && S->sc_step_kinds) {      // the step entry points read the resident copy of (s, z)
+        HK_CHECK(hipMemcpyAsync(S->d_sc_sz, s, m * sizeof(double), hipMemcpyDeviceToDevice, S->stream));
+        HK_CHECK(hipMemcpyAsync(S->d_sc_sz + m, z, m * sizeof(double), hipMemcpyDeviceToDevice, S->stream));
     }
     double *dw = S->d_sc_wl, *dl = S->d_sc_wl + m;
     launch_zero_words(S->stream, S->d_sc_fail, 1);
@@ -593,6 +599,7 @@ static int32_t update_scaling_impl(hipkkt_handle h, const double *s, const doubl
     int fail = 0;
     copy_sync(S->stream, &fail, S->d_sc_fail, sizeof(int), hipMemcpyDeviceToHost);
     if (scaling_ok) *scaling_ok = fail ? 0 : 1;
+    S->sc_scaled = fail == 0;
     return HIPKKT_OK;
     HK_LEAVE
 }

@@ -3,7 +3,8 @@
 //   hipkkt_setup.cpp   runtime objects, device residency of a plan, handle creation (finish_create)
 //   hipkkt_factor.cpp  the factorisation's launch sequence, its graph, hipkkt_refactor and the robust-order twin
 //   hipkkt_solve.cpp   LDL solves, device-side iterative refinement, the solve entry points
-// Host orchestration only; all numeric work is in kernels.hip / front_block.hip / assemble_dev.hip / scaling.hip.
+//   hipkkt_step.cpp    the cone algebra of an interior-point step around the reduced solve (hipkkt_cone_* / hipkkt_step_*)
+// Host orchestration only; all numeric work is in kernels.hip / front_block.hip / assemble_dev.hip / scaling.hip / step.hip.
 #pragma once
 #include "../../include/hipkkt.h"
 
@@ -16,6 +17,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <functional>
 #include <future>
 #include <memory>
 #include <mutex>
@@ -240,6 +242,14 @@ struct hipkkt_solver {
     int64_t *d_sc_rowhs = nullptr, *d_sc_socdesc = nullptr;
     double *d_sc_sz = nullptr, *d_sc_wl = nullptr, *d_sc_eta = nullptr, *d_sc_R = nullptr, *d_sc_W = nullptr;
     int *d_sc_fail = nullptr;
+    // the step entry points (hipkkt_step.cpp, step.hip) work on the resident (s, z) | (w, lambda) | eta of the last scaling
+    bool sc_step_kinds = false;                            // the registration names Zero / Nonnegative / SecondOrder cones only
+    bool sc_scaled = false;                                // the last hipkkt_update_scaling[_dev] since that registration succeeded
+    double *d_st_step = nullptr;                           // [dx | dz | ds] of the last fused step call
+    double *d_st_in = nullptr, *d_st_work = nullptr;       // [rhs.x | workz | variables.x]; four work vectors of length m
+    double *d_st_part = nullptr, *d_st_out = nullptr;      // partial results of the step length / the norms; 2 + 8 results
+    double *d_st_eq = nullptr;                             // [d | e | dinv | einv] (hipkkt_set_equilibration)
+    bool st_have_step = false;
     // N1, the non-symmetric cones (hipkkt_set_cone_types_ex + hipkkt_update_scaling_ex): tables built once per registration
     bool ns_active = false;                                // the last registration named an Exponential / Power / GenPower cone
     int ns_nexp = 0, ns_npow = 0, ns_ngenpow = 0;
@@ -377,6 +387,10 @@ void enqueue_ldl_solve(hipkkt_solver *S, SolveCtx &C, const double *in, double *
 int32_t solve_many(hipkkt_solver *S, int nrhs, int ir_enable, double reltol, double abstol, int64_t max_iter, double stop_ratio,
                    int64_t *ir_steps, double *const *out_dev, int nm);
 hipkkt_solver *solve_target(hipkkt_solver *S);
+int32_t kkt_solve_reduced_impl(hipkkt_solver *S, const double *rhs_x, const double *workz, const double *var_x, const double *in_dev,
+                               const double *scal_in, int32_t const_pending, double *lhs_x, double *lhs_z, double *lhs_dev,
+                               double *scal_out, int32_t ir_enable, double reltol, double abstol, int64_t max_iter, double stop_ratio,
+                               int64_t *ir_steps, const std::function<void(hipStream_t, const double *)> *after_reduce);
 void account_fallback_solve(hipkkt_solver *S, hipkkt_solver *T);
 
 template <class F>

@@ -338,10 +338,14 @@ int32_t hipkkt_solve_multi_dev(hipkkt_handle h, int64_t nrhs, const double *rhs_
 // Both solves are started before anything is waited for; the reduction (dots, dtau, axpys) and the copies of the step are
 // enqueued behind them speculatively; the host synchronises once.  Only if a solve needed more refinement steps than the one that
 // is part of its graph (rare) the reduction is repeated after those steps.
-static int32_t kkt_solve_reduced_impl(hipkkt_solver *S, const double *rhs_x, const double *workz, const double *var_x,
-                                      const double *in_dev, const double *scal_in, int32_t const_pending, double *lhs_x,
-                                      double *lhs_z, double *lhs_dev, double *scal_out, int32_t ir_enable, double reltol,
-                                      double abstol, int64_t max_iter, double stop_ratio, int64_t *ir_steps) {
+// after_reduce (hipkkt_step.cpp): work enqueued behind every reduction on the same stream, from the step [dx | dz] it left in d_lhs.
+}  // extern "C"
+namespace hipkkt_host {
+int32_t kkt_solve_reduced_impl(hipkkt_solver *S, const double *rhs_x, const double *workz, const double *var_x,
+                               const double *in_dev, const double *scal_in, int32_t const_pending, double *lhs_x,
+                               double *lhs_z, double *lhs_dev, double *scal_out, int32_t ir_enable, double reltol,
+                               double abstol, int64_t max_iter, double stop_ratio, int64_t *ir_steps,
+                               const std::function<void(hipStream_t, const double *)> *after_reduce) {
     const int64_t n = S->img.n, m = S->img.m, p = S->img.p;
     const int nm = (int)(n + m);
     if (!S->d_red) {
@@ -382,6 +386,7 @@ static int32_t kkt_solve_reduced_impl(hipkkt_solver *S, const double *rhs_x, con
             if (lhs_x && n) HK_CHECK(hipMemcpyAsync(lhs_x, d_lhs, n * sizeof(double), hipMemcpyDeviceToHost, A.stream));
             if (lhs_z && m) HK_CHECK(hipMemcpyAsync(lhs_z, d_lhs + n, m * sizeof(double), hipMemcpyDeviceToHost, A.stream));
             HK_CHECK(hipMemcpyAsync(S->h_scal_red, d_sc, 10 * sizeof(double), hipMemcpyDeviceToHost, A.stream));
+            if (after_reduce) (*after_reduce)(A.stream, d_lhs);
         };
         reduce();
         int64_t st1 = 0, st2 = 0;
@@ -411,6 +416,8 @@ static int32_t kkt_solve_reduced_impl(hipkkt_solver *S, const double *rhs_x, con
     }
     return HIPKKT_ERR_DEVICE;
 }
+}  // namespace hipkkt_host
+extern "C" {
 
 int32_t hipkkt_kkt_solve_reduced(hipkkt_handle h, const double *rhs_x, const double *workz, const double *var_x, const double *scal_in4,
                                  int32_t const_pending, double *lhs_x, double *lhs_z, double *scal_out10, int32_t ir_enable,
@@ -422,7 +429,7 @@ int32_t hipkkt_kkt_solve_reduced(hipkkt_handle h, const double *rhs_x, const dou
         return HIPKKT_ERR_ARGUMENT;
     }
     return kkt_solve_reduced_impl(S, rhs_x, workz, var_x, nullptr, scal_in4, const_pending, lhs_x, lhs_z, nullptr, scal_out10, ir_enable,
-                                  reltol, abstol, max_iter, stop_ratio, ir_steps2);
+                                  reltol, abstol, max_iter, stop_ratio, ir_steps2, nullptr);
     HK_LEAVE
 }
 
@@ -435,7 +442,7 @@ int32_t hipkkt_kkt_solve_reduced_dev(hipkkt_handle h, const double *in_dev, cons
         return HIPKKT_ERR_ARGUMENT;
     }
     return kkt_solve_reduced_impl(S, nullptr, nullptr, nullptr, in_dev, scal_in4, const_pending, nullptr, nullptr, lhs_dev, scal_out10,
-                                  ir_enable, reltol, abstol, max_iter, stop_ratio, ir_steps2);
+                                  ir_enable, reltol, abstol, max_iter, stop_ratio, ir_steps2, nullptr);
     HK_LEAVE
 }
 

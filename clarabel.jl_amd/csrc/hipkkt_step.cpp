@@ -1,0 +1,235 @@
+// The cone algebra of an interior-point step on the device (step.hip) and its fusion with the reduced solve of hipkkt_solve.cpp:
+// hipkkt_cone_* (one operation each, host pointers), hipkkt_set_equilibration, hipkkt_step_* (everything resident, scalars only cross
+// PCIe).  Zero, Nonnegative and SecondOrder cones; they work on the (s, z, w, lambda, eta) of the last successful hipkkt_update_scaling.
+#include "hipkkt_internal.h"
+
+#pragma clang fp contract(off)      // the scalars below repeat the caller's expressions (variables.jl:14-43, :124-162) rounding by rounding
+
+namespace hipkkt_host {
+
+// the cone set and its scaling allow the step entry points
+static bool step_ready(hipkkt_solver *S, const char *who) {
+    if (!S->l1 || !S->sc_ready || !S->sc_step_kinds) {
+        S->err = std::string(who) + ": needs an L1 handle whose registered cones are Zero / Nonnegative / SecondOrder only";
+        return false;
+    }
+    if (!S->sc_scaled) { S->err = std::string(who) + ": no successful hipkkt_update_scaling since the cones were registered"; return false; }
+    return true;
+}
+
+static void ensure_step_buffers(hipkkt_solver *S) {
+    if (S->d_st_step) return;
+    const int64_t n = S->img.n, m = S->img.m;
+    const int64_t pairs = step_len_pairs(m, (int)S->cone_numel.size());      // (a later registration has at most this many cones)
+    S->d_st_step = S->dalloc<double>(n + 2 * m);
+    S->d_st_in = S->dalloc<double>(2 * n + m);
+    S->d_st_work = S->dalloc<double>(4 * m);
+    S->d_st_part = S->dalloc<double>((size_t)std::max<int64_t>(2 * pairs, step_norm_part_doubles()));
+    S->d_st_out = S->dalloc<double>(16);
+}
+
+struct ConeTables {
+    const signed char *kind; int nsoc; const int64_t *desc;
+    const double *s, *z, *w, *lam, *eta;
+    int64_t m;
+};
+static ConeTables tables(hipkkt_solver *S) {
+    const int64_t m = S->img.m;
+    return {S->d_sc_kind, S->sc_nsoc, S->d_sc_socdesc, S->d_sc_sz, S->d_sc_sz + m, S->d_sc_wl, S->d_sc_wl + m, S->d_sc_eta, m};
+}
+
+// one operation on host vectors of length m: `nin` inputs are staged, op(in0, in1, out) runs, `nout` doubles come back
+template <class F>
+static int32_t cone_op_host(hipkkt_solver *S, const double *in0, const double *in1, double *out, int64_t nout, F &&op) {
+    const int64_t m = S->img.m;
+    ensure_step_buffers(S);
+    S->ensure_stage(3 * m + 2);
+    double *d0 = S->d_stage, *d1 = d0 + m, *dout = d1 + m;
+    if (in0 && m) HK_CHECK(hipMemcpyAsync(d0, in0, m * sizeof(double), hipMemcpyHostToDevice, S->stream));
+    if (in1 && m) HK_CHECK(hipMemcpyAsync(d1, in1, m * sizeof(double), hipMemcpyHostToDevice, S->stream));
+    op(d0, d1, dout);
+    copy_sync(S->stream, out, dout, (size_t)nout * sizeof(double), hipMemcpyDeviceToHost);
+    if (!nout) HK_CHECK(hipStreamSynchronize(S->stream));
+    return HIPKKT_OK;
+}
+
+struct StepScalars { double tau, kappa, rhs_tau, rhs_kappa; };
+
+// the part of kkt_solve! (kktsystem.jl:135-215) both fused calls share: d_st_in holds [rhs.x | workz | variables.x], addc the constant
+// term of ds.  The solve and its reduction are hipkkt_kkt_solve_reduced_dev's; ds = -(Hs dz + addc) (:203-207) and the step length of
+// the cones (alpha_max = 1) are enqueued behind every reduction, so the host still synchronises once.
+static int32_t fused_solve(hipkkt_solver *S, const StepScalars &sc, const double *addc, int32_t const_pending, double step_fraction,
+                           double *scal_out15, int32_t ir_enable, double reltol, double abstol, int64_t max_iter, double stop_ratio,
+                           int64_t *ir_steps2) {
+    const int64_t n = S->img.n, m = S->img.m;
+    const ConeTables T = tables(S);
+    if (solve_target(S) != S) HK_CHECK(hipStreamSynchronize(S->stream));      // the robust-order twin solves on its own stream
+    double *h2 = S->h_scal_red + 10;
+    const std::function<void(hipStream_t, const double *)> after = [&](hipStream_t st, const double *d_lhs) {
+        double *dz = S->d_st_step + n, *ds = dz + m;
+        HK_CHECK(hipMemcpyAsync(S->d_st_step, d_lhs, (size_t)(n + m) * sizeof(double), hipMemcpyDeviceToDevice, st));
+        launch_step_mulhs(st, T.kind, T.nsoc, T.desc, T.w, T.eta, dz, addc, ds, m);
+        launch_step_length(st, T.kind, T.nsoc, T.desc, T.z, T.s, dz, ds, 1.0, S->d_st_part, S->d_st_out, m);
+        HK_CHECK(hipMemcpyAsync(h2, S->d_st_out, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+    };
+    const double scal_in[4] = {sc.tau, sc.kappa, sc.rhs_tau, sc.rhs_kappa};
+    double red[10];
+    S->st_have_step = false;
+    const int32_t rc = kkt_solve_reduced_impl(S, nullptr, nullptr, nullptr, S->d_st_in, scal_in, const_pending, nullptr, nullptr, nullptr, red,
+                                              ir_enable, reltol, abstol, max_iter, stop_ratio, ir_steps2, &after);
+    if (rc != HIPKKT_OK) return rc;
+    S->st_have_step = true;
+    // variables.jl:14-43 (the cones' part ran with alpha_max = 1: the minimum is exact in any order), kktsystem.jl:209
+    const double dtau = red[0];
+    const double dkappa = -(sc.rhs_kappa + sc.kappa * dtau) / sc.tau;
+    const double a_tau = dtau < 0.0 ? -sc.tau / dtau : 1.7976931348623157e308;
+    const double a_kap = dkappa < 0.0 ? -sc.kappa / dkappa : 1.7976931348623157e308;
+    double alpha = std::min(std::min(a_tau, a_kap), 1.0);
+    alpha = std::min(std::min(alpha, h2[0]), h2[1]);
+    alpha *= step_fraction;
+    scal_out15[0] = alpha; scal_out15[1] = dtau; scal_out15[2] = dkappa; scal_out15[3] = h2[0]; scal_out15[4] = h2[1];
+    memcpy(scal_out15 + 5, red, sizeof(red));
+    return HIPKKT_OK;
+}
+
+}  // namespace hipkkt_host
+
+extern "C" {
+
+int32_t hipkkt_cone_affine_ds(hipkkt_handle h, double *ds_out) {
+    HK_ENTER(h)
+    if (!step_ready(S, "cone_affine_ds") || (S->img.m && !ds_out)) return HIPKKT_ERR_ARGUMENT;
+    const ConeTables T = tables(S);
+    return cone_op_host(S, nullptr, nullptr, ds_out, T.m, [&](double *, double *, double *out) {
+        launch_step_affine_ds(S->stream, T.kind, T.nsoc, T.desc, T.lam, out, T.m);
+    });
+    HK_LEAVE
+}
+
+int32_t hipkkt_cone_combined_ds_shift(hipkkt_handle h, const double *step_z, const double *step_s, double sigma_mu, double *shift_out) {
+    HK_ENTER(h)
+    if (!step_ready(S, "cone_combined_ds_shift") || (S->img.m && (!step_z || !step_s || !shift_out))) return HIPKKT_ERR_ARGUMENT;
+    const ConeTables T = tables(S);
+    return cone_op_host(S, step_z, step_s, shift_out, T.m, [&](double *dz, double *ds, double *out) {
+        launch_step_shift(S->stream, T.kind, T.nsoc, T.desc, T.w, T.eta, dz, ds, sigma_mu, out, T.m);
+    });
+    HK_LEAVE
+}
+
+int32_t hipkkt_cone_ds_from_dz_offset(hipkkt_handle h, const double *ds, double *out) {
+    HK_ENTER(h)
+    if (!step_ready(S, "cone_ds_from_dz_offset") || (S->img.m && (!ds || !out))) return HIPKKT_ERR_ARGUMENT;
+    const ConeTables T = tables(S);
+    return cone_op_host(S, ds, nullptr, out, T.m, [&](double *dds, double *, double *dout) {
+        launch_step_offset(S->stream, T.kind, T.nsoc, T.desc, T.z, T.w, T.lam, T.eta, dds, dout, T.m);
+    });
+    HK_LEAVE
+}
+
+int32_t hipkkt_cone_mul_hs(hipkkt_handle h, const double *x, double *y_out) {
+    HK_ENTER(h)
+    if (!step_ready(S, "cone_mul_hs") || (S->img.m && (!x || !y_out))) return HIPKKT_ERR_ARGUMENT;
+    const ConeTables T = tables(S);
+    return cone_op_host(S, x, nullptr, y_out, T.m, [&](double *dx, double *, double *dy) {
+        launch_step_mulhs(S->stream, T.kind, T.nsoc, T.desc, T.w, T.eta, dx, nullptr, dy, T.m);
+    });
+    HK_LEAVE
+}
+
+int32_t hipkkt_cone_step_length(hipkkt_handle h, const double *dz, const double *ds, double alpha_max, double *alpha_out2) {
+    HK_ENTER(h)
+    if (!step_ready(S, "cone_step_length") || !alpha_out2 || (S->img.m && (!dz || !ds))) return HIPKKT_ERR_ARGUMENT;
+    const ConeTables T = tables(S);
+    return cone_op_host(S, dz, ds, alpha_out2, 2, [&](double *ddz, double *dds, double *dout) {
+        launch_step_length(S->stream, T.kind, T.nsoc, T.desc, T.z, T.s, ddz, dds, alpha_max, S->d_st_part, dout, T.m);
+    });
+    HK_LEAVE
+}
+
+int32_t hipkkt_set_equilibration(hipkkt_handle h, const double *d, const double *e) {
+    HK_ENTER(h)
+    const int64_t n = S->img.n, m = S->img.m;
+    if (!S->l1 || (n && !d) || (m && !e)) { S->err = "set_equilibration: bad arguments / not an L1 handle"; return HIPKKT_ERR_ARGUMENT; }
+    // dinv = 1 ./ d, einv = 1 ./ e as problemdata.jl forms them (IEEE division: the caller's bits)
+    std::vector<double> eq((size_t)(2 * n + 2 * m) + 1);
+    for (int64_t i = 0; i < n; i++) { eq[i] = d[i]; eq[n + m + i] = 1.0 / d[i]; }
+    for (int64_t i = 0; i < m; i++) { eq[n + i] = e[i]; eq[2 * n + m + i] = 1.0 / e[i]; }
+    if (!S->d_st_eq) S->d_st_eq = S->dalloc<double>(2 * n + 2 * m);
+    copy_sync(S->stream, S->d_st_eq, eq.data(), (size_t)(2 * n + 2 * m) * sizeof(double), hipMemcpyHostToDevice);
+    return HIPKKT_OK;
+    HK_LEAVE
+}
+
+int32_t hipkkt_step_affine_dev(hipkkt_handle h, const double *xzs_dev, const double *res_dev, const double *scal_in3, int32_t const_pending,
+                               double *scal_out15, int32_t ir_enable, double reltol, double abstol, int64_t max_iter, double stop_ratio,
+                               int64_t *ir_steps2) {
+    HK_ENTER(h)
+    if (!step_ready(S, "step_affine_dev")) return HIPKKT_ERR_ARGUMENT;
+    if (!S->d_qb || !xzs_dev || !res_dev || !scal_in3 || !scal_out15) { S->err = "step_affine_dev: call hipkkt_set_qb first / bad arguments"; return HIPKKT_ERR_ARGUMENT; }
+    const int64_t n = S->img.n, m = S->img.m;
+    ensure_step_buffers(S);
+    const double tau = scal_in3[0], kappa = scal_in3[1], r_tau = scal_in3[2];
+    // variables_affine_step_rhs!, variables.jl:107-121; ds_const = s (kktsystem.jl:152-156)
+    launch_step_rhs(S->stream, S->d_st_in, xzs_dev, res_dev, nullptr, 1.0, n, m);
+    const StepScalars sc{tau, kappa, r_tau, tau * kappa};
+    return fused_solve(S, sc, xzs_dev + n + m, const_pending, 1.0, scal_out15, ir_enable, reltol, abstol, max_iter, stop_ratio, ir_steps2);
+    HK_LEAVE
+}
+
+int32_t hipkkt_step_combined_dev(hipkkt_handle h, const double *xzs_dev, const double *res_dev, const double *scal_in9,
+                                 int32_t const_pending, double *scal_out15, int32_t ir_enable, double reltol, double abstol,
+                                 int64_t max_iter, double stop_ratio, int64_t *ir_steps2) {
+    HK_ENTER(h)
+    if (!step_ready(S, "step_combined_dev")) return HIPKKT_ERR_ARGUMENT;
+    if (!S->d_qb || !xzs_dev || !res_dev || !scal_in9 || !scal_out15) { S->err = "step_combined_dev: call hipkkt_set_qb first / bad arguments"; return HIPKKT_ERR_ARGUMENT; }
+    if (!S->st_have_step) { S->err = "step_combined_dev: no affine step resident (hipkkt_step_affine_dev comes first)"; return HIPKKT_ERR_ARGUMENT; }
+    const int64_t n = S->img.n, m = S->img.m;
+    const double tau = scal_in9[0], kappa = scal_in9[1], r_tau = scal_in9[2], dtau_aff = scal_in9[3], dkappa_aff = scal_in9[4];
+    const double sigma = scal_in9[5], mu = scal_in9[6], m_corr = scal_in9[7], step_fraction = scal_in9[8];
+    const ConeTables T = tables(S);
+    hipStream_t st = S->stream;
+    // variables_combined_step_rhs!, variables.jl:124-162
+    const double sm = sigma * mu, oms = 1.0 - sigma;
+    const double rhs_kappa = -sm + m_corr * dtau_aff * dkappa_aff + tau * kappa;
+    double *w_dz = S->d_st_work, *w_rhs_s = w_dz + m, *w_shift = w_rhs_s + m, *w_dsc = w_shift + m;
+    const double *dz_aff = S->d_st_step + n, *ds_aff = dz_aff + m;
+    if (m_corr != 1.0) { launch_step_scale(st, w_dz, dz_aff, m_corr, m); dz_aff = w_dz; }
+    launch_step_affine_ds(st, T.kind, T.nsoc, T.desc, T.lam, w_rhs_s, m);
+    launch_step_shift(st, T.kind, T.nsoc, T.desc, T.w, T.eta, dz_aff, ds_aff, sm, w_shift, m);
+    launch_step_add(st, w_rhs_s, w_shift, m);                                                           // rhs.s = lambda o lambda + shift
+    launch_step_offset(st, T.kind, T.nsoc, T.desc, T.z, T.w, T.lam, T.eta, w_rhs_s, w_dsc, m);          // kktsystem.jl:157-163
+    launch_step_rhs(st, S->d_st_in, xzs_dev, res_dev, w_dsc, oms, n, m);
+    const StepScalars sc{tau, kappa, oms * r_tau, rhs_kappa};
+    return fused_solve(S, sc, w_dsc, const_pending, step_fraction, scal_out15, ir_enable, reltol, abstol, max_iter, stop_ratio, ir_steps2);
+    HK_LEAVE
+}
+
+int32_t hipkkt_step_apply_dev(hipkkt_handle h, double alpha, double *xzs_dev) {
+    HK_ENTER(h)
+    if (!step_ready(S, "step_apply_dev")) return HIPKKT_ERR_ARGUMENT;
+    if (!S->st_have_step || !xzs_dev) { S->err = "step_apply_dev: no step resident / null iterate"; return HIPKKT_ERR_ARGUMENT; }
+    launch_step_add_step(S->stream, xzs_dev, S->d_st_step, alpha, S->img.n + 2 * S->img.m);
+    // (no host synchronisation: whatever reads the iterate next runs on the same stream)
+    return HIPKKT_OK;
+    HK_LEAVE
+}
+
+int32_t hipkkt_step_info_norms_dev(hipkkt_handle h, const double *xzs_dev, const double *res_dev, double *out8) {
+    HK_ENTER(h)
+    if (!S->l1 || !S->d_st_eq || !xzs_dev || !res_dev || !out8) { S->err = "step_info_norms_dev: call hipkkt_set_equilibration first / bad arguments"; return HIPKKT_ERR_ARGUMENT; }
+    ensure_step_buffers(S);      // (needs no scaling: the first info_update! of a solve precedes it)
+    launch_step_info_norms(S->stream, xzs_dev, res_dev, S->d_st_eq, S->d_st_part, S->d_st_out + 4, S->img.n, S->img.m);
+    copy_sync(S->stream, out8, S->d_st_out + 4, 8 * sizeof(double), hipMemcpyDeviceToHost);
+    return HIPKKT_OK;
+    HK_LEAVE
+}
+
+int32_t hipkkt_step_get(hipkkt_handle h, double *out) {
+    HK_ENTER(h)
+    if (!S->l1 || !S->st_have_step || !out) { S->err = "step_get: no step resident"; return HIPKKT_ERR_ARGUMENT; }
+    copy_sync(S->stream, out, S->d_st_step, (size_t)(S->img.n + 2 * S->img.m) * sizeof(double), hipMemcpyDeviceToHost);
+    return HIPKKT_OK;
+    HK_LEAVE
+}
+
+}  // extern "C"

@@ -49,6 +49,29 @@ void launch_scaling_cone3(hipStream_t st, int nexp, int npow, const int64_t *row
                           double *kval, double *out, int *trips, int *fail);
 void launch_scaling_genpow(hipStream_t st, int ngenpow, const int64_t *desc, const double *alpha, const int64_t *idx,
                            const int64_t *map_hs, const double *z, double mu, double sqrtmu, double *kval, double *out, int *fail);
+// step.hip: the cone algebra of an interior-point step for Zero / Nonnegative / SecondOrder cones (row_kind, desc: the tables of the
+// scaling kernels).  part of launch_step_length: 2 * step_len_pairs(m, nsoc) doubles; of launch_step_info_norms: step_norm_part_doubles()
+int64_t step_len_pairs(int64_t m, int nsoc);
+int64_t step_norm_part_doubles();
+void launch_step_affine_ds(hipStream_t st, const signed char *row_kind, int nsoc, const int64_t *desc, const double *lam, double *out,
+                           int64_t m);
+void launch_step_shift(hipStream_t st, const signed char *row_kind, int nsoc, const int64_t *desc, const double *w, const double *eta,
+                       const double *dz, const double *ds, double sigma_mu, double *out, int64_t m);
+void launch_step_offset(hipStream_t st, const signed char *row_kind, int nsoc, const int64_t *desc, const double *z, const double *w,
+                        const double *lam, const double *eta, const double *ds, double *out, int64_t m);
+// addc != NULL: y = -(Hs x + addc)
+void launch_step_mulhs(hipStream_t st, const signed char *row_kind, int nsoc, const int64_t *desc, const double *w, const double *eta,
+                       const double *x, const double *addc, double *y, int64_t m);
+void launch_step_length(hipStream_t st, const signed char *row_kind, int nsoc, const int64_t *desc, const double *z, const double *s,
+                        const double *dz, const double *ds, double alpha_max, double *part, double *out2, int64_t m);
+void launch_step_add_step(hipStream_t st, double *v, const double *dv, double alpha, int64_t len);
+void launch_step_scale(hipStream_t st, double *out, const double *in, double f, int64_t len);
+void launch_step_add(hipStream_t st, double *acc, const double *b, int64_t len);
+// in = [rhs.x | workz | variables.x]: dsc == NULL the affine step (rx, s - rz), otherwise (f rx, dsc - f rz)
+void launch_step_rhs(hipStream_t st, double *in, const double *xzs, const double *res, const double *dsc, double f, int64_t n, int64_t m);
+// eq = [d | e | dinv | einv]
+void launch_step_info_norms(hipStream_t st, const double *xzs, const double *res, const double *eq, double *part, double *out8, int64_t n,
+                            int64_t m);
 void launch_block_products(hipStream_t st, const DevPlan &P, const double *x, const double *z, double *Px, double *ATz,
                            double *Ax, int n, int m);
 void launch_zero_words(hipStream_t st, void *p, int nwords);

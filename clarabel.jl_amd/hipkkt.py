@@ -38,7 +38,20 @@ SYMBOLS = [
     "hipkkt_solve_dev", "hipkkt_solve_multi", "hipkkt_solve_multi_dev", "hipkkt_kkt_solve_reduced", "hipkkt_kkt_solve_reduced_dev", "hipkkt_ldl_solve", "hipkkt_get_timing", "hipkkt_reset_timing", "hipkkt_get_profile", "hipkkt_get_profile_launches", "hipkkt_set_profiling",
     "hipkkt_get_counters", "hipkkt_debug_dump", "hipkkt_debug_extra_tiles", "hipkkt_debug_set", "hipkkt_debug_is_testing_build", "hipkkt_set_qb", "hipkkt_residuals", "hipkkt_residuals_dev",
     "hipkkt_selftest_mfma", "hipkkt_box_probe", "hipkkt_last_error",
+    # the interior-point step on the device (added within ABI version 5)
+    "hipkkt_cone_affine_ds", "hipkkt_cone_combined_ds_shift", "hipkkt_cone_ds_from_dz_offset", "hipkkt_cone_mul_hs", "hipkkt_cone_step_length",
+    "hipkkt_set_equilibration", "hipkkt_step_affine_dev", "hipkkt_step_combined_dev", "hipkkt_step_apply_dev", "hipkkt_step_info_norms_dev",
+    "hipkkt_step_get",
 ]
+
+
+# doubles the calls below move across PCIe, counted from their argument sizes (tools/step_path_compare.py reads and resets them)
+TRAFFIC = {"h2d_bytes": 0, "d2h_bytes": 0}
+
+
+def _count(h2d_doubles=0, d2h_doubles=0):
+    TRAFFIC["h2d_bytes"] += 8 * int(h2d_doubles)
+    TRAFFIC["d2h_bytes"] += 8 * int(d2h_doubles)
 
 
 class Opts(C.Structure):
@@ -125,6 +138,17 @@ def lib():
     L.hipkkt_set_qb.argtypes = [vp, _f64p, _f64p]
     L.hipkkt_residuals.argtypes = [vp, _f64p, _f64p, _f64p, f64, f64, vp, vp, vp, vp, vp, _f64p]
     L.hipkkt_residuals_dev.argtypes = [vp, vp, f64, f64, vp, _f64p]
+    L.hipkkt_cone_affine_ds.argtypes = [vp, _f64p]
+    L.hipkkt_cone_combined_ds_shift.argtypes = [vp, _f64p, _f64p, f64, _f64p]
+    L.hipkkt_cone_ds_from_dz_offset.argtypes = [vp, _f64p, _f64p]
+    L.hipkkt_cone_mul_hs.argtypes = [vp, _f64p, _f64p]
+    L.hipkkt_cone_step_length.argtypes = [vp, _f64p, _f64p, f64, _f64p]
+    L.hipkkt_set_equilibration.argtypes = [vp, _f64p, _f64p]
+    L.hipkkt_step_affine_dev.argtypes = [vp, vp, vp, _f64p, i32, _f64p, i32, f64, f64, i64, f64, vp]
+    L.hipkkt_step_combined_dev.argtypes = [vp, vp, vp, _f64p, i32, _f64p, i32, f64, f64, i64, f64, vp]
+    L.hipkkt_step_apply_dev.argtypes = [vp, f64, vp]
+    L.hipkkt_step_info_norms_dev.argtypes = [vp, vp, vp, _f64p]
+    L.hipkkt_step_get.argtypes = [vp, _f64p]
     L.hipkkt_debug_dump.argtypes = [vp, i32, vp, i64, C.POINTER(i64)]
     L.hipkkt_debug_extra_tiles.argtypes = [i32, i32, i32, C.POINTER(i32)]
     L.hipkkt_debug_extra_tiles.restype = i32
@@ -327,6 +351,7 @@ class Handle:
 
     def set_hs(self, hs):
         self._chk(self.L.hipkkt_set_hs(self.h, np.ascontiguousarray(hs, dtype=np.float64), len(hs)), "set_hs")
+        _count(len(hs))
 
     def set_hs_psd(self, hs_off, dims, w_all):
         """Hs blocks of PSD cones formed on the device from W = R R^T (include/hipkkt.h hipkkt_set_hs_psd)."""
@@ -359,12 +384,14 @@ class Handle:
         ok = C.c_int32(0)
         p = lambda a: None if a is None else a.ctypes.data
         self._chk(self.L.hipkkt_update_scaling(self.h, s, z, p(R), p(w), p(lam), p(eta), C.byref(ok)), "update_scaling")
+        _count(2 * self.m + (0 if R is None else R.size), (2 * self.m + self._n_soc_all) if want_outputs else 0)
         if not want_outputs:
             return bool(ok.value), None, None, None
         return bool(ok.value), w[: self.m], lam[: self.m], eta[: self._n_soc_all]
 
     def update_scaling_dev(self, s_ptr, z_ptr, R_ptr=None, w_ptr=None, lam_ptr=None, eta_ptr=None):
         ok = C.c_int32(0)
+        _count(0, 1)
         self._chk(self.L.hipkkt_update_scaling_dev(self.h, s_ptr, z_ptr, R_ptr, w_ptr, lam_ptr, eta_ptr, C.byref(ok)), "update_scaling_dev")
         return bool(ok.value)
 
@@ -431,6 +458,7 @@ class Handle:
         self._chk(self.L.hipkkt_set_soc_batch(self.h, len(eta2), np.ascontiguousarray(eta2, dtype=np.float64),
                                               np.ascontiguousarray(u_all, dtype=np.float64),
                                               np.ascontiguousarray(v_all, dtype=np.float64), len(u_all)), "set_soc_batch")
+        _count(2 * len(u_all) + len(eta2))
 
     def set_genpow(self, i, sqrtmu, p, q, r):
         f = lambda a: np.ascontiguousarray(a, dtype=np.float64)
@@ -452,6 +480,7 @@ class Handle:
     def setrhs(self, rhsx, rhsz):
         self._chk(self.L.hipkkt_setrhs(self.h, np.ascontiguousarray(rhsx, dtype=np.float64),
                                        np.ascontiguousarray(rhsz, dtype=np.float64)), "setrhs")
+        _count(self.n + self.m)
 
     def solve(self, lhsx, lhsz, ir_enable=True, reltol=1e-13, abstol=1e-12, max_iter=10, stop_ratio=5.0):
         steps = C.c_int64(0)
@@ -459,6 +488,7 @@ class Handle:
         pz = self._out_ptr(lhsz, self.m, "lhsz")
         rc = self._chk(self.L.hipkkt_solve(self.h, px, pz, int(ir_enable), reltol, abstol, max_iter, stop_ratio,
                                            C.byref(steps)), "solve")
+        _count(0, (0 if lhsx is None else self.n) + (0 if lhsz is None else self.m))
         return rc == 0, steps.value
 
     def solve_multi(self, rhsx, rhsz, lhsx, lhsz, ir_enable=True, reltol=1e-13, abstol=1e-12, max_iter=10, stop_ratio=5.0):
@@ -482,6 +512,7 @@ class Handle:
         pz = self._out_ptr(lhsz, nrhs * self.m, "lhsz")
         rc = self._chk(self.L.hipkkt_solve_multi(self.h, nrhs, rhsx, rhsz, px, pz, int(ir_enable), reltol, abstol, max_iter,
                                                  stop_ratio, steps.ctypes.data), "solve_multi")
+        _count(nrhs * (self.n + self.m), nrhs * ((0 if lhsx is None else self.n) + (0 if lhsz is None else self.m)))
         return rc == 0, steps[:nrhs]
 
     def kkt_solve_reduced(self, rhs_x, workz, var_x, tau, kappa, rhs_tau, rhs_kappa, const_pending, lhs_x, lhs_z, ir_enable=True,
@@ -497,6 +528,7 @@ class Handle:
         rc = self._chk(self.L.hipkkt_kkt_solve_reduced(self.h, f(rhs_x), f(workz), f(var_x), scal_in, int(bool(const_pending)), px, pz, scal,
                                                        int(ir_enable), reltol, abstol, max_iter, stop_ratio, steps.ctypes.data),
                        "kkt_solve_reduced")
+        _count(2 * self.n + self.m + 4, (0 if lhs_x is None else self.n) + (0 if lhs_z is None else self.m) + 10)
         return rc == 0, float(scal[0]), scal, steps
 
     def kkt_solve_reduced_dev(self, in_ptr, tau, kappa, rhs_tau, rhs_kappa, const_pending, out_ptr, ir_enable=True, reltol=1e-13,
@@ -550,12 +582,149 @@ class Handle:
         ptrs = [self._out_ptr(a, k, nm) for a, k, nm in ((rx, self.n, "rx"), (rz, self.m, "rz"), (rx_inf, self.n, "rx_inf"),
                                                           (rz_inf, self.m, "rz_inf"), (Px, self.n, "Px"))]
         self._chk(self.L.hipkkt_residuals(self.h, f(x), f(z), f(s), float(tau), float(kappa), *ptrs, scal), "residuals")
+        _count(self.n + 2 * self.m + 2, sum(k for a, k in zip(ptrs, (self.n, self.m, self.n, self.m, self.n)) if a is not None) + 5)
         return tuple(float(v) for v in scal)
+
+    def residuals_dev(self, xzs_ptr, tau, kappa, out_ptr):
+        """hipkkt_residuals_dev: xzs = [x | z | s] -> out = [rx | rz | rx_inf | rz_inf | Px] on the device; returns the five scalars"""
+        scal = np.zeros(5)
+        self._chk(self.L.hipkkt_residuals_dev(self.h, xzs_ptr, float(tau), float(kappa), out_ptr, scal), "residuals_dev")
+        _count(2, 5)
+        return tuple(float(v) for v in scal)
+
+    # ---- the interior-point step on the device (include/hipkkt.h hipkkt_cone_* / hipkkt_step_*): Zero / Nonnegative / SecondOrder cones,
+    # on the scaling the last update_scaling left resident.  ValueError = the handle cannot serve them (HIPKKT_ERR_ARGUMENT).
+    def _chk_step(self, rc, what):
+        if rc == -1:
+            raise ValueError(f"{what}: {self.L.hipkkt_last_error(self.h).decode()}")
+        return self._chk(rc, what)
+
+    def _vec_m(self, a, what):
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.size != self.m:
+            raise ValueError(f"{what}: vectors have length m = {self.m}")
+        return a if a.size else np.zeros(1)
+
+    def cone_affine_ds(self):
+        out = np.zeros(max(self.m, 1))
+        self._chk_step(self.L.hipkkt_cone_affine_ds(self.h, out), "cone_affine_ds")
+        return out[: self.m]
+
+    def cone_combined_ds_shift(self, step_z, step_s, sigma_mu):
+        out = np.zeros(max(self.m, 1))
+        self._chk_step(self.L.hipkkt_cone_combined_ds_shift(self.h, self._vec_m(step_z, "step_z"), self._vec_m(step_s, "step_s"),
+                                                            float(sigma_mu), out), "cone_combined_ds_shift")
+        return out[: self.m]
+
+    def cone_ds_from_dz_offset(self, ds):
+        out = np.zeros(max(self.m, 1))
+        self._chk_step(self.L.hipkkt_cone_ds_from_dz_offset(self.h, self._vec_m(ds, "ds"), out), "cone_ds_from_dz_offset")
+        return out[: self.m]
+
+    def cone_mul_hs(self, x):
+        out = np.zeros(max(self.m, 1))
+        self._chk_step(self.L.hipkkt_cone_mul_hs(self.h, self._vec_m(x, "x"), out), "cone_mul_hs")
+        return out[: self.m]
+
+    def cone_step_length(self, dz, ds, alpha_max):
+        out = np.zeros(2)
+        self._chk_step(self.L.hipkkt_cone_step_length(self.h, self._vec_m(dz, "dz"), self._vec_m(ds, "ds"), float(alpha_max), out),
+                       "cone_step_length")
+        return float(out[0]), float(out[1])
+
+    def set_equilibration(self, d, e):
+        f = lambda a: np.ascontiguousarray(a if len(a) else np.zeros(1), dtype=np.float64)
+        self._chk(self.L.hipkkt_set_equilibration(self.h, f(d), f(e)), "set_equilibration")
+
+    def _step_fused(self, fn, what, xzs_ptr, res_ptr, scal_in, const_pending, ir):
+        scal = np.zeros(15)
+        steps = np.zeros(2, dtype=np.int64)
+        rc = self._chk_step(fn(self.h, xzs_ptr, res_ptr, np.array(scal_in, dtype=np.float64), int(bool(const_pending)), scal,
+                               int(ir.get("ir_enable", True)), ir.get("reltol", 1e-13), ir.get("abstol", 1e-12), ir.get("max_iter", 10),
+                               ir.get("stop_ratio", 5.0), steps.ctypes.data), what)
+        _count(len(scal_in), 15)
+        return rc == 0, scal, steps
+
+    def step_affine_dev(self, xzs_ptr, res_ptr, tau, kappa, r_tau, const_pending, **ir):
+        """-> (ok, scal[15] = alpha, dtau, dkappa, alpha_z, alpha_s, the ten scalars of kkt_solve_reduced, steps[2])"""
+        return self._step_fused(self.L.hipkkt_step_affine_dev, "step_affine_dev", xzs_ptr, res_ptr, [tau, kappa, r_tau], const_pending, ir)
+
+    def step_combined_dev(self, xzs_ptr, res_ptr, tau, kappa, r_tau, dtau_aff, dkappa_aff, sigma, mu, m_corr, max_step_fraction,
+                          const_pending=False, **ir):
+        return self._step_fused(self.L.hipkkt_step_combined_dev, "step_combined_dev", xzs_ptr, res_ptr,
+                                [tau, kappa, r_tau, dtau_aff, dkappa_aff, sigma, mu, m_corr, max_step_fraction], const_pending, ir)
+
+    def step_apply_dev(self, alpha, xzs_ptr):
+        self._chk_step(self.L.hipkkt_step_apply_dev(self.h, float(alpha), xzs_ptr), "step_apply_dev")
+
+    def step_info_norms_dev(self, xzs_ptr, res_ptr):
+        out = np.zeros(8)
+        self._chk_step(self.L.hipkkt_step_info_norms_dev(self.h, xzs_ptr, res_ptr, out), "step_info_norms_dev")
+        _count(0, 8)
+        return out
+
+    def step_get(self):
+        out = np.zeros(max(self.n + 2 * self.m, 1))
+        self._chk_step(self.L.hipkkt_step_get(self.h, out), "step_get")
+        return out[: self.n + 2 * self.m]
 
     def ldl_solve(self, b):
         x = np.zeros(self.N)
         self._chk(self.L.hipkkt_ldl_solve(self.h, x, np.ascontiguousarray(b, dtype=np.float64)), "ldl_solve")
         return x
+
+
+class DeviceBuffer:
+    """`n` doubles of device memory, through the HIP runtime the library is linked with (what a Julia caller holds as a ROCArray).
+    Copies are synchronous; the bytes that cross PCIe are counted in TRAFFIC."""
+    _hip = None
+
+    def __init__(self, n):
+        if DeviceBuffer._hip is None:
+            hip = C.CDLL("libamdhip64.so")
+            hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+            hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+            hip.hipFree.argtypes = [C.c_void_p]
+            DeviceBuffer._hip = hip
+        self.n = int(n)
+        p = C.c_void_p()
+        if DeviceBuffer._hip.hipMalloc(C.byref(p), max(8 * self.n, 8)) != 0:
+            raise HipKKTError(f"hipMalloc of {8 * self.n} bytes failed")
+        self.ptr = p.value
+
+    def _copy(self, dst, src, nbytes, kind):
+        if nbytes and DeviceBuffer._hip.hipMemcpy(dst, src, nbytes, kind) != 0:
+            raise HipKKTError("hipMemcpy failed")
+
+    def upload(self, host):
+        host = np.ascontiguousarray(host, dtype=np.float64)
+        assert host.size == self.n
+        self._copy(self.ptr, host.ctypes.data, host.nbytes, 1)
+        _count(host.size, 0)
+
+    def download(self):
+        out = np.zeros(self.n)
+        self._copy(out.ctypes.data, self.ptr, out.nbytes, 2)
+        _count(0, out.size)
+        return out
+
+    def copy_from(self, other):
+        """device-to-device; done when it returns (the library's streams do not wait for the null stream)"""
+        assert other.n == self.n
+        self._copy(self.ptr, other.ptr, 8 * self.n, 3)
+        if DeviceBuffer._hip.hipDeviceSynchronize() != 0:
+            raise HipKKTError("hipDeviceSynchronize failed")
+
+    def close(self):
+        if getattr(self, "ptr", None):
+            DeviceBuffer._hip.hipFree(self.ptr)
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def box_probe(device=0):

@@ -18,6 +18,16 @@ from .settings import Settings
 _DEBUG = os.environ.get("HIPKKT_DEBUG", "0") == "1"
 
 
+def cone_set_steps_on_device(cones) -> bool:
+    """the step entry points (hipkkt_cone_* / hipkkt_step_*) serve cone sets of ZeroCone, NonnegativeCone and SecondOrderCone only: a PSD
+    cone's step length needs eigenvalue decompositions, the non-symmetric cones need backtracking and barriers"""
+    if not hasattr(cones, "kkt_cone_kinds"):
+        return False
+    kinds = cones.kkt_cone_kinds_ex()[0] if hasattr(cones, "kkt_cone_kinds_ex") else cones.kkt_cone_kinds()
+    kinds = np.asarray(kinds)
+    return kinds.size > 0 and bool(np.all((kinds >= 0) & (kinds <= 2)))
+
+
 class HipKKTSolver:
     def __init__(self, P, A, cones, m, n, settings: Settings, **optkw):
         """ref: DirectLDLKKTSolver{T}(P,A,cones,m,n,settings), kktsolver_directldl.jl:46-92.
@@ -58,6 +68,8 @@ class HipKKTSolver:
             self._has_cone_kinds = self.scales_nonsymmetric = True
         elif self._has_cone_kinds:
             self.h.set_cone_types(kinds)
+        # the interior-point step on the device (hipkkt_cone_* / hipkkt_step_*) serves Zero / Nonnegative / SecondOrder cone sets only
+        self._steps_on_device = cone_set_steps_on_device(cones)
         self.scaling_nonsym = None
         self.scaling_w = self.scaling_lambda = self.scaling_soc_eta = None
         self.diagonal_regularizer = 0.0
@@ -196,6 +208,78 @@ class HipKKTSolver:
         """fills the residual object `r` (rx, rz, rx_inf, rz_inf, Px, rtau, dot_*) from the variables `v` (x, z, s, tau, kappa)"""
         r.dot_qx, r.dot_bz, r.dot_sz, r.dot_xPx, r.rtau = self.h.residuals(v.x, v.z, v.s, v.tau, v.kappa, r.rx, r.rz, r.rx_inf,
                                                                           r.rz_inf, r.Px)
+
+    # ---- the interior-point step on the device (include/hipkkt.h hipkkt_cone_* / hipkkt_step_*) -------------------------------------
+    # What the caller's loop does between the calls above, on an iterate [x | z | s] and a residual buffer [rx | rz | rx_inf | rz_inf | Px]
+    # that stay in device memory (device_buffer); only scalars cross PCIe.  Zero / Nonnegative / SecondOrder cone sets.
+    @property
+    def steps_on_device(self) -> bool:
+        return self._steps_on_device
+
+    def device_buffer(self, n):
+        return hipkkt.DeviceBuffer(n)
+
+    def set_equilibration(self, d, e):
+        self.h.set_equilibration(d, e)
+
+    # the granular operations on the scaling the last kktsolver_update_scaled[_dev] left resident (vectors of length m, cone order)
+    def cone_affine_ds(self):
+        return self.h.cone_affine_ds()
+
+    def cone_combined_ds_shift(self, step_z, step_s, sigma_mu):
+        return self.h.cone_combined_ds_shift(step_z, step_s, sigma_mu)
+
+    def cone_ds_from_dz_offset(self, ds):
+        return self.h.cone_ds_from_dz_offset(ds)
+
+    def cone_mul_hs(self, x):
+        return self.h.cone_mul_hs(x)
+
+    def cone_step_length(self, dz, ds, alpha_max):
+        return self.h.cone_step_length(dz, ds, alpha_max)
+
+    def residuals_update_dev(self, xzs, res, tau, kappa):
+        """residuals_update! from the resident iterate into the resident buffer -> (dot_qx, dot_bz, dot_sz, dot_xPx, r_tau)"""
+        return self.h.residuals_dev(xzs.ptr, tau, kappa, res.ptr)
+
+    def kktsolver_info_norms(self, xzs, res):
+        """the eight scaled 2-norms of info_update! (info.jl:1-60): |d x|, |e z|, |einv s|, |dinv rx|, |einv rz|, |dinv rx_inf|,
+        |einv rz_inf|, |dinv Px|"""
+        return self.h.step_info_norms_dev(xzs.ptr, res.ptr)
+
+    def kktsolver_update_scaling_dev(self, xzs) -> bool:
+        """update_scaling! + get_Hs! from the resident (s, z); False = a cone's s or z is not interior"""
+        return self.h.update_scaling_dev(xzs.ptr + 8 * (self.n + self.m), xzs.ptr + 8 * self.n)
+
+    def kktsolver_refactor(self) -> bool:
+        return self._refactor()
+
+    def _ir(self):
+        st = self.settings
+        return dict(ir_enable=st.iterative_refinement_enable, reltol=st.iterative_refinement_reltol, abstol=st.iterative_refinement_abstol,
+                    max_iter=st.iterative_refinement_max_iter, stop_ratio=st.iterative_refinement_stop_ratio)
+
+    def _step_done(self, ok, scal, steps, const_pending):
+        self.last_ir_steps = int(steps[0])
+        self.total_ir_steps += int(steps[0]) + (int(steps[1]) if const_pending else 0)
+        self.nsolves += 2 if const_pending else 1
+        self.last_step_scalars = scal
+        return ok, float(scal[0]), float(scal[1]), float(scal[2])
+
+    def kktsolver_step_affine(self, xzs, res, tau, kappa, r_tau, const_pending):
+        """variables_affine_step_rhs! + kkt_solve!(:affine) + the affine step length -> (ok, alpha, dtau, dkappa); the step stays resident"""
+        ok, scal, steps = self.h.step_affine_dev(xzs.ptr, res.ptr, tau, kappa, r_tau, const_pending, **self._ir())
+        return self._step_done(ok, scal, steps, const_pending)
+
+    def kktsolver_step_combined(self, xzs, res, tau, kappa, r_tau, dtau_aff, dkappa_aff, sigma, mu, m_corr):
+        """variables_combined_step_rhs! + kkt_solve!(:combined) + the step length times max_step_fraction -> (ok, alpha, dtau, dkappa)"""
+        ok, scal, steps = self.h.step_combined_dev(xzs.ptr, res.ptr, tau, kappa, r_tau, dtau_aff, dkappa_aff, sigma, mu, m_corr,
+                                                   self.settings.max_step_fraction, False, **self._ir())
+        return self._step_done(ok, scal, steps, False)
+
+    def kktsolver_step_apply(self, alpha, xzs):
+        """[x | z | s] += alpha [dx | dz | ds] in place (not synchronised: the next call on the handle reads the result)"""
+        self.h.step_apply_dev(alpha, xzs.ptr)
 
     # ref: kktsolver_update_P!/A!, :374-386
     def kktsolver_update_P(self, P):

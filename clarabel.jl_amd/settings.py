@@ -55,4 +55,8 @@ class Settings:
     device_residuals: bool = False            # N4: residuals_update! computed by the plugin from the resident P, A
     device_scaling: bool = False              # N1: update_scaling! / get_Hs! of the symmetric cones formed by the plugin from (s, z)
     device_reduced: bool = False              # N2: the reduced-system algebra of kkt_solve! (d tau dots, quad_form, dx, dz) done by the plugin
+    # the cone algebra between those calls (affine_ds!, combined_ds_shift!, mul_Hs!, step length, add_step!, the norms of info_update!) done
+    # by the plugin on a device-resident iterate, for Zero / Nonnegative / SecondOrder cone sets (any other cone set takes the host path).
+    # Needs device_scaling, device_reduced and device_residuals: the caller raises ValueError when one of them is off.
+    device_step: bool = False
     extra: dict = field(default_factory=dict)

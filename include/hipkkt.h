@@ -71,7 +71,8 @@ int32_t hipkkt_is_available(void);
 /* Version of THIS interface.  A binding compares it with the HIPKKT_ABI_VERSION it was written against when it loads the library
  * and refuses a mismatch (the Julia glue and the ctypes mirror do): signatures may change between versions, never within one.
  * 4: hipkkt_get_profile / hipkkt_get_counters take the capacity of the caller's buffer (they wrote a fixed, growing number of values).
- * 5: hipkkt_set_cone_types_ex / hipkkt_get_nonsym_len / hipkkt_update_scaling_ex[_dev] (the bindings bind them when they load). */
+ * 5: hipkkt_set_cone_types_ex / hipkkt_get_nonsym_len / hipkkt_update_scaling_ex[_dev] (the bindings bind them when they load).
+ *    Added within 5, no signature changed: the step entry points hipkkt_cone_* / hipkkt_set_equilibration / hipkkt_step_*. */
 #define HIPKKT_ABI_VERSION 5
 int32_t hipkkt_abi_version(void);
 /* releases the process-wide cache of device memory blocks the library keeps between handles (not in the reference: an embedding
@@ -314,6 +315,60 @@ int32_t hipkkt_set_qb(hipkkt_handle h, const double *q, const double *b);
 int32_t hipkkt_residuals(hipkkt_handle h, const double *x, const double *z, const double *s, double tau, double kappa,
                          double *rx, double *rz, double *rx_inf, double *rz_inf, double *Px, double *scal5);
 int32_t hipkkt_residuals_dev(hipkkt_handle h, const double *xzs_dev, double tau, double kappa, double *out_dev, double *scal5);
+
+/* ---- the interior-point step on the device ------------------------------------------------ */
+
+/* The cone algebra BETWEEN the calls above -- affine_ds!, combined_ds_shift!, Delta_s_from_Delta_z_offset!, mul_Hs!, the step length,
+ * variables_add_step! and the norms of info_update! -- for cone sets of ZeroCone, NonnegativeCone and SecondOrderCone (kinds 0..2 of
+ * hipkkt_set_cone_types[_ex]).  Every operation works on the (s, z, w, lambda, eta) that the last successful
+ * hipkkt_update_scaling[_ex][_dev] left resident; expressions keep the reference's association (Zero / Nonnegative rows are the
+ * host's bit for bit), a `dot` of the reference is a tree sum.  No input is modified.
+ * All of them return HIPKKT_ERR_ARGUMENT on a handle whose registration names a PSD cone or a kind 4..6 (those keep their step algebra
+ * with the caller: eigenvalue decompositions, backtracking line search, barriers) and before the first successful scaling; the fused
+ * calls also before hipkkt_set_qb.  On any non-zero return the outputs are unspecified, as for hipkkt_kkt_solve_reduced.
+ *
+ * One operation each, host vectors of length m in cone order (the unit-tested surface):
+ *   hipkkt_cone_affine_ds            ds = lambda o lambda                  coneops_nncone.jl affine_ds!, coneops_socone.jl:219-228
+ *   hipkkt_cone_combined_ds_shift    shift = W^-1 step_s o W step_z - sigma mu e   coneops_symmetric_common.jl:1-36, coneops_socone.jl:300-347
+ *   hipkkt_cone_ds_from_dz_offset    out = ds ./ z resp. coneops_socone.jl:241-268
+ *   hipkkt_cone_mul_hs               y = Hs x                               coneops_nncone.jl:104-113, coneops_socone.jl:201-216
+ *   hipkkt_cone_step_length          alpha_out2 = (alpha_z, alpha_s) <= alpha_max   coneops_nncone.jl:151-170, coneops_socone.jl:270-286,
+ *                                    the exact minimum over all cones (coneops_compositecone.jl:216-252) */
+int32_t hipkkt_cone_affine_ds(hipkkt_handle h, double *ds_out);
+int32_t hipkkt_cone_combined_ds_shift(hipkkt_handle h, const double *step_z, const double *step_s, double sigma_mu, double *shift_out);
+int32_t hipkkt_cone_ds_from_dz_offset(hipkkt_handle h, const double *ds, double *out);
+int32_t hipkkt_cone_mul_hs(hipkkt_handle h, const double *x, double *y_out);
+int32_t hipkkt_cone_step_length(hipkkt_handle h, const double *dz, const double *ds, double alpha_max, double *alpha_out2);
+/* once per problem (L1 handles): the equilibration vectors d[n], e[m] of problemdata.jl:133-221 for hipkkt_step_info_norms_dev; the
+ * reciprocals are formed on the host as 1 ./ d, 1 ./ e like problemdata.jl does, so they are the caller's dinv / einv bit for bit */
+int32_t hipkkt_set_equilibration(hipkkt_handle h, const double *d, const double *e);
+/* The fused calls.  xzs_dev = [x | z | s] and res_dev = [rx | rz | rx_inf | rz_inf | Px] are the device buffers of hipkkt_residuals_dev;
+ * only scalars cross PCIe and each call synchronises with the host once (hipkkt_step_apply_dev: not at all).  The reduced solve is
+ * hipkkt_kkt_solve_reduced_dev's code path (const_pending as there); the step [dx | dz | ds] stays in the handle.
+ *   hipkkt_step_affine_dev    variables_affine_step_rhs! (variables.jl:107-121) + kkt_solve!(:affine) (kktsystem.jl:135-215) + the affine
+ *     step length (variables.jl:14-43).  scal_in3 = {tau, kappa, r_tau}: rhs.x = rx, workz = s - rz, rhs.tau = r_tau, rhs.kappa = tau kappa;
+ *     ds = -(Hs dz + s), dkappa = -(rhs.kappa + kappa dtau) / tau, alpha = min over tau, kappa, 1 and the cones.
+ *   hipkkt_step_combined_dev  variables_combined_step_rhs! (variables.jl:124-162) + kkt_solve!(:combined) + the step length times
+ *     max_step_fraction.  scal_in9 = {tau, kappa, r_tau, dtau_aff, dkappa_aff, sigma, mu, m_corr, max_step_fraction}; the affine step
+ *     must be resident: rhs.kappa = -sigma mu + m_corr dtau_aff dkappa_aff + tau kappa, dz_aff is scaled by m_corr when m_corr != 1,
+ *     rhs.s = lambda o lambda + shift, ds_const = Delta_s_from_Delta_z_offset(rhs.s), workz = ds_const - (1 - sigma) rz,
+ *     rhs.x = (1 - sigma) rx, rhs.tau = (1 - sigma) r_tau; ds = -(Hs dz + ds_const).
+ *   scal_out15 = {alpha, dtau, dkappa, alpha_z, alpha_s of the cones for alpha_max = 1, scal_out10 of hipkkt_kkt_solve_reduced};
+ *   ir_steps2 as there (may be NULL).
+ *   hipkkt_step_apply_dev     [x | z | s] += alpha [dx | dz | ds] in place; tau and kappa are the caller's, from the scalars it has.
+ *     Not synchronised with the host: xzs_dev must stay valid until the next synchronising call on this handle has returned.
+ *   hipkkt_step_info_norms_dev  out8 = |d x|, |e z|, |einv s|, |dinv rx|, |einv rz|, |dinv rx_inf|, |einv rz_inf|, |dinv Px| (2-norms of
+ *     info_update!, info.jl:1-60), summed in a fixed order.  Needs hipkkt_set_equilibration, no scaling.
+ *   hipkkt_step_get           out = the resident step [dx | dz | ds] (n + 2 m doubles, host; tests, debugging) */
+int32_t hipkkt_step_affine_dev(hipkkt_handle h, const double *xzs_dev, const double *res_dev, const double *scal_in3, int32_t const_pending,
+                               double *scal_out15, int32_t ir_enable, double reltol, double abstol, int64_t max_iter, double stop_ratio,
+                               int64_t *ir_steps2);
+int32_t hipkkt_step_combined_dev(hipkkt_handle h, const double *xzs_dev, const double *res_dev, const double *scal_in9,
+                                 int32_t const_pending, double *scal_out15, int32_t ir_enable, double reltol, double abstol,
+                                 int64_t max_iter, double stop_ratio, int64_t *ir_steps2);
+int32_t hipkkt_step_apply_dev(hipkkt_handle h, double alpha, double *xzs_dev);
+int32_t hipkkt_step_info_norms_dev(hipkkt_handle h, const double *xzs_dev, const double *res_dev, double *out8);
+int32_t hipkkt_step_get(hipkkt_handle h, double *out);
 
 /* ---- timing (device time on the handle's stream, HIP events) ------------------------------- */
 /* out[0] = ms of last refactor (value scatter + numeric LDL), out[1] = ms of last solve call

@@ -53,3 +53,74 @@ function hip_linear_solver_info(handle::Ptr{Cvoid})
     ccall((:hipkkt_info, libhipkkt), Int32, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), handle, nnzA, nnzL)
     LinearSolverInfo(:hip, 1, true, nnzA[], nnzL[])
 end
+
+# ---- the interior-point step on the device (include/hipkkt.h hipkkt_cone_* / hipkkt_step_*), Zero / Nonnegative / SecondOrder cone sets.
+# Thin wrappers on the handle: the solver object of kktsolver_hip.jl passes ks.handle.  The *_dev arguments are DEVICE pointers (e.g.
+# pointer(::ROCArray{Float64})): xzs = [x | z | s], res = [rx | rz | rx_inf | rz_inf | Px], the buffers of hipkkt_residuals_dev.
+# INTEGRATION.md ("The step on the device") says which hooks of the core would call them and how long the buffers must live.
+hip_step_check(handle::Ptr{Cvoid}, rc::Int32, what::String) =
+    rc < 0 ? error("$what failed ($rc): " * hip_last_error(handle)) : rc == 0
+
+function hip_cone_affine_ds!(handle::Ptr{Cvoid}, ds::Vector{Float64})
+    rc = ccall((:hipkkt_cone_affine_ds, libhipkkt), Int32, (Ptr{Cvoid}, Ptr{Float64}), handle, ds)
+    return hip_step_check(handle, rc, "hipkkt_cone_affine_ds")
+end
+function hip_cone_combined_ds_shift!(handle::Ptr{Cvoid}, shift::Vector{Float64}, step_z::Vector{Float64}, step_s::Vector{Float64}, σμ::Float64)
+    rc = ccall((:hipkkt_cone_combined_ds_shift, libhipkkt), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Float64, Ptr{Float64}),
+               handle, step_z, step_s, σμ, shift)
+    return hip_step_check(handle, rc, "hipkkt_cone_combined_ds_shift")
+end
+function hip_cone_ds_from_dz_offset!(handle::Ptr{Cvoid}, out::Vector{Float64}, ds::Vector{Float64})
+    rc = ccall((:hipkkt_cone_ds_from_dz_offset, libhipkkt), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), handle, ds, out)
+    return hip_step_check(handle, rc, "hipkkt_cone_ds_from_dz_offset")
+end
+function hip_cone_mul_hs!(handle::Ptr{Cvoid}, y::Vector{Float64}, x::Vector{Float64})
+    rc = ccall((:hipkkt_cone_mul_hs, libhipkkt), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), handle, x, y)
+    return hip_step_check(handle, rc, "hipkkt_cone_mul_hs")
+end
+function hip_cone_step_length(handle::Ptr{Cvoid}, dz::Vector{Float64}, ds::Vector{Float64}, αmax::Float64)
+    out = zeros(Float64, 2)
+    rc = ccall((:hipkkt_cone_step_length, libhipkkt), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Float64, Ptr{Float64}),
+               handle, dz, ds, αmax, out)
+    hip_step_check(handle, rc, "hipkkt_cone_step_length")
+    return (out[1], out[2])
+end
+function hip_set_equilibration!(handle::Ptr{Cvoid}, d::Vector{Float64}, e::Vector{Float64})
+    rc = ccall((:hipkkt_set_equilibration, libhipkkt), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), handle, d, e)
+    return hip_step_check(handle, rc, "hipkkt_set_equilibration")
+end
+# -> (is_success, scal_out15 = α, Δτ, Δκ, α_z, α_s, the ten scalars of hipkkt_kkt_solve_reduced); ir = (enable, reltol, abstol, max_iter, stop_ratio)
+function hip_step_affine_dev!(handle::Ptr{Cvoid}, xzs_dev::Ptr{Float64}, res_dev::Ptr{Float64}, τ::Float64, κ::Float64, rτ::Float64,
+                              const_pending::Bool, ir::Tuple{Bool,Float64,Float64,Int64,Float64})
+    scal_in = Float64[τ, κ, rτ]
+    scal_out = zeros(Float64, 15)
+    rc = ccall((:hipkkt_step_affine_dev, libhipkkt), Int32,
+               (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}, Int32, Float64, Float64, Int64, Float64, Ptr{Int64}),
+               handle, xzs_dev, res_dev, scal_in, const_pending ? 1 : 0, scal_out, ir[1], ir[2], ir[3], ir[4], ir[5], C_NULL)
+    return (hip_step_check(handle, rc, "hipkkt_step_affine_dev"), scal_out)
+end
+function hip_step_combined_dev!(handle::Ptr{Cvoid}, xzs_dev::Ptr{Float64}, res_dev::Ptr{Float64}, τ::Float64, κ::Float64, rτ::Float64,
+                                Δτ_aff::Float64, Δκ_aff::Float64, σ::Float64, μ::Float64, m_corr::Float64, max_step_fraction::Float64,
+                                ir::Tuple{Bool,Float64,Float64,Int64,Float64})
+    scal_in = Float64[τ, κ, rτ, Δτ_aff, Δκ_aff, σ, μ, m_corr, max_step_fraction]
+    scal_out = zeros(Float64, 15)
+    rc = ccall((:hipkkt_step_combined_dev, libhipkkt), Int32,
+               (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}, Int32, Float64, Float64, Int64, Float64, Ptr{Int64}),
+               handle, xzs_dev, res_dev, scal_in, 0, scal_out, ir[1], ir[2], ir[3], ir[4], ir[5], C_NULL)
+    return (hip_step_check(handle, rc, "hipkkt_step_combined_dev"), scal_out)
+end
+# not synchronised with the host: xzs_dev stays valid (and is not read by the host) until the next synchronising call on the handle
+function hip_step_apply_dev!(handle::Ptr{Cvoid}, α::Float64, xzs_dev::Ptr{Float64})
+    rc = ccall((:hipkkt_step_apply_dev, libhipkkt), Int32, (Ptr{Cvoid}, Float64, Ptr{Float64}), handle, α, xzs_dev)
+    return hip_step_check(handle, rc, "hipkkt_step_apply_dev")
+end
+function hip_step_info_norms_dev(handle::Ptr{Cvoid}, xzs_dev::Ptr{Float64}, res_dev::Ptr{Float64})
+    out = zeros(Float64, 8)
+    rc = ccall((:hipkkt_step_info_norms_dev, libhipkkt), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), handle, xzs_dev, res_dev, out)
+    hip_step_check(handle, rc, "hipkkt_step_info_norms_dev")
+    return out
+end
+function hip_step_get!(handle::Ptr{Cvoid}, out::Vector{Float64})
+    rc = ccall((:hipkkt_step_get, libhipkkt), Int32, (Ptr{Cvoid}, Ptr{Float64}), handle, out)
+    return hip_step_check(handle, rc, "hipkkt_step_get")
+end

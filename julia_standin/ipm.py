@@ -389,8 +389,18 @@ class Solver:
         ks = self.kktsystem.kktsolver
         self._device_residuals = bool(getattr(st, "device_residuals", False)) and hasattr(ks, "residuals_update")
         self._needs_qb = self._device_residuals or (bool(getattr(st, "device_reduced", False)) and hasattr(ks, "kktsolver_kkt_solve_reduced"))
+        # the cone algebra of the step on a device-resident iterate (settings.py device_step): Zero / Nonnegative / SecondOrder cone sets on
+        # a plugin that offers it; any other cone set silently takes the host loop, as the other device_* flags do
+        if getattr(st, "device_step", False) and not (getattr(st, "device_scaling", False) and getattr(st, "device_reduced", False)
+                                                      and getattr(st, "device_residuals", False)):
+            raise ValueError("Settings.device_step needs device_scaling, device_reduced and device_residuals")
+        self._device_step = bool(getattr(st, "device_step", False)) and hasattr(ks, "kktsolver_step_affine") and \
+            bool(getattr(ks, "steps_on_device", False))
+        self._needs_qb = self._needs_qb or (self._device_step and hasattr(ks, "set_problem_vectors"))
         if self._needs_qb:               # q, b resident in the plugin (N4 residuals, N2 reduced-system algebra)
             ks.set_problem_vectors(data.q, data.b)
+        if self._device_step:
+            ks.set_equilibration(data.d, data.e)
         self.info = Info()
         self.info.timers["kkt init"] = time.perf_counter() - t1
         self.step_lhs = Variables.zeros(n, m)
@@ -448,7 +458,8 @@ class Solver:
         r.dot_qx, r.dot_bz, r.dot_sz, r.dot_xPx = qx, bz, sz, xPx
 
     # ------------------------------------------------------------- info.jl:1-60
-    def _info_update(self, t_start):
+    def _info_update(self, t_start, norms=None):
+        """norms: the eight scaled 2-norms from the plugin (device_step), in the order they are first used below"""
         info, data, v, r = self.info, self.data, self.variables, self.residuals
         tauinv = 1.0 / v.tau
         normb = data.get_normb()
@@ -458,17 +469,23 @@ class Solver:
         xPx2 = r.dot_xPx * tauinv * tauinv / 2.0
         info.cost_primal = (r.dot_qx * tauinv + xPx2) * cinv
         info.cost_dual = (-r.dot_bz * tauinv - xPx2) * cinv
-        normx = _norm_scaled(d, v.x)
-        normz = _norm_scaled(e, v.z) * cinv
-        norms = _norm_scaled(einv, v.s)
-        info.res_primal_inf = (_norm_scaled(dinv, r.rx_inf) * cinv) / max(1.0, normz)
-        info.res_dual_inf = max(_norm_scaled(dinv, r.Px) / max(1.0, normx),
-                                _norm_scaled(einv, r.rz_inf) / max(1.0, normx + norms))
+        if norms is None:
+            n_dx, n_ez, n_es = _norm_scaled(d, v.x), _norm_scaled(e, v.z), _norm_scaled(einv, v.s)
+            n_rx, n_rz = _norm_scaled(dinv, r.rx), _norm_scaled(einv, r.rz)
+            n_rxinf, n_rzinf, n_Px = _norm_scaled(dinv, r.rx_inf), _norm_scaled(einv, r.rz_inf), _norm_scaled(dinv, r.Px)
+        else:
+            n_dx, n_ez, n_es, n_rx, n_rz, n_rxinf, n_rzinf, n_Px = (float(t) for t in norms)
+        normx = n_dx
+        normz = n_ez * cinv
+        norms = n_es
+        info.res_primal_inf = (n_rxinf * cinv) / max(1.0, normz)
+        info.res_dual_inf = max(n_Px / max(1.0, normx),
+                                n_rzinf / max(1.0, normx + norms))
         normx *= tauinv
         normz *= tauinv
         norms *= tauinv
-        info.res_primal = _norm_scaled(einv, r.rz) * tauinv / max(1.0, normb + normx + norms)
-        info.res_dual = _norm_scaled(dinv, r.rx) * tauinv * cinv / max(1.0, normq + normx + normz)
+        info.res_primal = n_rz * tauinv / max(1.0, normb + normx + norms)
+        info.res_dual = n_rx * tauinv * cinv / max(1.0, normq + normx + normz)
         info.gap_abs = abs(info.cost_primal - info.cost_dual)
         info.gap_rel = info.gap_abs / max(1.0, min(abs(info.cost_primal), abs(info.cost_dual)))
         info.ktratio = v.kappa * tauinv
@@ -509,18 +526,24 @@ class Solver:
                 info.status = MAX_TIME
         return info.status != UNSOLVED
 
-    def _save_prev_iterate(self):
+    def _save_prev_info(self):
         i = self.info
         i.prev_cost_primal, i.prev_cost_dual = i.cost_primal, i.cost_dual
         i.prev_res_primal, i.prev_res_dual = i.res_primal, i.res_dual
         i.prev_gap_abs, i.prev_gap_rel = i.gap_abs, i.gap_rel
-        self.prev_vars.copy_from(self.variables)
 
-    def _reset_to_prev_iterate(self):
+    def _reset_info_to_prev(self):
         i = self.info
         i.cost_primal, i.cost_dual = i.prev_cost_primal, i.prev_cost_dual
         i.res_primal, i.res_dual = i.prev_res_primal, i.prev_res_dual
         i.gap_abs, i.gap_rel = i.prev_gap_abs, i.prev_gap_rel
+
+    def _save_prev_iterate(self):
+        self._save_prev_info()
+        self.prev_vars.copy_from(self.variables)
+
+    def _reset_to_prev_iterate(self):
+        self._reset_info_to_prev()
         self.variables.copy_from(self.prev_vars)
 
     # ------------------------------------------------------------- variables.jl
@@ -594,12 +617,96 @@ class Solver:
         """The reference's host-side vector algebra is single-threaded Julia; numpy's OpenBLAS instead spins up a thread
         team for every 20k-element ``dot`` (4 ms instead of 4 us on an 8-core box), so the BLAS pool is limited to one
         thread while the loop runs."""
+        loop = self._solve_device_step if self._device_step else self._solve
         try:
             from threadpoolctl import threadpool_limits
         except ImportError:          # pragma: no cover - threadpoolctl ships with the image
-            return self._solve()
+            return loop()
         with threadpool_limits(limits=1, user_api="blas"):
-            return self._solve()
+            return loop()
+
+    # ------------------------------------------------------------- solver.jl:189-380 with the step on the device
+    def _solve_device_step(self):
+        """The loop of _solve for Settings.device_step: [x | z | s] and the residual buffer live in device memory for the whole solve and
+        the plugin does residuals, norms, scaling, both steps and the update there; tau, kappa, the termination test, sigma and the
+        strategy checkpoints stay here, fed by scalars.  Zero / Nonnegative / SecondOrder cone sets (symmetric: PrimalDual scaling, no
+        backtracking).  The default start runs on the host as in _solve and is uploaded once; the iterate comes back once, at the end."""
+        st, info, data, cones = self.settings, self.info, self.data, self.cones
+        v, r = self.variables, self.residuals
+        ks = self.kktsystem.kktsolver
+        n, m = data.n, data.m
+        tm = info.timers
+        for k in ("kkt update", "kkt solve", "scale cones", "default start"):
+            tm[k] = 0.0
+        it = 0
+        sigma, alpha, mu = 1.0, 0.0, FLOATMAX
+        info.status = UNSOLVED
+        info.iterations = 0
+        t_start = time.perf_counter()
+        t0 = time.perf_counter()
+        self._default_start()
+        xzs, res, prev = ks.device_buffer(n + 2 * m), ks.device_buffer(3 * n + 2 * m), ks.device_buffer(n + 2 * m)
+        xzs.upload(np.concatenate([v.x, v.z, v.s]))
+        prev_tau, prev_kappa = v.tau, v.kappa
+        tm["default start"] = time.perf_counter() - t0
+        t_loop = time.perf_counter()
+        while True:
+            r.dot_qx, r.dot_bz, r.dot_sz, r.dot_xPx, r.rtau = ks.residuals_update_dev(xzs, res, v.tau, v.kappa)
+            mu = (r.dot_sz + v.tau * v.kappa) / (cones.degree + 1)
+            info.mu, info.step_length, info.sigma, info.iterations = mu, alpha, sigma, it
+            self._info_update(t_start, norms=ks.kktsolver_info_norms(xzs, res))
+            if st.verbose:
+                print(f"{it:3d}  pcost {info.cost_primal: .4e}  dcost {info.cost_dual: .4e}  gap {info.gap_abs:.2e}"
+                      f"  pres {info.res_primal:.2e}  dres {info.res_dual:.2e}  k/t {info.ktratio:.2e}"
+                      f"  mu {mu:.2e}  step {alpha:.2e}")
+            if self.trace is not None:
+                self.trace.append(dict(iter=it, mu=mu, alpha=alpha, sigma=sigma, cost_primal=info.cost_primal,
+                                       cost_dual=info.cost_dual, res_primal=info.res_primal,
+                                       res_dual=info.res_dual, ktratio=info.ktratio))
+            if self._check_termination(it):
+                if info.status == INSUFFICIENT_PROGRESS:      # _strategy_checkpoint_insufficient_progress (:453-473)
+                    self._reset_info_to_prev()
+                    xzs.copy_from(prev)
+                    v.tau, v.kappa = prev_tau, prev_kappa
+                break
+            t0 = time.perf_counter()
+            ok_scaling = ks.kktsolver_update_scaling_dev(xzs)
+            tm["scale cones"] += time.perf_counter() - t0
+            if not ok_scaling:
+                info.status = NUMERICAL_ERROR
+                break
+            it += 1
+            t0 = time.perf_counter()
+            ok = ks.kktsolver_refactor()
+            tm["kkt update"] += time.perf_counter() - t0
+            t0 = time.perf_counter()
+            if ok:      # the constant-rhs solve of kkt_update! runs next to the affine solve, its solution stays resident
+                ok, alpha, dtau_aff, dkappa_aff = ks.kktsolver_step_affine(xzs, res, v.tau, v.kappa, r.rtau, True)
+            if ok:
+                sigma = (1.0 - alpha) ** 3
+                mcorr = 1.0 if it > 1 else alpha
+                ok, alpha, dtau, dkappa = ks.kktsolver_step_combined(xzs, res, v.tau, v.kappa, r.rtau, dtau_aff, dkappa_aff, sigma, mu,
+                                                                     mcorr)
+            tm["kkt solve"] += time.perf_counter() - t0
+            if not ok:  # _strategy_checkpoint_numerical_error (:476-490)
+                alpha = 0.0
+                info.status = NUMERICAL_ERROR
+                break
+            if alpha <= max(0.0, st.min_terminate_step_length):      # _strategy_checkpoint_small_step (:493-506)
+                info.status = INSUFFICIENT_PROGRESS
+                alpha = 0.0
+                break
+            self._save_prev_info()
+            prev.copy_from(xzs)
+            prev_tau, prev_kappa = v.tau, v.kappa
+            ks.kktsolver_step_apply(alpha, xzs)
+            v.tau += alpha * dtau
+            v.kappa += alpha * dkappa
+        back = xzs.download()
+        v.x[:], v.z[:], v.s[:] = back[:n], back[n:n + m], back[n + m:]
+        for b in (xzs, res, prev):
+            b.close()
+        return self._finish(t_start, t_loop, alpha, sigma, mu, it)
 
     # ------------------------------------------------------------- solver.jl:189-380
     def _solve(self):
@@ -705,6 +812,10 @@ class Solver:
             v.z += alpha * lhs.z
             v.tau += alpha * lhs.tau
             v.kappa += alpha * lhs.kappa
+        return self._finish(t_start, t_loop, alpha, sigma, mu, it)
+
+    def _finish(self, t_start, t_loop, alpha, sigma, mu, it):
+        st, info, data, v, tm = self.settings, self.info, self.data, self.variables, self.info.timers
         tm["IP iteration"] = time.perf_counter() - t_loop
         if alpha == 0.0:
             info.mu, info.step_length, info.sigma, info.iterations = mu, alpha, sigma, it

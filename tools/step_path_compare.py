@@ -1,0 +1,75 @@
+"""Developer tool: what Settings.device_step changes end to end.  Every configuration is solved by the numpy stand-in caller in ONE
+process on one GPU, first with device_scaling + device_reduced + device_residuals (the best path without the feature: the cone
+algebra between the device calls runs on the host, the iterate crosses PCIe several times per iteration), then with device_step
+added (the iterate stays in device memory, scalars cross).  Per path: one warm-up solve, then `--repeats` timed solves; the medians of
+wall time per iteration and of the stand-in's timers, the bytes the Python binding moved per iteration in each direction
+(clarabel.jl_amd/hipkkt.py TRAFFIC) and hipkkt_box_probe go into ONE JSON line on stdout.
+usage: step_path_compare.py [--cfgs 3,2a] [--repeats 5] [--one-solve CFG]   (--one-solve: a single device_step solve, for a kernel trace)"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import clarabel_jl_amd  # noqa: E402,F401
+import julia_standin as cl  # noqa: E402
+from clarabel_jl_amd import hipkkt, problems  # noqa: E402
+
+CONFIGS = {"3": ("portfolio_socp", problems.portfolio_socp), "2a": ("random_sparse_qp", problems.random_sparse_qp)}
+PARENT = dict(device_scaling=True, device_reduced=True, device_residuals=True)
+
+
+def one_solve(prob, **flags):
+    solver = cl.Solver(*prob, cl.Settings(**flags))
+    for k in hipkkt.TRAFFIC:
+        hipkkt.TRAFFIC[k] = 0
+    sol = solver.solve()
+    it = max(sol.iterations, 1)
+    tm = solver.info.timers
+    rec = dict(status=sol.status, iterations=sol.iterations, obj_val=sol.obj_val, device_step=bool(solver._device_step),
+               ms_per_iteration=1e3 * tm["IP iteration"] / it,
+               timers_ms_per_iteration={k: 1e3 * tm[k] / it for k in ("kkt update", "kkt solve", "scale cones")},
+               default_start_ms=1e3 * tm["default start"],
+               h2d_bytes_per_iteration=hipkkt.TRAFFIC["h2d_bytes"] / it, d2h_bytes_per_iteration=hipkkt.TRAFFIC["d2h_bytes"] / it)
+    return rec
+
+
+def median_of(runs):
+    out = dict(runs[0])
+    out["ms_per_iteration"] = statistics.median(r["ms_per_iteration"] for r in runs)
+    out["ms_per_iteration_all"] = [round(r["ms_per_iteration"], 4) for r in runs]
+    out["timers_ms_per_iteration"] = {k: statistics.median(r["timers_ms_per_iteration"][k] for r in runs)
+                                      for k in runs[0]["timers_ms_per_iteration"]}
+    out["default_start_ms"] = statistics.median(r["default_start_ms"] for r in runs)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--cfgs", default="3,2a")
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--one-solve", default=None)
+    args = ap.parse_args()
+    if args.one_solve:
+        rec = one_solve(CONFIGS[args.one_solve][1](), device_step=True, **PARENT)
+        print(json.dumps({"cfg": args.one_solve, "device_step": rec}))
+        return
+    result = {"tool": "step_path_compare", "repeats": args.repeats, "configs": {}}
+    for cfg in args.cfgs.split(","):
+        name, make = CONFIGS[cfg]
+        prob = make()
+        paths = {}
+        for label, flags in (("host_cone_algebra", PARENT), ("device_step", dict(device_step=True, **PARENT))):
+            one_solve(prob, **flags)                                   # warm-up: plan cache, graphs, code objects
+            paths[label] = median_of([one_solve(prob, **flags) for _ in range(args.repeats)])
+        assert paths["device_step"]["device_step"] and not paths["host_cone_algebra"]["device_step"]
+        result["configs"][cfg] = dict(problem=name, **paths,
+                                      speedup=paths["host_cone_algebra"]["ms_per_iteration"] / paths["device_step"]["ms_per_iteration"])
+    result["box_probe"] = hipkkt.box_probe(0)
+    print(json.dumps(result))
+
+
+if __name__ == "__main__":
+    main()
