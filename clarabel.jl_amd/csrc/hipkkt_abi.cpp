@@ -399,6 +399,16 @@ static int32_t set_cone_types_impl(hipkkt_handle h, int64_t ncones, const int32_
     S->sc_scaled = false;
     S->sc_step_kinds = true;
     for (int64_t c = 0; c < ncones; c++) S->sc_step_kinds = S->sc_step_kinds && kinds[c] >= 0 && kinds[c] <= 2;
+    // hipkkt_step_enable_cone3 is per registration: kinds {0, 1, 2, 4, 5} with at least one Exponential / Power cone qualify
+    S->st_cone3 = false;
+    S->sc_cone3_kinds = ex;
+    bool any3 = false;
+    for (int64_t c = 0; c < ncones; c++) {
+        const bool three = kinds[c] == HIPKKT_CONE_EXP || kinds[c] == HIPKKT_CONE_POW;
+        S->sc_cone3_kinds = S->sc_cone3_kinds && ((kinds[c] >= 0 && kinds[c] <= 2) || three);
+        any3 = any3 || three;
+    }
+    S->sc_cone3_kinds = S->sc_cone3_kinds && any3;
     // the non-symmetric cones: three-row cones in two lists (joined [Exponential | Power] below), GenPower descriptors of 8 values
     struct Row3 { int64_t row0, hs0, out0; double alpha; };
     std::vector<Row3> exp3, pow3;
@@ -563,7 +573,7 @@ static int32_t update_scaling_impl(hipkkt_handle h, const double *s, const doubl
             HK_CHECK(hipMemcpyAsync(S->d_sc_R, psd_R, (size_t)S->sc_psd_total * sizeof(double), hipMemcpyHostToDevice, S->stream));
             dR = S->d_sc_R;
         }
-    } else if (m && S->sc_step_kinds) {      // the step entry points read the resident copy of (s, z)
+    } else if (m && (S->sc_step_kinds || S->st_cone3)) {      // the step entry points read the resident copy of (s, z)
         HK_CHECK(hipMemcpyAsync(S->d_sc_sz, s, m * sizeof(double), hipMemcpyDeviceToDevice, S->stream));
         HK_CHECK(hipMemcpyAsync(S->d_sc_sz + m, z, m * sizeof(double), hipMemcpyDeviceToDevice, S->stream));
     }

@@ -250,6 +250,12 @@ struct hipkkt_solver {
     double *d_st_part = nullptr, *d_st_out = nullptr;      // partial results of the step length / the norms; 2 + 8 results
     double *d_st_eq = nullptr;                             // [d | e | dinv | einv] (hipkkt_set_equilibration)
     bool st_have_step = false;
+    // hipkkt_step_enable_cone3: the step entry points also serve the Exponential / Power cones of the registration (step_cone3.hip)
+    bool sc_cone3_kinds = false;                           // the registration names kinds {0, 1, 2, 4, 5} only, at least one 4 / 5
+    bool st_cone3 = false;                                 // enabled since that registration
+    double st_c3_step = 0.0, st_c3_amin = 0.0;             // linesearch_backtrack_step, min_terminate_step_length
+    int st_c3_trips = 0;                                   // bound of the backtracking loop: ceil(log amin / log step) + 2
+    double *d_st_bar = nullptr;                            // work buffer of the barrier (step3_barrier_doubles)
     // N1, the non-symmetric cones (hipkkt_set_cone_types_ex + hipkkt_update_scaling_ex): tables built once per registration
     bool ns_active = false;                                // the last registration named an Exponential / Power / GenPower cone
     int ns_nexp = 0, ns_npow = 0, ns_ngenpow = 0;

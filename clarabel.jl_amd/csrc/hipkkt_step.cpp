@@ -1,6 +1,8 @@
 // The cone algebra of an interior-point step on the device (step.hip) and its fusion with the reduced solve of hipkkt_solve.cpp:
 // hipkkt_cone_* (one operation each, host pointers), hipkkt_set_equilibration, hipkkt_step_* (everything resident, scalars only cross
 // PCIe).  Zero, Nonnegative and SecondOrder cones; they work on the (s, z, w, lambda, eta) of the last successful hipkkt_update_scaling.
+// After hipkkt_step_enable_cone3 also the Exponential / Power cones of the registration (step_cone3.hip), on the (s, z) and the
+// [Hs | H_dual | grad] that hipkkt_update_scaling_ex[_dev] left resident; then hipkkt_cone_barrier / hipkkt_step_barrier_dev as well.
 #include "hipkkt_internal.h"
 
 #pragma clang fp contract(off)      // the scalars below repeat the caller's expressions (variables.jl:14-43, :124-162) rounding by rounding
@@ -9,8 +11,9 @@ namespace hipkkt_host {
 
 // the cone set and its scaling allow the step entry points
 static bool step_ready(hipkkt_solver *S, const char *who) {
-    if (!S->l1 || !S->sc_ready || !S->sc_step_kinds) {
-        S->err = std::string(who) + ": needs an L1 handle whose registered cones are Zero / Nonnegative / SecondOrder only";
+    if (!S->l1 || !S->sc_ready || !(S->sc_step_kinds || S->st_cone3)) {
+        S->err = std::string(who) + ": needs an L1 handle whose registered cones are Zero / Nonnegative / SecondOrder only, or one with "
+                                    "Exponential / Power cones next to them after hipkkt_step_enable_cone3";
         return false;
     }
     if (!S->sc_scaled) { S->err = std::string(who) + ": no successful hipkkt_update_scaling since the cones were registered"; return false; }
@@ -25,17 +28,58 @@ static void ensure_step_buffers(hipkkt_solver *S) {
     S->d_st_in = S->dalloc<double>(2 * n + m);
     S->d_st_work = S->dalloc<double>(4 * m);
     S->d_st_part = S->dalloc<double>((size_t)std::max<int64_t>(2 * pairs, step_norm_part_doubles()));
-    S->d_st_out = S->dalloc<double>(16);
+    S->d_st_out = S->dalloc<double>(32);      // 0..3 step lengths, 4..11 norms, 12..27 barrier results
+    S->d_st_bar = S->dalloc<double>((size_t)step3_barrier_doubles((int64_t)S->cone_numel.size()));
 }
 
 struct ConeTables {
     const signed char *kind; int nsoc; const int64_t *desc;
     const double *s, *z, *w, *lam, *eta;
     int64_t m;
+    // the Exponential / Power cones of an enabled handle (all zero otherwise): tables [Exponential | Power], the scaling's output vector
+    int nexp, npow, n3;
+    const int64_t *row0, *out0;
+    const double *alpha, *nsout;
 };
 static ConeTables tables(hipkkt_solver *S) {
     const int64_t m = S->img.m;
-    return {S->d_sc_kind, S->sc_nsoc, S->d_sc_socdesc, S->d_sc_sz, S->d_sc_sz + m, S->d_sc_wl, S->d_sc_wl + m, S->d_sc_eta, m};
+    ConeTables T{S->d_sc_kind, S->sc_nsoc, S->d_sc_socdesc, S->d_sc_sz, S->d_sc_sz + m, S->d_sc_wl, S->d_sc_wl + m, S->d_sc_eta, m,
+                 0, 0, 0, nullptr, nullptr, nullptr, nullptr};
+    if (S->st_cone3) {
+        T.nexp = S->ns_nexp; T.npow = S->ns_npow; T.n3 = T.nexp + T.npow;
+        T.row0 = S->d_ns_row0; T.out0 = S->d_ns_out0; T.alpha = S->d_ns_alpha; T.nsout = S->d_ns_out;
+    }
+    return T;
+}
+
+// every operation: the kernels of step.hip on the Zero / Nonnegative / SecondOrder rows (unchanged), then the Exponential / Power rows
+static void op_affine_ds(hipStream_t st, const ConeTables &T, double *out) {
+    launch_step_affine_ds(st, T.kind, T.nsoc, T.desc, T.lam, out, T.m);
+    launch_step3_copy(st, T.n3, T.row0, T.s, out);
+}
+static void op_shift(hipStream_t st, const ConeTables &T, const double *dz, const double *ds, double sigma_mu, double *out) {
+    launch_step_shift(st, T.kind, T.nsoc, T.desc, T.w, T.eta, dz, ds, sigma_mu, out, T.m);
+    if (T.n3) launch_step3_shift(st, T.nexp, T.npow, T.row0, T.out0, T.alpha, T.nsout, T.z, dz, ds, sigma_mu, out);
+}
+static void op_offset(hipStream_t st, const ConeTables &T, const double *ds, double *out) {
+    launch_step_offset(st, T.kind, T.nsoc, T.desc, T.z, T.w, T.lam, T.eta, ds, out, T.m);
+    launch_step3_copy(st, T.n3, T.row0, ds, out);
+}
+static void op_mulhs(hipStream_t st, const ConeTables &T, const double *x, const double *addc, double *y) {
+    launch_step_mulhs(st, T.kind, T.nsoc, T.desc, T.w, T.eta, x, addc, y, T.m);
+    launch_step3_mulhs(st, T.n3, T.row0, T.out0, T.nsout, x, addc, y);
+}
+// out2 = (alpha_z, alpha_s) of the symmetric cones; with Exponential / Power cones the composite (alpha, alpha) of
+// coneops_compositecone.jl:216-252, started from min(alpha_tau, alpha_kappa, 1) when dtau (device) is given (variables.jl:14-43)
+static void op_length(hipkkt_solver *S, hipStream_t st, const ConeTables &T, const double *dz, const double *ds, double alpha_max,
+                      const double *dtau, double tau, double kappa, double rhs_kappa, double *out2) {
+    if (!T.n3) {
+        launch_step_length(st, T.kind, T.nsoc, T.desc, T.z, T.s, dz, ds, alpha_max, S->d_st_part, out2, T.m);
+        return;
+    }
+    launch_step_length(st, T.kind, T.nsoc, T.desc, T.z, T.s, dz, ds, alpha_max, S->d_st_part, S->d_st_out, T.m);
+    launch_step3_length(st, T.nexp, T.npow, T.row0, T.alpha, T.z, T.s, dz, ds, S->d_st_out, dtau, tau, kappa, rhs_kappa, alpha_max,
+                        S->st_c3_step, S->st_c3_amin, S->st_c3_trips, S->d_st_part, out2);
 }
 
 // one operation on host vectors of length m: `nin` inputs are staged, op(in0, in1, out) runs, `nout` doubles come back
@@ -43,7 +87,7 @@ template <class F>
 static int32_t cone_op_host(hipkkt_solver *S, const double *in0, const double *in1, double *out, int64_t nout, F &&op) {
     const int64_t m = S->img.m;
     ensure_step_buffers(S);
-    S->ensure_stage(3 * m + 2);
+    S->ensure_stage(3 * m + 2 + 2 * step3_max_candidates());
     double *d0 = S->d_stage, *d1 = d0 + m, *dout = d1 + m;
     if (in0 && m) HK_CHECK(hipMemcpyAsync(d0, in0, m * sizeof(double), hipMemcpyHostToDevice, S->stream));
     if (in1 && m) HK_CHECK(hipMemcpyAsync(d1, in1, m * sizeof(double), hipMemcpyHostToDevice, S->stream));
@@ -68,9 +112,11 @@ static int32_t fused_solve(hipkkt_solver *S, const StepScalars &sc, const double
     const std::function<void(hipStream_t, const double *)> after = [&](hipStream_t st, const double *d_lhs) {
         double *dz = S->d_st_step + n, *ds = dz + m;
         HK_CHECK(hipMemcpyAsync(S->d_st_step, d_lhs, (size_t)(n + m) * sizeof(double), hipMemcpyDeviceToDevice, st));
-        launch_step_mulhs(st, T.kind, T.nsoc, T.desc, T.w, T.eta, dz, addc, ds, m);
-        launch_step_length(st, T.kind, T.nsoc, T.desc, T.z, T.s, dz, ds, 1.0, S->d_st_part, S->d_st_out, m);
-        HK_CHECK(hipMemcpyAsync(h2, S->d_st_out, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+        op_mulhs(st, T, dz, addc, ds);
+        // (with Exponential / Power cones the line search starts from min(alpha_tau, alpha_kappa, 1): dtau is the reduction's first scalar)
+        double *out2 = T.n3 ? S->d_st_out + 2 : S->d_st_out;
+        op_length(S, st, T, dz, ds, 1.0, S->d_red + 3 * (size_t)S->N + n, sc.tau, sc.kappa, sc.rhs_kappa, out2);
+        HK_CHECK(hipMemcpyAsync(h2, out2, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
     };
     const double scal_in[4] = {sc.tau, sc.kappa, sc.rhs_tau, sc.rhs_kappa};
     double red[10];
@@ -101,7 +147,7 @@ int32_t hipkkt_cone_affine_ds(hipkkt_handle h, double *ds_out) {
     if (!step_ready(S, "cone_affine_ds") || (S->img.m && !ds_out)) return HIPKKT_ERR_ARGUMENT;
     const ConeTables T = tables(S);
     return cone_op_host(S, nullptr, nullptr, ds_out, T.m, [&](double *, double *, double *out) {
-        launch_step_affine_ds(S->stream, T.kind, T.nsoc, T.desc, T.lam, out, T.m);
+        op_affine_ds(S->stream, T, out);
     });
     HK_LEAVE
 }
@@ -111,7 +157,7 @@ int32_t hipkkt_cone_combined_ds_shift(hipkkt_handle h, const double *step_z, con
     if (!step_ready(S, "cone_combined_ds_shift") || (S->img.m && (!step_z || !step_s || !shift_out))) return HIPKKT_ERR_ARGUMENT;
     const ConeTables T = tables(S);
     return cone_op_host(S, step_z, step_s, shift_out, T.m, [&](double *dz, double *ds, double *out) {
-        launch_step_shift(S->stream, T.kind, T.nsoc, T.desc, T.w, T.eta, dz, ds, sigma_mu, out, T.m);
+        op_shift(S->stream, T, dz, ds, sigma_mu, out);
     });
     HK_LEAVE
 }
@@ -121,7 +167,7 @@ int32_t hipkkt_cone_ds_from_dz_offset(hipkkt_handle h, const double *ds, double 
     if (!step_ready(S, "cone_ds_from_dz_offset") || (S->img.m && (!ds || !out))) return HIPKKT_ERR_ARGUMENT;
     const ConeTables T = tables(S);
     return cone_op_host(S, ds, nullptr, out, T.m, [&](double *dds, double *, double *dout) {
-        launch_step_offset(S->stream, T.kind, T.nsoc, T.desc, T.z, T.w, T.lam, T.eta, dds, dout, T.m);
+        op_offset(S->stream, T, dds, dout);
     });
     HK_LEAVE
 }
@@ -131,7 +177,7 @@ int32_t hipkkt_cone_mul_hs(hipkkt_handle h, const double *x, double *y_out) {
     if (!step_ready(S, "cone_mul_hs") || (S->img.m && (!x || !y_out))) return HIPKKT_ERR_ARGUMENT;
     const ConeTables T = tables(S);
     return cone_op_host(S, x, nullptr, y_out, T.m, [&](double *dx, double *, double *dy) {
-        launch_step_mulhs(S->stream, T.kind, T.nsoc, T.desc, T.w, T.eta, dx, nullptr, dy, T.m);
+        op_mulhs(S->stream, T, dx, nullptr, dy);
     });
     HK_LEAVE
 }
@@ -141,8 +187,68 @@ int32_t hipkkt_cone_step_length(hipkkt_handle h, const double *dz, const double 
     if (!step_ready(S, "cone_step_length") || !alpha_out2 || (S->img.m && (!dz || !ds))) return HIPKKT_ERR_ARGUMENT;
     const ConeTables T = tables(S);
     return cone_op_host(S, dz, ds, alpha_out2, 2, [&](double *ddz, double *dds, double *dout) {
-        launch_step_length(S->stream, T.kind, T.nsoc, T.desc, T.z, T.s, ddz, dds, alpha_max, S->d_st_part, dout, T.m);
+        op_length(S, S->stream, T, ddz, dds, alpha_max, nullptr, 0.0, 0.0, 0.0, dout);
     });
+    HK_LEAVE
+}
+
+// the barrier of the cone set and the shifted <z, s> at nalpha candidates: (z, s, dz, ds) and dout are device pointers
+// (without the enable T names no Exponential / Power cone: the symmetric cones' barrier)
+static void barrier_impl(hipkkt_solver *S, const ConeTables &T, const double *z, const double *s, const double *dz, const double *ds,
+                         const double *alphas, int64_t nalpha, double *dout) {
+    launch_step3_barrier(S->stream, T.kind, T.nsoc, T.desc, T.nexp, T.npow, T.row0, T.alpha, z, s, dz, ds, alphas, (int)nalpha,
+                         S->d_st_bar, dout, T.m);
+}
+
+int32_t hipkkt_step_enable_cone3(hipkkt_handle h, int32_t enable, double linesearch_backtrack_step, double min_terminate_step_length) {
+    HK_ENTER(h)
+    if (!enable) { S->st_cone3 = false; return HIPKKT_OK; }
+    if (!S->l1 || !S->sc_ready || !S->sc_cone3_kinds) {
+        S->err = "step_enable_cone3: needs an L1 handle whose last hipkkt_set_cone_types_ex names Zero / Nonnegative / SecondOrder / Exponential / "
+                 "Power cones only, at least one of the last two";
+        return HIPKKT_ERR_ARGUMENT;
+    }
+    const double step = linesearch_backtrack_step, amin = min_terminate_step_length;
+    if (!(step > 0.0 && step < 1.0) || !(amin > 0.0) || !std::isfinite(amin)) {
+        S->err = "step_enable_cone3: 0 < linesearch_backtrack_step < 1 and min_terminate_step_length > 0";
+        return HIPKKT_ERR_ARGUMENT;
+    }
+    // alpha0 <= 1, so alpha0 step^k < alpha_min after at most ceil(log alpha_min / log step) multiplications
+    const double trips = std::ceil(std::log(amin) / std::log(step)) + 2.0;
+    if (!(trips <= 4096.0)) { S->err = "step_enable_cone3: the line search would need more than 4096 trips"; return HIPKKT_ERR_ARGUMENT; }
+    S->st_c3_step = step; S->st_c3_amin = amin; S->st_c3_trips = (int)std::max(trips, 2.0);
+    S->st_cone3 = true;
+    S->sc_scaled = false;      // the step reads the resident (s, z) of a scaling that ran with the enable in place
+    S->st_have_step = false;
+    return HIPKKT_OK;
+    HK_LEAVE
+}
+
+int32_t hipkkt_cone_barrier(hipkkt_handle h, const double *dz, const double *ds, const double *alphas, int64_t nalpha, double *out) {
+    HK_ENTER(h)
+    if (!step_ready(S, "cone_barrier")) return HIPKKT_ERR_ARGUMENT;
+    if (!alphas || !out || nalpha < 1 || nalpha > step3_max_candidates() || (S->img.m && (!dz || !ds))) {
+        S->err = "cone_barrier: 1 <= nalpha <= 8 / null argument"; return HIPKKT_ERR_ARGUMENT;
+    }
+    const ConeTables T = tables(S);
+    return cone_op_host(S, dz, ds, out, 2 * nalpha, [&](double *ddz, double *dds, double *dout) {
+        barrier_impl(S, T, T.z, T.s, ddz, dds, alphas, nalpha, dout);
+    });
+    HK_LEAVE
+}
+
+int32_t hipkkt_step_barrier_dev(hipkkt_handle h, const double *xzs_dev, const double *alphas, int64_t nalpha, double *out) {
+    HK_ENTER(h)
+    if (!step_ready(S, "step_barrier_dev")) return HIPKKT_ERR_ARGUMENT;
+    if (!S->st_have_step || !xzs_dev || !alphas || !out || nalpha < 1 || nalpha > step3_max_candidates()) {
+        S->err = "step_barrier_dev: no step resident / 1 <= nalpha <= 8 / null argument"; return HIPKKT_ERR_ARGUMENT;
+    }
+    const int64_t n = S->img.n, m = S->img.m;
+    const ConeTables T = tables(S);
+    ensure_step_buffers(S);
+    barrier_impl(S, T, xzs_dev + n, xzs_dev + n + m, S->d_st_step + n, S->d_st_step + n + m, alphas, nalpha, S->d_st_out + 12);
+    copy_sync(S->stream, out, S->d_st_out + 12, (size_t)(2 * nalpha) * sizeof(double), hipMemcpyDeviceToHost);
+    return HIPKKT_OK;
     HK_LEAVE
 }
 
@@ -194,10 +300,10 @@ int32_t hipkkt_step_combined_dev(hipkkt_handle h, const double *xzs_dev, const d
     double *w_dz = S->d_st_work, *w_rhs_s = w_dz + m, *w_shift = w_rhs_s + m, *w_dsc = w_shift + m;
     const double *dz_aff = S->d_st_step + n, *ds_aff = dz_aff + m;
     if (m_corr != 1.0) { launch_step_scale(st, w_dz, dz_aff, m_corr, m); dz_aff = w_dz; }
-    launch_step_affine_ds(st, T.kind, T.nsoc, T.desc, T.lam, w_rhs_s, m);
-    launch_step_shift(st, T.kind, T.nsoc, T.desc, T.w, T.eta, dz_aff, ds_aff, sm, w_shift, m);
+    op_affine_ds(st, T, w_rhs_s);
+    op_shift(st, T, dz_aff, ds_aff, sm, w_shift);
     launch_step_add(st, w_rhs_s, w_shift, m);                                                           // rhs.s = lambda o lambda + shift
-    launch_step_offset(st, T.kind, T.nsoc, T.desc, T.z, T.w, T.lam, T.eta, w_rhs_s, w_dsc, m);          // kktsystem.jl:157-163
+    op_offset(st, T, w_rhs_s, w_dsc);                                                                   // kktsystem.jl:157-163
     launch_step_rhs(st, S->d_st_in, xzs_dev, res_dev, w_dsc, oms, n, m);
     const StepScalars sc{tau, kappa, oms * r_tau, rhs_kappa};
     return fused_solve(S, sc, w_dsc, const_pending, step_fraction, scal_out15, ir_enable, reltol, abstol, max_iter, stop_ratio, ir_steps2);

@@ -72,6 +72,22 @@ void launch_step_rhs(hipStream_t st, double *in, const double *xzs, const double
 // eq = [d | e | dinv | einv]
 void launch_step_info_norms(hipStream_t st, const double *xzs, const double *res, const double *eq, double *part, double *out8, int64_t n,
                             int64_t m);
+// step_cone3.hip: the same operations on the rows of the Exponential / Power cones (the [Exponential | Power] tables of
+// launch_scaling_cone3; nsout = its output vector: Hs 6, H_dual 6, grad 3 per cone), their backtracking step length and the barrier of
+// the whole cone set at nalpha <= step3_max_candidates() step lengths
+int step3_max_candidates();
+int64_t step3_barrier_doubles(int64_t ncones);
+void launch_step3_copy(hipStream_t st, int n3, const int64_t *row0, const double *src, double *out);
+void launch_step3_mulhs(hipStream_t st, int n3, const int64_t *row0, const int64_t *out0, const double *nsout, const double *x,
+                        const double *addc, double *y);
+void launch_step3_shift(hipStream_t st, int nexp, int npow, const int64_t *row0, const int64_t *out0, const double *alpha,
+                        const double *nsout, const double *z, const double *dz, const double *ds, double sigma_mu, double *out);
+void launch_step3_length(hipStream_t st, int nexp, int npow, const int64_t *row0, const double *alpha, const double *z, const double *s,
+                         const double *dz, const double *ds, const double *sym2, const double *dtau, double tau, double kappa,
+                         double rhs_kappa, double alpha_max, double step, double alpha_min, int trips, double *part, double *out2);
+void launch_step3_barrier(hipStream_t st, const signed char *row_kind, int nsoc, const int64_t *desc, int nexp, int npow,
+                          const int64_t *row0, const double *alpha, const double *z, const double *s, const double *dz, const double *ds,
+                          const double *alphas, int nalpha, double *work, double *out, int64_t m);
 void launch_block_products(hipStream_t st, const DevPlan &P, const double *x, const double *z, double *Px, double *ATz,
                            double *Ax, int n, int m);
 void launch_zero_words(hipStream_t st, void *p, int nwords);

@@ -42,6 +42,8 @@ SYMBOLS = [
     "hipkkt_cone_affine_ds", "hipkkt_cone_combined_ds_shift", "hipkkt_cone_ds_from_dz_offset", "hipkkt_cone_mul_hs", "hipkkt_cone_step_length",
     "hipkkt_set_equilibration", "hipkkt_step_affine_dev", "hipkkt_step_combined_dev", "hipkkt_step_apply_dev", "hipkkt_step_info_norms_dev",
     "hipkkt_step_get",
+    # ... for the Exponential / Power cones as well (opt-in), and the barrier of the line search (added within ABI version 5)
+    "hipkkt_step_enable_cone3", "hipkkt_cone_barrier", "hipkkt_step_barrier_dev",
 ]
 
 
@@ -149,6 +151,9 @@ def lib():
     L.hipkkt_step_apply_dev.argtypes = [vp, f64, vp]
     L.hipkkt_step_info_norms_dev.argtypes = [vp, vp, vp, _f64p]
     L.hipkkt_step_get.argtypes = [vp, _f64p]
+    L.hipkkt_step_enable_cone3.argtypes = [vp, i32, f64, f64]
+    L.hipkkt_cone_barrier.argtypes = [vp, _f64p, _f64p, _f64p, i64, _f64p]
+    L.hipkkt_step_barrier_dev.argtypes = [vp, vp, _f64p, i64, _f64p]
     L.hipkkt_debug_dump.argtypes = [vp, i32, vp, i64, C.POINTER(i64)]
     L.hipkkt_debug_extra_tiles.argtypes = [i32, i32, i32, C.POINTER(i32)]
     L.hipkkt_debug_extra_tiles.restype = i32
@@ -439,6 +444,7 @@ class Handle:
         p = lambda a: None if a is None else a.ctypes.data
         self._chk(self.L.hipkkt_update_scaling_ex(self.h, s, z, p(R), float(mu), int(strategy), p(w), p(lam), p(eta), p(ns), C.byref(ok)),
                   "update_scaling_ex")
+        _count(2 * self.m + 1 + (0 if R is None else R.size), (2 * self.m + self._n_soc_all + nlen) if want_outputs else 0)
         if not want_outputs:
             return bool(ok.value), None, None, None, None
         return bool(ok.value), w[: self.m], lam[: self.m], eta[: self._n_soc_all], ns[:nlen]
@@ -449,6 +455,7 @@ class Handle:
         ok = C.c_int32(0)
         self._chk(self.L.hipkkt_update_scaling_ex_dev(self.h, s_ptr, z_ptr, R_ptr, float(mu), int(strategy), w_ptr, lam_ptr, eta_ptr,
                                                       nonsym_ptr, C.byref(ok)), "update_scaling_ex_dev")
+        _count(1, 1)
         return bool(ok.value)
 
     def set_soc(self, i, eta2, u, v):
@@ -667,6 +674,35 @@ class Handle:
         out = np.zeros(max(self.n + 2 * self.m, 1))
         self._chk_step(self.L.hipkkt_step_get(self.h, out), "step_get")
         return out[: self.n + 2 * self.m]
+
+    # ---- the same entry points for the Exponential / Power cones (opt-in per registration) and the barrier of the line search
+    def step_enable_cone3(self, enable, linesearch_backtrack_step, min_terminate_step_length):
+        """ValueError unless the registration names kinds {0, 1, 2, 4, 5} only with a 4 / 5, 0 < step < 1, alpha_min > 0"""
+        self._chk_step(self.L.hipkkt_step_enable_cone3(self.h, int(bool(enable)), float(linesearch_backtrack_step),
+                                                       float(min_terminate_step_length)), "step_enable_cone3")
+
+    @staticmethod
+    def _alphas(alphas):
+        a = np.ascontiguousarray(alphas, dtype=np.float64).ravel()
+        if not 1 <= a.size <= 8:
+            raise ValueError("barrier: between 1 and 8 candidate step lengths per call")
+        return a
+
+    def cone_barrier(self, dz, ds, alphas):
+        """-> (barrier[nalpha], dot[nalpha]): the cones' barrier and <z + a dz, s + a ds> at every candidate a, for host vectors dz, ds"""
+        a = self._alphas(alphas)
+        out = np.zeros(2 * a.size)
+        self._chk_step(self.L.hipkkt_cone_barrier(self.h, self._vec_m(dz, "dz"), self._vec_m(ds, "ds"), a, a.size, out), "cone_barrier")
+        _count(2 * self.m + a.size, 2 * a.size)
+        return out[0::2].copy(), out[1::2].copy()
+
+    def step_barrier_dev(self, xzs_ptr, alphas):
+        """the same on the resident iterate [x | z | s] and the resident step of the last fused call"""
+        a = self._alphas(alphas)
+        out = np.zeros(2 * a.size)
+        self._chk_step(self.L.hipkkt_step_barrier_dev(self.h, xzs_ptr, a, a.size, out), "step_barrier_dev")
+        _count(a.size, 2 * a.size)
+        return out[0::2].copy(), out[1::2].copy()
 
     def ldl_solve(self, b):
         x = np.zeros(self.N)

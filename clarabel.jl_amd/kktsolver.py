@@ -18,14 +18,19 @@ from .settings import Settings
 _DEBUG = os.environ.get("HIPKKT_DEBUG", "0") == "1"
 
 
-def cone_set_steps_on_device(cones) -> bool:
+def cone_set_steps_on_device(cones, nonsymmetric=False) -> bool:
     """the step entry points (hipkkt_cone_* / hipkkt_step_*) serve cone sets of ZeroCone, NonnegativeCone and SecondOrderCone only: a PSD
-    cone's step length needs eigenvalue decompositions, the non-symmetric cones need backtracking and barriers"""
+    cone's step length needs eigenvalue decompositions, the non-symmetric cones need backtracking and barriers.
+    nonsymmetric=True: ExponentialCone and PowerCone members qualify as well (hipkkt_step_enable_cone3); Generalized Power and PSD
+    members still do not"""
     if not hasattr(cones, "kkt_cone_kinds"):
         return False
     kinds = cones.kkt_cone_kinds_ex()[0] if hasattr(cones, "kkt_cone_kinds_ex") else cones.kkt_cone_kinds()
     kinds = np.asarray(kinds)
-    return kinds.size > 0 and bool(np.all((kinds >= 0) & (kinds <= 2)))
+    ok = (kinds >= 0) & (kinds <= 2)
+    if nonsymmetric:
+        ok = ok | (kinds == 4) | (kinds == 5)
+    return kinds.size > 0 and bool(np.all(ok))
 
 
 class HipKKTSolver:
@@ -70,6 +75,12 @@ class HipKKTSolver:
             self.h.set_cone_types(kinds)
         # the interior-point step on the device (hipkkt_cone_* / hipkkt_step_*) serves Zero / Nonnegative / SecondOrder cone sets only
         self._steps_on_device = cone_set_steps_on_device(cones)
+        # ... and, opted in by Settings.device_step_nonsymmetric, sets with Exponential / Power members
+        self.steps_nonsymmetric = False
+        if not self._steps_on_device and getattr(settings, "device_step_nonsymmetric", False) and self.scales_nonsymmetric \
+                and cone_set_steps_on_device(cones, nonsymmetric=True):
+            self.h.step_enable_cone3(True, settings.linesearch_backtrack_step, settings.min_terminate_step_length)
+            self._steps_on_device = self.steps_nonsymmetric = True
         self.scaling_nonsym = None
         self.scaling_w = self.scaling_lambda = self.scaling_soc_eta = None
         self.diagonal_regularizer = 0.0
@@ -250,6 +261,19 @@ class HipKKTSolver:
     def kktsolver_update_scaling_dev(self, xzs) -> bool:
         """update_scaling! + get_Hs! from the resident (s, z); False = a cone's s or z is not interior"""
         return self.h.update_scaling_dev(xzs.ptr + 8 * (self.n + self.m), xzs.ptr + 8 * self.n)
+
+    def kktsolver_update_scaling_dev_ex(self, xzs, mu, strategy) -> bool:
+        """the same with Exponential / Power members: mu and the strategy ("primal_dual" / "dual" or 0 / 1) as kktsolver_update_scaled"""
+        strategy = {"primal_dual": 0, "dual": 1}.get(strategy, strategy)
+        return self.h.update_scaling_ex_dev(xzs.ptr + 8 * (self.n + self.m), xzs.ptr + 8 * self.n, mu, strategy)
+
+    def cone_barrier(self, dz, ds, alphas):
+        """(barrier, dot) per candidate step length: the cones' compute_barrier and <z + a dz, s + a ds> on the resident (s, z)"""
+        return self.h.cone_barrier(dz, ds, alphas)
+
+    def kktsolver_step_barrier(self, xzs, alphas):
+        """the same on the resident iterate and the resident step of the last fused call (at most 8 candidates per call)"""
+        return self.h.step_barrier_dev(xzs.ptr, alphas)
 
     def kktsolver_refactor(self) -> bool:
         return self._refactor()

@@ -59,4 +59,8 @@ class Settings:
     # by the plugin on a device-resident iterate, for Zero / Nonnegative / SecondOrder cone sets (any other cone set takes the host path).
     # Needs device_scaling, device_reduced and device_residuals: the caller raises ValueError when one of them is off.
     device_step: bool = False
+    # device_step for cone sets that also hold Exponential / Power cones (backtracking line search, third-order correction and the
+    # barrier of the Dual strategy on the device); Generalized Power and PSD cone sets keep the host path.  Needs device_step: the
+    # caller raises ValueError otherwise.
+    device_step_nonsymmetric: bool = False
     extra: dict = field(default_factory=dict)

@@ -72,7 +72,8 @@ int32_t hipkkt_is_available(void);
  * and refuses a mismatch (the Julia glue and the ctypes mirror do): signatures may change between versions, never within one.
  * 4: hipkkt_get_profile / hipkkt_get_counters take the capacity of the caller's buffer (they wrote a fixed, growing number of values).
  * 5: hipkkt_set_cone_types_ex / hipkkt_get_nonsym_len / hipkkt_update_scaling_ex[_dev] (the bindings bind them when they load).
- *    Added within 5, no signature changed: the step entry points hipkkt_cone_* / hipkkt_set_equilibration / hipkkt_step_*. */
+ *    Added within 5, no signature changed: the step entry points hipkkt_cone_* / hipkkt_set_equilibration / hipkkt_step_*;
+ *    hipkkt_step_enable_cone3 / hipkkt_cone_barrier / hipkkt_step_barrier_dev. */
 #define HIPKKT_ABI_VERSION 5
 int32_t hipkkt_abi_version(void);
 /* releases the process-wide cache of device memory blocks the library keeps between handles (not in the reference: an embedding
@@ -327,6 +328,23 @@ int32_t hipkkt_residuals_dev(hipkkt_handle h, const double *xzs_dev, double tau,
  * with the caller: eigenvalue decompositions, backtracking line search, barriers) and before the first successful scaling; the fused
  * calls also before hipkkt_set_qb.  On any non-zero return the outputs are unspecified, as for hipkkt_kkt_solve_reduced.
  *
+ * Opt-in for ExponentialCone / PowerCone (kinds 4, 5): after hipkkt_step_enable_cone3 on a registration of kinds {0, 1, 2, 4, 5} every
+ * call of this section serves all rows of that handle, on the (s, z) and the per-cone [Hs | H_dual | grad] that the next successful
+ * hipkkt_update_scaling_ex[_dev] leaves resident (a scaling from before the enable does not count).  On the rows of a kind 4 / 5 cone
+ *   affine_ds = the resident s; ds_from_dz_offset = ds; mul_hs = the resident 3 x 3 Hs block times x (what the matrix holds);
+ *   combined_ds_shift = grad sigma mu - higher_correction(step_s, step_z) (coneops_expcone.jl:319-367, coneops_powcone.jl:329-405;
+ *     0 when the 3 x 3 Cholesky of H_dual breaks down, as in the reference);
+ *   step length = the composite rule of coneops_compositecone.jl:216-252: the symmetric cones first, then from
+ *     alpha0 = min(that, 1 - sqrt(eps)) every kind 4 / 5 cone backtracks alpha <- step alpha separately for z + alpha dz and s + alpha ds
+ *     until the point is strictly feasible or alpha < alpha_min, which gives 0 (coneops_nonsymmetric_common.jl:5-33); the result is
+ *     the minimum, returned in both slots.  All cones walk the grid alpha0 step^k, so the minimum is the reference's sequential result.
+ *     In the fused calls alpha0 also takes min(alpha_tau, alpha_kappa, 1) first, formed on the device (variables.jl:14-43), and
+ *     scal_out15[3..4] hold the composite (alpha, alpha) before max_step_fraction.
+ * Rows of kinds 0..2 go through the same kernels as without the enable, bit for bit.  Every loop on the device is bounded: the
+ * backtracking by ceil(log alpha_min / log step) + 2 trips (at most 4096, else the enable is refused), Newton iterations by the
+ * reference's 100 steps; a direction that leaves a cone for every alpha gives alpha = 0, never a trap.
+ * Kinds 3 (PSD) and 6 (GenPower) stay refused, at hipkkt_step_enable_cone3 and therefore everywhere.
+ *
  * One operation each, host vectors of length m in cone order (the unit-tested surface):
  *   hipkkt_cone_affine_ds            ds = lambda o lambda                  coneops_nncone.jl affine_ds!, coneops_socone.jl:219-228
  *   hipkkt_cone_combined_ds_shift    shift = W^-1 step_s o W step_z - sigma mu e   coneops_symmetric_common.jl:1-36, coneops_socone.jl:300-347
@@ -339,6 +357,18 @@ int32_t hipkkt_cone_combined_ds_shift(hipkkt_handle h, const double *step_z, con
 int32_t hipkkt_cone_ds_from_dz_offset(hipkkt_handle h, const double *ds, double *out);
 int32_t hipkkt_cone_mul_hs(hipkkt_handle h, const double *x, double *y_out);
 int32_t hipkkt_cone_step_length(hipkkt_handle h, const double *dz, const double *ds, double alpha_max, double *alpha_out2);
+/* enable != 0: HIPKKT_ERR_ARGUMENT unless the last hipkkt_set_cone_types_ex names kinds {0, 1, 2, 4, 5} only with at least one 4 / 5,
+ * 0 < linesearch_backtrack_step < 1, min_terminate_step_length > 0 and the implied trip count is at most 4096.  enable == 0 switches
+ * it off.  Every hipkkt_set_cone_types[_ex] clears it. */
+int32_t hipkkt_step_enable_cone3(hipkkt_handle h, int32_t enable, double linesearch_backtrack_step, double min_terminate_step_length);
+/* compute_barrier of the cone set (Zero 0, Nonnegative -sum log((s + a ds)(z + a dz)), coneops_socone.jl:288-305,
+ * coneops_expcone.jl:189-248, coneops_powcone.jl:228-251) and dot_shifted (mathutils.jl:23-43) at nalpha <= 8 candidate step lengths:
+ * out[2 j] = the barrier, out[2 j + 1] = <z + a_j dz, s + a_j ds>, both summed over fixed slices in a fixed order.  A point outside a
+ * cone gives +Inf or what logsafe gives.  dz, ds: host vectors of length m; (s, z) are the resident ones.
+ * hipkkt_step_barrier_dev: the same for the iterate xzs_dev = [x | z | s] and the resident step of the last fused call; one host
+ * synchronisation per call. */
+int32_t hipkkt_cone_barrier(hipkkt_handle h, const double *dz, const double *ds, const double *alphas, int64_t nalpha, double *out);
+int32_t hipkkt_step_barrier_dev(hipkkt_handle h, const double *xzs_dev, const double *alphas, int64_t nalpha, double *out);
 /* once per problem (L1 handles): the equilibration vectors d[n], e[m] of problemdata.jl:133-221 for hipkkt_step_info_norms_dev; the
  * reciprocals are formed on the host as 1 ./ d, 1 ./ e like problemdata.jl does, so they are the caller's dinv / einv bit for bit */
 int32_t hipkkt_set_equilibration(hipkkt_handle h, const double *d, const double *e);

@@ -120,6 +120,27 @@ function hip_step_info_norms_dev(handle::Ptr{Cvoid}, xzs_dev::Ptr{Float64}, res_
     hip_step_check(handle, rc, "hipkkt_step_info_norms_dev")
     return out
 end
+# opt-in per registration: the step entry points also serve the Exponential / Power cones (kinds 4, 5) of the handle
+function hip_step_enable_cone3!(handle::Ptr{Cvoid}, enable::Bool, backtrack_step::Float64, min_terminate_step_length::Float64)
+    rc = ccall((:hipkkt_step_enable_cone3, libhipkkt), Int32, (Ptr{Cvoid}, Int32, Float64, Float64), handle, enable ? 1 : 0,
+               backtrack_step, min_terminate_step_length)
+    return hip_step_check(handle, rc, "hipkkt_step_enable_cone3")
+end
+# -> out[2j-1] = the cones' barrier, out[2j] = <z + αⱼΔz, s + αⱼΔs> for at most 8 candidates αⱼ
+function hip_cone_barrier(handle::Ptr{Cvoid}, Δz::Vector{Float64}, Δs::Vector{Float64}, αs::Vector{Float64})
+    out = zeros(Float64, 2 * length(αs))
+    rc = ccall((:hipkkt_cone_barrier, libhipkkt), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}),
+               handle, Δz, Δs, αs, length(αs), out)
+    hip_step_check(handle, rc, "hipkkt_cone_barrier")
+    return out
+end
+function hip_step_barrier_dev(handle::Ptr{Cvoid}, xzs_dev::Ptr{Float64}, αs::Vector{Float64})
+    out = zeros(Float64, 2 * length(αs))
+    rc = ccall((:hipkkt_step_barrier_dev, libhipkkt), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}),
+               handle, xzs_dev, αs, length(αs), out)
+    hip_step_check(handle, rc, "hipkkt_step_barrier_dev")
+    return out
+end
 function hip_step_get!(handle::Ptr{Cvoid}, out::Vector{Float64})
     rc = ccall((:hipkkt_step_get, libhipkkt), Int32, (Ptr{Cvoid}, Ptr{Float64}), handle, out)
     return hip_step_check(handle, rc, "hipkkt_step_get")

@@ -394,8 +394,17 @@ class Solver:
         if getattr(st, "device_step", False) and not (getattr(st, "device_scaling", False) and getattr(st, "device_reduced", False)
                                                       and getattr(st, "device_residuals", False)):
             raise ValueError("Settings.device_step needs device_scaling, device_reduced and device_residuals")
+        if getattr(st, "device_step_nonsymmetric", False) and not getattr(st, "device_step", False):
+            raise ValueError("Settings.device_step_nonsymmetric needs device_step")
         self._device_step = bool(getattr(st, "device_step", False)) and hasattr(ks, "kktsolver_step_affine") and \
             bool(getattr(ks, "steps_on_device", False))
+        if self._device_step and not self.cones.is_symmetric():
+            # a set with Exponential / Power members (include/hipkkt.h kinds 4, 5) steps on the device when that is opted in and the
+            # plugin offers the calls; a Generalized Power member keeps the host loop
+            self._device_step = bool(getattr(st, "device_step_nonsymmetric", False)) and \
+                hasattr(ks, "kktsolver_update_scaling_dev_ex") and hasattr(ks, "kktsolver_step_barrier") and \
+                all(getattr(c, "is_symmetric", True) or getattr(c, "kind_code_ex", -1) in (4, 5) for c in self.cones)
+        self.barrier_searches = self.barrier_backtracks = 0      # _backtrack_step_to_barrier calls / candidates it rejected (last solve)
         self._needs_qb = self._needs_qb or (self._device_step and hasattr(ks, "set_problem_vectors"))
         if self._needs_qb:               # q, b resident in the plugin (N4 residuals, N2 reduced-system algebra)
             ks.set_problem_vectors(data.q, data.b)
@@ -567,10 +576,38 @@ class Solver:
     def _backtrack_step_to_barrier(self, alpha_init):  # solver.jl:427-445: distance to the boundary of the non-symmetric cones
         step = self.settings.linesearch_backtrack_step
         alpha = alpha_init
+        self.barrier_searches += 1
         for _ in range(50):
             if self._variables_barrier(alpha) < 1.0:
                 return alpha
+            self.barrier_backtracks += 1
             alpha = step * alpha
+        return alpha
+
+    def _backtrack_step_to_barrier_dev(self, ks, xzs, alpha_init, dtau, dkappa):
+        """_backtrack_step_to_barrier on the resident iterate and step: the candidates alpha, step alpha, ... are formed here by the same
+        repeated multiplication, eight per call; the plugin returns the cones' barrier and the shifted <z, s> of each and
+        _variables_barrier (variables.jl:46-74) is composed from them and the scalars"""
+        step = self.settings.linesearch_backtrack_step
+        v, central_coef = self.variables, self.cones.degree + 1
+        alpha, done = alpha_init, 0
+        self.barrier_searches += 1
+        while done < 50:
+            cand = []
+            for _ in range(min(8, 50 - done)):
+                cand.append(alpha)
+                alpha = step * alpha
+            bars, dots = ks.kktsolver_step_barrier(xzs, cand)
+            for a, bar, sz in zip(cand, bars, dots):
+                cur_tau = v.tau + a * dtau
+                cur_kappa = v.kappa + a * dkappa
+                mu = (float(sz) + cur_tau * cur_kappa) / central_coef
+                barrier = central_coef * _logsafe(mu) - _logsafe(cur_tau) - _logsafe(cur_kappa)
+                barrier += float(bar)
+                if barrier < 1.0:
+                    return a
+                self.barrier_backtracks += 1
+            done += len(cand)
         return alpha
 
     def _variables_barrier(self, alpha):  # variables.jl:46-74
@@ -617,7 +654,10 @@ class Solver:
         """The reference's host-side vector algebra is single-threaded Julia; numpy's OpenBLAS instead spins up a thread
         team for every 20k-element ``dot`` (4 ms instead of 4 us on an 8-core box), so the BLAS pool is limited to one
         thread while the loop runs."""
-        loop = self._solve_device_step if self._device_step else self._solve
+        loop = self._solve
+        if self._device_step:
+            loop = self._solve_device_step if self.cones.is_symmetric() else self._solve_device_step_nonsymmetric
+        self.barrier_searches = self.barrier_backtracks = 0
         try:
             from threadpoolctl import threadpool_limits
         except ImportError:          # pragma: no cover - threadpoolctl ships with the image
@@ -693,6 +733,110 @@ class Solver:
                 info.status = NUMERICAL_ERROR
                 break
             if alpha <= max(0.0, st.min_terminate_step_length):      # _strategy_checkpoint_small_step (:493-506)
+                info.status = INSUFFICIENT_PROGRESS
+                alpha = 0.0
+                break
+            self._save_prev_info()
+            prev.copy_from(xzs)
+            prev_tau, prev_kappa = v.tau, v.kappa
+            ks.kktsolver_step_apply(alpha, xzs)
+            v.tau += alpha * dtau
+            v.kappa += alpha * dkappa
+        back = xzs.download()
+        v.x[:], v.z[:], v.s[:] = back[:n], back[n:n + m], back[n + m:]
+        for b in (xzs, res, prev):
+            b.close()
+        return self._finish(t_start, t_loop, alpha, sigma, mu, it)
+
+    # ------------------------------------------------------------- the same for cone sets with Exponential / Power members
+    def _solve_device_step_nonsymmetric(self):
+        """_solve_device_step for Settings.device_step_nonsymmetric: the loop of _solve with its three strategy checkpoints
+        (solver.jl:453-506), fed by scalars.  mu and the strategy go to the scaling call; a re-run with the Dual strategy applies no
+        step, so the resident iterate is reused; under Dual the combined step is backtracked to the barrier (solver.jl:427-445) with
+        eight candidates per call.  The unit initialisation runs on the host and is uploaded once."""
+        st, info, data, cones = self.settings, self.info, self.data, self.cones
+        v, r = self.variables, self.residuals
+        ks = self.kktsystem.kktsolver
+        n, m = data.n, data.m
+        tm = info.timers
+        for k in ("kkt update", "kkt solve", "scale cones", "default start"):
+            tm[k] = 0.0
+        it = 0
+        sigma, alpha, mu = 1.0, 0.0, FLOATMAX
+        info.status = UNSOLVED
+        info.iterations = 0
+        t_start = time.perf_counter()
+        t0 = time.perf_counter()
+        self._default_start()
+        xzs, res, prev = ks.device_buffer(n + 2 * m), ks.device_buffer(3 * n + 2 * m), ks.device_buffer(n + 2 * m)
+        xzs.upload(np.concatenate([v.x, v.z, v.s]))
+        prev_tau, prev_kappa = v.tau, v.kappa
+        tm["default start"] = time.perf_counter() - t0
+        t_loop = time.perf_counter()
+        scaling = "primal_dual" if cones.allows_primal_dual_scaling() else "dual"      # solver.jl:222
+        while True:
+            r.dot_qx, r.dot_bz, r.dot_sz, r.dot_xPx, r.rtau = ks.residuals_update_dev(xzs, res, v.tau, v.kappa)
+            mu = (r.dot_sz + v.tau * v.kappa) / (cones.degree + 1)
+            info.mu, info.step_length, info.sigma, info.iterations = mu, alpha, sigma, it
+            self._info_update(t_start, norms=ks.kktsolver_info_norms(xzs, res))
+            if st.verbose:
+                print(f"{it:3d}  pcost {info.cost_primal: .4e}  dcost {info.cost_dual: .4e}  gap {info.gap_abs:.2e}"
+                      f"  pres {info.res_primal:.2e}  dres {info.res_dual:.2e}  k/t {info.ktratio:.2e}"
+                      f"  mu {mu:.2e}  step {alpha:.2e}")
+            if self.trace is not None:
+                self.trace.append(dict(iter=it, mu=mu, alpha=alpha, sigma=sigma, cost_primal=info.cost_primal,
+                                       cost_dual=info.cost_dual, res_primal=info.res_primal,
+                                       res_dual=info.res_dual, ktratio=info.ktratio))
+            if self._check_termination(it):
+                if info.status == INSUFFICIENT_PROGRESS:      # _strategy_checkpoint_insufficient_progress (:453-473)
+                    self._reset_info_to_prev()
+                    xzs.copy_from(prev)
+                    v.tau, v.kappa = prev_tau, prev_kappa
+                    if scaling == "primal_dual":              # continue with the dual-only scaling
+                        info.status = UNSOLVED
+                        scaling = "dual"
+                        continue
+                break
+            t0 = time.perf_counter()
+            ok = ks.kktsolver_update_scaling_dev_ex(xzs, mu, scaling)
+            if not ok:
+                # which cone is not interior decides, as on the host path with device_scaling: a symmetric member fails update_scaling!
+                # (NUMERICAL_ERROR, before the iteration counts); an Exponential / Power member makes kkt_update! fail, which is the
+                # numerical-error checkpoint below.  The plugin reports one flag, so the symmetric members are looked at here (rare)
+                back = xzs.download()
+                if not cones.update_scaling(back[n + m:], back[n:n + m], mu, scaling, host_nonsymmetric=False):
+                    tm["scale cones"] += time.perf_counter() - t0
+                    info.status = NUMERICAL_ERROR
+                    break
+            tm["scale cones"] += time.perf_counter() - t0
+            it += 1
+            t0 = time.perf_counter()
+            ok = ok and ks.kktsolver_refactor()
+            tm["kkt update"] += time.perf_counter() - t0
+            t0 = time.perf_counter()
+            if ok:
+                ok, alpha, dtau_aff, dkappa_aff = ks.kktsolver_step_affine(xzs, res, v.tau, v.kappa, r.rtau, True)
+            if ok:
+                sigma = (1.0 - alpha) ** 3
+                mcorr = 1.0 if it > 1 else alpha
+                ok, alpha, dtau, dkappa = ks.kktsolver_step_combined(xzs, res, v.tau, v.kappa, r.rtau, dtau_aff, dkappa_aff, sigma, mu,
+                                                                     mcorr)
+            tm["kkt solve"] += time.perf_counter() - t0
+            if not ok:  # _strategy_checkpoint_numerical_error (:476-490)
+                alpha = 0.0
+                if scaling == "primal_dual":
+                    scaling = "dual"
+                    continue
+                info.status = NUMERICAL_ERROR
+                break
+            if scaling == "dual":                             # _get_step_length, solver.jl:408-424
+                alpha = self._backtrack_step_to_barrier_dev(ks, xzs, alpha, dtau, dkappa)
+            # _strategy_checkpoint_small_step (:493-506)
+            if scaling == "primal_dual" and alpha < st.min_switch_step_length:
+                scaling = "dual"
+                alpha = 0.0
+                continue
+            if alpha <= max(0.0, st.min_terminate_step_length):
                 info.status = INSUFFICIENT_PROGRESS
                 alpha = 0.0
                 break

@@ -4,7 +4,7 @@ algebra between the device calls runs on the host, the iterate crosses PCIe seve
 added (the iterate stays in device memory, scalars cross).  Per path: one warm-up solve, then `--repeats` timed solves; the medians of
 wall time per iteration and of the stand-in's timers, the bytes the Python binding moved per iteration in each direction
 (clarabel.jl_amd/hipkkt.py TRAFFIC) and hipkkt_box_probe go into ONE JSON line on stdout.
-usage: step_path_compare.py [--cfgs 3,2a] [--repeats 5] [--one-solve CFG]   (--one-solve: a single device_step solve, for a kernel trace)"""
+usage: step_path_compare.py [--cfgs 3,2a,exp_pow] [--repeats 5] [--one-solve CFG]   (--one-solve: a single device_step solve, for a kernel trace)"""
 import argparse
 import json
 import os
@@ -17,8 +17,12 @@ import clarabel_jl_amd  # noqa: E402,F401
 import julia_standin as cl  # noqa: E402
 from clarabel_jl_amd import hipkkt, problems  # noqa: E402
 
-CONFIGS = {"3": ("portfolio_socp", problems.portfolio_socp), "2a": ("random_sparse_qp", problems.random_sparse_qp)}
+CONFIGS = {"3": ("portfolio_socp", problems.portfolio_socp), "2a": ("random_sparse_qp", problems.random_sparse_qp),
+           # Exponential / Power cones next to the symmetric ones: the device-step path needs device_step_nonsymmetric
+           "exp_pow": ("nonsymmetric_mix_exp_pow",
+                       lambda: problems.nonsymmetric_mix(n=80, nexp=30, npow=20, ngenpow=0, nn=20, nzero=3, socdim=5, seed=5))}
 PARENT = dict(device_scaling=True, device_reduced=True, device_residuals=True)
+STEP_EXTRA = {"exp_pow": dict(device_step_nonsymmetric=True)}      # what device_step needs on top, per configuration
 
 
 def one_solve(prob, **flags):
@@ -53,7 +57,7 @@ def main():
     ap.add_argument("--one-solve", default=None)
     args = ap.parse_args()
     if args.one_solve:
-        rec = one_solve(CONFIGS[args.one_solve][1](), device_step=True, **PARENT)
+        rec = one_solve(CONFIGS[args.one_solve][1](), device_step=True, **PARENT, **STEP_EXTRA.get(args.one_solve, {}))
         print(json.dumps({"cfg": args.one_solve, "device_step": rec}))
         return
     result = {"tool": "step_path_compare", "repeats": args.repeats, "configs": {}}
@@ -61,7 +65,7 @@ def main():
         name, make = CONFIGS[cfg]
         prob = make()
         paths = {}
-        for label, flags in (("host_cone_algebra", PARENT), ("device_step", dict(device_step=True, **PARENT))):
+        for label, flags in (("host_cone_algebra", PARENT), ("device_step", dict(device_step=True, **PARENT, **STEP_EXTRA.get(cfg, {})))):
             one_solve(prob, **flags)                                   # warm-up: plan cache, graphs, code objects
             paths[label] = median_of([one_solve(prob, **flags) for _ in range(args.repeats)])
         assert paths["device_step"]["device_step"] and not paths["host_cone_algebra"]["device_step"]
