@@ -1,6 +1,7 @@
 // Device helpers shared by the scaling (scaling.hip) and the step (step_cone3.hip) of the three-row non-symmetric cones: logsafe, the
 // Wright omega function, the feasibility tests, the dual gradient / Hessian and the primal gradient of the Exponential and the Power
-// cone, the 3 x 3 Cholesky.  Expressions keep the reference's association; both users are compiled with -ffp-contract=off.
+// cone, the 3 x 3 Cholesky; and the start of the non-symmetric cones' line search, which step_genpow.hip shares with step_cone3.hip.
+// Expressions keep the reference's association; every user is compiled with -ffp-contract=off.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -187,6 +188,28 @@ __device__ __forceinline__ void chol3_solve(const double L[6], const double b[3]
     x[0] = (c1 * l22 * l33 - c2 * l21 * l33 + c3 * l21 * l32 - c3 * l22 * l31) / (l11 * l22 * l33);
     x[1] = (c2 * l33 - c3 * l32) / (l22 * l33);
     x[2] = c3 / l33;
+}
+
+// ---- the start of the non-symmetric cones' line search (step_cone3.hip, step_genpow.hip) ---------------------------------------------
+constexpr double kFloatMax3 = 1.7976931348623157e308;
+constexpr double kSqrtEps = 1.4901161193847656e-08;
+
+// the scalars of variables.jl:14-43 a fused call hands to the step length: dtau comes from the reduction's device scalars
+struct StepTK { const double *dtau; double tau, kappa, rhs_kappa; };
+
+// alpha0 of the non-symmetric cones: min(alpha_tau, alpha_kappa, 1) when T.dtau is given, else alpha_max; then the symmetric cones'
+// (alpha_z, alpha_s); then 1 - sqrt(eps) (coneops_compositecone.jl:238-240)
+__device__ __forceinline__ double alpha_start(const double *sym2, const StepTK T, double alpha_max) {
+    double a = alpha_max;
+    if (T.dtau) {
+        const double dtau = T.dtau[0];
+        const double dkappa = -(T.rhs_kappa + T.kappa * dtau) / T.tau;
+        const double a_tau = dtau < 0.0 ? -T.tau / dtau : kFloatMax3;
+        const double a_kap = dkappa < 0.0 ? -T.kappa / dkappa : kFloatMax3;
+        a = fmin(fmin(a_tau, a_kap), 1.0);
+    }
+    a = fmin(fmin(a, sym2[0]), sym2[1]);
+    return fmin(a, 1.0 - kSqrtEps);
 }
 
 }  // namespace hipkkt

@@ -409,6 +409,15 @@ static int32_t set_cone_types_impl(hipkkt_handle h, int64_t ncones, const int32_
         any3 = any3 || three;
     }
     S->sc_cone3_kinds = S->sc_cone3_kinds && any3;
+    // hipkkt_step_enable_genpow likewise: kinds {0, 1, 2, 4, 5, 6} with at least one GenPower cone
+    S->st_genpow = false;
+    S->sc_genpow_kinds = ex;
+    bool anygp = false;
+    for (int64_t c = 0; c < ncones; c++) {
+        S->sc_genpow_kinds = S->sc_genpow_kinds && ((kinds[c] >= 0 && kinds[c] <= 2) || (kinds[c] >= HIPKKT_CONE_EXP && kinds[c] <= HIPKKT_CONE_GENPOW));
+        anygp = anygp || kinds[c] == HIPKKT_CONE_GENPOW;
+    }
+    S->sc_genpow_kinds = S->sc_genpow_kinds && anygp;
     // the non-symmetric cones: three-row cones in two lists (joined [Exponential | Power] below), GenPower descriptors of 8 values
     struct Row3 { int64_t row0, hs0, out0; double alpha; };
     std::vector<Row3> exp3, pow3;
@@ -465,7 +474,13 @@ static int32_t set_cone_types_impl(hipkkt_handle h, int64_t ncones, const int32_
             if (aoff + d1 > nalpha) { S->err = "set_cone_types_ex: alpha is shorter than the Power / GenPower cones need"; return HIPKKT_ERR_ARGUMENT; }
             for (int64_t i = 0; i < d1; i++)
                 if (!(alpha[aoff + i] > 0.0 && alpha[aoff + i] < 1.0)) { S->err = "set_cone_types_ex: the exponents of a GenPower cone lie in (0, 1)"; return HIPKKT_ERR_ARGUMENT; }
-            const int64_t d8[8] = {row, d1, d2, hs, ns_out, (int64_t)gpalpha.size(), (int64_t)gpidx.size(), 0};
+            // d8[7]: the bits of psi = 1 / <alpha, alpha> (cone_types.jl:301), which the step's Newton start reads (step_genpow.hip)
+            double asq = 0.0;
+            for (int64_t i = 0; i < d1; i++) asq += alpha[aoff + i] * alpha[aoff + i];
+            const double psi = 1.0 / asq;
+            int64_t psi_bits;
+            memcpy(&psi_bits, &psi, sizeof(psi_bits));
+            const int64_t d8[8] = {row, d1, d2, hs, ns_out, (int64_t)gpalpha.size(), (int64_t)gpidx.size(), psi_bits};
             gpdesc.insert(gpdesc.end(), d8, d8 + 8);
             gpalpha.insert(gpalpha.end(), alpha + aoff, alpha + aoff + d1);
             for (int t = 0; t < 3; t++) gpidx.insert(gpidx.end(), sm.vec[t].begin(), sm.vec[t].end());
@@ -594,6 +609,7 @@ static int32_t update_scaling_impl(hipkkt_handle h, const double *s, const doubl
             off += (int64_t)n * n;
         }
     }
+    if (ex) S->ns_mu = mu;
     if (ex && S->ns_active) {
         launch_scaling_cone3(S->stream, S->ns_nexp, S->ns_npow, S->d_ns_row0, S->d_ns_hs0, S->d_ns_out0, S->d_ns_alpha, S->d_mapHs, ds, dz,
                              mu, strategy, S->dp.kval, S->d_ns_out, S->d_ns_trips, S->d_sc_fail);

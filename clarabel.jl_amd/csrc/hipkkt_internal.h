@@ -255,6 +255,11 @@ struct hipkkt_solver {
     bool st_cone3 = false;                                 // enabled since that registration
     double st_c3_step = 0.0, st_c3_amin = 0.0;             // linesearch_backtrack_step, min_terminate_step_length
     int st_c3_trips = 0;                                   // bound of the backtracking loop: ceil(log amin / log step) + 2
+    // hipkkt_step_enable_genpow: the same for a registration with Generalized Power cones (step_genpow.hip); it sets st_cone3 as well, so
+    // that the three-row members of the set step with the same (step, alpha_min)
+    bool sc_genpow_kinds = false;                          // the registration names kinds {0, 1, 2, 4, 5, 6} only, at least one 6
+    bool st_genpow = false;                                // enabled since that registration
+    double ns_mu = 0.0;                                    // mu of the last hipkkt_update_scaling_ex[_dev] (mul_Hs of the GenPower cones)
     double *d_st_bar = nullptr;                            // work buffer of the barrier (step3_barrier_doubles)
     // N1, the non-symmetric cones (hipkkt_set_cone_types_ex + hipkkt_update_scaling_ex): tables built once per registration
     bool ns_active = false;                                // the last registration named an Exponential / Power / GenPower cone

@@ -3,6 +3,7 @@
 // PCIe).  Zero, Nonnegative and SecondOrder cones; they work on the (s, z, w, lambda, eta) of the last successful hipkkt_update_scaling.
 // After hipkkt_step_enable_cone3 also the Exponential / Power cones of the registration (step_cone3.hip), on the (s, z) and the
 // [Hs | H_dual | grad] that hipkkt_update_scaling_ex[_dev] left resident; then hipkkt_cone_barrier / hipkkt_step_barrier_dev as well.
+// After hipkkt_step_enable_genpow the Generalized Power cones too (step_genpow.hip), on their slot [grad | d1 | d2 | p | q | r].
 #include "hipkkt_internal.h"
 
 #pragma clang fp contract(off)      // the scalars below repeat the caller's expressions (variables.jl:14-43, :124-162) rounding by rounding
@@ -13,7 +14,8 @@ namespace hipkkt_host {
 static bool step_ready(hipkkt_solver *S, const char *who) {
     if (!S->l1 || !S->sc_ready || !(S->sc_step_kinds || S->st_cone3)) {
         S->err = std::string(who) + ": needs an L1 handle whose registered cones are Zero / Nonnegative / SecondOrder only, or one with "
-                                    "Exponential / Power cones next to them after hipkkt_step_enable_cone3";
+                                    "Exponential / Power cones next to them after hipkkt_step_enable_cone3, or with Generalized Power cones "
+                                    "after hipkkt_step_enable_genpow";
         return false;
     }
     if (!S->sc_scaled) { S->err = std::string(who) + ": no successful hipkkt_update_scaling since the cones were registered"; return false; }
@@ -40,11 +42,19 @@ struct ConeTables {
     int nexp, npow, n3;
     const int64_t *row0, *out0;
     const double *alpha, *nsout;
+    // the Generalized Power cones after hipkkt_step_enable_genpow (zero otherwise): descriptors, exponents, the mu of the last scaling
+    int ngp;
+    const int64_t *gpdesc;
+    const double *gpalpha;
+    double mu;
 };
 static ConeTables tables(hipkkt_solver *S) {
     const int64_t m = S->img.m;
     ConeTables T{S->d_sc_kind, S->sc_nsoc, S->d_sc_socdesc, S->d_sc_sz, S->d_sc_sz + m, S->d_sc_wl, S->d_sc_wl + m, S->d_sc_eta, m,
-                 0, 0, 0, nullptr, nullptr, nullptr, nullptr};
+                 0, 0, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0.0};
+    if (S->st_cone3 && S->st_genpow) {
+        T.ngp = S->ns_ngenpow; T.gpdesc = S->d_ns_gpdesc; T.gpalpha = S->d_ns_gpalpha; T.mu = S->ns_mu; T.nsout = S->d_ns_out;
+    }
     if (S->st_cone3) {
         T.nexp = S->ns_nexp; T.npow = S->ns_npow; T.n3 = T.nexp + T.npow;
         T.row0 = S->d_ns_row0; T.out0 = S->d_ns_out0; T.alpha = S->d_ns_alpha; T.nsout = S->d_ns_out;
@@ -52,34 +62,42 @@ static ConeTables tables(hipkkt_solver *S) {
     return T;
 }
 
-// every operation: the kernels of step.hip on the Zero / Nonnegative / SecondOrder rows (unchanged), then the Exponential / Power rows
+// every operation: the kernels of step.hip on the Zero / Nonnegative / SecondOrder rows (unchanged), then the Exponential / Power rows,
+// then the Generalized Power rows
 static void op_affine_ds(hipStream_t st, const ConeTables &T, double *out) {
     launch_step_affine_ds(st, T.kind, T.nsoc, T.desc, T.lam, out, T.m);
     launch_step3_copy(st, T.n3, T.row0, T.s, out);
+    launch_genpow_copy(st, T.ngp, T.gpdesc, T.s, out);
 }
 static void op_shift(hipStream_t st, const ConeTables &T, const double *dz, const double *ds, double sigma_mu, double *out) {
     launch_step_shift(st, T.kind, T.nsoc, T.desc, T.w, T.eta, dz, ds, sigma_mu, out, T.m);
     if (T.n3) launch_step3_shift(st, T.nexp, T.npow, T.row0, T.out0, T.alpha, T.nsout, T.z, dz, ds, sigma_mu, out);
+    launch_genpow_shift(st, T.ngp, T.gpdesc, T.nsout, sigma_mu, out);
 }
 static void op_offset(hipStream_t st, const ConeTables &T, const double *ds, double *out) {
     launch_step_offset(st, T.kind, T.nsoc, T.desc, T.z, T.w, T.lam, T.eta, ds, out, T.m);
     launch_step3_copy(st, T.n3, T.row0, ds, out);
+    launch_genpow_copy(st, T.ngp, T.gpdesc, ds, out);
 }
 static void op_mulhs(hipStream_t st, const ConeTables &T, const double *x, const double *addc, double *y) {
     launch_step_mulhs(st, T.kind, T.nsoc, T.desc, T.w, T.eta, x, addc, y, T.m);
     launch_step3_mulhs(st, T.n3, T.row0, T.out0, T.nsout, x, addc, y);
+    launch_genpow_mulhs(st, T.ngp, T.gpdesc, T.nsout, T.mu, x, addc, y);
 }
-// out2 = (alpha_z, alpha_s) of the symmetric cones; with Exponential / Power cones the composite (alpha, alpha) of
+// out2 = (alpha_z, alpha_s) of the symmetric cones; with Exponential / Power / Generalized Power cones the composite (alpha, alpha) of
 // coneops_compositecone.jl:216-252, started from min(alpha_tau, alpha_kappa, 1) when dtau (device) is given (variables.jl:14-43)
 static void op_length(hipkkt_solver *S, hipStream_t st, const ConeTables &T, const double *dz, const double *ds, double alpha_max,
                       const double *dtau, double tau, double kappa, double rhs_kappa, double *out2) {
-    if (!T.n3) {
+    if (!T.n3 && !T.ngp) {
         launch_step_length(st, T.kind, T.nsoc, T.desc, T.z, T.s, dz, ds, alpha_max, S->d_st_part, out2, T.m);
         return;
     }
     launch_step_length(st, T.kind, T.nsoc, T.desc, T.z, T.s, dz, ds, alpha_max, S->d_st_part, S->d_st_out, T.m);
+    // (d_st_part holds 2 (ceil(m / 256) + ncones) doubles: room for the three-row workgroups' partials and one per Generalized Power cone)
+    launch_genpow_length(st, T.ngp, T.gpdesc, T.gpalpha, T.z, T.s, dz, ds, S->d_st_out, dtau, tau, kappa, rhs_kappa, alpha_max,
+                         S->st_c3_step, S->st_c3_amin, S->st_c3_trips, S->d_st_part + step3_length_parts(T.nexp, T.npow));
     launch_step3_length(st, T.nexp, T.npow, T.row0, T.alpha, T.z, T.s, dz, ds, S->d_st_out, dtau, tau, kappa, rhs_kappa, alpha_max,
-                        S->st_c3_step, S->st_c3_amin, S->st_c3_trips, S->d_st_part, out2);
+                        S->st_c3_step, S->st_c3_amin, S->st_c3_trips, S->d_st_part, out2, T.ngp);
 }
 
 // one operation on host vectors of length m: `nin` inputs are staged, op(in0, in1, out) runs, `nout` doubles come back
@@ -114,7 +132,7 @@ static int32_t fused_solve(hipkkt_solver *S, const StepScalars &sc, const double
         HK_CHECK(hipMemcpyAsync(S->d_st_step, d_lhs, (size_t)(n + m) * sizeof(double), hipMemcpyDeviceToDevice, st));
         op_mulhs(st, T, dz, addc, ds);
         // (with Exponential / Power cones the line search starts from min(alpha_tau, alpha_kappa, 1): dtau is the reduction's first scalar)
-        double *out2 = T.n3 ? S->d_st_out + 2 : S->d_st_out;
+        double *out2 = (T.n3 || T.ngp) ? S->d_st_out + 2 : S->d_st_out;
         op_length(S, st, T, dz, ds, 1.0, S->d_red + 3 * (size_t)S->N + n, sc.tau, sc.kappa, sc.rhs_kappa, out2);
         HK_CHECK(hipMemcpyAsync(h2, out2, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
     };
@@ -196,31 +214,52 @@ int32_t hipkkt_cone_step_length(hipkkt_handle h, const double *dz, const double 
 // (without the enable T names no Exponential / Power cone: the symmetric cones' barrier)
 static void barrier_impl(hipkkt_solver *S, const ConeTables &T, const double *z, const double *s, const double *dz, const double *ds,
                          const double *alphas, int64_t nalpha, double *dout) {
+    // (d_st_bar has 8 doubles per registered cone for the per-cone partials: second-order, three-row and Generalized Power together)
+    launch_genpow_barrier(S->stream, T.ngp, T.gpdesc, T.gpalpha, z, s, dz, ds, alphas, (int)nalpha,
+                          step3_barrier_gppart(S->d_st_bar, T.nsoc, T.n3));
     launch_step3_barrier(S->stream, T.kind, T.nsoc, T.desc, T.nexp, T.npow, T.row0, T.alpha, z, s, dz, ds, alphas, (int)nalpha,
-                         S->d_st_bar, dout, T.m);
+                         S->d_st_bar, dout, T.m, T.ngp);
 }
 
-int32_t hipkkt_step_enable_cone3(hipkkt_handle h, int32_t enable, double linesearch_backtrack_step, double min_terminate_step_length) {
-    HK_ENTER(h)
-    if (!enable) { S->st_cone3 = false; return HIPKKT_OK; }
-    if (!S->l1 || !S->sc_ready || !S->sc_cone3_kinds) {
-        S->err = "step_enable_cone3: needs an L1 handle whose last hipkkt_set_cone_types_ex names Zero / Nonnegative / SecondOrder / Exponential / "
-                 "Power cones only, at least one of the last two";
-        return HIPKKT_ERR_ARGUMENT;
-    }
-    const double step = linesearch_backtrack_step, amin = min_terminate_step_length;
+// the parameter checks, the trip bound and the invalidation both enables share
+static int32_t enable_line_search(hipkkt_solver *S, const char *who, double step, double amin) {
     if (!(step > 0.0 && step < 1.0) || !(amin > 0.0) || !std::isfinite(amin)) {
-        S->err = "step_enable_cone3: 0 < linesearch_backtrack_step < 1 and min_terminate_step_length > 0";
+        S->err = std::string(who) + ": 0 < linesearch_backtrack_step < 1 and min_terminate_step_length > 0";
         return HIPKKT_ERR_ARGUMENT;
     }
     // alpha0 <= 1, so alpha0 step^k < alpha_min after at most ceil(log alpha_min / log step) multiplications
     const double trips = std::ceil(std::log(amin) / std::log(step)) + 2.0;
-    if (!(trips <= 4096.0)) { S->err = "step_enable_cone3: the line search would need more than 4096 trips"; return HIPKKT_ERR_ARGUMENT; }
+    if (!(trips <= 4096.0)) { S->err = std::string(who) + ": the line search would need more than 4096 trips"; return HIPKKT_ERR_ARGUMENT; }
     S->st_c3_step = step; S->st_c3_amin = amin; S->st_c3_trips = (int)std::max(trips, 2.0);
     S->st_cone3 = true;
     S->sc_scaled = false;      // the step reads the resident (s, z) of a scaling that ran with the enable in place
     S->st_have_step = false;
     return HIPKKT_OK;
+}
+
+int32_t hipkkt_step_enable_cone3(hipkkt_handle h, int32_t enable, double linesearch_backtrack_step, double min_terminate_step_length) {
+    HK_ENTER(h)
+    if (!enable) { S->st_cone3 = false; S->st_genpow = false; return HIPKKT_OK; }
+    if (!S->l1 || !S->sc_ready || !S->sc_cone3_kinds) {
+        S->err = "step_enable_cone3: needs an L1 handle whose last hipkkt_set_cone_types_ex names Zero / Nonnegative / SecondOrder / Exponential / "
+                 "Power cones only, at least one of the last two";
+        return HIPKKT_ERR_ARGUMENT;
+    }
+    return enable_line_search(S, "step_enable_cone3", linesearch_backtrack_step, min_terminate_step_length);
+    HK_LEAVE
+}
+
+int32_t hipkkt_step_enable_genpow(hipkkt_handle h, int32_t enable, double linesearch_backtrack_step, double min_terminate_step_length) {
+    HK_ENTER(h)
+    if (!enable) { S->st_cone3 = false; S->st_genpow = false; return HIPKKT_OK; }
+    if (!S->l1 || !S->sc_ready || !S->sc_genpow_kinds) {
+        S->err = "step_enable_genpow: needs an L1 handle whose last hipkkt_set_cone_types_ex names Zero / Nonnegative / SecondOrder / Exponential / "
+                 "Power / GenPower cones only, at least one GenPower";
+        return HIPKKT_ERR_ARGUMENT;
+    }
+    const int32_t rc = enable_line_search(S, "step_enable_genpow", linesearch_backtrack_step, min_terminate_step_length);
+    if (rc == HIPKKT_OK) S->st_genpow = true;
+    return rc;
     HK_LEAVE
 }
 

@@ -84,10 +84,27 @@ void launch_step3_shift(hipStream_t st, int nexp, int npow, const int64_t *row0,
                         const double *nsout, const double *z, const double *dz, const double *ds, double sigma_mu, double *out);
 void launch_step3_length(hipStream_t st, int nexp, int npow, const int64_t *row0, const double *alpha, const double *z, const double *s,
                          const double *dz, const double *ds, const double *sym2, const double *dtau, double tau, double kappa,
-                         double rhs_kappa, double alpha_max, double step, double alpha_min, int trips, double *part, double *out2);
+                         double rhs_kappa, double alpha_max, double step, double alpha_min, int trips, double *part, double *out2,
+                         int ngp = 0);
 void launch_step3_barrier(hipStream_t st, const signed char *row_kind, int nsoc, const int64_t *desc, int nexp, int npow,
                           const int64_t *row0, const double *alpha, const double *z, const double *s, const double *dz, const double *ds,
-                          const double *alphas, int nalpha, double *work, double *out, int64_t m);
+                          const double *alphas, int nalpha, double *work, double *out, int64_t m, int ngp = 0);
+// step_genpow.hip: the same operations on the rows of the Generalized Power cones, one wavefront per cone (desc, alpha: the tables of
+// launch_scaling_genpow, desc[8 c + 7] = the bits of 1 / <alpha, alpha>; nsout = the scaling's output vector; mu = the mu of that
+// scaling).  launch_genpow_length writes one partial per cone to `part`, which launch_step3_length(..., ngp) expects behind its own
+// step3_length_parts(nexp, npow) entries; launch_genpow_barrier writes nalpha <= step3_max_candidates() partials per cone (stride 8) to
+// cpart = step3_barrier_gppart(work, nsoc, nexp + npow), which launch_step3_barrier(..., ngp) adds to the cone set's barrier
+int step3_length_parts(int nexp, int npow);
+double *step3_barrier_gppart(double *work, int nsoc, int n3);
+void launch_genpow_copy(hipStream_t st, int ngp, const int64_t *desc, const double *src, double *out);
+void launch_genpow_shift(hipStream_t st, int ngp, const int64_t *desc, const double *nsout, double sigma_mu, double *out);
+void launch_genpow_mulhs(hipStream_t st, int ngp, const int64_t *desc, const double *nsout, double mu, const double *x, const double *addc,
+                         double *y);
+void launch_genpow_length(hipStream_t st, int ngp, const int64_t *desc, const double *alpha, const double *z, const double *s,
+                          const double *dz, const double *ds, const double *sym2, const double *dtau, double tau, double kappa,
+                          double rhs_kappa, double alpha_max, double step, double alpha_min, int trips, double *part);
+void launch_genpow_barrier(hipStream_t st, int ngp, const int64_t *desc, const double *alpha, const double *z, const double *s,
+                           const double *dz, const double *ds, const double *alphas, int nalpha, double *cpart);
 void launch_block_products(hipStream_t st, const DevPlan &P, const double *x, const double *z, double *Px, double *ATz,
                            double *Ax, int n, int m);
 void launch_zero_words(hipStream_t st, void *p, int nwords);

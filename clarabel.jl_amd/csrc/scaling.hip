@@ -262,7 +262,7 @@ __device__ __forceinline__ int wave_or(int v) {
 }
 
 // One wavefront (= one workgroup of 64) per Generalized Power cone.  desc[8 c ..] = {first row, dim1, dim2, first Hs entry, offset of
-// the cone's slot in `out`, offset of its exponents in alpha_all, offset of its index table in idx_all, unused}; the index table is
+// the cone's slot in `out`, offset of its exponents in alpha_all, offset of its index table in idx_all, the bits of 1 / <alpha, alpha> (step_genpow.hip reads them)}; the index table is
 // [map.q (dim1) | map.r (dim2) | map.p (dim) | map.D (3)] of the cone's GenPowExpansionMap (directldl_datamaps.jl:81-99), resident.
 // The cone always takes the Dual scaling with the caller's mu (coneops_genpowcone.jl:21, :64-80).  Products and sums over the cone
 // are butterfly reductions: every lane holds the same phi, |w|^2.

@@ -24,8 +24,6 @@ namespace hipkkt {
 
 namespace {
 
-constexpr double kFloatMax3 = 1.7976931348623157e308;
-constexpr double kSqrtEps = 1.4901161193847656e-08;
 constexpr int kBarBlocks = 64;        // fixed slices of the row sums of the barrier
 constexpr int kBarMax = 8;            // candidates per launch
 
@@ -116,24 +114,6 @@ __device__ __forceinline__ double pow_barrier(const double z[3], const double s[
     const double bp = logsafe(pow(-g[0] / a, 2.0 * a) * pow(-g[1] / (1.0 - a), 2.0 - 2.0 * a) - g[2] * g[2]) + (1.0 - a) * logsafe(-g[0]) +
                       a * logsafe(-g[1]) - 3.0;
     return bd + bp;
-}
-
-// the scalars of variables.jl:14-43 a fused call hands to the step length: dtau comes from the reduction's device scalars
-struct StepTK { const double *dtau; double tau, kappa, rhs_kappa; };
-
-// alpha0 of the non-symmetric cones: min(alpha_tau, alpha_kappa, 1) when T.dtau is given, else alpha_max; then the symmetric cones'
-// (alpha_z, alpha_s); then 1 - sqrt(eps) (coneops_compositecone.jl:238-240)
-__device__ __forceinline__ double alpha_start(const double *sym2, const StepTK T, double alpha_max) {
-    double a = alpha_max;
-    if (T.dtau) {
-        const double dtau = T.dtau[0];
-        const double dkappa = -(T.rhs_kappa + T.kappa * dtau) / T.tau;
-        const double a_tau = dtau < 0.0 ? -T.tau / dtau : kFloatMax3;
-        const double a_kap = dkappa < 0.0 ? -T.kappa / dkappa : kFloatMax3;
-        a = fmin(fmin(a_tau, a_kap), 1.0);
-    }
-    a = fmin(fmin(a, sym2[0]), sym2[1]);
-    return fmin(a, 1.0 - kSqrtEps);
 }
 
 // backtrack_search, coneops_nonsymmetric_common.jl:5-33, with the loop bounded by `trips`
@@ -307,7 +287,7 @@ k_bar_cone3(int first, int count, const int64_t *__restrict__ row0_t, const doub
 // one workgroup: out[2 j] = the cones' barrier, out[2 j + 1] = the shifted dot; every sum in a fixed order
 __global__ void __launch_bounds__(256)
 k_bar_final(const double *__restrict__ part, const double *__restrict__ socpart, int nsoc, const double *__restrict__ c3part, int n3,
-            int nalpha, double *__restrict__ out) {
+            const double *__restrict__ gppart, int ngp, int nalpha, double *__restrict__ out) {
     __shared__ double red[4];
     for (int j = 0; j < nalpha; j++) {
         double acc = 0.0;
@@ -316,10 +296,16 @@ k_bar_final(const double *__restrict__ part, const double *__restrict__ socpart,
         acc = 0.0;
         for (int c = threadIdx.x; c < n3; c += 256) acc += c3part[(int64_t)c * kBarMax + j];
         const double b3 = block_sum3(acc, red);
+        double bgp = 0.0;
+        if (ngp > 0) {                         // (uniform; a set without Generalized Power cones adds nothing, not even 0.0)
+            acc = 0.0;
+            for (int c = threadIdx.x; c < ngp; c += 256) acc += gppart[(int64_t)c * kBarMax + j];
+            bgp = block_sum3(acc, red);
+        }
         if (threadIdx.x == 0) {
             double b = 0.0, d = 0.0;
             for (int k = 0; k < kBarBlocks; k++) { b += part[(2 * j) * kBarBlocks + k]; d += part[(2 * j + 1) * kBarBlocks + k]; }
-            out[2 * j] = (b + bsoc) + b3;
+            out[2 * j] = ngp > 0 ? ((b + bsoc) + b3) + bgp : (b + bsoc) + b3;
             out[2 * j + 1] = d;
         }
     }
@@ -329,6 +315,10 @@ k_bar_final(const double *__restrict__ part, const double *__restrict__ socpart,
 static inline dim3 lanes_grid(int n) { return dim3((unsigned)((n + 255) / 256)); }
 
 int step3_max_candidates() { return kBarMax; }
+// where launch_step3_barrier expects the partials of the Generalized Power cones (kBarMax per cone) in its work buffer
+double *step3_barrier_gppart(double *work, int nsoc, int n3) {
+    return work + 2 * kBarMax * kBarBlocks + (int64_t)kBarMax * ((nsoc > 0 ? nsoc : 0) + n3);
+}
 // doubles of the barrier's work buffer for a handle with `ncones` cones
 int64_t step3_barrier_doubles(int64_t ncones) { return 2 * (int64_t)kBarMax * kBarBlocks + 2 * kBarMax * ncones + 2 * kBarMax; }
 
@@ -347,10 +337,12 @@ void launch_step3_shift(hipStream_t st, int nexp, int npow, const int64_t *row0,
         hipLaunchKernelGGL(k_step3_shift<true>, lanes_grid(npow), dim3(256), 0, st, nexp, npow, row0, out0, alpha, nsout, z, dz, ds, sigma_mu, out);
 }
 // sym2 = (alpha_z, alpha_s) of the symmetric cones (device); dtau (device, may be NULL: then alpha_max is the start) with tau, kappa,
-// rhs_kappa; part: at least (nexp + 255) / 256 + (npow + 255) / 256 doubles; out2 = the composite (alpha, alpha)
+// rhs_kappa; part: at least (nexp + 255) / 256 + (npow + 255) / 256 + ngp doubles, the last ngp of them already written on this stream by
+// launch_genpow_length (step_genpow.hip); out2 = the composite (alpha, alpha)
+int step3_length_parts(int nexp, int npow) { return (nexp + 255) / 256 + (npow + 255) / 256; }
 void launch_step3_length(hipStream_t st, int nexp, int npow, const int64_t *row0, const double *alpha, const double *z, const double *s,
                          const double *dz, const double *ds, const double *sym2, const double *dtau, double tau, double kappa,
-                         double rhs_kappa, double alpha_max, double step, double alpha_min, int trips, double *part, double *out2) {
+                         double rhs_kappa, double alpha_max, double step, double alpha_min, int trips, double *part, double *out2, int ngp) {
     const StepTK T{dtau, tau, kappa, rhs_kappa};
     const int be = (nexp + 255) / 256, bp = (npow + 255) / 256;
     if (nexp > 0)
@@ -359,12 +351,13 @@ void launch_step3_length(hipStream_t st, int nexp, int npow, const int64_t *row0
     if (npow > 0)
         hipLaunchKernelGGL(k_step3_len<true>, dim3(bp), dim3(256), 0, st, nexp, npow, row0, alpha, z, s, dz, ds, sym2, T, alpha_max, step,
                            alpha_min, trips, part + be);
-    hipLaunchKernelGGL(k_step3_len_final, dim3(1), dim3(256), 0, st, part, be + bp, sym2, T, alpha_max, out2);
+    hipLaunchKernelGGL(k_step3_len_final, dim3(1), dim3(256), 0, st, part, be + bp + ngp, sym2, T, alpha_max, out2);
 }
-// work: step3_barrier_doubles(ncones) doubles; out: 2 * nalpha doubles (device)
+// work: step3_barrier_doubles(ncones) doubles; out: 2 * nalpha doubles (device); with ngp > 0 launch_genpow_barrier (step_genpow.hip) has
+// written the Generalized Power cones' partials to step3_barrier_gppart(work, nsoc, nexp + npow) on this stream
 void launch_step3_barrier(hipStream_t st, const signed char *row_kind, int nsoc, const int64_t *desc, int nexp, int npow,
                           const int64_t *row0, const double *alpha, const double *z, const double *s, const double *dz, const double *ds,
-                          const double *alphas, int nalpha, double *work, double *out, int64_t m) {
+                          const double *alphas, int nalpha, double *work, double *out, int64_t m, int ngp) {
     BarAlphas A;
     A.n = nalpha;
     for (int j = 0; j < kBarMax; j++) A.a[j] = j < nalpha ? alphas[j] : 0.0;
@@ -373,7 +366,8 @@ void launch_step3_barrier(hipStream_t st, const signed char *row_kind, int nsoc,
     if (nsoc > 0) hipLaunchKernelGGL(k_bar_soc, dim3(nsoc), dim3(256), 0, st, desc, z, s, dz, ds, A, socpart);
     if (nexp > 0) hipLaunchKernelGGL(k_bar_cone3<false>, lanes_grid(nexp), dim3(256), 0, st, 0, nexp, row0, alpha, z, s, dz, ds, A, c3part);
     if (npow > 0) hipLaunchKernelGGL(k_bar_cone3<true>, lanes_grid(npow), dim3(256), 0, st, nexp, npow, row0, alpha, z, s, dz, ds, A, c3part);
-    hipLaunchKernelGGL(k_bar_final, dim3(1), dim3(256), 0, st, part, socpart, nsoc, c3part, nexp + npow, nalpha, out);
+    hipLaunchKernelGGL(k_bar_final, dim3(1), dim3(256), 0, st, part, socpart, nsoc, c3part, nexp + npow,
+                       c3part + (int64_t)kBarMax * (nexp + npow), ngp, nalpha, out);
 }
 
 }  // namespace hipkkt

@@ -43,7 +43,7 @@ SYMBOLS = [
     "hipkkt_set_equilibration", "hipkkt_step_affine_dev", "hipkkt_step_combined_dev", "hipkkt_step_apply_dev", "hipkkt_step_info_norms_dev",
     "hipkkt_step_get",
     # ... for the Exponential / Power cones as well (opt-in), and the barrier of the line search (added within ABI version 5)
-    "hipkkt_step_enable_cone3", "hipkkt_cone_barrier", "hipkkt_step_barrier_dev",
+    "hipkkt_step_enable_cone3", "hipkkt_cone_barrier", "hipkkt_step_barrier_dev", "hipkkt_step_enable_genpow",
 ]
 
 
@@ -152,6 +152,7 @@ def lib():
     L.hipkkt_step_info_norms_dev.argtypes = [vp, vp, vp, _f64p]
     L.hipkkt_step_get.argtypes = [vp, _f64p]
     L.hipkkt_step_enable_cone3.argtypes = [vp, i32, f64, f64]
+    L.hipkkt_step_enable_genpow.argtypes = [vp, i32, f64, f64]
     L.hipkkt_cone_barrier.argtypes = [vp, _f64p, _f64p, _f64p, i64, _f64p]
     L.hipkkt_step_barrier_dev.argtypes = [vp, vp, _f64p, i64, _f64p]
     L.hipkkt_debug_dump.argtypes = [vp, i32, vp, i64, C.POINTER(i64)]
@@ -680,6 +681,12 @@ class Handle:
         """ValueError unless the registration names kinds {0, 1, 2, 4, 5} only with a 4 / 5, 0 < step < 1, alpha_min > 0"""
         self._chk_step(self.L.hipkkt_step_enable_cone3(self.h, int(bool(enable)), float(linesearch_backtrack_step),
                                                        float(min_terminate_step_length)), "step_enable_cone3")
+
+    def step_enable_genpow(self, enable, linesearch_backtrack_step, min_terminate_step_length):
+        """the same for a registration with Generalized Power cones: ValueError unless it names kinds {0, 1, 2, 4, 5, 6} only with a 6;
+        the Exponential / Power members of the set step with the same parameters"""
+        self._chk_step(self.L.hipkkt_step_enable_genpow(self.h, int(bool(enable)), float(linesearch_backtrack_step),
+                                                        float(min_terminate_step_length)), "step_enable_genpow")
 
     @staticmethod
     def _alphas(alphas):

@@ -18,11 +18,12 @@ from .settings import Settings
 _DEBUG = os.environ.get("HIPKKT_DEBUG", "0") == "1"
 
 
-def cone_set_steps_on_device(cones, nonsymmetric=False) -> bool:
+def cone_set_steps_on_device(cones, nonsymmetric=False, genpower=False) -> bool:
     """the step entry points (hipkkt_cone_* / hipkkt_step_*) serve cone sets of ZeroCone, NonnegativeCone and SecondOrderCone only: a PSD
     cone's step length needs eigenvalue decompositions, the non-symmetric cones need backtracking and barriers.
     nonsymmetric=True: ExponentialCone and PowerCone members qualify as well (hipkkt_step_enable_cone3); Generalized Power and PSD
-    members still do not"""
+    members still do not.
+    genpower=True (with nonsymmetric=True): Generalized Power members qualify too (hipkkt_step_enable_genpow); PSD members do not"""
     if not hasattr(cones, "kkt_cone_kinds"):
         return False
     kinds = cones.kkt_cone_kinds_ex()[0] if hasattr(cones, "kkt_cone_kinds_ex") else cones.kkt_cone_kinds()
@@ -30,6 +31,8 @@ def cone_set_steps_on_device(cones, nonsymmetric=False) -> bool:
     ok = (kinds >= 0) & (kinds <= 2)
     if nonsymmetric:
         ok = ok | (kinds == 4) | (kinds == 5)
+        if genpower:
+            ok = ok | (kinds == 6)
     return kinds.size > 0 and bool(np.all(ok))
 
 
@@ -80,6 +83,12 @@ class HipKKTSolver:
         if not self._steps_on_device and getattr(settings, "device_step_nonsymmetric", False) and self.scales_nonsymmetric \
                 and cone_set_steps_on_device(cones, nonsymmetric=True):
             self.h.step_enable_cone3(True, settings.linesearch_backtrack_step, settings.min_terminate_step_length)
+            self._steps_on_device = self.steps_nonsymmetric = True
+        # ... and, opted in by Settings.device_step_genpower on top of it, sets with Generalized Power members
+        elif not self._steps_on_device and getattr(settings, "device_step_nonsymmetric", False) \
+                and getattr(settings, "device_step_genpower", False) and self.scales_nonsymmetric \
+                and cone_set_steps_on_device(cones, nonsymmetric=True, genpower=True):
+            self.h.step_enable_genpow(True, settings.linesearch_backtrack_step, settings.min_terminate_step_length)
             self._steps_on_device = self.steps_nonsymmetric = True
         self.scaling_nonsym = None
         self.scaling_w = self.scaling_lambda = self.scaling_soc_eta = None

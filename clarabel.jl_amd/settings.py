@@ -60,7 +60,11 @@ class Settings:
     # Needs device_scaling, device_reduced and device_residuals: the caller raises ValueError when one of them is off.
     device_step: bool = False
     # device_step for cone sets that also hold Exponential / Power cones (backtracking line search, third-order correction and the
-    # barrier of the Dual strategy on the device); Generalized Power and PSD cone sets keep the host path.  Needs device_step: the
+    # barrier of the Dual strategy on the device); Generalized Power (without device_step_genpower) and PSD cone sets keep the host path.  Needs device_step: the
     # caller raises ValueError otherwise.
     device_step_nonsymmetric: bool = False
+    # device_step_nonsymmetric for cone sets that also hold Generalized Power cones (hipkkt_step_enable_genpow: feasibility backtracking
+    # and the barrier with its Newton iteration for the primal gradient, one wavefront per cone); PSD cone sets keep the host path.
+    # Needs device_step_nonsymmetric: the caller raises ValueError otherwise.
+    device_step_genpower: bool = False
     extra: dict = field(default_factory=dict)

@@ -73,7 +73,7 @@ int32_t hipkkt_is_available(void);
  * 4: hipkkt_get_profile / hipkkt_get_counters take the capacity of the caller's buffer (they wrote a fixed, growing number of values).
  * 5: hipkkt_set_cone_types_ex / hipkkt_get_nonsym_len / hipkkt_update_scaling_ex[_dev] (the bindings bind them when they load).
  *    Added within 5, no signature changed: the step entry points hipkkt_cone_* / hipkkt_set_equilibration / hipkkt_step_*;
- *    hipkkt_step_enable_cone3 / hipkkt_cone_barrier / hipkkt_step_barrier_dev. */
+ *    hipkkt_step_enable_cone3 / hipkkt_cone_barrier / hipkkt_step_barrier_dev; hipkkt_step_enable_genpow. */
 #define HIPKKT_ABI_VERSION 5
 int32_t hipkkt_abi_version(void);
 /* releases the process-wide cache of device memory blocks the library keeps between handles (not in the reference: an embedding
@@ -343,7 +343,20 @@ int32_t hipkkt_residuals_dev(hipkkt_handle h, const double *xzs_dev, double tau,
  * Rows of kinds 0..2 go through the same kernels as without the enable, bit for bit.  Every loop on the device is bounded: the
  * backtracking by ceil(log alpha_min / log step) + 2 trips (at most 4096, else the enable is refused), Newton iterations by the
  * reference's 100 steps; a direction that leaves a cone for every alpha gives alpha = 0, never a trap.
- * Kinds 3 (PSD) and 6 (GenPower) stay refused, at hipkkt_step_enable_cone3 and therefore everywhere.
+ * Kinds 3 (PSD) and 6 (GenPower) stay refused at hipkkt_step_enable_cone3; kind 6 has its own opt-in, next.
+ *
+ * Opt-in for GenPowerCone (kind 6): after hipkkt_step_enable_genpow on a registration of kinds {0, 1, 2, 4, 5, 6} with at least one 6
+ * every call of this section serves all rows of that handle; the kind 4 / 5 members step as after hipkkt_step_enable_cone3 with the
+ * same parameters.  A kind 6 cone works on the resident (s, z), its slot [grad | d1 | d2 | p | q | r] of the scaling's output vector and
+ * the mu of that scaling (coneops_genpowcone.jl; the cone always takes the Dual scaling):
+ *   affine_ds = the resident s; ds_from_dz_offset = ds; combined_ds_shift = grad sigma mu (no third-order correction, :149-168);
+ *   mul_hs = mu (D x + (p.x) p - (q.x1) q - (r.x2) r) (:111-135), the three dots as tree sums;
+ *   step length = the same backtracking on the same grid alpha0 step^k with is_dual_feasible / is_primal_feasible of :249-292; the
+ *     composite step is the minimum over all kind 4 / 5 / 6 cones;
+ *   barrier = barrier_dual + barrier_primal (:209-234, :294-333), the primal gradient from the one-sided Newton iteration of :393-472
+ *     (at most 100 steps), one value per (cone, candidate) added to the cone set's barrier.
+ * Sums and products over a cone are tree reductions; otherwise expressions keep the reference's association.  A registration without
+ * kind 6 computes exactly what it computed before this call existed.  A PSD cone (kind 3) is refused here too.
  *
  * One operation each, host vectors of length m in cone order (the unit-tested surface):
  *   hipkkt_cone_affine_ds            ds = lambda o lambda                  coneops_nncone.jl affine_ds!, coneops_socone.jl:219-228
@@ -361,6 +374,10 @@ int32_t hipkkt_cone_step_length(hipkkt_handle h, const double *dz, const double 
  * 0 < linesearch_backtrack_step < 1, min_terminate_step_length > 0 and the implied trip count is at most 4096.  enable == 0 switches
  * it off.  Every hipkkt_set_cone_types[_ex] clears it. */
 int32_t hipkkt_step_enable_cone3(hipkkt_handle h, int32_t enable, double linesearch_backtrack_step, double min_terminate_step_length);
+/* enable != 0: HIPKKT_ERR_ARGUMENT unless the last hipkkt_set_cone_types_ex names kinds {0, 1, 2, 4, 5, 6} only with at least one 6; the
+ * parameter checks, the trip bound and the invalidation of the resident scaling are those of hipkkt_step_enable_cone3.  enable == 0
+ * switches the GenPower and the Exponential / Power step off.  Every hipkkt_set_cone_types[_ex] clears it. */
+int32_t hipkkt_step_enable_genpow(hipkkt_handle h, int32_t enable, double linesearch_backtrack_step, double min_terminate_step_length);
 /* compute_barrier of the cone set (Zero 0, Nonnegative -sum log((s + a ds)(z + a dz)), coneops_socone.jl:288-305,
  * coneops_expcone.jl:189-248, coneops_powcone.jl:228-251) and dot_shifted (mathutils.jl:23-43) at nalpha <= 8 candidate step lengths:
  * out[2 j] = the barrier, out[2 j + 1] = <z + a_j dz, s + a_j ds>, both summed over fixed slices in a fixed order.  A point outside a

@@ -126,6 +126,12 @@ function hip_step_enable_cone3!(handle::Ptr{Cvoid}, enable::Bool, backtrack_step
                backtrack_step, min_terminate_step_length)
     return hip_step_check(handle, rc, "hipkkt_step_enable_cone3")
 end
+# the same for a registration with Generalized Power cones (kind 6); its Exponential / Power members step with the same parameters
+function hip_step_enable_genpow!(handle::Ptr{Cvoid}, enable::Bool, backtrack_step::Float64, min_terminate_step_length::Float64)
+    rc = ccall((:hipkkt_step_enable_genpow, libhipkkt), Int32, (Ptr{Cvoid}, Int32, Float64, Float64), handle, enable ? 1 : 0,
+               backtrack_step, min_terminate_step_length)
+    return hip_step_check(handle, rc, "hipkkt_step_enable_genpow")
+end
 # -> out[2j-1] = the cones' barrier, out[2j] = <z + αⱼΔz, s + αⱼΔs> for at most 8 candidates αⱼ
 function hip_cone_barrier(handle::Ptr{Cvoid}, Δz::Vector{Float64}, Δs::Vector{Float64}, αs::Vector{Float64})
     out = zeros(Float64, 2 * length(αs))

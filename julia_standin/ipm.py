@@ -396,14 +396,17 @@ class Solver:
             raise ValueError("Settings.device_step needs device_scaling, device_reduced and device_residuals")
         if getattr(st, "device_step_nonsymmetric", False) and not getattr(st, "device_step", False):
             raise ValueError("Settings.device_step_nonsymmetric needs device_step")
+        if getattr(st, "device_step_genpower", False) and not getattr(st, "device_step_nonsymmetric", False):
+            raise ValueError("Settings.device_step_genpower needs device_step_nonsymmetric")
         self._device_step = bool(getattr(st, "device_step", False)) and hasattr(ks, "kktsolver_step_affine") and \
             bool(getattr(ks, "steps_on_device", False))
         if self._device_step and not self.cones.is_symmetric():
             # a set with Exponential / Power members (include/hipkkt.h kinds 4, 5) steps on the device when that is opted in and the
-            # plugin offers the calls; a Generalized Power member keeps the host loop
+            # plugin offers the calls; a Generalized Power member (kind 6) keeps the host loop unless device_step_genpower is set too
+            kinds_ok = (4, 5, 6) if getattr(st, "device_step_genpower", False) else (4, 5)
             self._device_step = bool(getattr(st, "device_step_nonsymmetric", False)) and \
                 hasattr(ks, "kktsolver_update_scaling_dev_ex") and hasattr(ks, "kktsolver_step_barrier") and \
-                all(getattr(c, "is_symmetric", True) or getattr(c, "kind_code_ex", -1) in (4, 5) for c in self.cones)
+                all(getattr(c, "is_symmetric", True) or getattr(c, "kind_code_ex", -1) in kinds_ok for c in self.cones)
         self.barrier_searches = self.barrier_backtracks = 0      # _backtrack_step_to_barrier calls / candidates it rejected (last solve)
         self._needs_qb = self._needs_qb or (self._device_step and hasattr(ks, "set_problem_vectors"))
         if self._needs_qb:               # q, b resident in the plugin (N4 residuals, N2 reduced-system algebra)
@@ -748,7 +751,7 @@ class Solver:
             b.close()
         return self._finish(t_start, t_loop, alpha, sigma, mu, it)
 
-    # ------------------------------------------------------------- the same for cone sets with Exponential / Power members
+    # ------------------------------------------------------------- the same for cone sets with Exponential / Power / GenPower members
     def _solve_device_step_nonsymmetric(self):
         """_solve_device_step for Settings.device_step_nonsymmetric: the loop of _solve with its three strategy checkpoints
         (solver.jl:453-506), fed by scalars.  mu and the strategy go to the scaling call; a re-run with the Dual strategy applies no
