@@ -418,6 +418,16 @@ static int32_t set_cone_types_impl(hipkkt_handle h, int64_t ncones, const int32_
         anygp = anygp || kinds[c] == HIPKKT_CONE_GENPOW;
     }
     S->sc_genpow_kinds = S->sc_genpow_kinds && anygp;
+    // hipkkt_step_enable_psd likewise: kinds {0, 1, 2, 3} with at least one PSD triangle cone (the sides are checked at the enable)
+    S->st_psd = false;
+    S->psd_fresh = false;
+    S->sc_psd_kinds = true;
+    bool anypsd = false;
+    for (int64_t c = 0; c < ncones; c++) {
+        S->sc_psd_kinds = S->sc_psd_kinds && kinds[c] >= 0 && kinds[c] <= 3;
+        anypsd = anypsd || kinds[c] == 3;
+    }
+    S->sc_psd_kinds = S->sc_psd_kinds && anypsd;
     // the non-symmetric cones: three-row cones in two lists (joined [Exponential | Power] below), GenPower descriptors of 8 values
     struct Row3 { int64_t row0, hs0, out0; double alpha; };
     std::vector<Row3> exp3, pow3;
@@ -426,7 +436,7 @@ static int32_t set_cone_types_impl(hipkkt_handle h, int64_t ncones, const int32_
     int64_t aoff = 0, ns_out = 0;
     std::vector<signed char> kind((size_t)std::max<int64_t>(m, 1), 2);
     std::vector<int64_t> rowhs((size_t)std::max<int64_t>(m, 1), 0), socdesc;
-    S->sc_psd_hs.clear(); S->sc_psd_n.clear(); S->sc_psd_total = 0; S->sc_nsoc = 0;
+    S->sc_psd_hs.clear(); S->sc_psd_n.clear(); S->sc_psd_row.clear(); S->sc_psd_total = 0; S->sc_nsoc = 0;
     int64_t row = 0, hs = 0;
     int sparse_idx = 0;
     for (int64_t c = 0; c < ncones; c++) {
@@ -455,6 +465,7 @@ static int32_t set_cone_types_impl(hipkkt_handle h, int64_t ncones, const int32_
             if (!dense || sk != 0 || n * (n + 1) / 2 != numel) { S->err = "set_cone_types: a PSD triangle cone has a dense block of triangular size"; return HIPKKT_ERR_ARGUMENT; }
             S->sc_psd_hs.push_back(hs);
             S->sc_psd_n.push_back(n);
+            S->sc_psd_row.push_back(row);
             S->sc_psd_total += n * n;
         } else if (ex && (kinds[c] == HIPKKT_CONE_EXP || kinds[c] == HIPKKT_CONE_POW)) {
             if (numel != 3 || !dense || sk != 0) { S->err = "set_cone_types_ex: an Exponential / Power cone has three rows, a dense Hs block and no expansion"; return HIPKKT_ERR_ARGUMENT; }
@@ -577,6 +588,11 @@ static int32_t update_scaling_impl(hipkkt_handle h, const double *s, const doubl
     if (ex && strategy != 0 && strategy != 1) { S->err = "update_scaling_ex: strategy is 0 (PrimalDual) or 1 (Dual)"; return HIPKKT_ERR_ARGUMENT; }
     const int64_t m = S->img.m;
     if (m && (!s || !z)) { S->err = "update_scaling: null s / z"; return HIPKKT_ERR_ARGUMENT; }
+    if (S->st_psd && (!psd_R || !S->psd_fresh)) {
+        S->sc_scaled = false;
+        S->err = "update_scaling: after hipkkt_step_enable_psd the call needs psd_R and the factors of a hipkkt_psd_set_factors[_dev] since the last scaling";
+        return HIPKKT_ERR_ARGUMENT;
+    }
     const double *ds = s, *dz = z, *dR = psd_R;
     if (!dev) {
         if (m) {
@@ -588,12 +604,23 @@ static int32_t update_scaling_impl(hipkkt_handle h, const double *s, const doubl
             HK_CHECK(hipMemcpyAsync(S->d_sc_R, psd_R, (size_t)S->sc_psd_total * sizeof(double), hipMemcpyHostToDevice, S->stream));
             dR = S->d_sc_R;
         }
-    } else if (m && (S->sc_step_kinds || S->st_cone3)) {      // the step entry points read the resident copy of (s, z)
+    } else if (m && (S->sc_step_kinds || S->st_cone3 || S->st_psd)) {      // the step entry points read the resident copy of (s, z)
         HK_CHECK(hipMemcpyAsync(S->d_sc_sz, s, m * sizeof(double), hipMemcpyDeviceToDevice, S->stream));
         HK_CHECK(hipMemcpyAsync(S->d_sc_sz + m, z, m * sizeof(double), hipMemcpyDeviceToDevice, S->stream));
     }
+    if (S->st_psd) {      // the PSD step reads the resident (R, Rinv, lambda): R next to the staged pair
+        if (dev) {
+            HK_CHECK(hipMemcpyAsync(S->d_sc_R, psd_R, (size_t)S->sc_psd_total * sizeof(double), hipMemcpyDeviceToDevice, S->stream));
+            dR = S->d_sc_R;
+        }
+        HK_CHECK(hipMemcpyAsync(S->d_psd_rinv, S->d_psd_stage, (size_t)S->sc_psd_total * sizeof(double), hipMemcpyDeviceToDevice, S->stream));
+        HK_CHECK(hipMemcpyAsync(S->d_psd_lam, S->d_psd_stage + S->sc_psd_total, (size_t)S->psd_lam_total * sizeof(double),
+                                hipMemcpyDeviceToDevice, S->stream));
+        S->psd_fresh = false;
+    }
     double *dw = S->d_sc_wl, *dl = S->d_sc_wl + m;
     launch_zero_words(S->stream, S->d_sc_fail, 1);
+    if (S->st_psd) launch_psd_step_check(S->stream, S->d_psd_lam, S->psd_lam_total, S->d_sc_fail);
     launch_scaling_diag(S->stream, S->d_sc_kind, S->d_sc_rowhs, S->d_mapHs, ds, dz, dw, dl, S->dp.kval, m);
     launch_scaling_soc(S->stream, S->sc_nsoc, S->d_sc_socdesc, S->d_mapHs, ds, dz, dw, dl, S->d_sc_eta, S->d_soc_u, S->d_soc_v,
                        S->d_soc_eta2, S->dp.kval, S->d_sc_fail);

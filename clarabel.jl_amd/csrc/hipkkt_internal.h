@@ -260,6 +260,18 @@ struct hipkkt_solver {
     bool sc_genpow_kinds = false;                          // the registration names kinds {0, 1, 2, 4, 5, 6} only, at least one 6
     bool st_genpow = false;                                // enabled since that registration
     double ns_mu = 0.0;                                    // mu of the last hipkkt_update_scaling_ex[_dev] (mul_Hs of the GenPower cones)
+    // hipkkt_step_enable_psd: the step entry points also serve the PSD triangle cones of the registration (step_psd.hip), from the
+    // caller's factors: hipkkt_psd_set_factors[_dev] stages [Rinv | lambda], the next hipkkt_update_scaling[_dev] makes them resident
+    // next to its psd_R (d_sc_R)
+    bool sc_psd_kinds = false;                             // the registration names kinds {0, 1, 2, 3} only, at least one 3
+    std::vector<int64_t> sc_psd_row;                       // per PSD cone: first row
+    bool st_psd = false;                                   // enabled since that registration
+    bool psd_fresh = false;                                // factors staged since the last scaling
+    int64_t psd_lam_total = 0;                             // sum of n over the PSD cones
+    int64_t psd_cap_cones = 0, psd_cap_mat = 0, psd_cap_lam = 0;   // capacities, as sc_cap_*
+    int64_t *d_psd_tab = nullptr;                          // 4 per cone: [row0 | n | offset of the factors | offset of lambda]
+    double *d_psd_rinv = nullptr, *d_psd_lam = nullptr;    // resident factors of the last scaling
+    double *d_psd_stage = nullptr;                         // staged [Rinv (sc_psd_total) | lambda (psd_lam_total)]
     double *d_st_bar = nullptr;                            // work buffer of the barrier (step3_barrier_doubles)
     // N1, the non-symmetric cones (hipkkt_set_cone_types_ex + hipkkt_update_scaling_ex): tables built once per registration
     bool ns_active = false;                                // the last registration named an Exponential / Power / GenPower cone

@@ -4,6 +4,7 @@
 // After hipkkt_step_enable_cone3 also the Exponential / Power cones of the registration (step_cone3.hip), on the (s, z) and the
 // [Hs | H_dual | grad] that hipkkt_update_scaling_ex[_dev] left resident; then hipkkt_cone_barrier / hipkkt_step_barrier_dev as well.
 // After hipkkt_step_enable_genpow the Generalized Power cones too (step_genpow.hip), on their slot [grad | d1 | d2 | p | q | r].
+// After hipkkt_step_enable_psd the PSD triangle cones of a symmetric registration (step_psd.hip), on the caller's (R, Rinv, lambda).
 #include "hipkkt_internal.h"
 
 #pragma clang fp contract(off)      // the scalars below repeat the caller's expressions (variables.jl:14-43, :124-162) rounding by rounding
@@ -12,10 +13,10 @@ namespace hipkkt_host {
 
 // the cone set and its scaling allow the step entry points
 static bool step_ready(hipkkt_solver *S, const char *who) {
-    if (!S->l1 || !S->sc_ready || !(S->sc_step_kinds || S->st_cone3)) {
+    if (!S->l1 || !S->sc_ready || !(S->sc_step_kinds || S->st_cone3 || S->st_psd)) {
         S->err = std::string(who) + ": needs an L1 handle whose registered cones are Zero / Nonnegative / SecondOrder only, or one with "
                                     "Exponential / Power cones next to them after hipkkt_step_enable_cone3, or with Generalized Power cones "
-                                    "after hipkkt_step_enable_genpow";
+                                    "after hipkkt_step_enable_genpow, or with PSD triangle cones after hipkkt_step_enable_psd";
         return false;
     }
     if (!S->sc_scaled) { S->err = std::string(who) + ": no successful hipkkt_update_scaling since the cones were registered"; return false; }
@@ -30,7 +31,7 @@ static void ensure_step_buffers(hipkkt_solver *S) {
     S->d_st_in = S->dalloc<double>(2 * n + m);
     S->d_st_work = S->dalloc<double>(4 * m);
     S->d_st_part = S->dalloc<double>((size_t)std::max<int64_t>(2 * pairs, step_norm_part_doubles()));
-    S->d_st_out = S->dalloc<double>(32);      // 0..3 step lengths, 4..11 norms, 12..27 barrier results
+    S->d_st_out = S->dalloc<double>(32);      // 0..3 step lengths, 4..11 norms, 12..27 barrier results, 28..29 the symmetric pair next to PSD cones
     S->d_st_bar = S->dalloc<double>((size_t)step3_barrier_doubles((int64_t)S->cone_numel.size()));
 }
 
@@ -47,11 +48,19 @@ struct ConeTables {
     const int64_t *gpdesc;
     const double *gpalpha;
     double mu;
+    // the PSD triangle cones after hipkkt_step_enable_psd (zero otherwise): the table [row0 | n | factor offset | lambda offset], factors
+    int npsd;
+    const int64_t *psdtab;
+    const double *psdR, *psdRinv, *psdlam;
 };
 static ConeTables tables(hipkkt_solver *S) {
     const int64_t m = S->img.m;
     ConeTables T{S->d_sc_kind, S->sc_nsoc, S->d_sc_socdesc, S->d_sc_sz, S->d_sc_sz + m, S->d_sc_wl, S->d_sc_wl + m, S->d_sc_eta, m,
-                 0, 0, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0.0};
+                 0, 0, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0.0,
+                 0, nullptr, nullptr, nullptr, nullptr};
+    if (S->st_psd) {
+        T.npsd = (int)S->sc_psd_n.size(); T.psdtab = S->d_psd_tab; T.psdR = S->d_sc_R; T.psdRinv = S->d_psd_rinv; T.psdlam = S->d_psd_lam;
+    }
     if (S->st_cone3 && S->st_genpow) {
         T.ngp = S->ns_ngenpow; T.gpdesc = S->d_ns_gpdesc; T.gpalpha = S->d_ns_gpalpha; T.mu = S->ns_mu; T.nsout = S->d_ns_out;
     }
@@ -63,31 +72,43 @@ static ConeTables tables(hipkkt_solver *S) {
 }
 
 // every operation: the kernels of step.hip on the Zero / Nonnegative / SecondOrder rows (unchanged), then the Exponential / Power rows,
-// then the Generalized Power rows
+// then the Generalized Power rows, then the PSD rows (a set has either non-symmetric or PSD members on this path)
 static void op_affine_ds(hipStream_t st, const ConeTables &T, double *out) {
     launch_step_affine_ds(st, T.kind, T.nsoc, T.desc, T.lam, out, T.m);
     launch_step3_copy(st, T.n3, T.row0, T.s, out);
     launch_genpow_copy(st, T.ngp, T.gpdesc, T.s, out);
+    launch_psd_step_affine_ds(st, T.npsd, T.psdtab, T.psdlam, out);
 }
 static void op_shift(hipStream_t st, const ConeTables &T, const double *dz, const double *ds, double sigma_mu, double *out) {
     launch_step_shift(st, T.kind, T.nsoc, T.desc, T.w, T.eta, dz, ds, sigma_mu, out, T.m);
     if (T.n3) launch_step3_shift(st, T.nexp, T.npow, T.row0, T.out0, T.alpha, T.nsout, T.z, dz, ds, sigma_mu, out);
     launch_genpow_shift(st, T.ngp, T.gpdesc, T.nsout, sigma_mu, out);
+    launch_psd_step_shift(st, T.npsd, T.psdtab, T.psdR, T.psdRinv, dz, ds, sigma_mu, out);
 }
 static void op_offset(hipStream_t st, const ConeTables &T, const double *ds, double *out) {
     launch_step_offset(st, T.kind, T.nsoc, T.desc, T.z, T.w, T.lam, T.eta, ds, out, T.m);
     launch_step3_copy(st, T.n3, T.row0, ds, out);
     launch_genpow_copy(st, T.ngp, T.gpdesc, ds, out);
+    launch_psd_step_offset(st, T.npsd, T.psdtab, T.psdR, T.psdlam, ds, out);
 }
 static void op_mulhs(hipStream_t st, const ConeTables &T, const double *x, const double *addc, double *y) {
     launch_step_mulhs(st, T.kind, T.nsoc, T.desc, T.w, T.eta, x, addc, y, T.m);
     launch_step3_mulhs(st, T.n3, T.row0, T.out0, T.nsout, x, addc, y);
     launch_genpow_mulhs(st, T.ngp, T.gpdesc, T.nsout, T.mu, x, addc, y);
+    launch_psd_step_mulhs(st, T.npsd, T.psdtab, T.psdR, x, addc, y);
 }
 // out2 = (alpha_z, alpha_s) of the symmetric cones; with Exponential / Power / Generalized Power cones the composite (alpha, alpha) of
 // coneops_compositecone.jl:216-252, started from min(alpha_tau, alpha_kappa, 1) when dtau (device) is given (variables.jl:14-43)
 static void op_length(hipkkt_solver *S, hipStream_t st, const ConeTables &T, const double *dz, const double *ds, double alpha_max,
                       const double *dtau, double tau, double kappa, double rhs_kappa, double *out2) {
+    if (T.npsd) {
+        // the symmetric rows' launch as it is, its pair parked in d_st_out[28..29]; the PSD cones' pairs follow its partials in d_st_part
+        // (2 (ceil(m / 256) + ncones) doubles: second-order and PSD cones together are at most ncones)
+        launch_step_length(st, T.kind, T.nsoc, T.desc, T.z, T.s, dz, ds, alpha_max, S->d_st_part, S->d_st_out + 28, T.m);
+        launch_psd_step_length(st, T.npsd, T.psdtab, T.psdR, T.psdRinv, T.psdlam, dz, ds, alpha_max, S->d_st_out + 28,
+                               S->d_st_part + 2 * step_len_pairs(T.m, T.nsoc), out2);
+        return;
+    }
     if (!T.n3 && !T.ngp) {
         launch_step_length(st, T.kind, T.nsoc, T.desc, T.z, T.s, dz, ds, alpha_max, S->d_st_part, out2, T.m);
         return;
@@ -263,9 +284,65 @@ int32_t hipkkt_step_enable_genpow(hipkkt_handle h, int32_t enable, double linese
     HK_LEAVE
 }
 
+int32_t hipkkt_step_enable_psd(hipkkt_handle h, int32_t enable) {
+    HK_ENTER(h)
+    if (!enable) { S->st_psd = false; return HIPKKT_OK; }
+    bool ok = S->l1 && S->sc_ready && S->sc_psd_kinds;
+    for (size_t c = 0; ok && c < S->sc_psd_n.size(); c++) ok = S->sc_psd_n[c] <= HIPKKT_PSD_STEP_MAX_DIM;
+    if (!ok) {
+        S->err = "step_enable_psd: needs an L1 handle whose last hipkkt_set_cone_types[_ex] names Zero / Nonnegative / SecondOrder / PSD "
+                 "triangle cones only, at least one PSD cone, every PSD side <= HIPKKT_PSD_STEP_MAX_DIM";
+        return HIPKKT_ERR_ARGUMENT;
+    }
+    // the cone table and the factor buffers: allocated on the first call, re-used while large enough (as the d_sc_* buffers)
+    const int64_t npsd = (int64_t)S->sc_psd_n.size();
+    std::vector<int64_t> tab((size_t)(4 * npsd));
+    int64_t foff = 0, loff = 0;
+    for (int64_t c = 0; c < npsd; c++) {
+        const int64_t n = S->sc_psd_n[c];
+        tab[4 * c] = S->sc_psd_row[c]; tab[4 * c + 1] = n; tab[4 * c + 2] = foff; tab[4 * c + 3] = loff;
+        foff += n * n; loff += n;
+    }
+    if (npsd > S->psd_cap_cones) { S->d_psd_tab = S->dalloc<int64_t>(4 * npsd); S->psd_cap_cones = npsd; }
+    if (foff > S->psd_cap_mat || loff > S->psd_cap_lam) {
+        S->d_psd_rinv = S->dalloc<double>(foff); S->d_psd_lam = S->dalloc<double>(loff); S->d_psd_stage = S->dalloc<double>(foff + loff);
+        S->psd_cap_mat = foff; S->psd_cap_lam = loff;
+    }
+    S->psd_lam_total = loff;
+    copy_sync(S->stream, S->d_psd_tab, tab.data(), tab.size() * sizeof(int64_t), hipMemcpyHostToDevice);
+    S->st_psd = true;
+    S->psd_fresh = false;
+    S->sc_scaled = false;      // the step reads the factors of a scaling that ran with the enable in place
+    S->st_have_step = false;
+    return HIPKKT_OK;
+    HK_LEAVE
+}
+
+static int32_t psd_set_factors_impl(hipkkt_handle h, const double *Rinv_all, const double *lambda_all, bool dev) {
+    HK_ENTER(h)
+    if (!S->st_psd || !Rinv_all || !lambda_all) {
+        S->err = "psd_set_factors: needs hipkkt_step_enable_psd first / null argument";
+        return HIPKKT_ERR_ARGUMENT;
+    }
+    const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    HK_CHECK(hipMemcpyAsync(S->d_psd_stage, Rinv_all, (size_t)S->sc_psd_total * sizeof(double), kind, S->stream));
+    HK_CHECK(hipMemcpyAsync(S->d_psd_stage + S->sc_psd_total, lambda_all, (size_t)S->psd_lam_total * sizeof(double), kind, S->stream));
+    if (!dev) HK_CHECK(hipStreamSynchronize(S->stream));      // (the caller may reuse its host arrays)
+    S->psd_fresh = true;
+    return HIPKKT_OK;
+    HK_LEAVE
+}
+int32_t hipkkt_psd_set_factors(hipkkt_handle h, const double *Rinv_all, const double *lambda_all) {
+    return psd_set_factors_impl(h, Rinv_all, lambda_all, false);
+}
+int32_t hipkkt_psd_set_factors_dev(hipkkt_handle h, const double *Rinv_all, const double *lambda_all) {
+    return psd_set_factors_impl(h, Rinv_all, lambda_all, true);
+}
+
 int32_t hipkkt_cone_barrier(hipkkt_handle h, const double *dz, const double *ds, const double *alphas, int64_t nalpha, double *out) {
     HK_ENTER(h)
     if (!step_ready(S, "cone_barrier")) return HIPKKT_ERR_ARGUMENT;
+    if (S->st_psd) { S->err = "cone_barrier: a set with PSD triangle cones is symmetric and needs no barrier"; return HIPKKT_ERR_ARGUMENT; }
     if (!alphas || !out || nalpha < 1 || nalpha > step3_max_candidates() || (S->img.m && (!dz || !ds))) {
         S->err = "cone_barrier: 1 <= nalpha <= 8 / null argument"; return HIPKKT_ERR_ARGUMENT;
     }
@@ -279,6 +356,7 @@ int32_t hipkkt_cone_barrier(hipkkt_handle h, const double *dz, const double *ds,
 int32_t hipkkt_step_barrier_dev(hipkkt_handle h, const double *xzs_dev, const double *alphas, int64_t nalpha, double *out) {
     HK_ENTER(h)
     if (!step_ready(S, "step_barrier_dev")) return HIPKKT_ERR_ARGUMENT;
+    if (S->st_psd) { S->err = "step_barrier_dev: a set with PSD triangle cones is symmetric and needs no barrier"; return HIPKKT_ERR_ARGUMENT; }
     if (!S->st_have_step || !xzs_dev || !alphas || !out || nalpha < 1 || nalpha > step3_max_candidates()) {
         S->err = "step_barrier_dev: no step resident / 1 <= nalpha <= 8 / null argument"; return HIPKKT_ERR_ARGUMENT;
     }

@@ -105,6 +105,22 @@ void launch_genpow_length(hipStream_t st, int ngp, const int64_t *desc, const do
                           double rhs_kappa, double alpha_max, double step, double alpha_min, int trips, double *part);
 void launch_genpow_barrier(hipStream_t st, int ngp, const int64_t *desc, const double *alpha, const double *z, const double *s,
                            const double *dz, const double *ds, const double *alphas, int nalpha, double *cpart);
+// step_psd.hip: the same operations on the rows of the PSD triangle cones after hipkkt_step_enable_psd, one workgroup per cone
+// (step length: per cone and per z / s).  tab = 4 int64 per cone [row0 | n | offset of the n x n factors | offset of lambda] with
+// n <= psd_step_max_dim(); R, Rinv = the cones' column-major factors concatenated, lam = their lambda concatenated.
+// launch_psd_step_length writes one (alpha_z, alpha_s) pair per cone to `part` and out2 = the minimum of those pairs and of sym2, the
+// pair launch_step_length left for the Zero / Nonnegative / SecondOrder rows.  launch_psd_step_check sets *fail when a lambda is not
+// finite or not positive.
+int psd_step_max_dim();
+void launch_psd_step_affine_ds(hipStream_t st, int npsd, const int64_t *tab, const double *lam, double *out);
+void launch_psd_step_mulhs(hipStream_t st, int npsd, const int64_t *tab, const double *R, const double *x, const double *addc, double *y);
+void launch_psd_step_shift(hipStream_t st, int npsd, const int64_t *tab, const double *R, const double *Rinv, const double *dz,
+                           const double *ds, double sigma_mu, double *out);
+void launch_psd_step_offset(hipStream_t st, int npsd, const int64_t *tab, const double *R, const double *lam, const double *ds,
+                            double *out);
+void launch_psd_step_length(hipStream_t st, int npsd, const int64_t *tab, const double *R, const double *Rinv, const double *lam,
+                            const double *dz, const double *ds, double alpha_max, const double *sym2, double *part, double *out2);
+void launch_psd_step_check(hipStream_t st, const double *lam, int64_t len, int *fail);
 void launch_block_products(hipStream_t st, const DevPlan &P, const double *x, const double *z, double *Px, double *ATz,
                            double *Ax, int n, int m);
 void launch_zero_words(hipStream_t st, void *p, int nwords);

@@ -44,7 +44,11 @@ SYMBOLS = [
     "hipkkt_step_get",
     # ... for the Exponential / Power cones as well (opt-in), and the barrier of the line search (added within ABI version 5)
     "hipkkt_step_enable_cone3", "hipkkt_cone_barrier", "hipkkt_step_barrier_dev", "hipkkt_step_enable_genpow",
+    # ... and for the PSD triangle cones from the caller's factors (opt-in, added within ABI version 5)
+    "hipkkt_step_enable_psd", "hipkkt_psd_set_factors", "hipkkt_psd_set_factors_dev",
 ]
+
+PSD_STEP_MAX_DIM = 64      # include/hipkkt.h HIPKKT_PSD_STEP_MAX_DIM
 
 
 # doubles the calls below move across PCIe, counted from their argument sizes (tools/step_path_compare.py reads and resets them)
@@ -153,6 +157,9 @@ def lib():
     L.hipkkt_step_get.argtypes = [vp, _f64p]
     L.hipkkt_step_enable_cone3.argtypes = [vp, i32, f64, f64]
     L.hipkkt_step_enable_genpow.argtypes = [vp, i32, f64, f64]
+    L.hipkkt_step_enable_psd.argtypes = [vp, i32]
+    L.hipkkt_psd_set_factors.argtypes = [vp, _f64p, _f64p]
+    L.hipkkt_psd_set_factors_dev.argtypes = [vp, vp, vp]
     L.hipkkt_cone_barrier.argtypes = [vp, _f64p, _f64p, _f64p, i64, _f64p]
     L.hipkkt_step_barrier_dev.argtypes = [vp, vp, _f64p, i64, _f64p]
     L.hipkkt_debug_dump.argtypes = [vp, i32, vp, i64, C.POINTER(i64)]
@@ -374,6 +381,7 @@ class Handle:
         nel = getattr(self, "_cone_numel", np.zeros(0, dtype=np.int64))[kinds == 3]
         nn = ((np.sqrt(8.0 * nel + 1.0) - 1.0) / 2.0 + 0.5).astype(np.int64)
         self._psd_r_len = int(np.sum(nn * nn))
+        self._psd_lam_len = int(np.sum(nn))
 
     def update_scaling(self, s, z, psd_R=None, want_outputs=True):
         """-> (ok, w, lam, soc_eta): Hs blocks / sparse second-order terms of K are rewritten on the device from (s, z)."""
@@ -407,6 +415,7 @@ class Handle:
         nel = getattr(self, "_cone_numel", np.zeros(0, dtype=np.int64))[kinds == 3]
         nn = ((np.sqrt(8.0 * nel + 1.0) - 1.0) / 2.0 + 0.5).astype(np.int64)
         self._psd_r_len = int(np.sum(nn * nn))
+        self._psd_lam_len = int(np.sum(nn))
 
     def set_cone_types_ex(self, kinds, alpha=()):
         """kinds 0..6 per cone, alpha = the exponents of the Power / GenPower cones concatenated in cone order"""
@@ -688,6 +697,25 @@ class Handle:
         self._chk_step(self.L.hipkkt_step_enable_genpow(self.h, int(bool(enable)), float(linesearch_backtrack_step),
                                                         float(min_terminate_step_length)), "step_enable_genpow")
 
+    def step_enable_psd(self, enable):
+        """the same for a symmetric registration with PSD triangle cones: ValueError unless it names kinds {0, 1, 2, 3} only with a 3
+        and every PSD side is at most PSD_STEP_MAX_DIM.  The step then works on the factors of psd_set_factors + update_scaling(psd_R)"""
+        self._chk_step(self.L.hipkkt_step_enable_psd(self.h, int(bool(enable))), "step_enable_psd")
+
+    def psd_set_factors(self, rinv, lam, dev=False):
+        """stages the PSD cones' Rinv (n x n column-major each, concatenated like psd_R) and lambda (n each) for the next update_scaling;
+        dev=True: rinv, lam are device pointers (not synchronised: they stay valid until the next synchronising call)"""
+        if dev:
+            self._chk_step(self.L.hipkkt_psd_set_factors_dev(self.h, rinv, lam), "psd_set_factors_dev")
+            return
+        rinv = np.ascontiguousarray(rinv, dtype=np.float64).ravel()
+        lam = np.ascontiguousarray(lam, dtype=np.float64).ravel()
+        nel = getattr(self, "_psd_lam_len", None)
+        if rinv.size != self._psd_r_len or (nel is not None and lam.size != nel):
+            raise ValueError(f"psd_set_factors: Rinv holds {self._psd_r_len} doubles and lambda {nel}, got {rinv.size} and {lam.size}")
+        self._chk_step(self.L.hipkkt_psd_set_factors(self.h, rinv, lam), "psd_set_factors")
+        _count(rinv.size + lam.size, 0)
+
     @staticmethod
     def _alphas(alphas):
         a = np.ascontiguousarray(alphas, dtype=np.float64).ravel()
@@ -748,6 +776,14 @@ class DeviceBuffer:
     def download(self):
         out = np.zeros(self.n)
         self._copy(out.ctypes.data, self.ptr, out.nbytes, 2)
+        _count(0, out.size)
+        return out
+
+    def download_range(self, start, count):
+        """`count` doubles from element `start`"""
+        assert 0 <= start and start + count <= self.n
+        out = np.zeros(count)
+        self._copy(out.ctypes.data, self.ptr + 8 * start, out.nbytes, 2)
         _count(0, out.size)
         return out
 

@@ -18,12 +18,14 @@ from .settings import Settings
 _DEBUG = os.environ.get("HIPKKT_DEBUG", "0") == "1"
 
 
-def cone_set_steps_on_device(cones, nonsymmetric=False, genpower=False) -> bool:
+def cone_set_steps_on_device(cones, nonsymmetric=False, genpower=False, psd=False) -> bool:
     """the step entry points (hipkkt_cone_* / hipkkt_step_*) serve cone sets of ZeroCone, NonnegativeCone and SecondOrderCone only: a PSD
     cone's step length needs eigenvalue decompositions, the non-symmetric cones need backtracking and barriers.
     nonsymmetric=True: ExponentialCone and PowerCone members qualify as well (hipkkt_step_enable_cone3); Generalized Power and PSD
     members still do not.
-    genpower=True (with nonsymmetric=True): Generalized Power members qualify too (hipkkt_step_enable_genpow); PSD members do not"""
+    genpower=True (with nonsymmetric=True): Generalized Power members qualify too (hipkkt_step_enable_genpow); PSD members do not.
+    psd=True: PSD triangle members qualify when every side is at most hipkkt.PSD_STEP_MAX_DIM and the set has no Exponential / Power /
+    Generalized Power member (hipkkt_step_enable_psd)"""
     if not hasattr(cones, "kkt_cone_kinds"):
         return False
     kinds = cones.kkt_cone_kinds_ex()[0] if hasattr(cones, "kkt_cone_kinds_ex") else cones.kkt_cone_kinds()
@@ -33,6 +35,11 @@ def cone_set_steps_on_device(cones, nonsymmetric=False, genpower=False) -> bool:
         ok = ok | (kinds == 4) | (kinds == 5)
         if genpower:
             ok = ok | (kinds == 6)
+    if psd and bool(np.any(kinds == 3)) and not bool(np.any(kinds >= 4)):
+        numel = np.asarray(cones.kkt_descriptors()[0])[kinds == 3]
+        sides = ((np.sqrt(8.0 * numel + 1.0) - 1.0) / 2.0 + 0.5).astype(np.int64)
+        if bool(np.all(sides <= hipkkt.PSD_STEP_MAX_DIM)):
+            ok = ok | (kinds == 3)
     return kinds.size > 0 and bool(np.all(ok))
 
 
@@ -90,6 +97,18 @@ class HipKKTSolver:
                 and cone_set_steps_on_device(cones, nonsymmetric=True, genpower=True):
             self.h.step_enable_genpow(True, settings.linesearch_backtrack_step, settings.min_terminate_step_length)
             self._steps_on_device = self.steps_nonsymmetric = True
+        # ... and, opted in by Settings.device_step_psd, symmetric sets with PSD triangle members: the Cholesky / SVD of their scaling stay
+        # with the caller, whose (R, Rinv, lambda) go to the device with every scaling (hipkkt_step_enable_psd)
+        self.steps_psd = False
+        if not self._steps_on_device and getattr(settings, "device_step_psd", False) and self._has_cone_kinds \
+                and not self.scales_nonsymmetric and cone_set_steps_on_device(cones, psd=True):
+            self.h.step_enable_psd(True)
+            self._steps_on_device = self.steps_psd = True
+            rows = [r for c, r in zip(cones.cones, cones.rng_cones) if hasattr(c, "RRt")]
+            self._psd_rows = rows
+            self._psd_span = (rows[0].start, rows[-1].stop)
+            self._psd_nr = int(np.sum(self._psd_dim * self._psd_dim))
+            self._psd_dev = None      # [R | Rinv | lambda] in device memory (kktsolver_update_scaling_dev)
         self.scaling_nonsym = None
         self.scaling_w = self.scaling_lambda = self.scaling_soc_eta = None
         self.diagonal_regularizer = 0.0
@@ -165,6 +184,8 @@ class HipKKTSolver:
                     soc += 1
             assert off == len(self.scaling_nonsym)
             return self._refactor()
+        if self.steps_psd:
+            self.h.psd_set_factors(*self._psd_factors())
         ok, self.scaling_w, self.scaling_lambda, self.scaling_soc_eta = self.h.update_scaling(s, z, R)
         if not ok:
             return False
@@ -267,8 +288,30 @@ class HipKKTSolver:
         |einv rz_inf|, |dinv Px|"""
         return self.h.step_info_norms_dev(xzs.ptr, res.ptr)
 
+    def _psd_factors(self):
+        """(Rinv, lambda) of the PSD cones' current scaling, concatenated like psd_R"""
+        return (np.concatenate([c.Rinv.ravel(order="F") for c in self._psd_cones]), np.concatenate([c.lam for c in self._psd_cones]))
+
+    def psd_rows_download(self, xzs):
+        """-> (s, z) of length m with the rows first PSD row .. last PSD row filled from the resident iterate (steps_psd: what the
+        caller's update_scaling! of the PSD cones needs), the rest zero"""
+        lo, hi = self._psd_span
+        s, z = np.zeros(self.m), np.zeros(self.m)
+        z[lo:hi] = xzs.download_range(self.n + lo, hi - lo)
+        s[lo:hi] = xzs.download_range(self.n + self.m + lo, hi - lo)
+        return s, z
+
     def kktsolver_update_scaling_dev(self, xzs) -> bool:
-        """update_scaling! + get_Hs! from the resident (s, z); False = a cone's s or z is not interior"""
+        """update_scaling! + get_Hs! from the resident (s, z); False = a cone's s or z is not interior.
+        steps_psd: the PSD cones' (R, Rinv, lambda) of the caller's update_scaling! go along in one upload"""
+        if self.steps_psd:
+            if self._psd_dev is None:
+                self._psd_dev = hipkkt.DeviceBuffer(2 * self._psd_nr + int(np.sum(self._psd_dim)))
+            rinv, lam = self._psd_factors()
+            self._psd_dev.upload(np.concatenate([np.concatenate([c.R.ravel(order="F") for c in self._psd_cones]), rinv, lam]))
+            p = self._psd_dev.ptr
+            self.h.psd_set_factors(p + 8 * self._psd_nr, p + 16 * self._psd_nr, dev=True)
+            return self.h.update_scaling_dev(xzs.ptr + 8 * (self.n + self.m), xzs.ptr + 8 * self.n, R_ptr=p)
         return self.h.update_scaling_dev(xzs.ptr + 8 * (self.n + self.m), xzs.ptr + 8 * self.n)
 
     def kktsolver_update_scaling_dev_ex(self, xzs, mu, strategy) -> bool:

@@ -67,4 +67,9 @@ class Settings:
     # and the barrier with its Newton iteration for the primal gradient, one wavefront per cone); PSD cone sets keep the host path.
     # Needs device_step_nonsymmetric: the caller raises ValueError otherwise.
     device_step_genpower: bool = False
+    # device_step for symmetric cone sets that also hold PSD triangle cones of side <= 64 (hipkkt_step_enable_psd: the triple products
+    # and the step length's smallest eigenvalue on the device, one workgroup per cone).  The Cholesky / SVD of the cones' scaling stay
+    # on the host: every iteration downloads the PSD rows of (s, z) and uploads (R, Rinv, lambda).  Needs device_step: the caller
+    # raises ValueError otherwise.
+    device_step_psd: bool = False
     extra: dict = field(default_factory=dict)

@@ -73,7 +73,8 @@ int32_t hipkkt_is_available(void);
  * 4: hipkkt_get_profile / hipkkt_get_counters take the capacity of the caller's buffer (they wrote a fixed, growing number of values).
  * 5: hipkkt_set_cone_types_ex / hipkkt_get_nonsym_len / hipkkt_update_scaling_ex[_dev] (the bindings bind them when they load).
  *    Added within 5, no signature changed: the step entry points hipkkt_cone_* / hipkkt_set_equilibration / hipkkt_step_*;
- *    hipkkt_step_enable_cone3 / hipkkt_cone_barrier / hipkkt_step_barrier_dev; hipkkt_step_enable_genpow. */
+ *    hipkkt_step_enable_cone3 / hipkkt_cone_barrier / hipkkt_step_barrier_dev; hipkkt_step_enable_genpow;
+ *    HIPKKT_PSD_STEP_MAX_DIM / hipkkt_step_enable_psd / hipkkt_psd_set_factors / hipkkt_psd_set_factors_dev. */
 #define HIPKKT_ABI_VERSION 5
 int32_t hipkkt_abi_version(void);
 /* releases the process-wide cache of device memory blocks the library keeps between handles (not in the reference: an embedding
@@ -324,8 +325,8 @@ int32_t hipkkt_residuals_dev(hipkkt_handle h, const double *xzs_dev, double tau,
  * hipkkt_set_cone_types[_ex]).  Every operation works on the (s, z, w, lambda, eta) that the last successful
  * hipkkt_update_scaling[_ex][_dev] left resident; expressions keep the reference's association (Zero / Nonnegative rows are the
  * host's bit for bit), a `dot` of the reference is a tree sum.  No input is modified.
- * All of them return HIPKKT_ERR_ARGUMENT on a handle whose registration names a PSD cone or a kind 4..6 (those keep their step algebra
- * with the caller: eigenvalue decompositions, backtracking line search, barriers) and before the first successful scaling; the fused
+ * All of them return HIPKKT_ERR_ARGUMENT on a handle whose registration names a PSD cone or a kind 4..6 (without the opt-ins below those
+ * keep their step algebra with the caller: eigenvalue decompositions, backtracking line search, barriers) and before the first successful scaling; the fused
  * calls also before hipkkt_set_qb.  On any non-zero return the outputs are unspecified, as for hipkkt_kkt_solve_reduced.
  *
  * Opt-in for ExponentialCone / PowerCone (kinds 4, 5): after hipkkt_step_enable_cone3 on a registration of kinds {0, 1, 2, 4, 5} every
@@ -358,6 +359,24 @@ int32_t hipkkt_residuals_dev(hipkkt_handle h, const double *xzs_dev, double tau,
  * Sums and products over a cone are tree reductions; otherwise expressions keep the reference's association.  A registration without
  * kind 6 computes exactly what it computed before this call existed.  A PSD cone (kind 3) is refused here too.
  *
+ * Opt-in for PSDTriangleCone (kind 3): after hipkkt_step_enable_psd on a registration of kinds {0, 1, 2, 3} with at least one 3 and every
+ * PSD side <= HIPKKT_PSD_STEP_MAX_DIM, the five hipkkt_cone_* operations, the fused calls and hipkkt_step_get serve all rows of that
+ * handle (the barrier calls keep refusing it: the set is symmetric).  The Cholesky / SVD of coneops_psdtrianglecone.jl:78-143 stay
+ * with the caller, who hands over (R, Rinv, lambda) per scaling: hipkkt_psd_set_factors[_dev], then a hipkkt_update_scaling[_ex][_dev]
+ * with psd_R.  With X = svec_to_mat of a cone's rows and results through mat_to_svec (:469-497):
+ *   affine_ds = lambda_k^2 at the diagonal positions, 0 elsewhere (:190-205);
+ *   mul_W :N  Y = R' X R, :T  Y = R X R', mul_Winv the same with Rinv (:409-437); mul_hs = W'(W x) (:164-187);
+ *   combined_ds_shift: A = W step_z, B = W^-T step_s, svec((B A + A B) / 2) with sigma mu subtracted at the diagonal positions
+ *     (coneops_symmetric_common.jl:1-35);
+ *   ds_from_dz_offset: X~_ij = 2 DS_ij / (lambda_i + lambda_j), out = R X~ R' (coneops_symmetric_common.jl:39-52);
+ *   step length: D = R' dZ R resp. Rinv dS Rinv', M = Lambda^-1/2 D Lambda^-1/2, gamma = lambda_min(M),
+ *     alpha = gamma < 0 ? min(1 / -gamma, alpha_max) : alpha_max (:230-254, :439-466); alpha_z and alpha_s each take the minimum with
+ *     the pair of the kind 0..2 rows.  gamma comes from a cyclic Jacobi iteration of at most 30 sweeps that stops at
+ *     off(M) <= eps |M|_F; an M with a non-finite entry gives a NaN gamma and therefore alpha_max, as the reference's comparison does.
+ * One workgroup per cone, matrices in LDS, every k-sum of a product in ascending order (deterministic; the association differs from
+ * the host's BLAS, so results agree to rounding, not bit for bit).  Rows of kinds 0..2 go through the same kernels as without the
+ * enable, bit for bit.  Kinds 4..6 next to a PSD cone stay refused.
+ *
  * One operation each, host vectors of length m in cone order (the unit-tested surface):
  *   hipkkt_cone_affine_ds            ds = lambda o lambda                  coneops_nncone.jl affine_ds!, coneops_socone.jl:219-228
  *   hipkkt_cone_combined_ds_shift    shift = W^-1 step_s o W step_z - sigma mu e   coneops_symmetric_common.jl:1-36, coneops_socone.jl:300-347
@@ -378,6 +397,21 @@ int32_t hipkkt_step_enable_cone3(hipkkt_handle h, int32_t enable, double linesea
  * parameter checks, the trip bound and the invalidation of the resident scaling are those of hipkkt_step_enable_cone3.  enable == 0
  * switches the GenPower and the Exponential / Power step off.  Every hipkkt_set_cone_types[_ex] clears it. */
 int32_t hipkkt_step_enable_genpow(hipkkt_handle h, int32_t enable, double linesearch_backtrack_step, double min_terminate_step_length);
+/* The largest PSD side the device step serves: three n x n double matrices (3 x 32 KiB) fit one workgroup's LDS (160 KiB per CU) with
+ * room to spare; larger cones keep the host loop. */
+#define HIPKKT_PSD_STEP_MAX_DIM 64
+/* enable != 0: HIPKKT_ERR_ARGUMENT unless the last hipkkt_set_cone_types[_ex] names kinds {0, 1, 2, 3} only with at least one 3 and every
+ * PSD side <= HIPKKT_PSD_STEP_MAX_DIM.  Enabling invalidates the resident scaling, as hipkkt_step_enable_cone3 does.  enable == 0
+ * switches it off.  Every hipkkt_set_cone_types[_ex] clears it. */
+int32_t hipkkt_step_enable_psd(hipkkt_handle h, int32_t enable);
+/* The factors of the PSD cones' scaling for the step (HIPKKT_ERR_ARGUMENT before hipkkt_step_enable_psd): Rinv_all = the cones' Rinv, each
+ * n x n column-major, concatenated like psd_R; lambda_all = the cones' lambda, n each, concatenated.  They are staged and consumed by
+ * the next hipkkt_update_scaling[_ex][_dev]; on an enabled handle that call needs a non-NULL psd_R and factors staged since the last
+ * scaling, otherwise it returns HIPKKT_ERR_ARGUMENT and the step calls stay refused until a scaling succeeds.  A lambda entry that is
+ * not finite or is <= 0 sets *scaling_ok = 0.  The _dev form does not synchronise with the host; its pointers must stay valid until the
+ * next synchronising call on this handle has returned (the rule of hipkkt_set_hs_dev). */
+int32_t hipkkt_psd_set_factors(hipkkt_handle h, const double *Rinv_all, const double *lambda_all);
+int32_t hipkkt_psd_set_factors_dev(hipkkt_handle h, const double *Rinv_all, const double *lambda_all);
 /* compute_barrier of the cone set (Zero 0, Nonnegative -sum log((s + a ds)(z + a dz)), coneops_socone.jl:288-305,
  * coneops_expcone.jl:189-248, coneops_powcone.jl:228-251) and dot_shifted (mathutils.jl:23-43) at nalpha <= 8 candidate step lengths:
  * out[2 j] = the barrier, out[2 j + 1] = <z + a_j dz, s + a_j ds>, both summed over fixed slices in a fixed order.  A point outside a

@@ -132,6 +132,21 @@ function hip_step_enable_genpow!(handle::Ptr{Cvoid}, enable::Bool, backtrack_ste
                backtrack_step, min_terminate_step_length)
     return hip_step_check(handle, rc, "hipkkt_step_enable_genpow")
 end
+# the same for a symmetric registration with PSD triangle cones (kind 3) of side <= 64: the step works on the caller's factors
+function hip_step_enable_psd!(handle::Ptr{Cvoid}, enable::Bool)
+    rc = ccall((:hipkkt_step_enable_psd, libhipkkt), Int32, (Ptr{Cvoid}, Int32), handle, enable ? 1 : 0)
+    return hip_step_check(handle, rc, "hipkkt_step_enable_psd")
+end
+# Rinv_all: the cones' Rinv (n x n column-major each, concatenated like psd_R), λ_all: their λ; consumed by the next hip update_scaling
+function hip_psd_set_factors!(handle::Ptr{Cvoid}, Rinv_all::Vector{Float64}, λ_all::Vector{Float64})
+    rc = ccall((:hipkkt_psd_set_factors, libhipkkt), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), handle, Rinv_all, λ_all)
+    return hip_step_check(handle, rc, "hipkkt_psd_set_factors")
+end
+# device pointers; not synchronised with the host: both stay valid until the next synchronising call on the handle
+function hip_psd_set_factors_dev!(handle::Ptr{Cvoid}, Rinv_dev::Ptr{Float64}, λ_dev::Ptr{Float64})
+    rc = ccall((:hipkkt_psd_set_factors_dev, libhipkkt), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), handle, Rinv_dev, λ_dev)
+    return hip_step_check(handle, rc, "hipkkt_psd_set_factors_dev")
+end
 # -> out[2j-1] = the cones' barrier, out[2j] = <z + αⱼΔz, s + αⱼΔs> for at most 8 candidates αⱼ
 function hip_cone_barrier(handle::Ptr{Cvoid}, Δz::Vector{Float64}, Δs::Vector{Float64}, αs::Vector{Float64})
     out = zeros(Float64, 2 * length(αs))

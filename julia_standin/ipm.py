@@ -398,6 +398,8 @@ class Solver:
             raise ValueError("Settings.device_step_nonsymmetric needs device_step")
         if getattr(st, "device_step_genpower", False) and not getattr(st, "device_step_nonsymmetric", False):
             raise ValueError("Settings.device_step_genpower needs device_step_nonsymmetric")
+        if getattr(st, "device_step_psd", False) and not getattr(st, "device_step", False):
+            raise ValueError("Settings.device_step_psd needs device_step")
         self._device_step = bool(getattr(st, "device_step", False)) and hasattr(ks, "kktsolver_step_affine") and \
             bool(getattr(ks, "steps_on_device", False))
         if self._device_step and not self.cones.is_symmetric():
@@ -407,6 +409,9 @@ class Solver:
             self._device_step = bool(getattr(st, "device_step_nonsymmetric", False)) and \
                 hasattr(ks, "kktsolver_update_scaling_dev_ex") and hasattr(ks, "kktsolver_step_barrier") and \
                 all(getattr(c, "is_symmetric", True) or getattr(c, "kind_code_ex", -1) in kinds_ok for c in self.cones)
+        # a symmetric set with PSD members (Settings.device_step_psd, a plugin with steps_psd): the loop of _solve_device_step, with the
+        # Cholesky / SVD of the PSD cones' scaling done here before every scaling call
+        self._device_step_psd = self._device_step and bool(getattr(ks, "steps_psd", False))
         self.barrier_searches = self.barrier_backtracks = 0      # _backtrack_step_to_barrier calls / candidates it rejected (last solve)
         self._needs_qb = self._needs_qb or (self._device_step and hasattr(ks, "set_problem_vectors"))
         if self._needs_qb:               # q, b resident in the plugin (N4 residuals, N2 reduced-system algebra)
@@ -673,7 +678,7 @@ class Solver:
         """The loop of _solve for Settings.device_step: [x | z | s] and the residual buffer live in device memory for the whole solve and
         the plugin does residuals, norms, scaling, both steps and the update there; tau, kappa, the termination test, sigma and the
         strategy checkpoints stay here, fed by scalars.  Zero / Nonnegative / SecondOrder cone sets (symmetric: PrimalDual scaling, no
-        backtracking).  The default start runs on the host as in _solve and is uploaded once; the iterate comes back once, at the end."""
+        backtracking); with Settings.device_step_psd also PSD triangle members, whose Cholesky / SVD run here per scaling.  The default start runs on the host as in _solve and is uploaded once; the iterate comes back once, at the end."""
         st, info, data, cones = self.settings, self.info, self.data, self.cones
         v, r = self.variables, self.residuals
         ks = self.kktsystem.kktsolver
@@ -713,7 +718,16 @@ class Solver:
                     v.tau, v.kappa = prev_tau, prev_kappa
                 break
             t0 = time.perf_counter()
-            ok_scaling = ks.kktsolver_update_scaling_dev(xzs)
+            ok_scaling = True
+            if self._device_step_psd:
+                # the PSD rows of the resident (s, z) come to the host, the cones' own update_scaling! gives R, Rinv, lambda (skron!
+                # stays deferred: the plugin forms the Hs block), and the plugin takes the factors along with its scaling call
+                s_h, z_h = ks.psd_rows_download(xzs)
+                for c, rr in zip(cones.cones, cones.rng_cones):
+                    if hasattr(c, "RRt") and not c.update_scaling(s_h[rr], z_h[rr], mu):
+                        ok_scaling = False
+                        break
+            ok_scaling = ok_scaling and ks.kktsolver_update_scaling_dev(xzs)
             tm["scale cones"] += time.perf_counter() - t0
             if not ok_scaling:
                 info.status = NUMERICAL_ERROR

@@ -4,7 +4,7 @@ algebra between the device calls runs on the host, the iterate crosses PCIe seve
 added (the iterate stays in device memory, scalars cross).  Per path: one warm-up solve, then `--repeats` timed solves; the medians of
 wall time per iteration and of the stand-in's timers, the bytes the Python binding moved per iteration in each direction
 (clarabel.jl_amd/hipkkt.py TRAFFIC) and hipkkt_box_probe go into ONE JSON line on stdout.
-usage: step_path_compare.py [--cfgs 3,2a,exp_pow,genpow] [--repeats 5] [--one-solve CFG]   (--one-solve: a single device_step solve, for a kernel trace)"""
+usage: step_path_compare.py [--cfgs 3,2a,exp_pow,genpow,psd] [--repeats 5] [--one-solve CFG]   (--one-solve: a single device_step solve, for a kernel trace)"""
 import argparse
 import json
 import os
@@ -23,10 +23,14 @@ CONFIGS = {"3": ("portfolio_socp", problems.portfolio_socp), "2a": ("random_spar
                        lambda: problems.nonsymmetric_mix(n=80, nexp=30, npow=20, ngenpow=0, nn=20, nzero=3, socdim=5, seed=5)),
            # ... and Generalized Power cones: device_step_genpower on top (the Dual strategy and its barrier search in every iteration)
            "genpow": ("nonsymmetric_mix_genpow",
-                      lambda: problems.nonsymmetric_mix(n=80, nexp=10, npow=10, ngenpow=20, nn=20, nzero=3, socdim=5, seed=5))}
+                      lambda: problems.nonsymmetric_mix(n=80, nexp=10, npow=10, ngenpow=20, nn=20, nzero=3, socdim=5, seed=5)),
+           # PSD triangle cones (benchmark configuration 5 at its size, 20 x PSD(50)): device_step_psd on top; the Cholesky / SVD of the
+           # scaling stay on the host
+           "psd": ("sdp_blocks", problems.sdp_blocks)}
 PARENT = dict(device_scaling=True, device_reduced=True, device_residuals=True)
 STEP_EXTRA = {"exp_pow": dict(device_step_nonsymmetric=True),
-              "genpow": dict(device_step_nonsymmetric=True, device_step_genpower=True)}      # what device_step needs on top, per configuration
+              "genpow": dict(device_step_nonsymmetric=True, device_step_genpower=True),
+              "psd": dict(device_step_psd=True)}      # what device_step needs on top, per configuration
 
 
 def one_solve(prob, **flags):
