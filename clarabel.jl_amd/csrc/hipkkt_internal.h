@@ -1,5 +1,6 @@
 // Internal declarations shared by the translation units of libclarabel_hipkkt.so's host side:
-//   hipkkt_abi.cpp     C entry points: creation / getters / value updates / residuals / scaling / diagnostics
+//   hipkkt_abi.cpp     C entry points: creation / getters / value updates / residuals / diagnostics
+//   hipkkt_cones.cpp   cone registration and scaling (hipkkt_set_cone_types[_ex], hipkkt_update_scaling[_ex][_dev])
 //   hipkkt_setup.cpp   runtime objects, device residency of a plan, handle creation (finish_create)
 //   hipkkt_factor.cpp  the factorisation's launch sequence, its graph, hipkkt_refactor and the robust-order twin
 //   hipkkt_solve.cpp   LDL solves, device-side iterative refinement, the solve entry points
@@ -27,7 +28,9 @@
 #include <vector>
 
 #include "assemble.h"
+#include "cone_layout.h"
 #include "device_plan.h"
+#include "hipkkt_cones.h"
 #include "kernels.h"
 #include "runtime_pool.h"
 #include "symbolic.h"
@@ -230,59 +233,10 @@ struct hipkkt_solver {
     int64_t *d_soc_uidx = nullptr, *d_soc_vidx = nullptr, *d_soc_didx = nullptr;
     int *d_soc_cone = nullptr;
     double *d_soc_u = nullptr, *d_soc_v = nullptr, *d_soc_eta2 = nullptr;
-    // N1: update_scaling! / get_Hs! on the device (hipkkt_set_cone_types + hipkkt_update_scaling, scaling.hip)
+    // N1: update_scaling! / get_Hs! on the device (hipkkt_set_cone_types + hipkkt_update_scaling, hipkkt_cones.cpp, scaling.hip)
     std::vector<int64_t> cone_numel;                       // as given to hipkkt_create_from_parts
     std::vector<int32_t> cone_hs_dense, cone_sparse_kind;
-    bool sc_ready = false;
-    int sc_nsoc = 0;                                       // ALL second-order cones (sparse and dense), cone order
-    std::vector<int64_t> sc_psd_hs, sc_psd_n;              // per PSD cone: first Hs entry, matrix dimension
-    int64_t sc_psd_total = 0;                              // sum of n * n
-    int64_t sc_cap_socdesc = 0, sc_cap_psd = 0;            // capacities of the d_sc_* buffers (allocated once, re-used by later calls)
-    signed char *d_sc_kind = nullptr;
-    int64_t *d_sc_rowhs = nullptr, *d_sc_socdesc = nullptr;
-    double *d_sc_sz = nullptr, *d_sc_wl = nullptr, *d_sc_eta = nullptr, *d_sc_R = nullptr, *d_sc_W = nullptr;
-    int *d_sc_fail = nullptr;
-    // the step entry points (hipkkt_step.cpp, step.hip) work on the resident (s, z) | (w, lambda) | eta of the last scaling
-    bool sc_step_kinds = false;                            // the registration names Zero / Nonnegative / SecondOrder cones only
-    bool sc_scaled = false;                                // the last hipkkt_update_scaling[_dev] since that registration succeeded
-    double *d_st_step = nullptr;                           // [dx | dz | ds] of the last fused step call
-    double *d_st_in = nullptr, *d_st_work = nullptr;       // [rhs.x | workz | variables.x]; four work vectors of length m
-    double *d_st_part = nullptr, *d_st_out = nullptr;      // partial results of the step length / the norms; 2 + 8 results
-    double *d_st_eq = nullptr;                             // [d | e | dinv | einv] (hipkkt_set_equilibration)
-    bool st_have_step = false;
-    // hipkkt_step_enable_cone3: the step entry points also serve the Exponential / Power cones of the registration (step_cone3.hip)
-    bool sc_cone3_kinds = false;                           // the registration names kinds {0, 1, 2, 4, 5} only, at least one 4 / 5
-    bool st_cone3 = false;                                 // enabled since that registration
-    double st_c3_step = 0.0, st_c3_amin = 0.0;             // linesearch_backtrack_step, min_terminate_step_length
-    int st_c3_trips = 0;                                   // bound of the backtracking loop: ceil(log amin / log step) + 2
-    // hipkkt_step_enable_genpow: the same for a registration with Generalized Power cones (step_genpow.hip); it sets st_cone3 as well, so
-    // that the three-row members of the set step with the same (step, alpha_min)
-    bool sc_genpow_kinds = false;                          // the registration names kinds {0, 1, 2, 4, 5, 6} only, at least one 6
-    bool st_genpow = false;                                // enabled since that registration
-    double ns_mu = 0.0;                                    // mu of the last hipkkt_update_scaling_ex[_dev] (mul_Hs of the GenPower cones)
-    // hipkkt_step_enable_psd: the step entry points also serve the PSD triangle cones of the registration (step_psd.hip), from the
-    // caller's factors: hipkkt_psd_set_factors[_dev] stages [Rinv | lambda], the next hipkkt_update_scaling[_dev] makes them resident
-    // next to its psd_R (d_sc_R)
-    bool sc_psd_kinds = false;                             // the registration names kinds {0, 1, 2, 3} only, at least one 3
-    std::vector<int64_t> sc_psd_row;                       // per PSD cone: first row
-    bool st_psd = false;                                   // enabled since that registration
-    bool psd_fresh = false;                                // factors staged since the last scaling
-    int64_t psd_lam_total = 0;                             // sum of n over the PSD cones
-    int64_t psd_cap_cones = 0, psd_cap_mat = 0, psd_cap_lam = 0;   // capacities, as sc_cap_*
-    int64_t *d_psd_tab = nullptr;                          // 4 per cone: [row0 | n | offset of the factors | offset of lambda]
-    double *d_psd_rinv = nullptr, *d_psd_lam = nullptr;    // resident factors of the last scaling
-    double *d_psd_stage = nullptr;                         // staged [Rinv (sc_psd_total) | lambda (psd_lam_total)]
-    double *d_st_bar = nullptr;                            // work buffer of the barrier (step3_barrier_doubles)
-    // N1, the non-symmetric cones (hipkkt_set_cone_types_ex + hipkkt_update_scaling_ex): tables built once per registration
-    bool ns_active = false;                                // the last registration named an Exponential / Power / GenPower cone
-    int ns_nexp = 0, ns_npow = 0, ns_ngenpow = 0;
-    int64_t ns_out_len = 0;                                // doubles of the output vector (hipkkt_get_nonsym_len)
-    int64_t ns_cap3 = 0, ns_cap_gp = 0, ns_cap_gpalpha = 0, ns_cap_gpidx = 0, ns_cap_out = 0;   // capacities, as sc_cap_*
-    int64_t *d_ns_row0 = nullptr, *d_ns_hs0 = nullptr, *d_ns_out0 = nullptr;                   // three-row cones, [Exponential | Power]
-    double *d_ns_alpha = nullptr;
-    int *d_ns_trips = nullptr;                             // Newton steps of the last update per table entry (debug_dump 23)
-    int64_t *d_ns_gpdesc = nullptr, *d_ns_gpidx = nullptr; // GenPower cones: 8 values per cone; [map.q | map.r | map.p | map.D] per cone
-    double *d_ns_gpalpha = nullptr, *d_ns_out = nullptr;
+    ConeState cones;                                       // registration, device tables, resident step (hipkkt_cones.h)
 
     // vectors
     double *d_b = nullptr, *d_x = nullptr, *d_dx = nullptr, *d_e = nullptr;

@@ -125,8 +125,7 @@ void setup_device(hipkkt_solver *S) {
     S->stage_cap = 0; S->d_stage = nullptr; S->d_stage_idx = nullptr;
     S->d_qb = S->d_res_in = S->d_res_out = S->d_res_part = nullptr;
     S->d_red = S->d_red_part = nullptr;
-    S->d_sc_kind = nullptr; S->sc_cap_socdesc = S->sc_cap_psd = 0; S->sc_ready = false;   // (slab memory of an earlier set-up is gone)
-    S->ns_active = false; S->ns_cap3 = S->ns_cap_gp = S->ns_cap_gpalpha = S->ns_cap_gpidx = S->ns_cap_out = 0;
+    S->cones = ConeState();   // (slab memory of an earlier set-up is gone: the device tables, the resident step, so the registration too)
     S->red_have_const = false;
 
     order_far_stages(S);

@@ -13,60 +13,72 @@ namespace hipkkt_host {
 
 // the cone set and its scaling allow the step entry points
 static bool step_ready(hipkkt_solver *S, const char *who) {
-    if (!S->l1 || !S->sc_ready || !(S->sc_step_kinds || S->st_cone3 || S->st_psd)) {
+    const ConeState &C = S->cones;
+    if (!S->l1 || !C.reg.ready || C.step.mode == StepMode::Off) {
         S->err = std::string(who) + ": needs an L1 handle whose registered cones are Zero / Nonnegative / SecondOrder only, or one with "
                                     "Exponential / Power cones next to them after hipkkt_step_enable_cone3, or with Generalized Power cones "
                                     "after hipkkt_step_enable_genpow, or with PSD triangle cones after hipkkt_step_enable_psd";
         return false;
     }
-    if (!S->sc_scaled) { S->err = std::string(who) + ": no successful hipkkt_update_scaling since the cones were registered"; return false; }
+    if (!C.step.scaled) { S->err = std::string(who) + ": no successful hipkkt_update_scaling since the cones were registered"; return false; }
     return true;
 }
 
 static void ensure_step_buffers(hipkkt_solver *S) {
-    if (S->d_st_step) return;
+    ConeState &C = S->cones;
+    if (C.step.step) return;
     const int64_t n = S->img.n, m = S->img.m;
     const int64_t pairs = step_len_pairs(m, (int)S->cone_numel.size());      // (a later registration has at most this many cones)
-    S->d_st_step = S->dalloc<double>(n + 2 * m);
-    S->d_st_in = S->dalloc<double>(2 * n + m);
-    S->d_st_work = S->dalloc<double>(4 * m);
-    S->d_st_part = S->dalloc<double>((size_t)std::max<int64_t>(2 * pairs, step_norm_part_doubles()));
-    S->d_st_out = S->dalloc<double>(32);      // 0..3 step lengths, 4..11 norms, 12..27 barrier results, 28..29 the symmetric pair next to PSD cones
-    S->d_st_bar = S->dalloc<double>((size_t)step3_barrier_doubles((int64_t)S->cone_numel.size()));
+    C.step.step = S->dalloc<double>(n + 2 * m);
+    C.step.in = S->dalloc<double>(2 * n + m);
+    C.step.work = S->dalloc<double>(4 * m);
+    C.step.part = S->dalloc<double>((size_t)std::max<int64_t>(2 * pairs, step_norm_part_doubles()));
+    C.step.out = S->dalloc<double>(kStOutDoubles);      // step lengths, norms, barrier results, the parked symmetric pair (cone_layout.h)
+    C.step.bar = S->dalloc<double>((size_t)step3_barrier_doubles((int64_t)S->cone_numel.size()));
 }
 
 struct ConeTables {
-    const signed char *kind; int nsoc; const int64_t *desc;
-    const double *s, *z, *w, *lam, *eta;
-    int64_t m;
-    // the Exponential / Power cones of an enabled handle (all zero otherwise): tables [Exponential | Power], the scaling's output vector
-    int nexp, npow, n3;
-    const int64_t *row0, *out0;
-    const double *alpha, *nsout;
-    // the Generalized Power cones after hipkkt_step_enable_genpow (zero otherwise): descriptors, exponents, the mu of the last scaling
-    int ngp;
-    const int64_t *gpdesc;
-    const double *gpalpha;
-    double mu;
-    // the PSD triangle cones after hipkkt_step_enable_psd (zero otherwise): the table [row0 | n | factor offset | lambda offset], factors
-    int npsd;
-    const int64_t *psdtab;
-    const double *psdR, *psdRinv, *psdlam;
+    StepMode mode = StepMode::Off;
+    const signed char *kind = nullptr; int nsoc = 0; const int64_t *desc = nullptr;
+    const double *s = nullptr, *z = nullptr, *w = nullptr, *lam = nullptr, *eta = nullptr;
+    int64_t m = 0;
+    // Cone3 / GenPow: the Exponential / Power cones, tables [Exponential | Power], the scaling's output vector
+    int nexp = 0, npow = 0, n3 = 0;
+    const int64_t *row0 = nullptr, *out0 = nullptr;
+    const double *alpha = nullptr, *nsout = nullptr;
+    // GenPow: the Generalized Power cones' descriptors, exponents, the mu of the last scaling
+    int ngp = 0;
+    const int64_t *gpdesc = nullptr;
+    const double *gpalpha = nullptr;
+    double mu = 0.0;
+    // Psd: the PSD triangle cones' table and factors
+    int npsd = 0;
+    const int64_t *psdtab = nullptr;
+    const double *psdR = nullptr, *psdRinv = nullptr, *psdlam = nullptr;
+    // the backtracking line search of the non-symmetric cones decides the step length
+    bool line_search() const { return mode == StepMode::Cone3 || mode == StepMode::GenPow; }
 };
 static ConeTables tables(hipkkt_solver *S) {
-    const int64_t m = S->img.m;
-    ConeTables T{S->d_sc_kind, S->sc_nsoc, S->d_sc_socdesc, S->d_sc_sz, S->d_sc_sz + m, S->d_sc_wl, S->d_sc_wl + m, S->d_sc_eta, m,
-                 0, 0, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0.0,
-                 0, nullptr, nullptr, nullptr, nullptr};
-    if (S->st_psd) {
-        T.npsd = (int)S->sc_psd_n.size(); T.psdtab = S->d_psd_tab; T.psdR = S->d_sc_R; T.psdRinv = S->d_psd_rinv; T.psdlam = S->d_psd_lam;
-    }
-    if (S->st_cone3 && S->st_genpow) {
-        T.ngp = S->ns_ngenpow; T.gpdesc = S->d_ns_gpdesc; T.gpalpha = S->d_ns_gpalpha; T.mu = S->ns_mu; T.nsout = S->d_ns_out;
-    }
-    if (S->st_cone3) {
-        T.nexp = S->ns_nexp; T.npow = S->ns_npow; T.n3 = T.nexp + T.npow;
-        T.row0 = S->d_ns_row0; T.out0 = S->d_ns_out0; T.alpha = S->d_ns_alpha; T.nsout = S->d_ns_out;
+    const ConeState &C = S->cones;
+    ConeTables T;
+    T.mode = C.step.mode;
+    T.m = S->img.m;
+    T.kind = C.tab.kind; T.nsoc = C.reg.nsoc; T.desc = C.tab.socdesc;
+    T.s = C.tab.sz; T.z = C.tab.sz + T.m; T.w = C.tab.wl; T.lam = C.tab.wl + T.m; T.eta = C.tab.eta;
+    switch (T.mode) {
+        case StepMode::Off:
+        case StepMode::Symmetric:
+            break;
+        case StepMode::GenPow:
+            T.ngp = C.reg.ngenpow; T.gpdesc = C.tab.gpdesc; T.gpalpha = C.tab.gpalpha; T.mu = C.step.mu;
+            [[fallthrough]];      // and the three-row members of the set
+        case StepMode::Cone3:
+            T.nexp = C.reg.nexp; T.npow = C.reg.npow; T.n3 = T.nexp + T.npow;
+            T.row0 = C.tab.row0; T.out0 = C.tab.out0; T.alpha = C.tab.alpha; T.nsout = C.tab.nsout;
+            break;
+        case StepMode::Psd:
+            T.npsd = (int)C.reg.psd_n.size(); T.psdtab = C.tab.psdtab; T.psdR = C.tab.R; T.psdRinv = C.tab.psd_rinv; T.psdlam = C.tab.psd_lam;
+            break;
     }
     return T;
 }
@@ -101,24 +113,33 @@ static void op_mulhs(hipStream_t st, const ConeTables &T, const double *x, const
 // coneops_compositecone.jl:216-252, started from min(alpha_tau, alpha_kappa, 1) when dtau (device) is given (variables.jl:14-43)
 static void op_length(hipkkt_solver *S, hipStream_t st, const ConeTables &T, const double *dz, const double *ds, double alpha_max,
                       const double *dtau, double tau, double kappa, double rhs_kappa, double *out2) {
-    if (T.npsd) {
-        // the symmetric rows' launch as it is, its pair parked in d_st_out[28..29]; the PSD cones' pairs follow its partials in d_st_part
-        // (2 (ceil(m / 256) + ncones) doubles: second-order and PSD cones together are at most ncones)
-        launch_step_length(st, T.kind, T.nsoc, T.desc, T.z, T.s, dz, ds, alpha_max, S->d_st_part, S->d_st_out + 28, T.m);
-        launch_psd_step_length(st, T.npsd, T.psdtab, T.psdR, T.psdRinv, T.psdlam, dz, ds, alpha_max, S->d_st_out + 28,
-                               S->d_st_part + 2 * step_len_pairs(T.m, T.nsoc), out2);
-        return;
+    const ConeState::Step &St = S->cones.step;
+    switch (T.mode) {
+        case StepMode::Off:
+        case StepMode::Symmetric:
+            launch_step_length(st, T.kind, T.nsoc, T.desc, T.z, T.s, dz, ds, alpha_max, St.part, out2, T.m);
+            break;
+        case StepMode::Psd: {
+            // the symmetric rows' launch as it is, its pair parked at kStOutSymPsd; the PSD cones' pairs follow its partials in St.part
+            // (2 (ceil(m / 256) + ncones) doubles: second-order and PSD cones together are at most ncones)
+            double *sym2 = St.out + kStOutSymPsd;
+            launch_step_length(st, T.kind, T.nsoc, T.desc, T.z, T.s, dz, ds, alpha_max, St.part, sym2, T.m);
+            launch_psd_step_length(st, T.npsd, T.psdtab, T.psdR, T.psdRinv, T.psdlam, dz, ds, alpha_max, sym2,
+                                   St.part + 2 * step_len_pairs(T.m, T.nsoc), out2);
+            break;
+        }
+        case StepMode::Cone3:
+        case StepMode::GenPow: {
+            double *sym2 = St.out + kStOutSym;
+            launch_step_length(st, T.kind, T.nsoc, T.desc, T.z, T.s, dz, ds, alpha_max, St.part, sym2, T.m);
+            // (St.part holds 2 (ceil(m / 256) + ncones) doubles: room for the three-row workgroups' partials and one per Generalized Power cone)
+            launch_genpow_length(st, T.ngp, T.gpdesc, T.gpalpha, T.z, T.s, dz, ds, sym2, dtau, tau, kappa, rhs_kappa, alpha_max,
+                                 St.ls_step, St.ls_amin, St.ls_trips, St.part + step3_length_parts(T.nexp, T.npow));
+            launch_step3_length(st, T.nexp, T.npow, T.row0, T.alpha, T.z, T.s, dz, ds, sym2, dtau, tau, kappa, rhs_kappa, alpha_max,
+                                St.ls_step, St.ls_amin, St.ls_trips, St.part, out2, T.ngp);
+            break;
+        }
     }
-    if (!T.n3 && !T.ngp) {
-        launch_step_length(st, T.kind, T.nsoc, T.desc, T.z, T.s, dz, ds, alpha_max, S->d_st_part, out2, T.m);
-        return;
-    }
-    launch_step_length(st, T.kind, T.nsoc, T.desc, T.z, T.s, dz, ds, alpha_max, S->d_st_part, S->d_st_out, T.m);
-    // (d_st_part holds 2 (ceil(m / 256) + ncones) doubles: room for the three-row workgroups' partials and one per Generalized Power cone)
-    launch_genpow_length(st, T.ngp, T.gpdesc, T.gpalpha, T.z, T.s, dz, ds, S->d_st_out, dtau, tau, kappa, rhs_kappa, alpha_max,
-                         S->st_c3_step, S->st_c3_amin, S->st_c3_trips, S->d_st_part + step3_length_parts(T.nexp, T.npow));
-    launch_step3_length(st, T.nexp, T.npow, T.row0, T.alpha, T.z, T.s, dz, ds, S->d_st_out, dtau, tau, kappa, rhs_kappa, alpha_max,
-                        S->st_c3_step, S->st_c3_amin, S->st_c3_trips, S->d_st_part, out2, T.ngp);
 }
 
 // one operation on host vectors of length m: `nin` inputs are staged, op(in0, in1, out) runs, `nout` doubles come back
@@ -145,25 +166,26 @@ static int32_t fused_solve(hipkkt_solver *S, const StepScalars &sc, const double
                            double *scal_out15, int32_t ir_enable, double reltol, double abstol, int64_t max_iter, double stop_ratio,
                            int64_t *ir_steps2) {
     const int64_t n = S->img.n, m = S->img.m;
+    ConeState &C = S->cones;
     const ConeTables T = tables(S);
     if (solve_target(S) != S) HK_CHECK(hipStreamSynchronize(S->stream));      // the robust-order twin solves on its own stream
     double *h2 = S->h_scal_red + 10;
     const std::function<void(hipStream_t, const double *)> after = [&](hipStream_t st, const double *d_lhs) {
-        double *dz = S->d_st_step + n, *ds = dz + m;
-        HK_CHECK(hipMemcpyAsync(S->d_st_step, d_lhs, (size_t)(n + m) * sizeof(double), hipMemcpyDeviceToDevice, st));
+        double *dz = C.step.step + n, *ds = dz + m;
+        HK_CHECK(hipMemcpyAsync(C.step.step, d_lhs, (size_t)(n + m) * sizeof(double), hipMemcpyDeviceToDevice, st));
         op_mulhs(st, T, dz, addc, ds);
         // (with Exponential / Power cones the line search starts from min(alpha_tau, alpha_kappa, 1): dtau is the reduction's first scalar)
-        double *out2 = (T.n3 || T.ngp) ? S->d_st_out + 2 : S->d_st_out;
+        double *out2 = C.step.out + (T.line_search() ? kStOutLen : kStOutSym);
         op_length(S, st, T, dz, ds, 1.0, S->d_red + 3 * (size_t)S->N + n, sc.tau, sc.kappa, sc.rhs_kappa, out2);
         HK_CHECK(hipMemcpyAsync(h2, out2, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
     };
     const double scal_in[4] = {sc.tau, sc.kappa, sc.rhs_tau, sc.rhs_kappa};
     double red[10];
-    S->st_have_step = false;
-    const int32_t rc = kkt_solve_reduced_impl(S, nullptr, nullptr, nullptr, S->d_st_in, scal_in, const_pending, nullptr, nullptr, nullptr, red,
+    C.step.have_step = false;
+    const int32_t rc = kkt_solve_reduced_impl(S, nullptr, nullptr, nullptr, C.step.in, scal_in, const_pending, nullptr, nullptr, nullptr, red,
                                               ir_enable, reltol, abstol, max_iter, stop_ratio, ir_steps2, &after);
     if (rc != HIPKKT_OK) return rc;
-    S->st_have_step = true;
+    C.step.have_step = true;
     // variables.jl:14-43 (the cones' part ran with alpha_max = 1: the minimum is exact in any order), kktsystem.jl:209
     const double dtau = red[0];
     const double dkappa = -(sc.rhs_kappa + sc.kappa * dtau) / sc.tau;
@@ -235,15 +257,16 @@ int32_t hipkkt_cone_step_length(hipkkt_handle h, const double *dz, const double 
 // (without the enable T names no Exponential / Power cone: the symmetric cones' barrier)
 static void barrier_impl(hipkkt_solver *S, const ConeTables &T, const double *z, const double *s, const double *dz, const double *ds,
                          const double *alphas, int64_t nalpha, double *dout) {
-    // (d_st_bar has 8 doubles per registered cone for the per-cone partials: second-order, three-row and Generalized Power together)
-    launch_genpow_barrier(S->stream, T.ngp, T.gpdesc, T.gpalpha, z, s, dz, ds, alphas, (int)nalpha,
-                          step3_barrier_gppart(S->d_st_bar, T.nsoc, T.n3));
-    launch_step3_barrier(S->stream, T.kind, T.nsoc, T.desc, T.nexp, T.npow, T.row0, T.alpha, z, s, dz, ds, alphas, (int)nalpha,
-                         S->d_st_bar, dout, T.m, T.ngp);
+    // (the work buffer has 8 doubles per registered cone for the per-cone partials: second-order, three-row and Generalized Power together)
+    double *bar = S->cones.step.bar;
+    launch_genpow_barrier(S->stream, T.ngp, T.gpdesc, T.gpalpha, z, s, dz, ds, alphas, (int)nalpha, step3_barrier_gppart(bar, T.nsoc, T.n3));
+    launch_step3_barrier(S->stream, T.kind, T.nsoc, T.desc, T.nexp, T.npow, T.row0, T.alpha, z, s, dz, ds, alphas, (int)nalpha, bar, dout,
+                         T.m, T.ngp);
 }
 
-// the parameter checks, the trip bound and the invalidation both enables share
-static int32_t enable_line_search(hipkkt_solver *S, const char *who, double step, double amin) {
+// the parameter checks, the trip bound and the invalidation both enables share; the handle is in `mode` afterwards
+static int32_t enable_line_search(hipkkt_solver *S, const char *who, StepMode mode, double step, double amin) {
+    ConeState &C = S->cones;
     if (!(step > 0.0 && step < 1.0) || !(amin > 0.0) || !std::isfinite(amin)) {
         S->err = std::string(who) + ": 0 < linesearch_backtrack_step < 1 and min_terminate_step_length > 0";
         return HIPKKT_ERR_ARGUMENT;
@@ -251,84 +274,91 @@ static int32_t enable_line_search(hipkkt_solver *S, const char *who, double step
     // alpha0 <= 1, so alpha0 step^k < alpha_min after at most ceil(log alpha_min / log step) multiplications
     const double trips = std::ceil(std::log(amin) / std::log(step)) + 2.0;
     if (!(trips <= 4096.0)) { S->err = std::string(who) + ": the line search would need more than 4096 trips"; return HIPKKT_ERR_ARGUMENT; }
-    S->st_c3_step = step; S->st_c3_amin = amin; S->st_c3_trips = (int)std::max(trips, 2.0);
-    S->st_cone3 = true;
-    S->sc_scaled = false;      // the step reads the resident (s, z) of a scaling that ran with the enable in place
-    S->st_have_step = false;
+    C.step.ls_step = step; C.step.ls_amin = amin; C.step.ls_trips = (int)std::max(trips, 2.0);
+    C.step.mode = mode;
+    C.step.scaled = false;      // the step reads the resident (s, z) of a scaling that ran with the enable in place
+    C.step.have_step = false;
     return HIPKKT_OK;
+}
+
+// enable = 0 of either entry point: Cone3 and GenPow go off, the other modes stay
+static void disable_line_search(ConeState &C) {
+    if (C.step.mode == StepMode::Cone3 || C.step.mode == StepMode::GenPow) C.step.mode = StepMode::Off;
 }
 
 int32_t hipkkt_step_enable_cone3(hipkkt_handle h, int32_t enable, double linesearch_backtrack_step, double min_terminate_step_length) {
     HK_ENTER(h)
-    if (!enable) { S->st_cone3 = false; S->st_genpow = false; return HIPKKT_OK; }
-    if (!S->l1 || !S->sc_ready || !S->sc_cone3_kinds) {
+    ConeState &C = S->cones;
+    if (!enable) { disable_line_search(C); return HIPKKT_OK; }
+    if (!S->l1 || !C.reg.ready || C.reg.cls != ConeClass::Cone3) {
         S->err = "step_enable_cone3: needs an L1 handle whose last hipkkt_set_cone_types_ex names Zero / Nonnegative / SecondOrder / Exponential / "
                  "Power cones only, at least one of the last two";
         return HIPKKT_ERR_ARGUMENT;
     }
-    return enable_line_search(S, "step_enable_cone3", linesearch_backtrack_step, min_terminate_step_length);
+    return enable_line_search(S, "step_enable_cone3", StepMode::Cone3, linesearch_backtrack_step, min_terminate_step_length);
     HK_LEAVE
 }
 
 int32_t hipkkt_step_enable_genpow(hipkkt_handle h, int32_t enable, double linesearch_backtrack_step, double min_terminate_step_length) {
     HK_ENTER(h)
-    if (!enable) { S->st_cone3 = false; S->st_genpow = false; return HIPKKT_OK; }
-    if (!S->l1 || !S->sc_ready || !S->sc_genpow_kinds) {
+    ConeState &C = S->cones;
+    if (!enable) { disable_line_search(C); return HIPKKT_OK; }
+    if (!S->l1 || !C.reg.ready || C.reg.cls != ConeClass::GenPow) {
         S->err = "step_enable_genpow: needs an L1 handle whose last hipkkt_set_cone_types_ex names Zero / Nonnegative / SecondOrder / Exponential / "
                  "Power / GenPower cones only, at least one GenPower";
         return HIPKKT_ERR_ARGUMENT;
     }
-    const int32_t rc = enable_line_search(S, "step_enable_genpow", linesearch_backtrack_step, min_terminate_step_length);
-    if (rc == HIPKKT_OK) S->st_genpow = true;
-    return rc;
+    return enable_line_search(S, "step_enable_genpow", StepMode::GenPow, linesearch_backtrack_step, min_terminate_step_length);
     HK_LEAVE
 }
 
 int32_t hipkkt_step_enable_psd(hipkkt_handle h, int32_t enable) {
     HK_ENTER(h)
-    if (!enable) { S->st_psd = false; return HIPKKT_OK; }
-    bool ok = S->l1 && S->sc_ready && S->sc_psd_kinds;
-    for (size_t c = 0; ok && c < S->sc_psd_n.size(); c++) ok = S->sc_psd_n[c] <= HIPKKT_PSD_STEP_MAX_DIM;
+    ConeState &C = S->cones;
+    if (!enable) { if (C.step.mode == StepMode::Psd) C.step.mode = StepMode::Off; return HIPKKT_OK; }
+    bool ok = S->l1 && C.reg.ready && C.reg.cls == ConeClass::Psd;
+    for (size_t c = 0; ok && c < C.reg.psd_n.size(); c++) ok = C.reg.psd_n[c] <= HIPKKT_PSD_STEP_MAX_DIM;
     if (!ok) {
         S->err = "step_enable_psd: needs an L1 handle whose last hipkkt_set_cone_types[_ex] names Zero / Nonnegative / SecondOrder / PSD "
                  "triangle cones only, at least one PSD cone, every PSD side <= HIPKKT_PSD_STEP_MAX_DIM";
         return HIPKKT_ERR_ARGUMENT;
     }
     // the cone table and the factor buffers: allocated on the first call, re-used while large enough (as the d_sc_* buffers)
-    const int64_t npsd = (int64_t)S->sc_psd_n.size();
-    std::vector<int64_t> tab((size_t)(4 * npsd));
+    const int64_t npsd = (int64_t)C.reg.psd_n.size();
+    std::vector<int64_t> tab((size_t)(kPsdTab * npsd));
     int64_t foff = 0, loff = 0;
     for (int64_t c = 0; c < npsd; c++) {
-        const int64_t n = S->sc_psd_n[c];
-        tab[4 * c] = S->sc_psd_row[c]; tab[4 * c + 1] = n; tab[4 * c + 2] = foff; tab[4 * c + 3] = loff;
+        const int64_t n = C.reg.psd_n[c];
+        int64_t *t = &tab[kPsdTab * c];
+        t[kPsdRow0] = C.reg.psd_row[c]; t[kPsdN] = n; t[kPsdFactor0] = foff; t[kPsdLambda0] = loff;
         foff += n * n; loff += n;
     }
-    if (npsd > S->psd_cap_cones) { S->d_psd_tab = S->dalloc<int64_t>(4 * npsd); S->psd_cap_cones = npsd; }
-    if (foff > S->psd_cap_mat || loff > S->psd_cap_lam) {
-        S->d_psd_rinv = S->dalloc<double>(foff); S->d_psd_lam = S->dalloc<double>(loff); S->d_psd_stage = S->dalloc<double>(foff + loff);
-        S->psd_cap_mat = foff; S->psd_cap_lam = loff;
+    if (npsd > C.tab.cap_psd_cones) { C.tab.psdtab = S->dalloc<int64_t>(kPsdTab * npsd); C.tab.cap_psd_cones = npsd; }
+    if (foff > C.tab.cap_psd_mat || loff > C.tab.cap_psd_lam) {
+        C.tab.psd_rinv = S->dalloc<double>(foff); C.tab.psd_lam = S->dalloc<double>(loff); C.tab.psd_stage = S->dalloc<double>(foff + loff);
+        C.tab.cap_psd_mat = foff; C.tab.cap_psd_lam = loff;
     }
-    S->psd_lam_total = loff;
-    copy_sync(S->stream, S->d_psd_tab, tab.data(), tab.size() * sizeof(int64_t), hipMemcpyHostToDevice);
-    S->st_psd = true;
-    S->psd_fresh = false;
-    S->sc_scaled = false;      // the step reads the factors of a scaling that ran with the enable in place
-    S->st_have_step = false;
+    copy_sync(S->stream, C.tab.psdtab, tab.data(), tab.size() * sizeof(int64_t), hipMemcpyHostToDevice);
+    C.step.mode = StepMode::Psd;
+    C.step.psd_fresh = false;
+    C.step.scaled = false;      // the step reads the factors of a scaling that ran with the enable in place
+    C.step.have_step = false;
     return HIPKKT_OK;
     HK_LEAVE
 }
 
 static int32_t psd_set_factors_impl(hipkkt_handle h, const double *Rinv_all, const double *lambda_all, bool dev) {
     HK_ENTER(h)
-    if (!S->st_psd || !Rinv_all || !lambda_all) {
+    ConeState &C = S->cones;
+    if (C.step.mode != StepMode::Psd || !Rinv_all || !lambda_all) {
         S->err = "psd_set_factors: needs hipkkt_step_enable_psd first / null argument";
         return HIPKKT_ERR_ARGUMENT;
     }
     const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    HK_CHECK(hipMemcpyAsync(S->d_psd_stage, Rinv_all, (size_t)S->sc_psd_total * sizeof(double), kind, S->stream));
-    HK_CHECK(hipMemcpyAsync(S->d_psd_stage + S->sc_psd_total, lambda_all, (size_t)S->psd_lam_total * sizeof(double), kind, S->stream));
+    HK_CHECK(hipMemcpyAsync(C.tab.psd_stage, Rinv_all, (size_t)C.reg.psd_total * sizeof(double), kind, S->stream));
+    HK_CHECK(hipMemcpyAsync(C.tab.psd_stage + C.reg.psd_total, lambda_all, (size_t)C.reg.psd_lam_total * sizeof(double), kind, S->stream));
     if (!dev) HK_CHECK(hipStreamSynchronize(S->stream));      // (the caller may reuse its host arrays)
-    S->psd_fresh = true;
+    C.step.psd_fresh = true;
     return HIPKKT_OK;
     HK_LEAVE
 }
@@ -341,8 +371,9 @@ int32_t hipkkt_psd_set_factors_dev(hipkkt_handle h, const double *Rinv_all, cons
 
 int32_t hipkkt_cone_barrier(hipkkt_handle h, const double *dz, const double *ds, const double *alphas, int64_t nalpha, double *out) {
     HK_ENTER(h)
+    ConeState &C = S->cones;
     if (!step_ready(S, "cone_barrier")) return HIPKKT_ERR_ARGUMENT;
-    if (S->st_psd) { S->err = "cone_barrier: a set with PSD triangle cones is symmetric and needs no barrier"; return HIPKKT_ERR_ARGUMENT; }
+    if (C.step.mode == StepMode::Psd) { S->err = "cone_barrier: a set with PSD triangle cones is symmetric and needs no barrier"; return HIPKKT_ERR_ARGUMENT; }
     if (!alphas || !out || nalpha < 1 || nalpha > step3_max_candidates() || (S->img.m && (!dz || !ds))) {
         S->err = "cone_barrier: 1 <= nalpha <= 8 / null argument"; return HIPKKT_ERR_ARGUMENT;
     }
@@ -355,30 +386,32 @@ int32_t hipkkt_cone_barrier(hipkkt_handle h, const double *dz, const double *ds,
 
 int32_t hipkkt_step_barrier_dev(hipkkt_handle h, const double *xzs_dev, const double *alphas, int64_t nalpha, double *out) {
     HK_ENTER(h)
+    ConeState &C = S->cones;
     if (!step_ready(S, "step_barrier_dev")) return HIPKKT_ERR_ARGUMENT;
-    if (S->st_psd) { S->err = "step_barrier_dev: a set with PSD triangle cones is symmetric and needs no barrier"; return HIPKKT_ERR_ARGUMENT; }
-    if (!S->st_have_step || !xzs_dev || !alphas || !out || nalpha < 1 || nalpha > step3_max_candidates()) {
+    if (C.step.mode == StepMode::Psd) { S->err = "step_barrier_dev: a set with PSD triangle cones is symmetric and needs no barrier"; return HIPKKT_ERR_ARGUMENT; }
+    if (!C.step.have_step || !xzs_dev || !alphas || !out || nalpha < 1 || nalpha > step3_max_candidates()) {
         S->err = "step_barrier_dev: no step resident / 1 <= nalpha <= 8 / null argument"; return HIPKKT_ERR_ARGUMENT;
     }
     const int64_t n = S->img.n, m = S->img.m;
     const ConeTables T = tables(S);
     ensure_step_buffers(S);
-    barrier_impl(S, T, xzs_dev + n, xzs_dev + n + m, S->d_st_step + n, S->d_st_step + n + m, alphas, nalpha, S->d_st_out + 12);
-    copy_sync(S->stream, out, S->d_st_out + 12, (size_t)(2 * nalpha) * sizeof(double), hipMemcpyDeviceToHost);
+    barrier_impl(S, T, xzs_dev + n, xzs_dev + n + m, C.step.step + n, C.step.step + n + m, alphas, nalpha, C.step.out + kStOutBarrier);
+    copy_sync(S->stream, out, C.step.out + kStOutBarrier, (size_t)(2 * nalpha) * sizeof(double), hipMemcpyDeviceToHost);
     return HIPKKT_OK;
     HK_LEAVE
 }
 
 int32_t hipkkt_set_equilibration(hipkkt_handle h, const double *d, const double *e) {
     HK_ENTER(h)
+    ConeState &C = S->cones;
     const int64_t n = S->img.n, m = S->img.m;
     if (!S->l1 || (n && !d) || (m && !e)) { S->err = "set_equilibration: bad arguments / not an L1 handle"; return HIPKKT_ERR_ARGUMENT; }
     // dinv = 1 ./ d, einv = 1 ./ e as problemdata.jl forms them (IEEE division: the caller's bits)
     std::vector<double> eq((size_t)(2 * n + 2 * m) + 1);
     for (int64_t i = 0; i < n; i++) { eq[i] = d[i]; eq[n + m + i] = 1.0 / d[i]; }
     for (int64_t i = 0; i < m; i++) { eq[n + i] = e[i]; eq[2 * n + m + i] = 1.0 / e[i]; }
-    if (!S->d_st_eq) S->d_st_eq = S->dalloc<double>(2 * n + 2 * m);
-    copy_sync(S->stream, S->d_st_eq, eq.data(), (size_t)(2 * n + 2 * m) * sizeof(double), hipMemcpyHostToDevice);
+    if (!C.step.eq) C.step.eq = S->dalloc<double>(2 * n + 2 * m);
+    copy_sync(S->stream, C.step.eq, eq.data(), (size_t)(2 * n + 2 * m) * sizeof(double), hipMemcpyHostToDevice);
     return HIPKKT_OK;
     HK_LEAVE
 }
@@ -387,13 +420,14 @@ int32_t hipkkt_step_affine_dev(hipkkt_handle h, const double *xzs_dev, const dou
                                double *scal_out15, int32_t ir_enable, double reltol, double abstol, int64_t max_iter, double stop_ratio,
                                int64_t *ir_steps2) {
     HK_ENTER(h)
+    ConeState &C = S->cones;
     if (!step_ready(S, "step_affine_dev")) return HIPKKT_ERR_ARGUMENT;
     if (!S->d_qb || !xzs_dev || !res_dev || !scal_in3 || !scal_out15) { S->err = "step_affine_dev: call hipkkt_set_qb first / bad arguments"; return HIPKKT_ERR_ARGUMENT; }
     const int64_t n = S->img.n, m = S->img.m;
     ensure_step_buffers(S);
     const double tau = scal_in3[0], kappa = scal_in3[1], r_tau = scal_in3[2];
     // variables_affine_step_rhs!, variables.jl:107-121; ds_const = s (kktsystem.jl:152-156)
-    launch_step_rhs(S->stream, S->d_st_in, xzs_dev, res_dev, nullptr, 1.0, n, m);
+    launch_step_rhs(S->stream, C.step.in, xzs_dev, res_dev, nullptr, 1.0, n, m);
     const StepScalars sc{tau, kappa, r_tau, tau * kappa};
     return fused_solve(S, sc, xzs_dev + n + m, const_pending, 1.0, scal_out15, ir_enable, reltol, abstol, max_iter, stop_ratio, ir_steps2);
     HK_LEAVE
@@ -403,9 +437,10 @@ int32_t hipkkt_step_combined_dev(hipkkt_handle h, const double *xzs_dev, const d
                                  int32_t const_pending, double *scal_out15, int32_t ir_enable, double reltol, double abstol,
                                  int64_t max_iter, double stop_ratio, int64_t *ir_steps2) {
     HK_ENTER(h)
+    ConeState &C = S->cones;
     if (!step_ready(S, "step_combined_dev")) return HIPKKT_ERR_ARGUMENT;
     if (!S->d_qb || !xzs_dev || !res_dev || !scal_in9 || !scal_out15) { S->err = "step_combined_dev: call hipkkt_set_qb first / bad arguments"; return HIPKKT_ERR_ARGUMENT; }
-    if (!S->st_have_step) { S->err = "step_combined_dev: no affine step resident (hipkkt_step_affine_dev comes first)"; return HIPKKT_ERR_ARGUMENT; }
+    if (!C.step.have_step) { S->err = "step_combined_dev: no affine step resident (hipkkt_step_affine_dev comes first)"; return HIPKKT_ERR_ARGUMENT; }
     const int64_t n = S->img.n, m = S->img.m;
     const double tau = scal_in9[0], kappa = scal_in9[1], r_tau = scal_in9[2], dtau_aff = scal_in9[3], dkappa_aff = scal_in9[4];
     const double sigma = scal_in9[5], mu = scal_in9[6], m_corr = scal_in9[7], step_fraction = scal_in9[8];
@@ -414,14 +449,14 @@ int32_t hipkkt_step_combined_dev(hipkkt_handle h, const double *xzs_dev, const d
     // variables_combined_step_rhs!, variables.jl:124-162
     const double sm = sigma * mu, oms = 1.0 - sigma;
     const double rhs_kappa = -sm + m_corr * dtau_aff * dkappa_aff + tau * kappa;
-    double *w_dz = S->d_st_work, *w_rhs_s = w_dz + m, *w_shift = w_rhs_s + m, *w_dsc = w_shift + m;
-    const double *dz_aff = S->d_st_step + n, *ds_aff = dz_aff + m;
+    double *w_dz = C.step.work, *w_rhs_s = w_dz + m, *w_shift = w_rhs_s + m, *w_dsc = w_shift + m;
+    const double *dz_aff = C.step.step + n, *ds_aff = dz_aff + m;
     if (m_corr != 1.0) { launch_step_scale(st, w_dz, dz_aff, m_corr, m); dz_aff = w_dz; }
     op_affine_ds(st, T, w_rhs_s);
     op_shift(st, T, dz_aff, ds_aff, sm, w_shift);
     launch_step_add(st, w_rhs_s, w_shift, m);                                                           // rhs.s = lambda o lambda + shift
     op_offset(st, T, w_rhs_s, w_dsc);                                                                   // kktsystem.jl:157-163
-    launch_step_rhs(st, S->d_st_in, xzs_dev, res_dev, w_dsc, oms, n, m);
+    launch_step_rhs(st, C.step.in, xzs_dev, res_dev, w_dsc, oms, n, m);
     const StepScalars sc{tau, kappa, oms * r_tau, rhs_kappa};
     return fused_solve(S, sc, w_dsc, const_pending, step_fraction, scal_out15, ir_enable, reltol, abstol, max_iter, stop_ratio, ir_steps2);
     HK_LEAVE
@@ -429,9 +464,10 @@ int32_t hipkkt_step_combined_dev(hipkkt_handle h, const double *xzs_dev, const d
 
 int32_t hipkkt_step_apply_dev(hipkkt_handle h, double alpha, double *xzs_dev) {
     HK_ENTER(h)
+    ConeState &C = S->cones;
     if (!step_ready(S, "step_apply_dev")) return HIPKKT_ERR_ARGUMENT;
-    if (!S->st_have_step || !xzs_dev) { S->err = "step_apply_dev: no step resident / null iterate"; return HIPKKT_ERR_ARGUMENT; }
-    launch_step_add_step(S->stream, xzs_dev, S->d_st_step, alpha, S->img.n + 2 * S->img.m);
+    if (!C.step.have_step || !xzs_dev) { S->err = "step_apply_dev: no step resident / null iterate"; return HIPKKT_ERR_ARGUMENT; }
+    launch_step_add_step(S->stream, xzs_dev, C.step.step, alpha, S->img.n + 2 * S->img.m);
     // (no host synchronisation: whatever reads the iterate next runs on the same stream)
     return HIPKKT_OK;
     HK_LEAVE
@@ -439,18 +475,20 @@ int32_t hipkkt_step_apply_dev(hipkkt_handle h, double alpha, double *xzs_dev) {
 
 int32_t hipkkt_step_info_norms_dev(hipkkt_handle h, const double *xzs_dev, const double *res_dev, double *out8) {
     HK_ENTER(h)
-    if (!S->l1 || !S->d_st_eq || !xzs_dev || !res_dev || !out8) { S->err = "step_info_norms_dev: call hipkkt_set_equilibration first / bad arguments"; return HIPKKT_ERR_ARGUMENT; }
+    ConeState &C = S->cones;
+    if (!S->l1 || !C.step.eq || !xzs_dev || !res_dev || !out8) { S->err = "step_info_norms_dev: call hipkkt_set_equilibration first / bad arguments"; return HIPKKT_ERR_ARGUMENT; }
     ensure_step_buffers(S);      // (needs no scaling: the first info_update! of a solve precedes it)
-    launch_step_info_norms(S->stream, xzs_dev, res_dev, S->d_st_eq, S->d_st_part, S->d_st_out + 4, S->img.n, S->img.m);
-    copy_sync(S->stream, out8, S->d_st_out + 4, 8 * sizeof(double), hipMemcpyDeviceToHost);
+    launch_step_info_norms(S->stream, xzs_dev, res_dev, C.step.eq, C.step.part, C.step.out + kStOutNorms, S->img.n, S->img.m);
+    copy_sync(S->stream, out8, C.step.out + kStOutNorms, 8 * sizeof(double), hipMemcpyDeviceToHost);
     return HIPKKT_OK;
     HK_LEAVE
 }
 
 int32_t hipkkt_step_get(hipkkt_handle h, double *out) {
     HK_ENTER(h)
-    if (!S->l1 || !S->st_have_step || !out) { S->err = "step_get: no step resident"; return HIPKKT_ERR_ARGUMENT; }
-    copy_sync(S->stream, out, S->d_st_step, (size_t)(S->img.n + 2 * S->img.m) * sizeof(double), hipMemcpyDeviceToHost);
+    ConeState &C = S->cones;
+    if (!S->l1 || !C.step.have_step || !out) { S->err = "step_get: no step resident"; return HIPKKT_ERR_ARGUMENT; }
+    copy_sync(S->stream, out, C.step.step, (size_t)(S->img.n + 2 * S->img.m) * sizeof(double), hipMemcpyDeviceToHost);
     return HIPKKT_OK;
     HK_LEAVE
 }

@@ -11,6 +11,8 @@
 #include <stdint.h>
 
 #include "cone3_math.h"
+#include "cone_layout.h"
+#include "cone_reduce.h"
 #include "kernels.h"
 
 namespace hipkkt {
@@ -33,20 +35,12 @@ k_scaling_diag(const signed char *__restrict__ row_kind, const int64_t *__restri
     }
 }
 
-__device__ __forceinline__ double block_sum(double v, double *red) {      // 256 threads; every thread gets the total
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-    __syncthreads();                                                    // red[] may still be read from the previous sum
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
 __device__ __forceinline__ double sqrt_soc_residual(double z0, double z1norm) {   // coneops_socone.jl:395-407
     const double r = (z0 - z1norm) * (z0 + z1norm);
     return r > 0.0 ? sqrt(r) : 0.0;
 }
 
-// one workgroup per second-order cone.  desc[c] = {first row, dim, first Hs entry, offset into the concatenated (u, v) of the sparse
-// cones or -1 for a dense (dim <= 4) block, ordinal among the sparse cones or -1}
+// one workgroup per second-order cone, desc: its descriptors (cone_layout.h kSoc*)
 __global__ void __launch_bounds__(256)
 k_scaling_soc(const int64_t *__restrict__ desc, const int64_t *__restrict__ map_hs, const double *__restrict__ s_all,
               const double *__restrict__ z_all, double *__restrict__ w_all, double *__restrict__ lam_all, double *__restrict__ eta_out,
@@ -54,7 +48,8 @@ k_scaling_soc(const int64_t *__restrict__ desc, const int64_t *__restrict__ map_
               int *__restrict__ fail) {
     __shared__ double red[4];
     const int c = blockIdx.x, t = threadIdx.x;
-    const int64_t row0 = desc[5 * c], dim = desc[5 * c + 1], hs0 = desc[5 * c + 2], uv0 = desc[5 * c + 3], ord = desc[5 * c + 4];
+    const int64_t row0 = desc[kSocDesc * c + kSocRow0], dim = desc[kSocDesc * c + kSocDim], hs0 = desc[kSocDesc * c + kSocHs0];
+    const int64_t uv0 = desc[kSocDesc * c + kSocUv0], ord = desc[kSocDesc * c + kSocOrd];
     const double *s = s_all + row0, *z = z_all + row0;
     double *w = w_all + row0, *lam = lam_all + row0;
     double a = 0.0, b = 0.0;
@@ -200,7 +195,7 @@ __device__ __forceinline__ void keep_positive_definite(double Hs[6]) {
 
 // One lane per three-row cone; a launch holds cones of one kind only (POW = false Exponential, true Power): the tables are ordered
 // by kind, this launch takes the `count` cones from `first` on.  strategy 0 PrimalDual, 1 Dual (types.jl:73-76).
-// Per cone: Hs (6) negated through map_hs into kval; Hs (6), H_dual (6), grad (3) into out[out0 ..).  trips (may be NULL) receives the
+// Per cone: Hs (6) negated through map_hs into kval; Hs (6), H_dual (6), grad (3) into its slot out[out0 ..) (cone_layout.h kSlot3*).  trips (may be NULL) receives the
 // steps of the Newton iteration.
 template <bool POW>
 __global__ void __launch_bounds__(256)
@@ -237,46 +232,34 @@ k_scaling_cone3(int first, int count, const int64_t *__restrict__ row0_t, const 
     if (trips_out) trips_out[c] = trips;
     if (!ok) {
         atomicOr(fail, 1);
-        for (int i = 0; i < 15; i++) o[i] = __builtin_nan("");
+        for (int i = 0; i < kSlot3; i++) o[i] = __builtin_nan("");
         return;
     }
     for (int i = 0; i < 6; i++) {
         kval[map_hs[hs0 + i]] = -Hs[i];
-        o[i] = Hs[i];
-        o[6 + i] = K.H[i];
+        o[kSlot3Hs + i] = Hs[i];
+        o[kSlot3Hdual + i] = K.H[i];
     }
-    for (int i = 0; i < 3; i++) o[12 + i] = K.g[i];
+    for (int i = 0; i < 3; i++) o[kSlot3Grad + i] = K.g[i];
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ double wave_prod(double v) {
-    for (int o = 32; o > 0; o >>= 1) v *= __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ int wave_or(int v) {
-    for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o);
-    return v;
-}
-
-// One wavefront (= one workgroup of 64) per Generalized Power cone.  desc[8 c ..] = {first row, dim1, dim2, first Hs entry, offset of
-// the cone's slot in `out`, offset of its exponents in alpha_all, offset of its index table in idx_all, the bits of 1 / <alpha, alpha> (step_genpow.hip reads them)}; the index table is
-// [map.q (dim1) | map.r (dim2) | map.p (dim) | map.D (3)] of the cone's GenPowExpansionMap (directldl_datamaps.jl:81-99), resident.
+// One wavefront (= one workgroup of 64) per Generalized Power cone.  desc: its descriptors (cone_layout.h kGp*; step_genpow.hip reads
+// the bits of psi); the index table is [map.q (dim1) | map.r (dim2) | map.p (dim) | map.D (3)] of the cone's GenPowExpansionMap
+// (directldl_datamaps.jl:81-99), resident.
 // The cone always takes the Dual scaling with the caller's mu (coneops_genpowcone.jl:21, :64-80).  Products and sums over the cone
 // are butterfly reductions: every lane holds the same phi, |w|^2.
-// out slot: grad (dim) | d1 (dim1) | d2 | p (dim) | q (dim1) | r (dim2).
+// out slot: cone_layout.h gp_slot.
 __global__ void __launch_bounds__(64)
 k_scaling_genpow(const int64_t *__restrict__ desc, const double *__restrict__ alpha_all, const int64_t *__restrict__ idx_all,
                  const int64_t *__restrict__ map_hs, const double *__restrict__ z_all, double mu, double sqrtmu,
                  double *__restrict__ kval, double *__restrict__ out, int *__restrict__ fail) {
     const int c = blockIdx.x, t = threadIdx.x;
-    const int64_t *d = desc + 8 * (int64_t)c;
-    const int64_t row0 = d[0], dim1 = d[1], dim2 = d[2], hs0 = d[3], dim = dim1 + dim2;
-    const double *z = z_all + row0, *a = alpha_all + d[5];
-    const int64_t *qi = idx_all + d[6], *ri = qi + dim1, *pi = ri + dim2, *Di = pi + dim;
-    double *g = out + d[4], *od1 = g + dim, *od2 = od1 + dim1, *op = od2 + 1, *oq = op + dim, *orr = oq + dim1;
+    const int64_t *d = desc + kGpDesc * (int64_t)c;
+    const int64_t row0 = d[kGpRow0], dim1 = d[kGpDim1], dim2 = d[kGpDim2], hs0 = d[kGpHs0], dim = dim1 + dim2;
+    const double *z = z_all + row0, *a = alpha_all + d[kGpAlpha0];
+    const int64_t *qi = idx_all + d[kGpIdx0], *ri = qi + dim1, *pi = ri + dim2, *Di = pi + dim;
+    // (the slot's pointers stay chained and its length 3 dim + dim1 + 1 spelled out: gp_slot() gives other address arithmetic)
+    double *g = out + d[kGpOut0], *od1 = g + dim, *od2 = od1 + dim1, *op = od2 + 1, *oq = op + dim, *orr = oq + dim1;
     // update_dual_grad_H, :343-396
     double phi = 1.0, n2 = 0.0;
     int bad = 0;

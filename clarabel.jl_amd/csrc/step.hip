@@ -17,6 +17,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "cone_layout.h"
+#include "cone_reduce.h"
 #include "kernels.h"
 
 namespace hipkkt {
@@ -25,20 +27,6 @@ namespace {
 
 constexpr double kFloatMax = 1.7976931348623157e308;
 
-__device__ __forceinline__ double block_sum(double v, double *red) {      // 256 threads; every thread gets the total (as scaling.hip)
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-__device__ __forceinline__ double block_min(double v, double *red) {
-    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_down(v, o));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return fmin(fmin(red[0], red[1]), fmin(red[2], red[3]));
-}
 // dot(a[1:], b[1:]) over one cone
 __device__ __forceinline__ double tail_dot(const double *a, const double *b, int64_t dim, double *red) {
     double acc = 0.0;
@@ -66,7 +54,7 @@ __global__ void __launch_bounds__(256)
 k_step_affine_ds_soc(const int64_t *__restrict__ desc, const double *__restrict__ lam_all, double *__restrict__ out_all) {
     __shared__ double red[4];
     const int c = blockIdx.x, t = threadIdx.x;
-    const int64_t row0 = desc[5 * c], dim = desc[5 * c + 1];
+    const int64_t row0 = desc[kSocDesc * c + kSocRow0], dim = desc[kSocDesc * c + kSocDim];
     const double *lam = lam_all + row0;
     double *out = out_all + row0;
     double acc = 0.0;
@@ -92,7 +80,7 @@ k_step_shift_soc(const int64_t *__restrict__ desc, const double *__restrict__ w_
                  const double *__restrict__ dz_all, const double *__restrict__ ds_all, double sigma_mu, double *__restrict__ out_all) {
     __shared__ double red[4];
     const int c = blockIdx.x, t = threadIdx.x;
-    const int64_t row0 = desc[5 * c], dim = desc[5 * c + 1];
+    const int64_t row0 = desc[kSocDesc * c + kSocRow0], dim = desc[kSocDesc * c + kSocDim];
     const double *w = w_all + row0, *dz = dz_all + row0, *ds = ds_all + row0;
     double *out = out_all + row0;
     const double eta = eta_all[c], etainv = 1.0 / eta, w0 = w[0];
@@ -128,7 +116,7 @@ k_step_offset_soc(const int64_t *__restrict__ desc, const double *__restrict__ z
                   double *__restrict__ out_all) {
     __shared__ double red[4];
     const int c = blockIdx.x, t = threadIdx.x;
-    const int64_t row0 = desc[5 * c], dim = desc[5 * c + 1];
+    const int64_t row0 = desc[kSocDesc * c + kSocRow0], dim = desc[kSocDesc * c + kSocDim];
     const double *z = z_all + row0, *w = w_all + row0, *lam = lam_all + row0, *ds = ds_all + row0;
     double *out = out_all + row0;
     const double eta = eta_all[c];
@@ -161,7 +149,7 @@ k_step_mulhs_soc(const int64_t *__restrict__ desc, const double *__restrict__ w_
                  const double *__restrict__ x_all, const double *__restrict__ addc_all, double *__restrict__ y_all) {
     __shared__ double red[4];
     const int c = blockIdx.x, t = threadIdx.x;
-    const int64_t row0 = desc[5 * c], dim = desc[5 * c + 1];
+    const int64_t row0 = desc[kSocDesc * c + kSocRow0], dim = desc[kSocDesc * c + kSocDim];
     const double *w = w_all + row0, *x = x_all + row0;
     double *y = y_all + row0;
     const double eta2 = eta_all[c] * eta_all[c];
@@ -214,7 +202,7 @@ k_step_len_soc(const int64_t *__restrict__ desc, const double *__restrict__ z_al
                const double *__restrict__ dz_all, const double *__restrict__ ds_all, double alpha_max, double *__restrict__ part) {
     __shared__ double red[4];
     const int c = blockIdx.x;
-    const int64_t row0 = desc[5 * c], dim = desc[5 * c + 1];
+    const int64_t row0 = desc[kSocDesc * c + kSocRow0], dim = desc[kSocDesc * c + kSocDim];
     const double az = soc_step_component(z_all + row0, dz_all + row0, dim, alpha_max, red);
     const double as = soc_step_component(s_all + row0, ds_all + row0, dim, alpha_max, red);
     if (threadIdx.x == 0) { part[2 * c] = az; part[2 * c + 1] = as; }

@@ -1,6 +1,6 @@
 // The cone algebra of one interior-point step for the three-row non-symmetric cones (Exponential, Power) on the device, next to
 // step.hip's Zero / Nonnegative / SecondOrder kernels, plus the barrier of a whole cone set.  Everything works on what
-// hipkkt_update_scaling_ex[_dev] left resident: (s, z) and, per cone, 15 doubles [pack_triu(Hs) | pack_triu(H_dual) | grad].
+// hipkkt_update_scaling_ex[_dev] left resident: (s, z) and, per cone, its slot [pack_triu(Hs) | pack_triu(H_dual) | grad] (cone_layout.h).
 //   affine_ds            ds = s                                   coneops_expcone.jl / coneops_powcone.jl affine_ds!
 //   ds_from_dz_offset    out = ds
 //   mul_Hs               y = Hs x with the resident 3 x 3 block (what the matrix holds)      coneops_expcone.jl:103-116
@@ -18,6 +18,8 @@
 #include <stdint.h>
 
 #include "cone3_math.h"
+#include "cone_layout.h"
+#include "cone_reduce.h"
 #include "kernels.h"
 
 namespace hipkkt {
@@ -26,21 +28,6 @@ namespace {
 
 constexpr int kBarBlocks = 64;        // fixed slices of the row sums of the barrier
 constexpr int kBarMax = 8;            // candidates per launch
-
-__device__ __forceinline__ double block_sum3(double v, double *red) {      // 256 threads; every thread gets the total (as step.hip)
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-__device__ __forceinline__ double block_min3(double v, double *red) {
-    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_down(v, o));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return fmin(fmin(red[0], red[1]), fmin(red[2], red[3]));
-}
 
 // higher_correction!, coneops_expcone.jl:319-367: u = H_dual^-1 ds, v = step_z, at the scaling point z
 __device__ __forceinline__ void exp_higher_correction(const double Hd[6], const double z[3], const double ds[3], const double v[3],
@@ -150,7 +137,7 @@ k_step3_mulhs(int n3, const int64_t *__restrict__ row0_t, const int64_t *__restr
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= n3) return;
     const int64_t r = row0_t[c];
-    const double *H = nsout + out0_t[c];      // pack_triu {00, 01, 11, 02, 12, 22}
+    const double *H = nsout + out0_t[c] + kSlot3Hs;      // pack_triu {00, 01, 11, 02, 12, 22}
     const double Hf[3][3] = {{H[0], H[1], H[3]}, {H[1], H[2], H[4]}, {H[3], H[4], H[5]}};
     const double x0 = x[r], x1 = x[r + 1], x2 = x[r + 2];
     for (int i = 0; i < 3; i++) {
@@ -171,14 +158,15 @@ k_step3_shift(int first, int count, const int64_t *__restrict__ row0_t, const in
     const int c = first + k;
     const int64_t r = row0_t[c];
     const double *o = nsout + out0_t[c];
-    const double Hd[6] = {o[6], o[7], o[8], o[9], o[10], o[11]};
+    const double *hd = o + kSlot3Hdual;
+    const double Hd[6] = {hd[0], hd[1], hd[2], hd[3], hd[4], hd[5]};
     const double z[3] = {z_all[r], z_all[r + 1], z_all[r + 2]};
     const double v[3] = {dz_all[r], dz_all[r + 1], dz_all[r + 2]};
     const double ds[3] = {ds_all[r], ds_all[r + 1], ds_all[r + 2]};
     double eta[3];
     if (POW) pow_higher_correction(Hd, z, alpha_t[c], ds, v, eta);
     else exp_higher_correction(Hd, z, ds, v, eta);
-    for (int i = 0; i < 3; i++) out[r + i] = o[12 + i] * sigma_mu - eta[i];
+    for (int i = 0; i < 3; i++) out[r + i] = o[kSlot3Grad + i] * sigma_mu - eta[i];
 }
 
 // ---- step_length ------------------------------------------------------------------------------------------------------------------------
@@ -203,7 +191,7 @@ k_step3_len(int first, int count, const int64_t *__restrict__ row0_t, const doub
         const double as = backtrack<POW, false>(s, ds, a, a0, alpha_min, step, trips);
         v = fmin(az, as);
     }
-    v = block_min3(v, red);
+    v = block_min(v, red);
     if (threadIdx.x == 0) part[blockIdx.x] = v;
 }
 __global__ void __launch_bounds__(256)
@@ -212,7 +200,7 @@ k_step3_len_final(const double *__restrict__ part, int nparts, const double *__r
     __shared__ double red[4];
     double v = alpha_start(sym2, T, alpha_max);
     for (int k = threadIdx.x; k < nparts; k += 256) v = fmin(v, part[k]);
-    v = block_min3(v, red);
+    v = block_min(v, red);
     if (threadIdx.x == 0) { out2[0] = v; out2[1] = v; }
 }
 
@@ -239,7 +227,7 @@ k_bar_rows(const signed char *__restrict__ row_kind, const double *__restrict__ 
     }
     for (int j = 0; j < kBarMax; j++) {
         if (j >= A.n) break;                   // (uniform over the workgroup)
-        const double b = block_sum3(bar[j], red), d = block_sum3(dot[j], red);
+        const double b = block_sum(bar[j], red), d = block_sum(dot[j], red);
         if (threadIdx.x == 0) { part[(2 * j) * kBarBlocks + blockIdx.x] = b; part[(2 * j + 1) * kBarBlocks + blockIdx.x] = d; }
     }
 }
@@ -249,7 +237,7 @@ k_bar_soc(const int64_t *__restrict__ desc, const double *__restrict__ z_all, co
           const double *__restrict__ dz_all, const double *__restrict__ ds_all, BarAlphas A, double *__restrict__ cpart) {
     __shared__ double red[4];
     const int c = blockIdx.x, t = threadIdx.x;
-    const int64_t row0 = desc[5 * c], dim = desc[5 * c + 1];
+    const int64_t row0 = desc[kSocDesc * c + kSocRow0], dim = desc[kSocDesc * c + kSocDim];
     const double *z = z_all + row0, *s = s_all + row0, *dz = dz_all + row0, *ds = ds_all + row0;
     for (int j = 0; j < kBarMax; j++) {
         if (j >= A.n) break;
@@ -259,7 +247,7 @@ k_bar_soc(const int64_t *__restrict__ desc, const double *__restrict__ z_all, co
             const double zz = z[i] + a * dz[i], ss = s[i] + a * ds[i];
             accz += zz * zz; accs += ss * ss;
         }
-        const double z1 = sqrt(block_sum3(accz, red)), s1 = sqrt(block_sum3(accs, red));
+        const double z1 = sqrt(block_sum(accz, red)), s1 = sqrt(block_sum(accs, red));
         const double z0 = z[0] + a * dz[0], s0 = s[0] + a * ds[0];
         const double res_z = (z0 - z1) * (z0 + z1), res_s = (s0 - s1) * (s0 + s1);
         const double v = (res_s > 0.0 && res_z > 0.0) ? -logsafe(res_s * res_z) / 2.0 : __builtin_huge_val();
@@ -292,15 +280,15 @@ k_bar_final(const double *__restrict__ part, const double *__restrict__ socpart,
     for (int j = 0; j < nalpha; j++) {
         double acc = 0.0;
         for (int c = threadIdx.x; c < nsoc; c += 256) acc += socpart[(int64_t)c * kBarMax + j];
-        const double bsoc = block_sum3(acc, red);
+        const double bsoc = block_sum(acc, red);
         acc = 0.0;
         for (int c = threadIdx.x; c < n3; c += 256) acc += c3part[(int64_t)c * kBarMax + j];
-        const double b3 = block_sum3(acc, red);
+        const double b3 = block_sum(acc, red);
         double bgp = 0.0;
         if (ngp > 0) {                         // (uniform; a set without Generalized Power cones adds nothing, not even 0.0)
             acc = 0.0;
             for (int c = threadIdx.x; c < ngp; c += 256) acc += gppart[(int64_t)c * kBarMax + j];
-            bgp = block_sum3(acc, red);
+            bgp = block_sum(acc, red);
         }
         if (threadIdx.x == 0) {
             double b = 0.0, d = 0.0;

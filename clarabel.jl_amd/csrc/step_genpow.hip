@@ -1,7 +1,7 @@
 // The cone algebra of one interior-point step for the Generalized Power cones on the device (coneops_genpowcone.jl), next to step.hip
 // (Zero / Nonnegative / SecondOrder) and step_cone3.hip (Exponential / Power).  Everything works on what hipkkt_update_scaling_ex[_dev]
 // left resident: (s, z), the cone's slot [grad (dim) | d1 (dim1) | d2 | p (dim) | q (dim1) | r (dim2)] written by k_scaling_genpow, the
-// descriptor table (8 int64 per cone, scaling.hip) and the exponents.
+// descriptor table (cone_layout.h kGp*) and the exponents.
 //   affine_ds            ds = s                                                                        :137-147
 //   ds_from_dz_offset    out = ds                                                                      :170-183
 //   combined_ds_shift    grad sigma mu (no third-order correction)                                     :149-168
@@ -18,6 +18,8 @@
 #include <stdint.h>
 
 #include "cone3_math.h"
+#include "cone_layout.h"
+#include "cone_reduce.h"
 #include "kernels.h"
 
 namespace hipkkt {
@@ -27,24 +29,11 @@ namespace {
 constexpr int kGpBarMax = 8;          // candidates per launch (step3_max_candidates())
 constexpr double kEps = 2.220446049250313e-16;
 
-__device__ __forceinline__ double gp_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ double gp_prod(double v) {
-    for (int o = 32; o > 0; o >>= 1) v *= __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ int gp_or(int v) {
-    for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o);
-    return v;
-}
-
 struct GpCone { int64_t row0, dim1, dim2, out0; const double *a; double psi; };
 __device__ __forceinline__ GpCone gp_cone(const int64_t *desc, const double *alpha_all, int c) {
-    const int64_t *d = desc + 8 * (int64_t)c;
-    GpCone K{d[0], d[1], d[2], d[4], alpha_all + d[5], 0.0};
-    K.psi = __longlong_as_double(d[7]);      // 1 / <alpha, alpha> (cone_types.jl GenPowerConeData), the host's bits
+    const int64_t *d = desc + kGpDesc * (int64_t)c;
+    GpCone K{d[kGpRow0], d[kGpDim1], d[kGpDim2], d[kGpOut0], alpha_all + d[kGpAlpha0], 0.0};
+    K.psi = __longlong_as_double(d[kGpPsiBits]);      // 1 / <alpha, alpha> (cone_types.jl GenPowerConeData), the host's bits
     return K;
 }
 
@@ -62,9 +51,9 @@ __device__ __forceinline__ bool gp_feasible(const GpCone &K, const double *q, co
         const double w = q[K.dim1 + i] + alpha * dq[K.dim1 + i];
         n2 += w * w;
     }
-    bad = gp_or(bad);
-    res = gp_sum(res);
-    n2 = gp_sum(n2);
+    bad = wave_or(bad);
+    res = wave_sum(res);
+    n2 = wave_sum(n2);
     if (bad) return false;
     return exp(res) - n2 > 0.0;
 }
@@ -94,9 +83,9 @@ __device__ __forceinline__ double gp_barrier_dual(const GpCone &K, const double 
         const double w = z[K.dim1 + i] + al * dz[K.dim1 + i];
         n2 += w * w;
     }
-    res = gp_sum(res);
-    n2 = gp_sum(n2);
-    lg = gp_sum(lg);
+    res = wave_sum(res);
+    n2 = wave_sum(n2);
+    lg = wave_sum(lg);
     return -logsafe(exp(res) - n2) - lg;
 }
 
@@ -112,8 +101,8 @@ __device__ __forceinline__ double gp_newton(const GpCone &K, const double *s, co
             f0 += 2.0 * a * (logsafe(x * norm_r + (1.0 + a) / a) - logsafe(p));
             f1 += 2.0 * a * norm_r / (norm_r * x + (1.0 + a) / a);
         }
-        f0 = -logsafe(2.0 * x / norm_r + x * x) + gp_sum(f0);
-        const double dfdx = -(2.0 * x + 2.0 / norm_r) / (x * x + 2.0 * x / norm_r) + gp_sum(f1);
+        f0 = -logsafe(2.0 * x / norm_r + x * x) + wave_sum(f0);
+        const double dfdx = -(2.0 * x + 2.0 / norm_r) / (x * x + 2.0 * x / norm_r) + wave_sum(f1);
         const double dx = -f0 / dfdx;
         if (dx < kEps || fabs(dx / x) < kSqrtEps || fabs(dfdx) < kEps) break;      // (uniform: f0, dfdx come from butterflies)
         x += dx;
@@ -129,8 +118,8 @@ __device__ __forceinline__ double gp_barrier_primal(const GpCone &K, const doubl
         const double w = s[K.dim1 + i] + al * ds[K.dim1 + i];
         n2 += w * w;
     }
-    phi = gp_prod(phi);
-    const double norm_r = sqrt(gp_sum(n2));
+    phi = wave_prod(phi);
+    const double norm_r = sqrt(wave_sum(n2));
     const bool far = norm_r > kEps;                  // (uniform)
     const double g1 = far ? gp_newton(K, s, ds, al, norm_r, phi, t) : 0.0;
     // barrier_dual(-g): -g[i] = (1 + a + a g1 |r|) / p[i], -g[dim1 + i] = -(g1 r[i] / |r|)
@@ -147,9 +136,9 @@ __device__ __forceinline__ double gp_barrier_primal(const GpCone &K, const doubl
             const double gr = g1 * w / norm_r;
             m2 += gr * gr;
         }
-    res = gp_sum(res);
-    m2 = gp_sum(m2);
-    lg = gp_sum(lg);
+    res = wave_sum(res);
+    m2 = wave_sum(m2);
+    lg = wave_sum(lg);
     const double bd = -logsafe(exp(res) - m2) - lg;
     return -bd - (double)(K.dim1 + 1);
 }
@@ -161,17 +150,17 @@ struct GpAlphas { double a[kGpBarMax]; int n; };
 // ---- row copies: affine_ds (src = the resident s), ds_from_dz_offset (src = ds) ------------------------------------------------------
 __global__ void __launch_bounds__(64)
 k_gp_copy(const int64_t *__restrict__ desc, const double *__restrict__ src, double *__restrict__ out) {
-    const int64_t *d = desc + 8 * (int64_t)blockIdx.x;
-    const int64_t row0 = d[0], dim = d[1] + d[2];
+    const int64_t *d = desc + kGpDesc * (int64_t)blockIdx.x;
+    const int64_t row0 = d[kGpRow0], dim = d[kGpDim1] + d[kGpDim2];
     for (int64_t i = threadIdx.x; i < dim; i += 64) out[row0 + i] = src[row0 + i];
 }
 
 // ---- combined_ds_shift ------------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(64)
 k_gp_shift(const int64_t *__restrict__ desc, const double *__restrict__ nsout, double sigma_mu, double *__restrict__ out) {
-    const int64_t *d = desc + 8 * (int64_t)blockIdx.x;
-    const int64_t row0 = d[0], dim = d[1] + d[2];
-    const double *g = nsout + d[4];
+    const int64_t *d = desc + kGpDesc * (int64_t)blockIdx.x;
+    const int64_t row0 = d[kGpRow0], dim = d[kGpDim1] + d[kGpDim2];
+    const double *g = nsout + d[kGpOut0];
     for (int64_t i = threadIdx.x; i < dim; i += 64) out[row0 + i] = g[i] * sigma_mu;
 }
 
@@ -180,14 +169,15 @@ __global__ void __launch_bounds__(64)
 k_gp_mulhs(const int64_t *__restrict__ desc, const double *__restrict__ nsout, double mu, const double *__restrict__ x_all,
            const double *__restrict__ addc, double *__restrict__ y_all) {
     const int t = threadIdx.x;
-    const int64_t *d = desc + 8 * (int64_t)blockIdx.x;
-    const int64_t row0 = d[0], dim1 = d[1], dim2 = d[2], dim = dim1 + dim2;
-    const double *g = nsout + d[4], *od1 = g + dim, *od2 = od1 + dim1, *p = od2 + 1, *q = p + dim, *r = q + dim1;
+    const int64_t *d = desc + kGpDesc * (int64_t)blockIdx.x;
+    const int64_t row0 = d[kGpRow0], dim1 = d[kGpDim1], dim2 = d[kGpDim2], dim = dim1 + dim2;
+    // (the slot's pointers stay chained, as in k_scaling_genpow)
+    const double *g = nsout + d[kGpOut0], *od1 = g + dim, *od2 = od1 + dim1, *p = od2 + 1, *q = p + dim, *r = q + dim1;
     const double *x = x_all + row0;
     double cp = 0.0, cq = 0.0, cr = 0.0;
     for (int64_t i = t; i < dim1; i += 64) { cp += p[i] * x[i]; cq += q[i] * x[i]; }
     for (int64_t i = t; i < dim2; i += 64) { cp += p[dim1 + i] * x[dim1 + i]; cr += r[i] * x[dim1 + i]; }
-    cp = gp_sum(cp); cq = gp_sum(cq); cr = gp_sum(cr);
+    cp = wave_sum(cp); cq = wave_sum(cq); cr = wave_sum(cr);
     const double d2 = od2[0];
     for (int64_t i = t; i < dim; i += 64) {
         double v = i < dim1 ? od1[i] * x[i] - cq * q[i] : d2 * x[i] - cr * r[i - dim1];

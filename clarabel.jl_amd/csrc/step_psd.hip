@@ -14,11 +14,13 @@
 // Products are plain FP64 FMA chains, every k-sum in ascending order: deterministic.  The smallest eigenvalue comes from a cyclic
 // two-sided Jacobi iteration in LDS (round-robin sets of disjoint rotations), at most kMaxSweeps sweeps; a non-finite M gives a NaN
 // gamma and therefore alpha_max, as the reference's `gamma < 0` does.  No assert, no trap, every loop has a fixed trip bound.
-// The cone table: 4 int64 per cone, [row0 | n | offset of the n x n factors | offset of lambda]; n <= kMaxN is the enable's condition
+// The cone table: cone_layout.h kPsd* ([row0 | n | offset of the n x n factors | offset of lambda]); n <= kMaxN is the enable's condition
 // and is checked again here (a larger cone is left alone).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "cone_layout.h"
+#include "cone_reduce.h"
 #include "kernels.h"
 
 namespace hipkkt {
@@ -35,31 +37,14 @@ struct Cone { int64_t row0; int n, ld; int64_t foff, loff; bool ok; };
 
 __device__ __forceinline__ Cone cone_of(const int64_t *__restrict__ tab, int c) {
     Cone K;
-    K.row0 = tab[4 * c];
-    const int64_t n = tab[4 * c + 1];
-    K.foff = tab[4 * c + 2];
-    K.loff = tab[4 * c + 3];
+    K.row0 = tab[kPsdTab * c + kPsdRow0];
+    const int64_t n = tab[kPsdTab * c + kPsdN];
+    K.foff = tab[kPsdTab * c + kPsdFactor0];
+    K.loff = tab[kPsdTab * c + kPsdLambda0];
     K.ok = n >= 1 && n <= kMaxN;
     K.n = K.ok ? (int)n : 0;
     K.ld = (K.n % 32 == 0) ? K.n + 1 : K.n;
     return K;
-}
-
-__device__ __forceinline__ double block_sum(double v, double *red) {      // 256 threads; every thread gets the total (as step.hip)
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-// a minimum that keeps a NaN
-__device__ __forceinline__ double nan_min(double a, double b) { return (a < b || a != a) ? a : b; }
-__device__ __forceinline__ double block_nan_min(double v, double *red) {
-    for (int o = 32; o > 0; o >>= 1) v = nan_min(v, __shfl_down(v, o));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return nan_min(nan_min(red[0], red[1]), nan_min(red[2], red[3]));
 }
 
 // F = the cone's n x n column-major factor

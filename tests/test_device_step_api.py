@@ -16,6 +16,7 @@ from clarabel_jl_amd.kktsolver import cone_set_steps_on_device
 from julia_standin import ipm
 from julia_standin.cones import CompositeCone
 from tests import fixtures as fx
+from tests.step_support import STEP_SETTINGS, _FakeStepPlugin
 from tests.test_julia_glue import JL_FILES, c_prototypes, jl_ccalls
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -72,164 +73,12 @@ def test_steps_on_device_only_for_zero_nonnegative_and_second_order_cones():
 
 # ---- orchestration -------------------------------------------------------------------------------------------------------------------
 
-class _HostBuffer:
-    """what the plugin hands out as device memory, here a numpy array"""
-
-    def __init__(self, n):
-        self.a = np.zeros(n)
-
-    def upload(self, host):
-        self.a[:] = host
-
-    def download(self):
-        return self.a.copy()
-
-    def copy_from(self, other):
-        self.a[:] = other.a
-
-    def close(self):
-        pass
-
-
-class _Data:
-    pass
-
-
-class _FakeStepPlugin:
-    """The plugin interface of the device_step loop (clarabel.jl_amd/kktsolver.py) served on the host: the KKT solves by the CPU
-    oracle, the cone algebra by the stand-in's numpy cones and its own kkt_solve -- exactly what the host loop computes, so the two
-    trajectories must coincide bit for bit if the loop hands the right quantities over in the right order."""
-    steps_on_device = True
-
-    def __init__(self, P, A, cones, m, n, settings):
-        from oracle.kkt_oracle import OracleKKTSolver
-
-        self.settings = settings
-        self.inner = OracleKKTSolver(P, A, cones, m, n, settings)
-        self.cones, self.m, self.n = cones, m, n
-        self.data = _Data()
-        self.data.P, self.data.A = P, A
-        self.sys = ipm.KKTSystem(self.inner, m, n)
-        self.lhs, self.rhs = ipm.Variables.zeros(n, m), ipm.Variables.zeros(n, m)
-        self.calls = []
-
-    # the contract methods the default start needs
-    def kktsolver_update(self, cones):
-        return self.inner.kktsolver_update(cones)
-
-    def kktsolver_setrhs(self, rx, rz):
-        self.inner.kktsolver_setrhs(rx, rz)
-
-    def kktsolver_solve(self, lx, lz):
-        return self.inner.kktsolver_solve(lx, lz)
-
-    def set_problem_vectors(self, q, b):
-        self.data.q, self.data.b = q, b
-
-    def set_equilibration(self, d, e):
-        self.d, self.e, self.dinv, self.einv = d, e, 1.0 / d, 1.0 / e
-
-    def device_buffer(self, n):
-        return _HostBuffer(n)
-
-    def _split(self, xzs):
-        n, m = self.n, self.m
-        return xzs.a[:n], xzs.a[n:n + m], xzs.a[n + m:]
-
-    def _res(self, res):
-        n, m = self.n, self.m
-        o = np.cumsum([0, n, m, n, m, n])
-        return [res.a[o[k]:o[k + 1]] for k in range(5)]
-
-    def residuals_update_dev(self, xzs, res, tau, kappa):      # residuals.jl:1-37 as ipm.Solver._residuals_update
-        self.calls.append("residuals")
-        x, z, s = self._split(xzs)
-        rx, rz, rx_inf, rz_inf, Px = self._res(res)
-        d = self.data
-        qx, bz, sz = float(np.dot(d.q, x)), float(np.dot(d.b, z)), float(np.dot(s, z))
-        Px[:] = ipm._symv(d.P, x)
-        xPx = float(np.dot(x, Px))
-        rx_inf[:] = -(d.A.T @ z)
-        rz_inf[:] = s + d.A @ x
-        rx[:] = rx_inf - Px - d.q * tau
-        rz[:] = rz_inf - d.b * tau
-        return qx, bz, sz, xPx, qx + bz + kappa + xPx / tau
-
-    def kktsolver_info_norms(self, xzs, res):
-        self.calls.append("norms")
-        x, z, s = self._split(xzs)
-        rx, rz, rx_inf, rz_inf, Px = self._res(res)
-        ns = ipm._norm_scaled
-        return [ns(self.d, x), ns(self.e, z), ns(self.einv, s), ns(self.dinv, rx), ns(self.einv, rz), ns(self.dinv, rx_inf),
-                ns(self.einv, rz_inf), ns(self.dinv, Px)]
-
-    def kktsolver_update_scaling_dev(self, xzs):
-        self.calls.append("scaling")
-        _, z, s = self._split(xzs)
-        return self.cones.update_scaling(s, z, 0.0)
-
-    def kktsolver_refactor(self):
-        self.calls.append("refactor")
-        return self.sys.kkt_update(self.data, self.cones)
-
-    def _vars(self, xzs, tau, kappa):
-        x, z, s = self._split(xzs)
-        return ipm.Variables(x, s, z, tau, kappa)
-
-    def _alpha(self, v, fraction):      # variables.jl:14-43
-        step = self.lhs
-        a_tau = -v.tau / step.tau if step.tau < 0 else ipm.FLOATMAX
-        a_kap = -v.kappa / step.kappa if step.kappa < 0 else ipm.FLOATMAX
-        alpha = min(a_tau, a_kap, 1.0)
-        az, as_ = self.cones.step_length(step.z, step.s, v.z, v.s, alpha)
-        return min(az, as_) * fraction
-
-    def kktsolver_step_affine(self, xzs, res, tau, kappa, r_tau, const_pending):
-        self.calls.append("affine")
-        assert const_pending
-        v, rhs, lhs = self._vars(xzs, tau, kappa), self.rhs, self.lhs
-        rx, rz = self._res(res)[:2]
-        rhs.x[:] = rx
-        rhs.z[:] = rz
-        self.cones.affine_ds(rhs.s, v.s)
-        rhs.tau, rhs.kappa = r_tau, tau * kappa
-        if not self.sys.kkt_solve(lhs, rhs, self.data, v, self.cones, "affine"):
-            return False, 0.0, 0.0, 0.0
-        return True, self._alpha(v, 1.0), lhs.tau, lhs.kappa
-
-    def kktsolver_step_combined(self, xzs, res, tau, kappa, r_tau, dtau_aff, dkappa_aff, sigma, mu, m_corr):
-        self.calls.append("combined")
-        v, rhs, lhs = self._vars(xzs, tau, kappa), self.rhs, self.lhs
-        assert (dtau_aff, dkappa_aff) == (lhs.tau, lhs.kappa)
-        rx, rz = self._res(res)[:2]
-        sm = sigma * mu
-        rhs.x[:] = (1.0 - sigma) * rx
-        rhs.tau = (1.0 - sigma) * r_tau
-        rhs.kappa = -sm + m_corr * lhs.tau * lhs.kappa + tau * kappa
-        if m_corr != 1.0:
-            lhs.z *= m_corr
-        self.cones.affine_ds(rhs.s, v.s)
-        self.cones.combined_ds_shift(rhs.z, lhs.z, lhs.s, sm)
-        rhs.s += rhs.z
-        rhs.z[:] = (1.0 - sigma) * rz
-        if not self.sys.kkt_solve(lhs, rhs, self.data, v, self.cones, "combined"):
-            return False, 0.0, 0.0, 0.0
-        return True, self._alpha(v, self.settings.max_step_fraction), lhs.tau, lhs.kappa
-
-    def kktsolver_step_apply(self, alpha, xzs):
-        self.calls.append("apply")
-        x, z, s = self._split(xzs)
-        x += alpha * self.lhs.x
-        z += alpha * self.lhs.z
-        s += alpha * self.lhs.s
-
 
 ORCHESTRATION_CASES = {
     "basic_qp": (fx.basic_qp, ipm.SOLVED), "basic_lp": (fx.basic_lp, ipm.SOLVED), "basic_socp": (fx.basic_socp, ipm.SOLVED),
     "lasso_socp": (fx.lasso_socp, ipm.SOLVED), "basic_qp_dualinf": (fx.basic_qp_dualinf, ipm.DUAL_INFEASIBLE),
     "eq_constrained": (fx.eq_constrained, ipm.SOLVED),
 }
-STEP_SETTINGS = dict(device_step=True, device_scaling=True, device_reduced=True, device_residuals=True)
 
 
 @pytest.mark.parametrize("name", list(ORCHESTRATION_CASES))

@@ -15,7 +15,7 @@ from clarabel_jl_amd.kktsolver import cone_set_steps_on_device
 from julia_standin import ipm
 from julia_standin.cones import CompositeCone
 from tests import fixtures as fx
-from tests.test_device_step_nonsym_api import NONSYM_SETTINGS, _FakeNonsymPlugin
+from tests.step_support import NONSYM_SETTINGS, _FakeNonsymPlugin
 from tests.test_julia_glue import JL_FILES, c_prototypes, jl_ccalls
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

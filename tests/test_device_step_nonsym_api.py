@@ -17,13 +17,12 @@ from clarabel_jl_amd.kktsolver import cone_set_steps_on_device
 from julia_standin import ipm
 from julia_standin.cones import CompositeCone
 from tests import fixtures as fx
-from tests.test_device_step_api import STEP_SETTINGS, _FakeStepPlugin
+from tests.step_support import NONSYM_SETTINGS, STEP_SETTINGS, _FakeNonsymPlugin
 from tests.test_julia_glue import JL_FILES, c_prototypes, jl_ccalls
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 NEW_SYMBOLS = ["hipkkt_step_enable_cone3", "hipkkt_cone_barrier", "hipkkt_step_barrier_dev"]
-NONSYM_SETTINGS = dict(STEP_SETTINGS, device_step_nonsymmetric=True)
 
 
 def test_the_setting_is_off_by_default_and_needs_device_step():
@@ -70,23 +69,6 @@ def test_header_binding_and_julia_glue_agree_on_the_new_entry_points():
 
 
 # ---- orchestration -------------------------------------------------------------------------------------------------------------------
-
-class _FakeNonsymPlugin(_FakeStepPlugin):
-    """_FakeStepPlugin plus what the non-symmetric loop calls: the scaling with (mu, strategy) and the barrier of the resident step"""
-
-    def kktsolver_update_scaling_dev_ex(self, xzs, mu, strategy):
-        self.calls.append("scaling_ex:" + strategy)
-        _, z, s = self._split(xzs)
-        return self.cones.update_scaling(s, z, mu, strategy)
-
-    def kktsolver_step_barrier(self, xzs, alphas):
-        self.calls.append("barrier")
-        assert 1 <= len(alphas) <= 8
-        _, z, s = self._split(xzs)
-        dz, ds = self.lhs.z, self.lhs.s
-        bars = [self.cones.compute_barrier(z, s, dz, ds, a) for a in alphas]
-        dots = [float(np.dot(z + a * dz, s + a * ds)) for a in alphas]
-        return bars, dots
 
 
 def _mix20():

@@ -36,8 +36,7 @@ from clarabel_jl_amd import problems
 from clarabel_jl_amd.kktsolver import HipKKTSolver
 from julia_standin.cones import NonnegativeCone, SecondOrderCone, ZeroCone
 from tests import cone3_reference as c3
-from tests.test_gpu_device_step import _Timeout
-from tests.test_gpu_device_step_nonsym import NONSYM, PARITY, SQRT_EPS, SUM_TOL, _is3, _prep, _problem
+from tests.step_support import NONSYM, PARITY, SQRT_EPS, SUM_TOL, _is3, _prep, _problem, _Timeout
 
 pytestmark = pytest.mark.gpu
 

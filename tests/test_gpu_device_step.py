@@ -10,59 +10,19 @@ Gates (the project's own):
   * step lengths and end-to-end quantities: 1e-10 relative.
 The second-order cones of the host object ADOPT the device's (w, lambda, eta) before anything is compared, so both sides work on the
 same scaling (the scaling itself is test_gpu_kkt.py's subject)."""
-import math
-import signal
-
 import numpy as np
 import pytest
-import scipy.sparse as sp
 
 import clarabel_jl_amd  # noqa: F401
 import julia_standin as cl
 from clarabel_jl_amd import problems
-from clarabel_jl_amd.cone_api import nvars
 from clarabel_jl_amd.kktsolver import HipKKTSolver
 from julia_standin import ipm
-from julia_standin.cones import NonnegativeCone, SecondOrderCone, ZeroCone
 from tests import fixtures as fx
+from tests.step_support import (PARITY, STEP_FLAGS, SUM_TOL, _adopt, _allowance, _check_cone_vector, _mixed_problem, _prep,
+                                _soc_affine_ds, _soc_mul_hs, _soc_offset, _soc_shift, _Timeout)
 
 pytestmark = pytest.mark.gpu
-
-SUM_TOL = 1e-13
-PARITY = 1e-10
-
-
-def _mixed_problem(seed, n=24):
-    """Zero, Nonnegative, sparse second-order cones (dim 6, 101) and dense ones (dim 2, 3, 4)"""
-    rng = np.random.default_rng(seed)
-    specs = [cl.ZeroConeT(3), cl.NonnegativeConeT(37), cl.SecondOrderConeT(6), cl.SecondOrderConeT(2), cl.SecondOrderConeT(101),
-             cl.NonnegativeConeT(300), cl.SecondOrderConeT(3), cl.SecondOrderConeT(4), cl.ZeroConeT(1)]
-    m = sum(nvars(c) for c in specs)
-    A = sp.random(m, n, density=0.15, random_state=np.random.RandomState(seed), format="csc") + \
-        sp.vstack([sp.identity(n), sp.csc_matrix((m - n, n))]).tocsc()
-    Pm = sp.random(n, n, density=0.1, random_state=np.random.RandomState(seed + 1))
-    P = (Pm @ Pm.T + sp.identity(n)).tocsc()
-    return P, rng.standard_normal(n), A.tocsc(), rng.standard_normal(m), specs
-
-
-def _prep(prob):
-    P, q, A, b, specs = prob
-    cones = cl.CompositeCone(cl.cones_new_collapsed(specs))
-    Pt = sp.triu(sp.csc_matrix(P), format="csc")
-    Pt.sort_indices()
-    A = sp.csc_matrix(A)
-    A.sort_indices()
-    return Pt, A, cones
-
-
-def _adopt(cones, w, lam, eta):
-    k = 0
-    for c, r in zip(cones.cones, cones.rng_cones):
-        if isinstance(c, SecondOrderCone):
-            c.adopt_symmetric_scaling(w[r], lam[r], eta[k])
-            k += 1
-        elif isinstance(c, NonnegativeCone):
-            assert np.array_equal(c.w, w[r]) and np.array_equal(c.lam, lam[r])      # bit-exact already (test_gpu_kkt.py)
 
 
 def _scaled_solver(seed, late):
@@ -77,88 +37,6 @@ def _scaled_solver(seed, late):
     _adopt(cones, w, lam, eta)
     return hk, cones, s, z, rng
 
-
-# ---- the reference's second-order-cone expressions with a pluggable `dot`, for the allowance of a result that is a function of sums ----
-
-class _Sums:
-    """dot products in evaluation order; `bump` moves the k-th one by its allowance SUM_TOL * sum|terms|"""
-
-    def __init__(self, bump=None):
-        self.k, self.bump = 0, bump
-
-    def dot(self, a, b):
-        v = float(np.dot(a, b))
-        if self.k == self.bump:
-            v += SUM_TOL * float(np.dot(np.abs(a), np.abs(b)))
-        self.k += 1
-        return v
-
-
-def _resid(S, z):
-    z1 = math.sqrt(S.dot(z[1:], z[1:]))
-    return (z[0] - z1) * (z[0] + z1)
-
-
-def _soc_affine_ds(S, K):
-    out = np.empty(K.dim)
-    out[0] = S.dot(K.lam, K.lam)
-    out[1:] = K.lam[0] * K.lam[1:] + K.lam[0] * K.lam[1:]
-    return out
-
-
-def _soc_shift(S, K, dz, ds, sm):
-    w, eta = K.w, K.eta
-    zz, zs = S.dot(w[1:], dz[1:]), S.dot(w[1:], ds[1:])
-    zW, sW = np.empty(K.dim), np.empty(K.dim)
-    zW[0] = eta * (w[0] * dz[0] + zz)
-    zW[1:] = eta * (dz[1:] + (dz[0] + zz / (1.0 + w[0])) * w[1:])
-    sW[0] = (1.0 / eta) * (w[0] * ds[0] - zs)
-    sW[1:] = (1.0 / eta) * (ds[1:] + (-ds[0] + zs / (1.0 + w[0])) * w[1:])
-    out = np.empty(K.dim)
-    out[0] = S.dot(sW, zW) - sm
-    out[1:] = sW[0] * zW[1:] + zW[0] * sW[1:]
-    return out
-
-
-def _soc_offset(S, K, z, ds):
-    resz = _resid(S, z)
-    l1, w1 = S.dot(K.lam[1:], ds[1:]), S.dot(K.w[1:], ds[1:])
-    out = -z.copy()
-    out[0] = z[0]
-    out *= (K.lam[0] * ds[0] - l1) / resz
-    out[0] += K.eta * w1
-    out[1:] += K.eta * (ds[1:] + w1 / (1.0 + K.w[0]) * K.w[1:])
-    return out * (1.0 / K.lam[0])
-
-
-def _soc_mul_hs(S, K, x):
-    c = 2.0 * S.dot(K.w, x)
-    y = x.copy()
-    y[0] = -x[0]
-    return (y + c * K.w) * (K.eta * K.eta)
-
-
-def _allowance(fn, nsums, *args):
-    """first-order propagation of every sum's allowance through fn, plus SUM_TOL of the element itself"""
-    ref = fn(_Sums(), *args)
-    tol = SUM_TOL * np.abs(ref) + 1e-300
-    for k in range(nsums):
-        tol = tol + np.abs(fn(_Sums(k), *args) - ref)
-    return ref, tol
-
-
-def _check_cone_vector(cones, got, ref, soc_allowance, what):
-    """Zero / Nonnegative rows bit-identical to the stand-in's `ref`; second-order rows within soc_allowance(cone, range)"""
-    for c, r in zip(cones.cones, cones.rng_cones):
-        if isinstance(c, (ZeroCone, NonnegativeCone)):
-            assert np.array_equal(got[r], ref[r]), (what, type(c).__name__)
-        else:
-            twin, tol = soc_allowance(c, r)
-            assert np.all(np.abs(twin - ref[r]) <= tol), (what, "the test's twin of the reference expressions drifted")
-            err = np.abs(got[r] - ref[r])
-            print(f"[device-step {what}] SOC({c.dim}): max |got - ref| / allowance = {float(np.max(err / tol)):.3f}, "
-                  f"relative to max |ref| = {float(np.max(err) / max(np.max(np.abs(ref[r])), 1e-300)):.2e}")
-            assert np.all(err <= tol), (what, c.dim, float(np.max(err / tol)))
 
 
 CASES = [(seed, late) for late in (False, True) for seed in (3, 4, 5)]
@@ -217,26 +95,6 @@ def test_step_length_matches_the_host_cones(seed, late):
             assert az == amax and as_ == amax, name
         if name == "hits the boundary":
             assert 0.0 < min(az, as_) < 1.0
-
-
-class _Timeout:
-    """a time limit of its own for one case (SIGALRM: raises in the interpreter)"""
-
-    def __init__(self, seconds):
-        self.seconds = seconds
-
-    def __enter__(self):
-        def fire(*_):
-            raise TimeoutError(f"case exceeded {self.seconds} s")
-        self.old = signal.signal(signal.SIGALRM, fire)
-        signal.alarm(self.seconds)
-
-    def __exit__(self, *exc):
-        signal.alarm(0)
-        signal.signal(signal.SIGALRM, self.old)
-
-
-STEP_FLAGS = dict(device_scaling=True, device_reduced=True, device_residuals=True)
 
 
 @pytest.mark.parametrize("seed,late", [(3, False), (4, False), (5, True)])

@@ -22,26 +22,21 @@ import math
 
 import numpy as np
 import pytest
-import scipy.sparse as sp
 
 import clarabel_jl_amd  # noqa: F401
 import julia_standin as cl
 from clarabel_jl_amd import hipkkt, problems
-from clarabel_jl_amd.cone_api import nvars
 from clarabel_jl_amd.kktsolver import HipKKTSolver
 from julia_standin import cones_nonsym as cn
 from julia_standin import ipm
 from julia_standin.cones import SecondOrderCone
 from tests import fixtures as fx
-from tests.test_gpu_device_step import STEP_FLAGS, _Timeout
+from tests.step_support import (NONSYM, PARITY, SQRT_EPS, STEP_FLAGS, _check_barrier, _is3, _prep, _problem, _symmetric_twin_handle, _Timeout,
+                                _twin_step_length)
 
 pytestmark = pytest.mark.gpu
 
-PARITY = 1e-10
-SUM_TOL = 1e-13
 MARGIN = 1e-10
-SQRT_EPS = math.sqrt(float(np.finfo(np.float64).eps))
-NONSYM = dict(device_step=True, device_step_nonsymmetric=True, **STEP_FLAGS)
 
 
 def _interleaved_many():
@@ -64,30 +59,6 @@ CONE_SETS = {
 }
 
 
-def _problem(specs, seed):
-    rng = np.random.default_rng(seed)
-    m = sum(nvars(c) for c in specs)
-    n = min(6, m)
-    A = sp.random(m, n, density=min(1.0, 12.0 / m + 0.2), random_state=np.random.RandomState(seed), format="csc") + \
-        sp.vstack([sp.identity(n), sp.csc_matrix((m - n, n))]).tocsc()
-    P = sp.identity(n, format="csc") * 1.5
-    return P, rng.standard_normal(n), A.tocsc(), rng.standard_normal(m), specs
-
-
-def _prep(prob):
-    P, q, A, b, specs = prob
-    cones = cl.CompositeCone(cl.cones_new_collapsed(specs))
-    Pt = sp.triu(sp.csc_matrix(P), format="csc")
-    Pt.sort_indices()
-    A = sp.csc_matrix(A)
-    A.sort_indices()
-    return Pt, A, cones
-
-
-def _is3(c):
-    return isinstance(c, cn._Cone3)
-
-
 def _scaled(setname, strategy, seed):
     """an enabled handle at a central fixture point, the host cones holding the DEVICE's scaling"""
     Pt, A, cones = _prep(_problem(CONE_SETS[setname](), seed))
@@ -108,26 +79,6 @@ def _symmetric_twin(cones, s, z, seed):
     if twin is not None:
         assert twin.h.update_scaling(s[rows], z[rows])[0]
     return twin, rows
-
-
-def _twin_step_length(twin, rows, dz, ds, alpha_max):
-    """min(alpha_z, alpha_s) of the symmetric cones from the device's own kernels (alpha_max without such cones)"""
-    return alpha_max if twin is None else min(twin.cone_step_length(dz[rows], ds[rows], alpha_max))
-
-
-def _symmetric_twin_handle(cones, seed):
-    specs, rows = [], []
-    for c, r in zip(cones.cones, cones.rng_cones):
-        if getattr(c, "is_symmetric", True):
-            specs.append({0: cl.ZeroConeT, 1: cl.NonnegativeConeT, 2: cl.SecondOrderConeT}[c.kind_code](c.numel))
-            rows.extend(range(r.start, r.stop))
-    if not specs:
-        return None, None
-    Pt, A, tc = _prep(_problem(specs, seed + 90))
-    m, n = A.shape
-    twin = HipKKTSolver(Pt, A, tc, m, n, cl.Settings())
-    assert twin.steps_on_device and not twin.steps_nonsymmetric
-    return twin, np.array(rows)
 
 
 # ---- the host's backtracking, walked again for its margins --------------------------------------------------------------------------
@@ -210,23 +161,6 @@ def _check_step_length(got, cones, dz, ds, z, s, alpha_max, st, what, sym_alpha)
               f"{near}, a second-order cone binds {soc_bound}")
         assert near > 0, (what, got, ref)
     return near, n3, soc_bound
-
-
-def _barrier_reference(cones, z, s, dz, ds, a):
-    terms = [c.compute_barrier(z[r], s[r], dz[r], ds[r], a) for c, r in zip(cones.cones, cones.rng_cones)]
-    zz, ss = z + a * dz, s + a * ds
-    return float(sum(terms)), float(sum(abs(t) for t in terms)), float(np.dot(zz, ss)), float(np.dot(np.abs(zz), np.abs(ss)))
-
-
-def _check_barrier(bars, dots, cones, z, s, dz, ds, alphas, what):
-    worst_b = worst_d = 0.0
-    for a, b, d in zip(alphas, bars, dots):
-        rb, tb, rd, td = _barrier_reference(cones, z, s, dz, ds, a)
-        eb, ed = abs(b - rb) / max(1.0, tb), abs(d - rd) / max(td, 1e-300)
-        worst_b, worst_d = max(worst_b, eb), max(worst_d, ed)
-        assert eb <= PARITY, (what, a, b, rb)
-        assert ed <= SUM_TOL, (what, a, d, rd)
-    print(f"[nonsym barrier {what}] max |barrier - ref| / max(1, sum |terms|) = {worst_b:.2e}, max |dot - ref| / sum |terms| = {worst_d:.2e}")
 
 
 # ---- granular ----------------------------------------------------------------------------------------------------------------------------

@@ -25,8 +25,7 @@ from julia_standin.cones import SecondOrderCone
 from tests import cone3_reference as c3
 from tests import fixtures as fx
 from tests import genpow_reference as gp
-from tests.test_gpu_device_step import STEP_FLAGS, _Timeout
-from tests.test_gpu_device_step_nonsym import PARITY, SUM_TOL, _check_barrier, _symmetric_twin_handle, _twin_step_length
+from tests.step_support import PARITY, STEP_FLAGS, SUM_TOL, _check_barrier, _symmetric_twin_handle, _Timeout, _twin_step_length
 
 pytestmark = pytest.mark.gpu
 

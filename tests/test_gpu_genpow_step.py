@@ -23,8 +23,7 @@ from julia_standin import cones_nonsym as cn
 from tests import cone3_reference as c3
 from tests import fixtures as fx
 from tests import genpow_reference as gp
-from tests.test_gpu_device_step import STEP_FLAGS, _Timeout
-from tests.test_gpu_device_step_nonsym import SUM_TOL, _check_barrier, _prep, _problem
+from tests.step_support import STEP_FLAGS, SUM_TOL, _check_barrier, _prep, _problem, _Timeout
 
 pytestmark = pytest.mark.gpu
 
@@ -398,5 +397,54 @@ def test_refusals():
     kinds, alpha = cones.kkt_cone_kinds_ex()
     hk.h.set_cone_types_ex(kinds, alpha)
     assert hk.h.update_scaling_ex(s, z, mu, 1)[0]
+    with pytest.raises(ValueError):
+        hk.cone_affine_ds()
+
+
+def test_switching_one_mode_off():
+    """The three enables move one step state: what switching one of them off does to a handle another one serves."""
+    plain = dict(device_step=True, device_step_nonsymmetric=True, **STEP_FLAGS)
+    # Generalized Power: hipkkt_step_enable_cone3(0) takes the enable away as well
+    Pt, A, cones = _prep(fx.basic_genpow())
+    m, n = A.shape
+    assert m <= 8
+    hk = HipKKTSolver(Pt, A, cones, m, n, cl.Settings(**plain))
+    s, z, mu = fx.scale_cones_nonsymmetric(cones, np.random.default_rng(2), "dual")
+    hk.h.step_enable_genpow(True, 0.8, 1e-4)
+    assert hk.h.update_scaling_ex(s, z, mu, 1)[0]
+    assert np.array_equal(hk.cone_affine_ds(), s)
+    hk.h.step_enable_cone3(False, 0.8, 1e-4)
+    with pytest.raises(ValueError):
+        hk.cone_affine_ds()
+    # Exponential: hipkkt_step_enable_psd(0) leaves it alone, hipkkt_step_enable_genpow(0) switches it off
+    Pt, A, cones = _prep(fx.basic_exp())
+    m, n = A.shape
+    assert m <= 8
+    hk = HipKKTSolver(Pt, A, cones, m, n, cl.Settings(**plain))
+    s, z, mu = fx.scale_cones_nonsymmetric(cones, np.random.default_rng(3), "dual")
+    hk.h.step_enable_cone3(True, 0.8, 1e-4)
+    assert hk.h.update_scaling_ex(s, z, mu, 1)[0]
+    before = hk.cone_affine_ds()
+    hk.h.step_enable_psd(False)
+    assert np.array_equal(hk.cone_affine_ds(), before)
+    hk.h.step_enable_genpow(False, 0.8, 1e-4)
+    with pytest.raises(ValueError):
+        hk.cone_affine_ds()
+    # PSD: the other two leave it alone, hipkkt_step_enable_psd(0) switches it off
+    Pt, A, _ = _prep(_problem([cl.PSDTriangleConeT(3), cl.NonnegativeConeT(2)], 4))
+    cones = cl.CompositeCone([cl.PSDTriangleConeT(3), cl.NonnegativeConeT(2)])
+    m, n = A.shape
+    assert m <= 8
+    hk = HipKKTSolver(Pt, A, cones, m, n, cl.Settings())
+    s, z = fx.scale_cones(cones, np.random.default_rng(4))
+    hk.h.step_enable_psd(True)
+    hk.h.psd_set_factors(*hk._psd_factors())
+    assert hk.h.update_scaling(s, z, cones.cones[0].R.ravel(order="F"))[0]
+    before = hk.cone_affine_ds()
+    hk.h.step_enable_cone3(False, 0.8, 1e-4)
+    assert np.array_equal(hk.cone_affine_ds(), before)
+    hk.h.step_enable_genpow(False, 0.8, 1e-4)
+    assert np.array_equal(hk.cone_affine_ds(), before)
+    hk.h.step_enable_psd(False)
     with pytest.raises(ValueError):
         hk.cone_affine_ds()

@@ -23,7 +23,7 @@ from julia_standin import ipm
 from julia_standin.cones import NonnegativeCone, PSDTriangleCone, SecondOrderCone, ZeroCone
 from tests import fixtures as fx
 from tests import psd_step_reference as pr
-from tests.test_gpu_device_step import PARITY, STEP_FLAGS, _allowance, _soc_mul_hs, _Timeout
+from tests.step_support import PARITY, STEP_FLAGS, _allowance, _soc_mul_hs, _Timeout
 
 pytestmark = pytest.mark.gpu
 

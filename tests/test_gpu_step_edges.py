@@ -22,8 +22,8 @@ from clarabel_jl_amd.kktsolver import HipKKTSolver
 from julia_standin import ipm
 from julia_standin.cones import NonnegativeCone, SecondOrderCone, ZeroCone
 from tests import step_reference as sr
-from tests.test_gpu_device_step import (PARITY, STEP_FLAGS, SUM_TOL, _adopt, _allowance, _check_cone_vector, _mixed_problem, _prep,
-                                        _soc_affine_ds, _soc_mul_hs, _soc_offset, _soc_shift)
+from tests.step_support import (PARITY, STEP_FLAGS, SUM_TOL, _adopt, _allowance, _check_cone_vector, _mixed_problem, _prep, _soc_affine_ds,
+                                _soc_mul_hs, _soc_offset, _soc_shift)
 
 pytestmark = pytest.mark.gpu
 

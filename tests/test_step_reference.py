@@ -33,7 +33,7 @@ import clarabel_jl_amd  # noqa: F401
 import julia_standin as cl
 from julia_standin.cones import SecondOrderCone, _step_length_soc_component
 from tests import step_reference as sr
-from tests.test_gpu_device_step import _mixed_problem
+from tests.step_support import _mixed_problem
 
 FIXTURES = [(False, "scale_cones"), (True, "scale_cones_late")]
 
