@@ -123,7 +123,7 @@ int32_t hipkkt_create_from_parts(int32_t device_id, int64_t n, int64_t m, const 
             } catch (const DeviceError &e) {
                 g_create_error = e.msg; delete S; return HIPKKT_ERR_DEVICE;
             }
-            S->t_init_runtime = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            S->stats.t_init_runtime = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
             err = assemble_kkt_device((void *)S->stream, n, m, Pp.data(), Pi.data(), Pnzval, Ap.data(), Ai.data(), Anzval, ncones, cone_numel,
                                       cone_hs_dense, cone_sparse_kind, dim1.data(), S->img);
         }
@@ -192,7 +192,7 @@ int32_t hipkkt_get_kkt(hipkkt_handle h, int64_t *colptr, int64_t *rowval, double
 
 int32_t hipkkt_get_perm(hipkkt_handle h, int64_t *perm) {
     if (!h || !perm) return HIPKKT_ERR_ARGUMENT;
-    const hipkkt_solver *T = (h->using_fallback && h->fallback) ? h->fallback : h;   // the order of the factorisation in use
+    const hipkkt_solver *T = (h->twin.using_fallback && h->twin.fallback) ? h->twin.fallback : h;   // the order of the factorisation in use
     for (int k = 0; k < h->N; k++) perm[k] = T->plan.perm[k] + h->opts.index_base;
     return HIPKKT_OK;
 }
@@ -316,25 +316,25 @@ int32_t hipkkt_set_qb(hipkkt_handle h, const double *q, const double *b) {
     HK_ENTER(h)
     const int64_t n = S->img.n, m = S->img.m;
     if (!S->l1 || (n && !q) || (m && !b)) { S->err = "set_qb: bad arguments / not an L1 handle"; return HIPKKT_ERR_ARGUMENT; }
-    if (!S->d_qb) {
-        S->d_qb = S->dalloc<double>(n + m);
-        S->d_res_in = S->dalloc<double>(n + 2 * m);                  // x | z | s
-        S->d_res_out = S->dalloc<double>(3 * n + 2 * m + 8);         // rx | rz | rx_inf | rz_inf | Px | 5 scalars
-        S->d_res_part = S->dalloc<double>(4 * (size_t)residual_blocks((int)n, (int)m) + 4);
+    if (!S->res.d_qb) {
+        S->res.d_qb = S->dalloc<double>(n + m);
+        S->res.d_in = S->dalloc<double>(n + 2 * m);                  // x | z | s
+        S->res.d_out = S->dalloc<double>(3 * n + 2 * m + 8);         // rx | rz | rx_inf | rz_inf | Px | 5 scalars
+        S->res.d_part = S->dalloc<double>(4 * (size_t)residual_blocks((int)n, (int)m) + 4);
     }
-    if (n) HK_CHECK(hipMemcpyAsync(S->d_qb, q, n * sizeof(double), hipMemcpyHostToDevice, S->stream));
-    if (m) HK_CHECK(hipMemcpyAsync(S->d_qb + n, b, m * sizeof(double), hipMemcpyHostToDevice, S->stream));
+    if (n) HK_CHECK(hipMemcpyAsync(S->res.d_qb, q, n * sizeof(double), hipMemcpyHostToDevice, S->stream));
+    if (m) HK_CHECK(hipMemcpyAsync(S->res.d_qb + n, b, m * sizeof(double), hipMemcpyHostToDevice, S->stream));
     HK_CHECK(hipStreamSynchronize(S->stream));
-    S->red_have_const = false;   // the resident constant-rhs solution (x2, z2) solved the OLD [-q; b]: never combine it with the new terms
+    S->red.have_const = false;   // the resident constant-rhs solution (x2, z2) solved the OLD [-q; b]: never combine it with the new terms
     return HIPKKT_OK;
     HK_LEAVE
 }
 
 static int32_t residuals_impl(hipkkt_solver *S, const double *xzs_dev, double tau, double kappa, double *out_dev, double *scal5) {
     const int64_t n = S->img.n, m = S->img.m;
-    launch_residuals(S->stream, S->dp, xzs_dev, xzs_dev + n, xzs_dev + n + m, S->d_qb, S->d_qb + n, tau, kappa, out_dev, S->d_res_part,
-                     S->d_res_out + 3 * n + 2 * m, (int)n, (int)m);
-    copy_sync(S->stream, scal5, S->d_res_out + 3 * n + 2 * m, 5 * sizeof(double), hipMemcpyDeviceToHost);
+    launch_residuals(S->stream, S->dp, xzs_dev, xzs_dev + n, xzs_dev + n + m, S->res.d_qb, S->res.d_qb + n, tau, kappa, out_dev, S->res.d_part,
+                     S->res.d_out + 3 * n + 2 * m, (int)n, (int)m);
+    copy_sync(S->stream, scal5, S->res.d_out + 3 * n + 2 * m, 5 * sizeof(double), hipMemcpyDeviceToHost);
     return HIPKKT_OK;
 }
 
@@ -342,12 +342,12 @@ int32_t hipkkt_residuals(hipkkt_handle h, const double *x, const double *z, cons
                          double *rz, double *rx_inf, double *rz_inf, double *Px, double *scal5) {
     HK_ENTER(h)
     const int64_t n = S->img.n, m = S->img.m;
-    if (!S->l1 || !S->d_qb || !scal5 || (n && !x) || (m && (!z || !s))) { S->err = "residuals: call hipkkt_set_qb first / bad arguments"; return HIPKKT_ERR_ARGUMENT; }
-    if (n) HK_CHECK(hipMemcpyAsync(S->d_res_in, x, n * sizeof(double), hipMemcpyHostToDevice, S->stream));
-    if (m) HK_CHECK(hipMemcpyAsync(S->d_res_in + n, z, m * sizeof(double), hipMemcpyHostToDevice, S->stream));
-    if (m) HK_CHECK(hipMemcpyAsync(S->d_res_in + n + m, s, m * sizeof(double), hipMemcpyHostToDevice, S->stream));
-    const int32_t rc = residuals_impl(S, S->d_res_in, tau, kappa, S->d_res_out, scal5);
-    double *o = S->d_res_out;
+    if (!S->l1 || !S->res.d_qb || !scal5 || (n && !x) || (m && (!z || !s))) { S->err = "residuals: call hipkkt_set_qb first / bad arguments"; return HIPKKT_ERR_ARGUMENT; }
+    if (n) HK_CHECK(hipMemcpyAsync(S->res.d_in, x, n * sizeof(double), hipMemcpyHostToDevice, S->stream));
+    if (m) HK_CHECK(hipMemcpyAsync(S->res.d_in + n, z, m * sizeof(double), hipMemcpyHostToDevice, S->stream));
+    if (m) HK_CHECK(hipMemcpyAsync(S->res.d_in + n + m, s, m * sizeof(double), hipMemcpyHostToDevice, S->stream));
+    const int32_t rc = residuals_impl(S, S->res.d_in, tau, kappa, S->res.d_out, scal5);
+    double *o = S->res.d_out;
     struct { double *dst; const double *src; int64_t len; } cp[5] = {{rx, o, n}, {rz, o + n, m}, {rx_inf, o + n + m, n}, {rz_inf, o + 2 * n + m, m}, {Px, o + 2 * n + 2 * m, n}};
     for (auto &c : cp)
         if (c.dst && c.len) HK_CHECK(hipMemcpyAsync(c.dst, c.src, c.len * sizeof(double), hipMemcpyDeviceToHost, S->stream));
@@ -358,7 +358,7 @@ int32_t hipkkt_residuals(hipkkt_handle h, const double *x, const double *z, cons
 
 int32_t hipkkt_residuals_dev(hipkkt_handle h, const double *xzs_dev, double tau, double kappa, double *out_dev, double *scal5) {
     HK_ENTER(h)
-    if (!S->l1 || !S->d_qb || !xzs_dev || !out_dev || !scal5) { S->err = "residuals_dev: call hipkkt_set_qb first / bad arguments"; return HIPKKT_ERR_ARGUMENT; }
+    if (!S->l1 || !S->res.d_qb || !xzs_dev || !out_dev || !scal5) { S->err = "residuals_dev: call hipkkt_set_qb first / bad arguments"; return HIPKKT_ERR_ARGUMENT; }
     return residuals_impl(S, xzs_dev, tau, kappa, out_dev, scal5);
     HK_LEAVE
 }
@@ -388,13 +388,13 @@ int32_t hipkkt_set_hs_psd(hipkkt_handle h, int64_t npsd, const int64_t *hs_off, 
 int32_t hipkkt_set_soc_batch(hipkkt_handle h, int64_t nsoc, const double *eta2, const double *u_all, const double *v_all,
                              int64_t total) {
     HK_ENTER(h)
-    if (!S->l1 || nsoc != S->nsoc || total != S->soc_total) { S->err = "set_soc_batch: size mismatch"; return HIPKKT_ERR_ARGUMENT; }
+    if (!S->l1 || nsoc != S->soc.n || total != S->soc.total) { S->err = "set_soc_batch: size mismatch"; return HIPKKT_ERR_ARGUMENT; }
     if (nsoc == 0) return HIPKKT_OK;
-    HK_CHECK(hipMemcpyAsync(S->d_soc_u, u_all, total * sizeof(double), hipMemcpyHostToDevice, S->stream));
-    HK_CHECK(hipMemcpyAsync(S->d_soc_v, v_all, total * sizeof(double), hipMemcpyHostToDevice, S->stream));
-    HK_CHECK(hipMemcpyAsync(S->d_soc_eta2, eta2, nsoc * sizeof(double), hipMemcpyHostToDevice, S->stream));
-    launch_soc_batch(S->stream, S->dp.kval, S->d_soc_uidx, S->d_soc_vidx, S->d_soc_cone, S->d_soc_u, S->d_soc_v,
-                     S->d_soc_eta2, total, S->d_soc_didx, (int)nsoc);
+    HK_CHECK(hipMemcpyAsync(S->soc.d_u, u_all, total * sizeof(double), hipMemcpyHostToDevice, S->stream));
+    HK_CHECK(hipMemcpyAsync(S->soc.d_v, v_all, total * sizeof(double), hipMemcpyHostToDevice, S->stream));
+    HK_CHECK(hipMemcpyAsync(S->soc.d_eta2, eta2, nsoc * sizeof(double), hipMemcpyHostToDevice, S->stream));
+    launch_soc_batch(S->stream, S->dp.kval, S->soc.d_uidx, S->soc.d_vidx, S->soc.d_cone, S->soc.d_u, S->soc.d_v,
+                     S->soc.d_eta2, total, S->soc.d_didx, (int)nsoc);
     HK_CHECK(hipStreamSynchronize(S->stream));
     return HIPKKT_OK;
     HK_LEAVE
@@ -403,16 +403,16 @@ int32_t hipkkt_set_soc_batch(hipkkt_handle h, int64_t nsoc, const double *eta2, 
 int32_t hipkkt_set_soc(hipkkt_handle h, int64_t sparse_idx, double eta2, const double *u, const double *v, int64_t dim) {
     HK_ENTER(h)
     if (!S->l1 || sparse_idx < 0 || sparse_idx >= (int64_t)S->img.smaps.size()) return HIPKKT_ERR_ARGUMENT;
-    const int o = S->soc_of_sparse[sparse_idx];
-    if (o < 0 || S->soc_off[o + 1] - S->soc_off[o] != dim) { S->err = "set_soc: not a SOC map / wrong dim"; return HIPKKT_ERR_ARGUMENT; }
-    const int64_t off = S->soc_off[o];
-    HK_CHECK(hipMemcpyAsync(S->d_soc_u + off, u, dim * sizeof(double), hipMemcpyHostToDevice, S->stream));
-    HK_CHECK(hipMemcpyAsync(S->d_soc_v + off, v, dim * sizeof(double), hipMemcpyHostToDevice, S->stream));
-    launch_scatter_values(S->stream, S->dp.kval, S->d_soc_uidx + off, S->d_soc_u + off, dim, -eta2);
-    launch_scatter_values(S->stream, S->dp.kval, S->d_soc_vidx + off, S->d_soc_v + off, dim, -eta2);
+    const int o = S->soc.of_sparse[sparse_idx];
+    if (o < 0 || S->soc.off[o + 1] - S->soc.off[o] != dim) { S->err = "set_soc: not a SOC map / wrong dim"; return HIPKKT_ERR_ARGUMENT; }
+    const int64_t off = S->soc.off[o];
+    HK_CHECK(hipMemcpyAsync(S->soc.d_u + off, u, dim * sizeof(double), hipMemcpyHostToDevice, S->stream));
+    HK_CHECK(hipMemcpyAsync(S->soc.d_v + off, v, dim * sizeof(double), hipMemcpyHostToDevice, S->stream));
+    launch_scatter_values(S->stream, S->dp.kval, S->soc.d_uidx + off, S->soc.d_u + off, dim, -eta2);
+    launch_scatter_values(S->stream, S->dp.kval, S->soc.d_vidx + off, S->soc.d_v + off, dim, -eta2);
     const double dv[2] = {-eta2, eta2};
     HK_CHECK(hipMemcpyAsync(S->d_stage, dv, 2 * sizeof(double), hipMemcpyHostToDevice, S->stream));
-    launch_scatter_values(S->stream, S->dp.kval, S->d_soc_didx + 2 * o, S->d_stage, 2, 1.0);
+    launch_scatter_values(S->stream, S->dp.kval, S->soc.d_didx + 2 * o, S->d_stage, 2, 1.0);
     HK_CHECK(hipStreamSynchronize(S->stream));
     return HIPKKT_OK;
     HK_LEAVE
@@ -469,8 +469,8 @@ int32_t hipkkt_update_A(hipkkt_handle h, const double *Anzval, int64_t nnzA) {
 
 int32_t hipkkt_get_timing(hipkkt_handle h, double *o) {
     if (!h || !o) return HIPKKT_ERR_ARGUMENT;
-    o[0] = h->t_last_factor; o[1] = h->t_last_solve; o[2] = h->t_acc_factor; o[3] = h->t_acc_solve;
-    o[4] = (double)h->n_factor; o[5] = (double)h->n_solvecalls; o[6] = (double)h->n_ldlsolves; o[7] = h->t_last_update;
+    o[0] = h->stats.t_last_factor; o[1] = h->stats.t_last_solve; o[2] = h->stats.t_acc_factor; o[3] = h->stats.t_acc_solve;
+    o[4] = (double)h->stats.n_factor; o[5] = (double)h->stats.n_solvecalls; o[6] = (double)h->stats.n_ldlsolves; o[7] = h->stats.t_last_update;
     return HIPKKT_OK;
 }
 
@@ -488,21 +488,21 @@ int32_t hipkkt_box_probe(int32_t device_id, double *out, int64_t cap) {
 
 int32_t hipkkt_get_profile(hipkkt_handle h, double *out, int64_t cap) {
     if (!h || !out || cap < 0) return HIPKKT_ERR_ARGUMENT;
-    const double o[12] = {h->t_last_update, h->prof_dense4_ms, h->prof_dense4_flops, (double)h->prof_dense4_launches, h->prof_fb_ms,
-                          (double)h->prof_fb_launches, (double)h->prof_fb_panels, h->prof_fb_flops, h->prof_extra_tiles, h->prof_extra_flops,
-                          (double)h->last_npolish, (double)h->n_accurate_factorisations};
+    const double o[12] = {h->stats.t_last_update, h->stats.prof_dense4_ms, h->stats.prof_dense4_flops, (double)h->stats.prof_dense4_launches, h->stats.prof_fb_ms,
+                          (double)h->stats.prof_fb_launches, (double)h->stats.prof_fb_panels, h->stats.prof_fb_flops, h->stats.prof_extra_tiles, h->stats.prof_extra_flops,
+                          (double)h->last_npolish, (double)h->stats.n_accurate_factorisations};
     for (int64_t i = 0; i < cap && i < 12; i++) out[i] = o[i];   // never more than the caller's buffer holds
     return HIPKKT_OK;
 }
 
 int32_t hipkkt_get_profile_launches(hipkkt_handle h, double *ms, double *flops, double *tiles, int64_t cap, int64_t *count) {
     if (!h) return HIPKKT_ERR_ARGUMENT;
-    const int64_t n = (int64_t)h->prof_launch_ms.size();
+    const int64_t n = (int64_t)h->stats.prof_launch_ms.size();
     if (count) *count = n;
     for (int64_t i = 0; i < n && i < cap; i++) {
-        if (ms) ms[i] = h->prof_launch_ms[i];
-        if (flops) flops[i] = h->prof_launch_flops[i];
-        if (tiles) tiles[i] = h->prof_launch_tiles[i];
+        if (ms) ms[i] = h->stats.prof_launch_ms[i];
+        if (flops) flops[i] = h->stats.prof_launch_flops[i];
+        if (tiles) tiles[i] = h->stats.prof_launch_tiles[i];
     }
     return HIPKKT_OK;
 }
@@ -510,15 +510,15 @@ int32_t hipkkt_get_profile_launches(hipkkt_handle h, double *ms, double *flops, 
 int32_t hipkkt_get_counters(hipkkt_handle h, int64_t *out, int64_t cap) {
     if (!h || !out || cap < 0) return HIPKKT_ERR_ARGUMENT;
     int64_t o[15];
-    o[0] = h->n_sweep_timeouts; o[1] = h->use_persist ? 1 : 0; o[2] = h->n_twin_refactors; o[3] = h->fallback ? 1 : 0;
-    o[4] = h->using_fallback ? 1 : 0; o[5] = h->plan.ordering_used; o[6] = (int64_t)h->plan.fronts.size(); o[7] = h->nseg;
-    o[8] = (int64_t)h->fbatches.size(); o[9] = h->use_front_block ? 1 : 0;
+    o[0] = h->stats.n_sweep_timeouts; o[1] = h->persist.use ? 1 : 0; o[2] = h->stats.n_twin_refactors; o[3] = h->twin.fallback ? 1 : 0;
+    o[4] = h->twin.using_fallback ? 1 : 0; o[5] = h->plan.ordering_used; o[6] = (int64_t)h->plan.fronts.size(); o[7] = h->sched.nseg;
+    o[8] = (int64_t)h->fb.batches.size(); o[9] = h->fb.sw.use ? 1 : 0;
     plan_cache_counts(&o[10], &o[11]);   // process-wide: symbolic plans taken from / not found in the plan cache
-    o[12] = h->fb_streamed ? 1 : 0;
-    o[13] = h->n_accurate_factorisations;
+    o[12] = h->fb.sw.streamed ? 1 : 0;
+    o[13] = h->stats.n_accurate_factorisations;
     o[14] = 0;                                                            // gather entries that run on the side stream (split_gather_stages)
-    for (int l = 0; l < h->plan.nlevels && l < (int)h->gath_split.size(); l++)
-        if (h->gath_split[l] >= 0) o[14] += h->plan.gath_stage_ptr[l + 1] - h->plan.gath_stage_ptr[l] - h->gath_split[l];
+    for (int l = 0; l < h->plan.nlevels && l < (int)h->split.gath.size(); l++)
+        if (h->split.gath[l] >= 0) o[14] += h->plan.gath_stage_ptr[l + 1] - h->plan.gath_stage_ptr[l] - h->split.gath[l];
     for (int64_t i = 0; i < cap && i < 15; i++) out[i] = o[i];
     return HIPKKT_OK;
 }
@@ -539,16 +539,16 @@ int32_t hipkkt_debug_dump(hipkkt_handle h, int32_t what, double *out, int64_t ca
         if (out && cap >= n) for (int64_t i = 0; i < n; i++) out[i] = (double)f(i);
     };
     switch (what) {
-        case 0: dev(S->d_y, S->N); break;
-        case 1: dev(S->d_z, S->N); break;
-        case 2: dev(S->d_xp, S->N); break;
+        case 0: dev(S->ctx[0].d_y, S->N); break;
+        case 1: dev(S->ctx[0].d_z, S->N); break;
+        case 2: dev(S->ctx[0].d_xp, S->N); break;
         case 3: dev(S->dp.ubuf, P.ubuf_len); break;
         case 4: dev(S->dp.kval, S->nnzK); break;
         case 5: dev(S->dp.D, S->N); break;
         case 6: dev(S->dp.Dinv, S->N); break;
         case 9:
-            if (!S->d_fb_trace) return HIPKKT_ERR_ARGUMENT;
-            dev((const double *)S->d_fb_trace, (int64_t)S->fbatches.size() * 128);   // raw int64 stamps (100 MHz) in double-sized words
+            if (!S->fb.d_trace) return HIPKKT_ERR_ARGUMENT;
+            dev((const double *)S->fb.d_trace, (int64_t)S->fb.batches.size() * 128);   // raw int64 stamps (100 MHz) in double-sized words
             break;
         case 17: {    // refinement state of the last refined solve on context 0: ||e|| before the last step, ||b||, ||e|| after it, steps
             const RefineState *r = S->ctx[0].h_rs;
@@ -558,8 +558,8 @@ int32_t hipkkt_debug_dump(hipkkt_handle h, int32_t what, double *out, int64_t ca
         }
         case 18: dev(S->ctx[0].d_e, S->N); break;       // residual b - K x of the last SpMV on context 0 (original ordering)
         case 19: host(1, [&](int64_t) { return (double)P.dtri.size(); }); break;   // dense triangles of K outside the symmetric view
-        case 15: dev(S->d_fb_stream, std::max<int64_t>(S->fb_stream_doubles, 1)); break;   // stream records of the front batches (raw)
-        case 16: dev(S->d_fb_scratch, (int64_t)kFbScratch * (int64_t)std::max<size_t>(S->fbatches.size(), 1)); break;
+        case 15: dev(S->fb.d_stream, std::max<int64_t>(S->fb.stream_doubles, 1)); break;   // stream records of the front batches (raw)
+        case 16: dev(S->fb.d_scratch, (int64_t)kFbScratch * (int64_t)std::max<size_t>(S->fb.batches.size(), 1)); break;
         case 20: {   // the dense tiles of the plan, 6 values each: stage, tasks, sum of source widths, tasks through a tile map, full-tile
                      // flag, sum over tasks of rows x columns x width (development: what a stage's update launch is made of)
             std::vector<double> v;
@@ -586,7 +586,7 @@ int32_t hipkkt_debug_dump(hipkkt_handle h, int32_t what, double *out, int64_t ca
                      // of its row slots (development: what a hop of k_fwd_seg waits for)
             std::vector<double> v;
             for (int s = 0; s < P.nsuper; s++) {
-                if (!(P.sn_front[s] < 0 && P.sn_level[s] >= S->seg_lstar[S->seg_of_level[P.sn_level[s]]])) continue;
+                if (!(P.sn_front[s] < 0 && P.sn_level[s] >= S->sched.seg_lstar[S->sched.seg_of_level[P.sn_level[s]]])) continue;
                 const int64_t a = P.sn_rowptr[s], b = P.sn_rowptr[s + 1];
                 int64_t mx = 0;
                 for (int64_t q = a; q < b; q++) mx = std::max<int64_t>(mx, P.g_ptr[q + 1] - P.g_ptr[q]);
@@ -614,13 +614,13 @@ int32_t hipkkt_debug_dump(hipkkt_handle h, int32_t what, double *out, int64_t ca
             host(S->cones.reg.npow, [&](int64_t i) { return v[i]; });
             break;
         }
-        case 7: dev(S->d_soc_u, S->soc_total); break;
-        case 8: dev(S->d_soc_v, S->soc_total); break;
+        case 7: dev(S->soc.d_u, S->soc.total); break;
+        case 8: dev(S->soc.d_v, S->soc.total); break;
         case 10: host(P.nsuper + 1, [&](int64_t i) { return P.sn_first[i]; }); break;
         case 11: host(P.nsuper, [&](int64_t i) { return P.sn_level[i]; }); break;
         case 12: host(P.nsuper, [&](int64_t i) { return P.sn_rowptr[i + 1] - P.sn_rowptr[i]; }); break;
         case 13: host(P.nsuper, [&](int64_t i) { return P.sn_parent[i]; }); break;
-        case 14: host(P.nsuper, [&](int64_t i) { return P.sn_front[i] < 0 && P.sn_level[i] >= S->seg_lstar[S->seg_of_level[P.sn_level[i]]] ? 1 : 0; }); break;
+        case 14: host(P.nsuper, [&](int64_t i) { return P.sn_front[i] < 0 && P.sn_level[i] >= S->sched.seg_lstar[S->sched.seg_of_level[P.sn_level[i]]] ? 1 : 0; }); break;
         default: return HIPKKT_ERR_ARGUMENT;
     }
     return HIPKKT_OK;
@@ -629,8 +629,8 @@ int32_t hipkkt_debug_dump(hipkkt_handle h, int32_t what, double *out, int64_t ca
 
 int32_t hipkkt_reset_timing(hipkkt_handle h) {
     if (!h) return HIPKKT_ERR_ARGUMENT;
-    h->t_acc_factor = h->t_acc_solve = 0;
-    h->n_factor = h->n_solvecalls = h->n_ldlsolves = 0;
+    h->stats.t_acc_factor = h->stats.t_acc_solve = 0;
+    h->stats.n_factor = h->stats.n_solvecalls = h->stats.n_ldlsolves = 0;
     return HIPKKT_OK;
 }
 

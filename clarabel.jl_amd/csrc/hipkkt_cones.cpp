@@ -60,9 +60,9 @@ static int32_t set_cone_types_impl(hipkkt_handle h, int64_t ncones, const int32_
         } else if (kinds[c] == 2) {
             int64_t uv0 = -1, ord = -1;
             if (sk == 1) {
-                ord = S->soc_of_sparse[sparse_idx];
-                uv0 = S->soc_off[ord];
-                if (dense || S->soc_off[ord + 1] - uv0 != numel) { S->err = "set_cone_types: sparse second-order cone does not match its expansion map"; return HIPKKT_ERR_ARGUMENT; }
+                ord = S->soc.of_sparse[sparse_idx];
+                uv0 = S->soc.off[ord];
+                if (dense || S->soc.off[ord + 1] - uv0 != numel) { S->err = "set_cone_types: sparse second-order cone does not match its expansion map"; return HIPKKT_ERR_ARGUMENT; }
             } else if (!dense || numel < 2 || numel > 4 || sk != 0) {
                 // cone_types.jl:86-118: dim <= SOC_NO_EXPANSION_MAX_SIZE (4) is the dense form, everything larger the sparse one
                 S->err = "set_cone_types: a second-order cone is either sparse-expanded or dense with dim <= 4"; return HIPKKT_ERR_ARGUMENT;
@@ -236,11 +236,11 @@ static int32_t update_scaling_impl(hipkkt_handle h, const double *s, const doubl
     launch_zero_words(S->stream, C.tab.fail, 1);
     if (psd_step) launch_psd_step_check(S->stream, C.tab.psd_lam, C.reg.psd_lam_total, C.tab.fail);
     launch_scaling_diag(S->stream, C.tab.kind, C.tab.rowhs, S->d_mapHs, ds, dz, dw, dl, S->dp.kval, m);
-    launch_scaling_soc(S->stream, C.reg.nsoc, C.tab.socdesc, S->d_mapHs, ds, dz, dw, dl, C.tab.eta, S->d_soc_u, S->d_soc_v,
-                       S->d_soc_eta2, S->dp.kval, C.tab.fail);
-    if (S->nsoc > 0)      // u, v, D entries of the sparse cones (the same kernel hipkkt_set_soc_batch uses)
-        launch_soc_batch(S->stream, S->dp.kval, S->d_soc_uidx, S->d_soc_vidx, S->d_soc_cone, S->d_soc_u, S->d_soc_v, S->d_soc_eta2,
-                         S->soc_total, S->d_soc_didx, S->nsoc);
+    launch_scaling_soc(S->stream, C.reg.nsoc, C.tab.socdesc, S->d_mapHs, ds, dz, dw, dl, C.tab.eta, S->soc.d_u, S->soc.d_v,
+                       S->soc.d_eta2, S->dp.kval, C.tab.fail);
+    if (S->soc.n > 0)      // u, v, D entries of the sparse cones (the same kernel hipkkt_set_soc_batch uses)
+        launch_soc_batch(S->stream, S->dp.kval, S->soc.d_uidx, S->soc.d_vidx, S->soc.d_cone, S->soc.d_u, S->soc.d_v, S->soc.d_eta2,
+                         S->soc.total, S->soc.d_didx, S->soc.n);
     if (dR) {
         int64_t off = 0;
         for (size_t c = 0; c < C.reg.psd_n.size(); c++) {

@@ -7,6 +7,18 @@ using namespace hipkkt_host;
 
 namespace hipkkt_host {
 
+static double slot_value(const hipkkt_solver *S, int slot) {
+    double v;
+    memcpy(&v, (const char *)S->h_scal + slot * sizeof(double), sizeof(double));
+    return v;  // the slot holds the raw bit pattern of a non-negative double (or NaN)
+}
+
+static void read_scalars(hipkkt_solver *S) {
+    HK_CHECK(hipMemcpyAsync(S->h_flags, S->dp.flags, FL_COUNT * sizeof(int), hipMemcpyDeviceToHost, S->stream));
+    HK_CHECK(hipMemcpyAsync(S->h_scal, S->dp.scal, SC_COUNT * sizeof(double), hipMemcpyDeviceToHost, S->stream));
+    HK_CHECK(hipStreamSynchronize(S->stream));
+}
+
 // ---- enqueue helpers (no synchronisation inside; capturable) ---------------------------------
 
 // narrow levels (w <= 8): LDS-resident kernel; wide panels: the register-resident 8-wave kernel
@@ -23,30 +35,30 @@ void enqueue_factor_level(hipkkt_solver *S, int l) {
 // one update batch of a front (front_block2.hip; the first form of the kernel, front_block.hip, exists in the testing build only)
 static void enqueue_front_batch(hipkkt_solver *S, const FrontBatch &B) {
 #ifdef HIPKKT_TESTING
-    if (!S->fb_v2) {
-        launch_front_block(S->stream, S->dp, B, S->d_fb_sync, S->d_fb_scratch, S->d_fb_stream, S->opts.dynamic_reg_eps,
-                           S->opts.dynamic_reg_delta, S->fb_streamed, S->d_fb_trace);
+    if (!S->fb.sw.v2) {
+        launch_front_block(S->stream, S->dp, B, S->fb.d_sync, S->fb.d_scratch, S->fb.d_stream, S->opts.dynamic_reg_eps,
+                           S->opts.dynamic_reg_delta, S->fb.sw.streamed, S->fb.d_trace);
         return;
     }
 #endif
-    launch_front_block2(S->stream, S->dp, B, S->d_fb_sync, S->d_fb_scratch, S->d_fb_stream, S->opts.dynamic_reg_eps,
-                        S->opts.dynamic_reg_delta, S->d_fb_trace);
+    launch_front_block2(S->stream, S->dp, B, S->fb.d_sync, S->fb.d_scratch, S->fb.d_stream, S->opts.dynamic_reg_eps,
+                        S->opts.dynamic_reg_delta, S->fb.d_trace);
 }
 
 // split-K part of a stage's dense updates (hipkkt_setup.cpp plan_split_k): the chunk tiles, then their fixed-order reduction
 void enqueue_split_k(hipkkt_solver *S, int l) {
-    if (S->split_group_count[l] <= 0) return;
-    launch_update_dense(S->stream, S->dp, S->split_group_begin[l], S->split_group_count[l], false);
-    launch_split_reduce(S->stream, S->dp, S->d_split_recs + S->split_rec_ptr[l], S->split_rec_ptr[l + 1] - S->split_rec_ptr[l]);
+    if (S->split.group_count[l] <= 0) return;
+    launch_update_dense(S->stream, S->dp, S->split.group_begin[l], S->split.group_count[l], false);
+    launch_split_reduce(S->stream, S->dp, S->split.d_recs + S->split.rec_ptr[l], S->split.rec_ptr[l + 1] - S->split.rec_ptr[l]);
 }
 
 // The stage's per-entry gather lists; a split stage (hipkkt_setup.cpp split_gather_stages) runs its deferred part on the side stream
 void enqueue_gather(hipkkt_solver *S, int l) {
     const HostPlan &P = S->plan;
-    const int64_t e0 = P.gath_stage_ptr[l], n = P.gath_stage_ptr[l + 1] - e0, h0 = S->gath_heavy_ptr[l], nh = S->gath_heavy_ptr[l + 1] - h0;
-    const int64_t head = S->gath_split[l];
+    const int64_t e0 = P.gath_stage_ptr[l], n = P.gath_stage_ptr[l + 1] - e0, h0 = S->split.heavy_ptr[l], nh = S->split.heavy_ptr[l + 1] - h0;
+    const int64_t head = S->split.gath[l];
     if (head < 0 || S->side_join_level >= 0) { launch_update_gather(S->stream, S->dp, e0, n, h0, nh); return; }
-    const int64_t hh = S->gath_heavy_split[l];
+    const int64_t hh = S->split.gath_heavy[l];
     launch_update_gather(S->stream, S->dp, e0, head, h0, hh);
     HK_CHECK(hipEventRecord(S->ev_fork, S->stream));
     HK_CHECK(hipStreamWaitEvent(S->idle_stream, S->ev_fork, 0));
@@ -125,42 +137,42 @@ int fb_extra_tiles_of_stage(int nd, int ncrit, int next_blk, int *per_wave_out) 
     return best_r;
 }
 
-void enqueue_factor(hipkkt_solver *S, int static_enable, double eps_const, double eps_prop) {
+static void enqueue_factor(hipkkt_solver *S, int static_enable, double eps_const, double eps_prop) {
     const HostPlan &P = S->plan;
     hipStream_t st = S->stream;
     S->side_join_level = -1;
     launch_zero_words(st, S->dp.scal, 2);                 // SC_MAXDIAG  (kernels.hip: why not hipMemsetAsync)
     launch_zero_words(st, S->dp.flags, FL_COUNT);
     launch_maxabs_gather(st, S->dp.kval, S->d_diag_full, S->N, (unsigned long long *)S->dp.scal + SC_MAXDIAG);
-    HK_CHECK(hipMemsetAsync(S->dp.Lx, 0, (size_t)(P.panel_doubles + S->split_scratch_doubles) * sizeof(double), st));   // (incl. the split-K partial tiles: a factorisation that aborted between a chunk launch and its reduce must not leave sums behind)
+    HK_CHECK(hipMemsetAsync(S->dp.Lx, 0, (size_t)(P.panel_doubles + S->split.scratch_doubles) * sizeof(double), st));   // (incl. the split-K partial tiles: a factorisation that aborted between a chunk launch and its reduce must not leave sums behind)
     launch_init_panels(st, S->dp, S->nnzK, static_enable, eps_const, eps_prop);
-    const bool fb = S->use_front_block && !S->fbatches.empty();
-    if (fb) launch_fb_reset(st, S->d_fb_sync, 128 * (int)S->fbatches.size(), S->d_fb_stream, S->fb_stream_doubles);
+    const bool fb = S->fb.sw.use && !S->fb.batches.empty();
+    if (fb) launch_fb_reset(st, S->fb.d_sync, 128 * (int)S->fb.batches.size(), S->fb.d_stream, S->fb.stream_doubles);
     int cur_bi = -1;
     int extra_begin = 0, extra_count = 0, extra_pw = 1;   // dense tiles handed to the next k_front_block launch, tiles per wavefront there
     for (int l = 0; l < P.nlevels; l++) {
-        if (fb && S->lvl_fb[l] != -1) {
+        if (fb && S->fb.lvl[l] != -1) {
             // a front's update batch: one launch for its panels and their just-in-time updates, then the batch's far stage
-            if (S->lvl_fb[l] >= 0) {
-                cur_bi = S->lvl_fb[l];
-                join_side(S, S->fb_last_level[(size_t)cur_bi]);       // (a batch that reaches beyond the join level touches deferred targets)
-                FrontBatch B = S->fbatches[(size_t)cur_bi];
+            if (S->fb.lvl[l] >= 0) {
+                cur_bi = S->fb.lvl[l];
+                join_side(S, S->fb.last_level[(size_t)cur_bi]);       // (a batch that reaches beyond the join level touches deferred targets)
+                FrontBatch B = S->fb.batches[(size_t)cur_bi];
                 B.x_begin = extra_begin; B.x_count = extra_count; B.pad = extra_pw;     // far tiles of the stage before (fb_extra_tiles_of_stage)
                 extra_begin = extra_count = 0;
                 enqueue_front_batch(S, B);
             }
-            const bool last = l + 1 >= P.nlevels || S->lvl_fb[l + 1] != -2;
+            const bool last = l + 1 >= P.nlevels || S->fb.lvl[l + 1] != -2;
             if (!last) continue;                          // the stages inside the batch are applied by the kernel itself
         } else {
             enqueue_factor_level(S, l);
         }
         int skip = 0;
-        if (fb && S->fb_extra && cur_bi >= 0 && S->lvl_fb[l] != -1 && S->next_batch[(size_t)cur_bi].has_next) {
+        if (fb && S->fb.sw.extra && cur_bi >= 0 && S->fb.lvl[l] != -1 && S->fb.next[(size_t)cur_bi].has_next) {
             // The far stage of a front batch runs in rounds of 1024 tiles (one per SIMD; 2048 with two co-resident wavefronts); what is
             // left after the whole rounds keeps a fraction of the device busy for a full tile time.  Those tiles -- taken from the END
             // of the [columns of the next batch | rest] order, so the next panel kernel does not need them -- ride in the next
             // k_front_block launch as extra workgroups on the compute units it leaves idle.
-            const hipkkt_solver::NextBatch &A = S->next_batch[(size_t)cur_bi];
+            const NextBatch &A = S->fb.next[(size_t)cur_bi];
             const int r = fb_extra_tiles_of_stage(P.upd_stage_ndense[l], A.ncrit, A.next_blk, &extra_pw);
             if (r > 0 && P.upd_stage_flops_dense[l] >= 1.5e6 * P.upd_stage_ndense[l]) {
                 skip = r;
@@ -197,24 +209,24 @@ static int32_t refactor_once(hipkkt_handle h, int32_t static_reg_enable, double 
 // choice) and the factorisation is repeated, so robustness is never worse than with that order.
 int32_t hipkkt_refactor(hipkkt_handle h, int32_t static_reg_enable, double eps_const, double eps_prop,
                         double *eps_used, int64_t *n_dynamic_reg) {
-    if (h) h->using_fallback = false;
+    if (h) h->twin.using_fallback = false;
     int32_t rc = refactor_once(h, static_reg_enable, eps_const, eps_prop, eps_used, n_dynamic_reg);
     // tests: HIPKKT_FORCE_TWIN=1 treats every successful factorisation in the cheap order as broken down, so that the robust-order
     // twin can be checked in ITS permutation on problems a scalar CPU factorisation finishes in seconds
     // (read once per handle in init_runtime: no getenv on the refactor path)
-    if (h && h->force_twin && rc == HIPKKT_OK && h && h->plan.ordering_used == 1) rc = HIPKKT_NUMERICAL_FAILURE;
+    if (h && h->twin.force && rc == HIPKKT_OK && h && h->plan.ordering_used == 1) rc = HIPKKT_NUMERICAL_FAILURE;
     if (rc != HIPKKT_NUMERICAL_FAILURE || !h || h->plan.ordering_used != 1) return rc;
     hipkkt_solver *S = h;
     try {
         if (hipSetDevice(S->device) != hipSuccess) return rc;
-        if (!S->fallback) {
+        if (!S->twin.fallback) {
             // built in a local owner: a set-up that throws half-way (e.g. device OOM) must not leave a twin with null
             // streams / device pointers behind -- the next failing factorisation then simply tries again
             std::unique_ptr<hipkkt_solver> T;
             const auto t_a = std::chrono::steady_clock::now();
-            if (S->twin_future.valid()) {               // analysed (and made device-resident) ahead on a host thread (finish_create): wait for it
-                const std::string err = S->twin_future.get();
-                T = std::move(S->twin_pending);
+            if (S->twin.future.valid()) {               // analysed (and made device-resident) ahead on a host thread (finish_create): wait for it
+                const std::string err = S->twin.future.get();
+                T = std::move(S->twin.pending);
                 if (!err.empty() && err.rfind("twin device set-up", 0) == 0) {
                     // the analysis is fine, only its residency failed on the thread: release what it got and repeat that part here
                     std::unique_ptr<hipkkt_solver> T2(new hipkkt_solver());
@@ -238,7 +250,7 @@ int32_t hipkkt_refactor(hipkkt_handle h, int32_t static_reg_enable, double eps_c
                 T->plan_opts = po;
             }
             const auto t_b = std::chrono::steady_clock::now();
-            if (!T->device_ready) {
+            if (!T->twin.device_ready) {
                 init_runtime(T.get());
                 setup_device(T.get());
             }
@@ -246,27 +258,27 @@ int32_t hipkkt_refactor(hipkkt_handle h, int32_t static_reg_enable, double eps_c
                 fprintf(stderr, "hipkkt: robust-order twin (minimum degree on K): N %d nnzL %lld levels %d: waited %.2f ms for its symbolic analysis (%s), device set-up %.2f ms\n",
                         T->plan.N, (long long)T->plan.nnzL, T->plan.nlevels, 1e3 * std::chrono::duration<double>(t_b - t_a).count(),
                         T->plan.timing_note.c_str(), 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t_b).count());
-            S->fallback = T.release();
+            S->twin.fallback = T.release();
         }
-        copy_sync(S->stream, S->fallback->dp.kval, S->dp.kval, (size_t)S->nnzK * sizeof(double), hipMemcpyDeviceToDevice);
+        copy_sync(S->stream, S->twin.fallback->dp.kval, S->dp.kval, (size_t)S->nnzK * sizeof(double), hipMemcpyDeviceToDevice);
     } catch (...) {
         S->err = "building the fallback (minimum-degree) factorisation failed";
         return HIPKKT_ERR_DEVICE;
     }
-    rc = refactor_once(S->fallback, static_reg_enable, eps_const, eps_prop, eps_used, n_dynamic_reg);
-    S->using_fallback = true;
-    S->n_twin_refactors++;
-    S->last_eps = S->fallback->last_eps;
-    S->last_nreg = S->fallback->last_nreg;
-    S->t_last_factor += S->fallback->t_last_factor;      // the failed attempt + the repeated one
-    S->t_acc_factor += S->fallback->t_last_factor;
+    rc = refactor_once(S->twin.fallback, static_reg_enable, eps_const, eps_prop, eps_used, n_dynamic_reg);
+    S->twin.using_fallback = true;
+    S->stats.n_twin_refactors++;
+    S->last_eps = S->twin.fallback->last_eps;
+    S->last_nreg = S->twin.fallback->last_nreg;
+    S->stats.t_last_factor += S->twin.fallback->stats.t_last_factor;      // the failed attempt + the repeated one
+    S->stats.t_acc_factor += S->twin.fallback->stats.t_last_factor;
     return rc;
 }
 
 static int32_t refactor_once(hipkkt_handle h, int32_t static_reg_enable, double eps_const, double eps_prop,
                              double *eps_used, int64_t *n_dynamic_reg) {
     HK_ENTER(h)
-    S->red_have_const = false;   // the resident constant-rhs solution (N2) belongs to the previous factorisation
+    S->red.have_const = false;   // the resident constant-rhs solution (N2) belongs to the previous factorisation
     HK_CHECK(hipEventRecord(S->ev0, S->stream));
     if (S->profiling) {
         // eager, with the dense-update launches timed separately (adds event overhead)
@@ -276,19 +288,19 @@ static int32_t refactor_once(hipkkt_handle h, int32_t static_reg_enable, double 
         launch_zero_words(st, S->dp.scal, 2);
         launch_zero_words(st, S->dp.flags, FL_COUNT);
         launch_maxabs_gather(st, S->dp.kval, S->d_diag_full, S->N, (unsigned long long *)S->dp.scal + SC_MAXDIAG);
-        HK_CHECK(hipMemsetAsync(S->dp.Lx, 0, (size_t)(P.panel_doubles + S->split_scratch_doubles) * sizeof(double), st));   // (incl. the split-K partial tiles: a factorisation that aborted between a chunk launch and its reduce must not leave sums behind)
+        HK_CHECK(hipMemsetAsync(S->dp.Lx, 0, (size_t)(P.panel_doubles + S->split.scratch_doubles) * sizeof(double), st));   // (incl. the split-K partial tiles: a factorisation that aborted between a chunk launch and its reduce must not leave sums behind)
         launch_init_panels(st, S->dp, S->nnzK, static_reg_enable, eps_const, eps_prop);
         std::vector<hipEvent_t> evs, evd;   // evs: all update kernels of a stage; evd: its k_update_dense<4,4> launch alone
         std::vector<int> evd_level;
-        const bool fb = S->use_front_block && !S->fbatches.empty();
-        if (fb) launch_fb_reset(st, S->d_fb_sync, 128 * (int)S->fbatches.size(), S->d_fb_stream, S->fb_stream_doubles);
+        const bool fb = S->fb.sw.use && !S->fb.batches.empty();
+        if (fb) launch_fb_reset(st, S->fb.d_sync, 128 * (int)S->fb.batches.size(), S->fb.d_stream, S->fb.stream_doubles);
         std::vector<hipEvent_t> evf;        // around every k_front_block launch
         int fb_panels = 0;
         double fb_flops = 0;                // update flops of the stages inside the batches (executed by k_front_block)
         int cur_bi = -1, extra_begin = 0, extra_count = 0, extra_pw = 1;
         std::vector<double> evd_flops;      // flops / tiles of the timed dense launches (a launch may have handed tiles to the next k_front_block)
         std::vector<int> evd_tiles;
-        S->prof_extra_tiles = 0; S->prof_extra_flops = 0;
+        S->stats.prof_extra_tiles = 0; S->stats.prof_extra_flops = 0;
         auto dense_flops = [&](int gb, int n) {
             double f = 0;
             for (int g = gb; g < gb + n; g++)
@@ -299,24 +311,24 @@ static int32_t refactor_once(hipkkt_handle h, int32_t static_reg_enable, double 
             return f;
         };
         for (int l = 0; l < P.nlevels; l++) {
-            if (fb && S->lvl_fb[l] != -1) {
-                if (S->lvl_fb[l] >= 0) {
+            if (fb && S->fb.lvl[l] != -1) {
+                if (S->fb.lvl[l] >= 0) {
                     hipEvent_t a, b;
                     HK_CHECK(hipEventCreate(&a));
                     HK_CHECK(hipEventCreate(&b));
                     HK_CHECK(hipEventRecord(a, st));
-                    cur_bi = S->lvl_fb[l];
-                    join_side(S, S->fb_last_level[(size_t)cur_bi]);
-                    FrontBatch B = S->fbatches[(size_t)cur_bi];
+                    cur_bi = S->fb.lvl[l];
+                    join_side(S, S->fb.last_level[(size_t)cur_bi]);
+                    FrontBatch B = S->fb.batches[(size_t)cur_bi];
                     B.x_begin = extra_begin; B.x_count = extra_count; B.pad = extra_pw;
                     extra_begin = extra_count = 0;
                     enqueue_front_batch(S, B);
                     HK_CHECK(hipEventRecord(b, st));
                     evf.push_back(a);
                     evf.push_back(b);
-                    fb_panels += S->fbatches[S->lvl_fb[l]].nb;
+                    fb_panels += S->fb.batches[S->fb.lvl[l]].nb;
                 }
-                if (l + 1 < P.nlevels && S->lvl_fb[l + 1] == -2) { fb_flops += P.upd_stage_flops_dense[l]; continue; }   // applied by the kernel
+                if (l + 1 < P.nlevels && S->fb.lvl[l + 1] == -2) { fb_flops += P.upd_stage_flops_dense[l]; continue; }   // applied by the kernel
             } else {
                 enqueue_factor_level(S, l);
             }
@@ -328,13 +340,13 @@ static int32_t refactor_once(hipkkt_handle h, int32_t static_reg_enable, double 
                 const int g0 = P.upd_stage_ptr[l], nd = P.upd_stage_ndense[l], ng = P.upd_stage_ngather[l];
                 join_side(S, l);
                 int skip = 0;                                              // (the same rule as enqueue_factor)
-                if (fb && S->fb_extra && !S->profiling_no_extra && cur_bi >= 0 && S->lvl_fb[l] != -1 && S->next_batch[(size_t)cur_bi].has_next &&
+                if (fb && S->fb.sw.extra && !S->profiling_no_extra && cur_bi >= 0 && S->fb.lvl[l] != -1 && S->fb.next[(size_t)cur_bi].has_next &&
                     P.upd_stage_flops_dense[l] >= 1.5e6 * nd) {
-                    skip = fb_extra_tiles_of_stage(nd, S->next_batch[(size_t)cur_bi].ncrit, S->next_batch[(size_t)cur_bi].next_blk, &extra_pw);
+                    skip = fb_extra_tiles_of_stage(nd, S->fb.next[(size_t)cur_bi].ncrit, S->fb.next[(size_t)cur_bi].next_blk, &extra_pw);
                     if (skip > 0) { extra_begin = g0 + nd - skip; extra_count = skip; }
                 }
                 const double xf = skip > 0 ? dense_flops(g0 + nd - skip, skip) : 0.0;
-                S->prof_extra_tiles += skip; S->prof_extra_flops += xf;
+                S->stats.prof_extra_tiles += skip; S->stats.prof_extra_flops += xf;
                 launch_update_dense(st, S->dp, g0, nd - skip, nd > 0 && P.upd_stage_flops_dense[l] >= 1.5e6 * nd);
                 enqueue_split_k(S, l);
                 if (nd - skip > 384) {   // the one-wavefront-per-tile variant (see launch_update_dense)
@@ -363,28 +375,28 @@ static int32_t refactor_once(hipkkt_handle h, int32_t static_reg_enable, double 
             (void)hipEventElapsedTime(&ms, evs[i], evs[i + 1]);
             tot += ms;
         }
-        S->prof_dense4_ms = 0; S->prof_dense4_flops = 0; S->prof_dense4_launches = 0;
-        S->prof_launch_ms.clear(); S->prof_launch_flops.clear(); S->prof_launch_tiles.clear();
+        S->stats.prof_dense4_ms = 0; S->stats.prof_dense4_flops = 0; S->stats.prof_dense4_launches = 0;
+        S->stats.prof_launch_ms.clear(); S->stats.prof_launch_flops.clear(); S->stats.prof_launch_tiles.clear();
         for (size_t i = 0; i + 1 < evd.size(); i += 2) {
             float ms = 0;
             (void)hipEventElapsedTime(&ms, evd[i], evd[i + 1]);
-            S->prof_dense4_ms += ms;
-            S->prof_dense4_flops += evd_flops[i / 2];
-            S->prof_dense4_launches++;
-            S->prof_launch_ms.push_back(ms);
-            S->prof_launch_flops.push_back(evd_flops[i / 2]);
-            S->prof_launch_tiles.push_back(evd_tiles[i / 2]);
+            S->stats.prof_dense4_ms += ms;
+            S->stats.prof_dense4_flops += evd_flops[i / 2];
+            S->stats.prof_dense4_launches++;
+            S->stats.prof_launch_ms.push_back(ms);
+            S->stats.prof_launch_flops.push_back(evd_flops[i / 2]);
+            S->stats.prof_launch_tiles.push_back(evd_tiles[i / 2]);
         }
         for (size_t i = 1; i < evd.size(); i += 2) (void)hipEventDestroy(evd[i]);
         for (hipEvent_t e : evs) (void)hipEventDestroy(e);
-        S->prof_fb_ms = 0; S->prof_fb_launches = (int)(evf.size() / 2); S->prof_fb_panels = fb_panels; S->prof_fb_flops = fb_flops;
+        S->stats.prof_fb_ms = 0; S->stats.prof_fb_launches = (int)(evf.size() / 2); S->stats.prof_fb_panels = fb_panels; S->stats.prof_fb_flops = fb_flops;
         for (size_t i = 0; i + 1 < evf.size(); i += 2) {
             float ms = 0;
             (void)hipEventElapsedTime(&ms, evf[i], evf[i + 1]);
-            S->prof_fb_ms += ms;
+            S->stats.prof_fb_ms += ms;
         }
         for (hipEvent_t e : evf) (void)hipEventDestroy(e);
-        S->t_last_update = tot;
+        S->stats.t_last_update = tot;
     } else {
         GraphSlot &g = S->g_factor;
         const bool same = g.static_enable == static_reg_enable && g.eps_const == eps_const && g.eps_prop == eps_prop;
@@ -397,19 +409,19 @@ static int32_t refactor_once(hipkkt_handle h, int32_t static_reg_enable, double 
     S->kval_event_pending = false;       // (the main stream has been synchronised: every value update before it is complete)
     float ms = 0;
     HK_CHECK(hipEventElapsedTime(&ms, S->ev0, S->ev1));
-    S->t_last_factor = ms;
-    S->t_acc_factor += ms;
-    S->n_factor++;
-    if (S->h_flags[FL_FACFAIL] && S->use_front_block) {
+    S->stats.t_last_factor = ms;
+    S->stats.t_acc_factor += ms;
+    S->stats.n_factor++;
+    if (S->h_flags[FL_FACFAIL] && S->fb.sw.use) {
         // a spin of k_front_block ran out (a stalled workgroup): repeat this factorisation with one launch per panel, and keep that
-        S->use_front_block = false;
+        S->fb.sw.use = false;
         S->g_factor.valid = false;
         fprintf(stderr, "hipkkt: a hand-off of the front-batch factorisation timed out; repeating it with one launch per panel (kept from now on)\n");
-        S->n_sweep_timeouts++;
+        S->stats.n_sweep_timeouts++;
         return refactor_once(h, static_reg_enable, eps_const, eps_prop, eps_used, n_dynamic_reg);
     }
     S->last_npolish = S->h_flags[FL_NPOLISH];            // wide diagonal blocks whose solves take a refinement step (kernels.hip k_invert_diag_wide)
-    if (S->last_npolish > 0) S->n_accurate_factorisations++;
+    if (S->last_npolish > 0) S->stats.n_accurate_factorisations++;
     const double maxdiag = slot_value(S, SC_MAXDIAG);
     S->last_eps = static_reg_enable ? eps_const + eps_prop * maxdiag : 0.0;
     S->last_nreg = S->h_flags[FL_NREG];

@@ -3,8 +3,10 @@
 //   hipkkt_cones.cpp   cone registration and scaling (hipkkt_set_cone_types[_ex], hipkkt_update_scaling[_ex][_dev])
 //   hipkkt_setup.cpp   runtime objects, device residency of a plan, handle creation (finish_create)
 //   hipkkt_factor.cpp  the factorisation's launch sequence, its graph, hipkkt_refactor and the robust-order twin
+//   solve_schedule.cpp the solve schedule of a plan: level lists, segments, item order (host arithmetic only; solve_schedule.h)
 //   hipkkt_solve.cpp   LDL solves, device-side iterative refinement, the solve entry points
 //   hipkkt_step.cpp    the cone algebra of an interior-point step around the reduced solve (hipkkt_cone_* / hipkkt_step_*)
+// hipkkt_parts.h holds the parts a handle is made of besides its cones (hipkkt_cones.h).
 // Host orchestration only; all numeric work is in kernels.hip / front_block.hip / assemble_dev.hip / scaling.hip / step.hip.
 #pragma once
 #include "../../include/hipkkt.h"
@@ -31,8 +33,10 @@
 #include "cone_layout.h"
 #include "device_plan.h"
 #include "hipkkt_cones.h"
+#include "hipkkt_parts.h"
 #include "kernels.h"
 #include "runtime_pool.h"
+#include "solve_schedule.h"
 #include "symbolic.h"
 
 namespace hipkkt { int box_probe(int device, double *out); }   // probe.hip
@@ -113,6 +117,13 @@ struct GraphSlot {
 using namespace hipkkt;        // internal header of one library: the host files all work inside these two namespaces
 using namespace hipkkt_host;
 
+// The parameters of iterative refinement as the C entry points receive them (include/hipkkt.h); everything below the ABI passes this.
+struct RefineOpts {
+    int32_t enable; double reltol, abstol; int64_t max_iter; double stop_ratio;
+    // the values baked into a captured refinement graph (enable only picks the graph)
+    bool same_graph(const RefineOpts &o) const { return reltol == o.reltol && abstol == o.abstol && max_iter == o.max_iter && stop_ratio == o.stop_ratio; }
+};
+
 // One solve context = everything a refined KKT solve mutates: its stream, work vectors, the hand-off / counter words
 // of the persistent sweeps (a private copy of those DevPlan pointers), the device-side refinement state and its
 // captured graphs.  Two contexts let two right-hand sides be solved CONCURRENTLY on one factorisation (SURVEY
@@ -128,11 +139,9 @@ struct SolveCtx {
     RefineState *d_rs = nullptr, *h_rs = nullptr;   // device state, pinned host copy
     int *h_flags = nullptr;                         // pinned copy of dp.flags
     hipkkt_host::GraphSlot g_ldl, g_first, g_step;               // plain LDL solve (d_b -> d_x0) / refined solve incl. its first step / one more step
-    double g_reltol = -1, g_abstol = -1, g_stop = -1;   // parameters baked into g_first / g_step
-    int64_t g_maxit = -1;
+    RefineOpts g_opts{-1, -1.0, -1.0, -1, -1.0};    // parameters baked into g_first / g_step (no caller passes these: the first comparison fails)
     hipEvent_t ev_a = nullptr, ev_b = nullptr;
     double last_ms = 0;
-    int64_t last_steps = 0;
     bool ir_used = false;
     bool extra_steps = false;     // the last solve_finish ran refinement steps beyond the one inside the solve's graph
     const double *result() const { return (ir_used && h_rs->cur) ? d_x1 : d_x0; }
@@ -142,143 +151,57 @@ struct hipkkt_solver {
     int device = 0;
     SolveCtx ctx[kNumCtx];
     hipStream_t stream = nullptr;
+    hipStream_t idle_stream = nullptr;   // never carries work: see init_runtime (hipkkt_setup.cpp)
     hipkkt_opts opts{};
     bool l1 = false;
     KKTImage img;      // L1: assembled image; L0: colptr/rowval/nzval/dsigns copied in
     HostPlan plan;
+    PlanOptions plan_opts;       // as used for the current plan
+    SolveSchedule sched;         // which supernode goes to which solve launch (solve_schedule.h)
     DevPlan dp{};
     std::vector<std::pair<void *, size_t>> allocs;   // device slabs (RuntimePool blocks: pointer, capacity)
     std::string err;
 
     int N = 0;
     int64_t nnzK = 0;
-    // solve item lists (256-row blocks) per level
-    std::vector<FacItem> slv_items, bwd_items;
-    std::vector<int> slv_lvl_ptr, bwd_lvl_ptr;
-    std::vector<int> reg_lvl_sn, reg_lvl_ptr;   // supernodes of every level that are NOT front panels
-    std::vector<int> lvl_wnarrow, all_lvl_wnarrow;   // [nlevels] widest narrow supernode of the level
-    std::vector<int> lvl_nnarrow;                // [nlevels] the first lvl_nnarrow[l] supernodes of a level's list are narrow (one thread each)
-    // the same level lists over ALL supernodes (front panels included), appended to the same item arrays: the path without
-    // any persistent kernel, taken after a sweep time-out
-    std::vector<int> all_slv_lvl_ptr, all_bwd_lvl_ptr, all_reg_lvl_ptr;
-    std::vector<int> all_lvl_nnarrow;
-    // persistent sweeps over the regular supernodes: segments = level ranges between front kernels
-    bool use_persist = true;
-    double t_init_runtime = 0;           // seconds (HIPKKT_VERBOSE)
     std::chrono::steady_clock::time_point t_created{};   // when the assembly returned
-    // front batches factored by one launch each (front_block.hip); a time-out inside one downgrades the handle to one launch per panel
-    bool use_front_block = true;
-    std::vector<FrontBatch> fbatches;
-    std::vector<int> lvl_fb;             // [nlevels] index of the batch that starts at this level, -2 inside a batch, -1 otherwise
-    std::vector<int> fb_last_level;      // per batch
-    int *d_fb_sync = nullptr;
-    double *d_fb_scratch = nullptr;
-    // streamed pivot chain of k_front_block (front_block.hip): per (batch, panel, 8-pivot block) one record of 528 doubles that the
-    // diagonal workgroup publishes as it eliminates and the next diagonal workgroup polls (sentinel-filled before every factorisation)
-    double *d_fb_stream = nullptr;
-    hipStream_t idle_stream = nullptr;   // never carries work: see init_runtime (hipkkt_setup.cpp)
-    int64_t fb_stream_doubles = 0;
-    bool fb_streamed = true;             // HIPKKT_FB_STREAM=0: the round-3 chain (hand-off of the explicit inverse after all 64 pivots)
-    // per front batch: what the next batch of the same front needs from this batch's far stage ([columns of the next batch | rest]
-    // order of the stage's dense tiles, hipkkt_setup.cpp order_far_stages) -- the rest may ride in the next k_front_block launch
-    struct NextBatch {
-        int next_blk = 0;                               // workgroups of the next batch's panel kernel
-        bool has_next = false;                          // the next batch of the same front follows at once: [chain | rest] order valid
-        int ncrit = 0;                                  // far stage: the first ncrit dense groups are the next batch's columns
-    };
-    std::vector<NextBatch> next_batch;
-    int64_t split_scratch_doubles = 0;   // split-K partial tiles behind the panels in Lx (cleared with them before every factorisation)
+    PersistState persist;
+    FrontBatchState fb;
+    UpdateSplit split;
+    SocTables soc;
+    ResidualBuffers res;
+    ReducedSolve red;
+    TwinState twin;
+    SolverStats stats;
+    ConeState cones;                     // registration, device tables, resident step (hipkkt_cones.h)
     // refined block solves (kernels.hip k_invert_diag_wide): wide diagonal blocks whose explicit inverse has an entry above the threshold
-    double accurate_threshold = 64.0;    // HIPKKT_ACCURATE=<threshold> ("0" = never, "-1" = every wide block)
+    double accurate_threshold = 64.0;    // ACCURATE=<threshold> ("0" = never, "-1" = every wide block)
     int last_npolish = 0;                // marked blocks of the last factorisation
-    int64_t n_accurate_factorisations = 0;   // factorisations with at least one
-    bool fb_v2 = true;                   // front batches by front_block2.hip (tiles transposed in the accumulators, round 5); HIPKKT_FB_V2=0: front_block.hip
-    bool force_twin = false;             // HIPKKT_FORCE_TWIN=1 at create (tests): see hipkkt_refactor
-    bool fb_extra = true;                // the partial last round of a batch's far updates rides in the next k_front_block launch (HIPKKT_FB_EXTRA=0: off)
-    long long *d_fb_trace = nullptr;     // HIPKKT_FB_TRACE=1: wall-clock stamps of the first 8 workgroups of every batch (debug_dump 9)
-    bool persist_allowed = true;         // false: HIPKKT_NO_PERSIST (never tried)
-    int64_t persist_retry_at = -1;       // after a sweep time-out: the LDL-solve count at which the persistent kernels are tried again
-    int64_t persist_backoff = 0;         // doubles with every time-out (64, 128, ...)
-    int64_t n_sweep_timeouts = 0;
-    int64_t n_twin_refactors = 0;        // factorisations repeated on the robust-order twin
-    int nseg = 0;
-    std::vector<int> seg_of_level;               // [nlevels]
-    std::vector<int> fseg_ptr, bseg_ptr;         // [nseg+1] into slv_items / pbwd_items
-    std::vector<int> seg_lo, seg_hi, seg_lstar;  // per segment: level range [lo, hi] and the first level handled by the
-                                                 // persistent kernels (wide bottom levels keep one launch per level)
-    std::vector<FacItem> pbwd_items;
-    int wmax_all = 1;
     int inv_nsmall = 0, inv_wsmall = 1, inv_nwide = 0;   // split of the diagonal-block inversions (kernels.hip)
-    std::vector<int64_t> p_off;
-    // split-K of stages with few target tiles and long contribution lists (hipkkt_setup.cpp plan_split_k): per level, the range of the
-    // sub-groups appended to the dense-group records and of the reduce records
-    std::vector<int> split_group_begin, split_group_count, split_rec_ptr;
-    SplitRec *d_split_recs = nullptr;
-    std::vector<int64_t> gath_heavy_ptr;   // [nlevels+1] into the list of heavy gather entries (kernels.hip k_update_gather_heavy)
-    // Deferred part of a big gather stage (hipkkt_setup.cpp split_gather_stages): the entries of stage l are ordered [targets the next
-    // update batch factors or updates | targets beyond it]; the second part runs on the side stream NEXT TO the levels of the next
-    // batch and is joined before that batch's far stage (hipkkt_factor.cpp enqueue_gather / join_side).  gath_split[l] = entries of
-    // the first part (-1: the stage is not split), gath_heavy_split[l] = how many of the stage's heavy entries belong to it.
-    std::vector<int64_t> gath_split, gath_heavy_split;
-    int side_join_level = -1;              // >= 0 while a side-stream gather is in flight: the first level whose update stage must wait for it
+    int side_join_level = -1;            // >= 0 while a side-stream gather is in flight: the first level whose update stage must wait for it
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
 
     // device index arrays for value updates
     int64_t *d_mapHs = nullptr, *d_mapP = nullptr, *d_mapA = nullptr, *d_diag_full = nullptr;
-    // all sparse SOC cones concatenated
-    int64_t soc_total = 0;
-    int nsoc = 0;
-    std::vector<int64_t> soc_off;  // per sparse map (SOC only) offset into the concatenated arrays
-    std::vector<int> soc_of_sparse; // sparse-map index -> soc ordinal or -1
-    int64_t *d_soc_uidx = nullptr, *d_soc_vidx = nullptr, *d_soc_didx = nullptr;
-    int *d_soc_cone = nullptr;
-    double *d_soc_u = nullptr, *d_soc_v = nullptr, *d_soc_eta2 = nullptr;
     // N1: update_scaling! / get_Hs! on the device (hipkkt_set_cone_types + hipkkt_update_scaling, hipkkt_cones.cpp, scaling.hip)
     std::vector<int64_t> cone_numel;                       // as given to hipkkt_create_from_parts
     std::vector<int32_t> cone_hs_dense, cone_sparse_kind;
-    ConeState cones;                                       // registration, device tables, resident step (hipkkt_cones.h)
 
-    // vectors
-    double *d_b = nullptr, *d_x = nullptr, *d_dx = nullptr, *d_e = nullptr;
-    double *d_sin = nullptr, *d_sout = nullptr, *d_y = nullptr, *d_z = nullptr, *d_xp = nullptr;
-    double *d_qb = nullptr, *d_res_in = nullptr, *d_res_out = nullptr, *d_res_part = nullptr;   // residuals_update! on the device (N4)
-    double *d_red = nullptr, *d_red_part = nullptr;   // reduced-system algebra of kkt_solve! (N2): [x1;z1] | [x2;z2] | step | variables.x | scalars
-    double *h_scal_red = nullptr;                     // pinned read-back of its ten scalars
-    bool red_have_const = false;                      // (x2, z2) of the current factorisation is resident
     double *d_stage = nullptr;   // staging for host-supplied values
     int64_t *d_stage_idx = nullptr;
     int64_t stage_cap = 0;
     double *h_scal = nullptr;    // pinned read-back area
+    double *h_scal_red = nullptr;   // ... its second half: the ten scalars of the reduced solve
     int *h_flags = nullptr;
 
     hipkkt_host::GraphSlot g_factor;
     bool use_graph = true;
     bool runtime_ready = false;   // init_runtime done (streams, events, pinned areas)
-    PlanOptions plan_opts;       // as used for the current plan
-    // robust-order twin (minimum degree on K), created on the first factorisation that fails in the
-    // "variables last" order; every later factorisation still tries the fast order first
-    hipkkt_solver *fallback = nullptr;
-    // the twin's symbolic analysis runs on a host thread from the moment the cheap order is chosen (finish_create)
-    bool device_ready = false;      // (a twin:) init_runtime + setup_device already ran on the speculation thread
-    std::unique_ptr<hipkkt_solver> twin_pending;
-    std::future<std::string> twin_future;
-    std::shared_ptr<std::atomic<bool>> twin_cancel;   // set when the twin turns out not to be needed
-    std::shared_ptr<std::atomic<int>> twin_go;        // 0: the owner has not chosen its order yet, 1: cheap order chosen (the twin may take device memory), 2: not needed
-    bool using_fallback = false;
     bool profiling = false;
     bool profiling_no_extra = false;     // hipkkt_set_profiling(h, 2): the profiled refactorisations keep every far tile in its stage's own launch
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
     bool kval_event_pending = false;     // ev3 marks an asynchronous value update of the resident K on the main stream (hipkkt_set_hs_dev)
-    double t_last_factor = 0, t_last_solve = 0, t_acc_factor = 0, t_acc_solve = 0, t_last_update = 0;
-    int64_t n_factor = 0, n_solvecalls = 0, n_ldlsolves = 0, n_rhs_solved = 0;
     double last_eps = 0;
-    double prof_fb_flops = 0;
-    double prof_fb_ms = 0;               // last profiled refactorisation: the k_front_block launches
-    double prof_extra_tiles = 0, prof_extra_flops = 0;   // ... dense update tiles / flops that rode in them (HIPKKT_FB_EXTRA)
-    int prof_fb_launches = 0, prof_fb_panels = 0;
-    double prof_dense4_ms = 0, prof_dense4_flops = 0;   // last profiled refactorisation: k_update_dense<4,4> alone
-    int prof_dense4_launches = 0;
-    std::vector<double> prof_launch_ms, prof_launch_flops, prof_launch_tiles;   // per k_update_dense<4,4> launch of that refactorisation
     int64_t last_nreg = 0;
 
     // Device memory comes from a few slabs (bump allocation, 256-byte aligned) instead of one hipMalloc per array:
@@ -316,22 +239,24 @@ struct hipkkt_solver {
         d_stage_idx = dalloc<int64_t>(cap);
         stage_cap = cap;
     }
+    template <class F>
+    void for_each_graph_slot(F &&f) {    // every captured graph of the handle
+        f(g_factor); for (SolveCtx &C : ctx) { f(C.g_ldl); f(C.g_first); f(C.g_step); }
+    }
     ~hipkkt_solver() {
-        if (twin_cancel) twin_cancel->store(true);
-        if (twin_go && twin_go->load() == 0) twin_go->store(2);
-        if (twin_future.valid()) twin_future.wait();     // the thread reads twin_pending's image (a cancelled one ends at its next phase)
-        twin_pending.reset();
-        delete fallback;
+        if (twin.cancel) twin.cancel->store(true);
+        if (twin.go && twin.go->load() == 0) twin.go->store(2);
+        if (twin.future.valid()) twin.future.wait();     // the thread reads twin.pending's image (a cancelled one ends at its next phase)
+        twin.pending.reset();
+        delete twin.fallback;
         (void)hipSetDevice(device);
         // everything below goes back to the process-wide cache (runtime_pool.h): the streams must be idle first
         RuntimePool &rp = RuntimePool::get();
         if (stream) (void)hipStreamSynchronize(stream);
         for (SolveCtx &C : ctx)
             if (C.own_stream && C.stream) (void)hipStreamSynchronize(C.stream);
-        if (g_factor.exec) (void)hipGraphExecDestroy(g_factor.exec);
+        for_each_graph_slot([](hipkkt_host::GraphSlot &g) { if (g.exec) (void)hipGraphExecDestroy(g.exec); });
         for (SolveCtx &C : ctx) {
-            for (hipkkt_host::GraphSlot *g : {&C.g_ldl, &C.g_first, &C.g_step})
-                if (g->exec) (void)hipGraphExecDestroy(g->exec);
             rp.pinned_free(device, C.h_rs);
             rp.pinned_free(device, C.h_flags);
             for (hipEvent_t e : {C.ev_a, C.ev_b}) rp.event_put(device, e);
@@ -348,27 +273,36 @@ struct hipkkt_solver {
 
 namespace hipkkt_host {
 
-// seg_sync = [forward tickets | backward tickets] padded to whole 128-byte lines, then fdone [kSegSub = 8 arrays of nsuper],
-// then the error word (kernels.hip seg_sync())
-inline size_t seg_sync_ints(int nseg, int nsuper) { return (size_t)((2 * nseg + 31) & ~31) + 8 * (size_t)nsuper + 16; }
+// The words a sweep time-out leaves in an undefined state, per solve context (recover_from_sweep_failure re-arms what
+// alloc_solve_scratch cleared).  seg_sync = [forward tickets | backward tickets] padded to whole 128-byte lines, then fdone
+// [kSegSub = 8 arrays of nsuper], then the error word (kernels.hip seg_sync())
+struct SyncWords { size_t seg, front; };
+inline SyncWords sync_words(const hipkkt_solver *S) {
+    return {(size_t)((2 * S->sched.nseg + 31) & ~31) + 8 * (size_t)S->plan.nsuper + 16, (size_t)std::max(S->plan.front_sync_ints, 16)};
+}
 
 // hipkkt_setup.cpp
 void plan_cache_counts(int64_t *hits, int64_t *misses);   // process-wide cache of symbolic plans (same pattern + options)
 void init_runtime(hipkkt_solver *S);
 void setup_device(hipkkt_solver *S);
 int32_t finish_create(hipkkt_solver *S, const hipkkt_opts *opts, hipkkt_handle *out);
-// hipkkt_factor.cpp
-void enqueue_factor(hipkkt_solver *S, int static_enable, double eps_const, double eps_prop);
 // hipkkt_solve.cpp
-void enqueue_ldl_solve(hipkkt_solver *S, SolveCtx &C, const double *in, double *out, int *zero = nullptr, int nzero = 0);
-int32_t solve_many(hipkkt_solver *S, int nrhs, int ir_enable, double reltol, double abstol, int64_t max_iter, double stop_ratio,
-                   int64_t *ir_steps, double *const *out_dev, int nm);
+int32_t solve_many(hipkkt_solver *S, hipkkt_solver *T, int nrhs, const RefineOpts &ir, int64_t *ir_steps, double *const *out_dev, int nm);
 hipkkt_solver *solve_target(hipkkt_solver *S);
-int32_t kkt_solve_reduced_impl(hipkkt_solver *S, const double *rhs_x, const double *workz, const double *var_x, const double *in_dev,
-                               const double *scal_in, int32_t const_pending, double *lhs_x, double *lhs_z, double *lhs_dev,
-                               double *scal_out, int32_t ir_enable, double reltol, double abstol, int64_t max_iter, double stop_ratio,
-                               int64_t *ir_steps, const std::function<void(hipStream_t, const double *)> *after_reduce);
-void account_fallback_solve(hipkkt_solver *S, hipkkt_solver *T);
+// kkt_solve! around the two solves (hipkkt_kkt_solve_reduced*, hipkkt_step_*_dev): input either on the host or [rhs.x | workz | variables.x]
+// on the device; outputs whichever of them are set
+struct ReducedIn {
+    const double *rhs_x, *workz, *var_x, *in_dev;
+    static ReducedIn host(const double *rhs_x, const double *workz, const double *var_x) { return {rhs_x, workz, var_x, nullptr}; }
+    static ReducedIn device(const double *in_dev) { return {nullptr, nullptr, nullptr, in_dev}; }
+};
+struct ReducedScalars { const double *scal_in4; int32_t const_pending; };   // tau, kappa, rhs_tau, rhs_kappa
+struct ReducedOut {
+    double *lhs_x = nullptr, *lhs_z = nullptr, *lhs_dev = nullptr, *scal_out = nullptr;
+    int64_t *ir_steps = nullptr;
+    const std::function<void(hipStream_t, const double *)> *after_reduce = nullptr;   // enqueued behind every reduction, from the step in d_lhs
+};
+int32_t kkt_solve_reduced_impl(hipkkt_solver *S, const ReducedIn &in, const ReducedScalars &sc, const ReducedOut &out, const RefineOpts &ir);
 
 template <class F>
 void run_graphed(hipkkt_solver *S, hipStream_t stream, GraphSlot &slot, bool reusable, F &&enqueue) {
@@ -391,18 +325,6 @@ void run_graphed(hipkkt_solver *S, hipStream_t stream, GraphSlot &slot, bool reu
         slot.valid = true;
     }
     HK_CHECK(hipGraphLaunch(slot.exec, stream));
-}
-
-inline double slot_value(const hipkkt_solver *S, int slot) {
-    double v;
-    memcpy(&v, (const char *)S->h_scal + slot * sizeof(double), sizeof(double));
-    return v;  // the slot holds the raw bit pattern of a non-negative double (or NaN)
-}
-
-inline void read_scalars(hipkkt_solver *S) {
-    HK_CHECK(hipMemcpyAsync(S->h_flags, S->dp.flags, FL_COUNT * sizeof(int), hipMemcpyDeviceToHost, S->stream));
-    HK_CHECK(hipMemcpyAsync(S->h_scal, S->dp.scal, SC_COUNT * sizeof(double), hipMemcpyDeviceToHost, S->stream));
-    HK_CHECK(hipStreamSynchronize(S->stream));
 }
 
 }  // namespace hipkkt_host

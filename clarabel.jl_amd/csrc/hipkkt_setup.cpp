@@ -65,14 +65,14 @@ void init_runtime(hipkkt_solver *S) {
     {
         // test / experiment switches (hipkkt_debug_set; the production library keeps the defaults), latched per handle
         const DebugOpts &o = debug_opts();
-        S->fb_extra = o.fb_extra;            // false: every far stage applies all of its tiles in its own launch (A/B timing, bit-identity test)
-        S->fb_streamed = o.fb_stream;        // false: the pivot chain of k_front_block hands over L11^-T D^-1 after all 64 pivots (round-3 form)
-        S->fb_v2 = o.fb_v2 && S->fb_streamed;   // false: the first form of the front-batch kernel (front_block.hip; the round-3 chain exists only there)
+        S->fb.sw.extra = o.fb_extra;            // false: every far stage applies all of its tiles in its own launch (A/B timing, bit-identity test)
+        S->fb.sw.streamed = o.fb_stream;        // false: the pivot chain of k_front_block hands over L11^-T D^-1 after all 64 pivots (round-3 form)
+        S->fb.sw.v2 = o.fb_v2 && S->fb.sw.streamed;   // false: the first form of the front-batch kernel (front_block.hip; the round-3 chain exists only there)
 #ifndef HIPKKT_TESTING
-        S->fb_streamed = S->fb_v2 = true;    // (the production library does not contain the first form)
+        S->fb.sw.streamed = S->fb.sw.v2 = true;    // (the production library does not contain the first form)
 #endif
         S->accurate_threshold = o.accurate;  // largest |entry| of a wide block's explicit inverse above which its solves take a refinement step
-        S->force_twin = o.force_twin;        // tests: every successful factorisation in the cheap order counts as broken down (hipkkt_refactor)
+        S->twin.force = o.force_twin;        // tests: every successful factorisation in the cheap order counts as broken down (hipkkt_refactor)
     }
     static_assert(SC_COUNT * sizeof(double) <= RuntimePool::kPinned && sizeof(RefineState) <= RuntimePool::kPinned, "pinned chunk too small");
     for (hipEvent_t *e : {&S->ev0, &S->ev1, &S->ev2, &S->ev3, &S->ev_fork, &S->ev_join}) *e = (hipEvent_t)need(rp.event_get(S->device));
@@ -96,475 +96,12 @@ void init_runtime(hipkkt_solver *S) {
     }
 }
 
-
-// (re)builds every device-resident structure from S->plan and S->img (values included)
-static void build_front_batches(hipkkt_solver *S);
-static void order_far_stages(hipkkt_solver *S);
-static void split_gather_stages(hipkkt_solver *S);
-static int64_t plan_split_k(hipkkt_solver *S, std::vector<DenseGroup> &dg);
-void setup_device(hipkkt_solver *S) {
-    HK_CHECK(hipSetDevice(S->device));
-    for (GraphSlot *g : {&S->g_factor, &S->ctx[0].g_ldl, &S->ctx[0].g_first, &S->ctx[0].g_step, &S->ctx[1].g_ldl, &S->ctx[1].g_first,
-                         &S->ctx[1].g_step}) {
-        if (g->exec) (void)hipGraphExecDestroy(g->exec);
-        *g = GraphSlot();
-    }
-    if (!S->allocs.empty() && S->stream) (void)hipStreamSynchronize(S->stream);   // hipFree used to wait implicitly
-    for (auto &a : S->allocs) RuntimePool::get().dev_free(S->device, a.first, a.second);
-    S->allocs.clear();
-    S->slab_cur = nullptr;
-    S->slab_left = 0;
-    S->slv_items.clear(); S->bwd_items.clear(); S->reg_lvl_sn.clear(); S->pbwd_items.clear();
-    {
-        S->use_persist = !debug_opts().no_persist;
-        S->persist_allowed = S->use_persist;
-        S->persist_retry_at = -1;
-    }
-    S->soc_off.clear(); S->soc_of_sparse.clear();
-    S->nsoc = 0; S->soc_total = 0; S->wmax_all = 1;
-    S->stage_cap = 0; S->d_stage = nullptr; S->d_stage_idx = nullptr;
-    S->d_qb = S->d_res_in = S->d_res_out = S->d_res_part = nullptr;
-    S->d_red = S->d_red_part = nullptr;
-    S->cones = ConeState();   // (slab memory of an earlier set-up is gone: the device tables, the resident step, so the registration too)
-    S->red_have_const = false;
-
-    order_far_stages(S);
-    split_gather_stages(S);
-    HostPlan &P = S->plan;
-    const int N = P.N;
-    S->N = N;
-    S->nnzK = P.nnzK;
-    // solve items: 64-row blocks (kSlvRows in kernels.hip)
-    S->slv_lvl_ptr.assign(P.nlevels + 1, 0);
-    S->bwd_lvl_ptr.assign(P.nlevels + 1, 0);
-    S->p_off.assign(P.nsuper + 1, 0);
-    for (int s = 0; s < P.nsuper; s++) {
-        int w = P.sn_first[s + 1] - P.sn_first[s];
-        int64_t r = P.sn_rowptr[s + 1] - P.sn_rowptr[s];
-        int64_t nb = std::max<int64_t>(1, (r - w + 63) / 64);
-        S->p_off[s + 1] = S->p_off[s] + nb * w;
-    }
-    S->reg_lvl_ptr.assign(P.nlevels + 1, 0);
-    const bool allow_narrow = true;
-    // ---- segments of the persistent sweeps = level ranges between two front kernels; inside a segment the wide bottom
-    //      levels (thousands of leaf supernodes) are cheaper as one launch per level, the persistent kernels take over
-    //      from the first level with fewer than kPersistMaxItems items (seg_lstar)
-    std::vector<int> dep_ptr(P.nsuper + 1, 0), dep_idx, sn_nitems(P.nsuper, 0), sn_bparent(P.nsuper, -1);
-    std::vector<int> rows_seg;
-    {
-        S->seg_of_level.assign(P.nlevels, 0);
-        std::vector<char> boundary(P.nlevels + 1, 0);
-        for (const FrontDesc &F : P.fronts) boundary[F.level_last] = 1;   // the front runs after regular level level_last
-        int sg = 0;
-        for (int l = 0; l < P.nlevels; l++) { S->seg_of_level[l] = sg; if (boundary[l]) sg++; }
-        S->nseg = sg + 1;
-        std::vector<int> lvl_items(P.nlevels, 0);      // forward items of the regular (non-front) supernodes of a level
-        for (int s = 0; s < P.nsuper; s++) {
-            if (P.sn_front[s] >= 0) continue;
-            const int64_t r = P.sn_rowptr[s + 1] - P.sn_rowptr[s];
-            const int w = P.sn_first[s + 1] - P.sn_first[s];
-            lvl_items[P.sn_level[s]] += (int)std::max<int64_t>(1, (r - w + 63) / 64);
-        }
-        const int kPersistMaxItems = 1024;
-        S->seg_lo.assign(S->nseg, P.nlevels); S->seg_hi.assign(S->nseg, -1); S->seg_lstar.assign(S->nseg, 0);
-        for (int l = 0; l < P.nlevels; l++) {
-            const int g = S->seg_of_level[l];
-            S->seg_lo[g] = std::min(S->seg_lo[g], l);
-            S->seg_hi[g] = std::max(S->seg_hi[g], l);
-        }
-        for (int g = 0; g < S->nseg; g++) {
-            int ls = S->seg_lo[g];
-            while (ls <= S->seg_hi[g] && lvl_items[ls] >= kPersistMaxItems) ls++;
-            S->seg_lstar[g] = ls;
-        }
-    }
-    // Level lists of the per-level solve kernels, appended to slv_items / bwd_items / reg_lvl_sn.  Variant 0 leaves out the
-    // panels of the fronts (the persistent front kernels solve those); variant 1 holds EVERY supernode and is what a
-    // handle falls back to after a persistent sweep timed out (front kernels included: no persistent kernel at all).
-    // On a level that gets its own launches the NARROW supernodes (<= kNarrowW columns, <= kNarrowR rows below the
-    // block: the leaves) are listed first and solved one THREAD each (k_fwd_narrow / k_bwd_narrow); they have no items.
-    std::vector<char> has_child(P.nsuper, 0);
-    for (int c = 0; c < P.nsuper; c++)
-        if (P.sn_parent[c] >= 0) has_child[P.sn_parent[c]] = 1;
-    auto build_level_lists = [&](bool with_fronts, std::vector<int> &slv_ptr, std::vector<int> &bwd_ptr, std::vector<int> &reg_ptr,
-                                 std::vector<int> &nnarrow, std::vector<int> &wnarrow) {
-        slv_ptr.assign(P.nlevels + 1, (int)S->slv_items.size());
-        bwd_ptr.assign(P.nlevels + 1, (int)S->bwd_items.size());
-        reg_ptr.assign(P.nlevels + 1, (int)S->reg_lvl_sn.size());
-        nnarrow.assign(P.nlevels, 0);
-        wnarrow.assign(P.nlevels, 1);
-        std::vector<int> nar, reg;
-        for (int l = 0; l < P.nlevels; l++) {
-            const bool own_launches = with_fronts || l < S->seg_lstar[S->seg_of_level[l]];
-            nar.clear(); reg.clear();
-            bool all_tiny = true;    // every supernode of the level has <= 4 columns and <= 16 rows below the block
-            for (int q = P.lvl_ptr[l]; q < P.lvl_ptr[l + 1]; q++) {
-                int s = P.lvl_sn[q];
-                int w = P.sn_first[s + 1] - P.sn_first[s];
-                S->wmax_all = std::max(S->wmax_all, w);
-                if (!with_fronts && P.sn_front[s] >= 0) continue;      // solved by the persistent front kernels
-                int64_t r = P.sn_rowptr[s + 1] - P.sn_rowptr[s];
-                all_tiny = all_tiny && w <= 4 && r - w <= 16;
-            }
-            for (int q = P.lvl_ptr[l]; q < P.lvl_ptr[l + 1]; q++) {
-                int s = P.lvl_sn[q];
-                int w = P.sn_first[s + 1] - P.sn_first[s];
-                if (!with_fronts && P.sn_front[s] >= 0) continue;
-                int64_t r = P.sn_rowptr[s + 1] - P.sn_rowptr[s];
-                // one thread per supernode pays for every gather of a child's update vector with a serial memory round trip:
-                // a level goes to the thread kernels as a whole when all of it is tiny; otherwise only its childless
-                // supernodes (leaves: nothing to gather) do, up to kNarrowW x kNarrowR
-                // (a thread walks its w x (r - w) panel entries one strided load after the other: bounded work per thread, and
-                // only worth it where the workgroup-per-item kernel would need several rounds of the chip: >= 2048 leaves)
-                const bool thr = all_tiny || (!has_child[s] && w <= kNarrowW && r - w <= kNarrowR && (int64_t)w * (r - w) <= 128);
-                (allow_narrow && own_launches && thr ? nar : reg).push_back(s);
-            }
-            if (nar.size() < (all_tiny ? 256u : 2048u)) { reg.insert(reg.end(), nar.begin(), nar.end()); std::sort(reg.begin(), reg.end()); nar.clear(); }
-            nnarrow[l] = (int)nar.size();
-            for (int s : nar) wnarrow[l] = std::max(wnarrow[l], P.sn_first[s + 1] - P.sn_first[s]);
-            S->reg_lvl_sn.insert(S->reg_lvl_sn.end(), nar.begin(), nar.end());
-            for (int s : reg) {
-                int w = P.sn_first[s + 1] - P.sn_first[s];
-                int64_t r = P.sn_rowptr[s + 1] - P.sn_rowptr[s];
-                int nb = (int)std::max<int64_t>(1, (r - w + 63) / 64);
-                for (int b = 0; b < nb; b++) S->slv_items.push_back({s, b});
-                if (nb > 1)
-                    for (int b = 0; b < nb; b++) S->bwd_items.push_back({s, b});
-                S->reg_lvl_sn.push_back(s);
-            }
-            slv_ptr[l + 1] = (int)S->slv_items.size();
-            bwd_ptr[l + 1] = (int)S->bwd_items.size();
-            reg_ptr[l + 1] = (int)S->reg_lvl_sn.size();
-        }
-    };
-    build_level_lists(false, S->slv_lvl_ptr, S->bwd_lvl_ptr, S->reg_lvl_ptr, S->lvl_nnarrow, S->lvl_wnarrow);
-    if (!P.fronts.empty() || S->nseg > 0) build_level_lists(true, S->all_slv_lvl_ptr, S->all_bwd_lvl_ptr, S->all_reg_lvl_ptr, S->all_lvl_nnarrow, S->all_lvl_wnarrow);
-    // ---- persistent sweeps: dependency lists, backward item order
-    {
-        auto seg_of = [&](int s) { return S->seg_of_level[P.sn_level[s]]; };
-        auto persistent = [&](int s) { return P.sn_level[s] >= S->seg_lstar[seg_of(s)]; };
-        std::vector<std::vector<int>> kids(P.nsuper);
-        for (int c = 0; c < P.nsuper; c++) {
-            const int p = P.sn_parent[c];
-            if (P.sn_front[c] >= 0) continue;
-            const int64_t r = P.sn_rowptr[c + 1] - P.sn_rowptr[c];
-            const int w = P.sn_first[c + 1] - P.sn_first[c];
-            sn_nitems[c] = (int)std::max<int64_t>(1, (r - w + 63) / 64);
-            if (p >= 0 && P.sn_front[p] < 0 && seg_of(p) == seg_of(c) && persistent(c) && persistent(p)) {
-                kids[p].push_back(c);
-                sn_bparent[c] = p;
-            }
-        }
-        for (int s = 0; s < P.nsuper; s++) {
-            dep_ptr[s + 1] = dep_ptr[s] + (int)kids[s].size();
-            dep_idx.insert(dep_idx.end(), kids[s].begin(), kids[s].end());
-        }
-        // tagged hand-off of the persistent backward sweep: mark the rows whose x is produced inside the same launch
-        {
-            auto in_seg_kernel = [&](int s) { return P.sn_front[s] < 0 && persistent(s); };
-            std::vector<int> col_sn(N, -1);
-            for (int c = 0; c < P.nsuper; c++)
-                for (int k = P.sn_first[c]; k < P.sn_first[c + 1]; k++) col_sn[k] = c;
-            rows_seg.assign(P.sn_rows.begin(), P.sn_rows.end());
-            for (int s = 0; s < P.nsuper; s++) {
-                if (!in_seg_kernel(s)) continue;
-                for (int64_t slot = P.sn_rowptr[s]; slot < P.sn_rowptr[s + 1]; slot++) {
-                    const int a = col_sn[P.sn_rows[slot]];
-                    if (a != s && a >= 0 && in_seg_kernel(a) && seg_of(a) == seg_of(s)) rows_seg[(size_t)slot] = P.sn_rows[slot] | 0x40000000;
-                }
-            }
-        }
-        // forward segments: slv_items is level-ordered, a segment is a level range
-        S->fseg_ptr.assign(2 * S->nseg, 0);   // [2g] first persistent item, [2g+1] end, of segment g
-        for (int g = 0; g < S->nseg; g++) {
-            const int ls = std::min(S->seg_lstar[g], P.nlevels);
-            S->fseg_ptr[2 * g] = S->seg_hi[g] >= 0 ? S->slv_lvl_ptr[std::min(ls, S->seg_hi[g] + 1)] : 0;
-            S->fseg_ptr[2 * g + 1] = S->seg_hi[g] >= 0 ? S->slv_lvl_ptr[S->seg_hi[g] + 1] : 0;
-        }
-        // backward items: segments in DESCENDING order of level; inside a segment levels descending, partial
-        // blocks of a level before its finalisers
-        S->bseg_ptr.assign(S->nseg + 1, 0);
-        for (int g = S->nseg - 1; g >= 0; g--) {
-            for (int l = P.nlevels - 1; l >= 0; l--) {
-                if (S->seg_of_level[l] != g || l < S->seg_lstar[g]) continue;
-                for (int q = S->reg_lvl_ptr[l]; q < S->reg_lvl_ptr[l + 1]; q++) {
-                    const int s = S->reg_lvl_sn[q];
-                    if (sn_nitems[s] > 1)
-                        for (int b = 0; b < sn_nitems[s]; b++) S->pbwd_items.push_back({s, b});
-                }
-                for (int q = S->reg_lvl_ptr[l]; q < S->reg_lvl_ptr[l + 1]; q++) S->pbwd_items.push_back({S->reg_lvl_sn[q], -1});
-            }
-            S->bseg_ptr[S->nseg - g] = (int)S->pbwd_items.size();   // bseg_ptr is indexed by launch order
-        }
-    }
-    std::vector<signed char> sgn_perm(N), kdiag(S->nnzK, 0);
-    for (int k = 0; k < N; k++) sgn_perm[k] = (signed char)(S->img.dsigns[P.perm[k]] >= 0 ? 1 : -1);
-    for (int j = 0; j < N; j++)
-        for (int64_t q = S->img.colptr[j]; q < S->img.colptr[j + 1]; q++)
-            if (S->img.rowval[q] == j) kdiag[q] = (signed char)(S->img.dsigns[j] >= 0 ? 1 : -1);
-
-    DevPlan &D = S->dp;
-    D.sn_first = S->upload(P.sn_first);
-    D.sn_rowptr = S->upload(P.sn_rowptr);
-    D.sn_rows = S->upload(P.sn_rows);
-    D.sn_panel = S->upload(P.sn_panel);
-    D.sn_diag = S->upload(P.sn_diag);
-    D.u_off = S->upload(P.u_off);
-    D.p_off = S->upload(S->p_off);
-    D.lt_off = S->upload(P.lt_off);
-    D.bwd_items = S->upload(S->bwd_items);
-    D.lvl_sn = S->upload(S->reg_lvl_sn);
-    D.perm = S->upload(P.perm);
-    D.sgn_perm = S->upload(sgn_perm);
-    {
-        // diagonal blocks wider than 16 columns (and at most 64, the blocked kernel's size) are inverted by
-        // k_invert_diag_wide, the rest by the one-wave kernel with LDS sized for the widest of them
-        std::vector<int> small, wide;
-        S->inv_wsmall = 1;
-        for (int s = 0; s < P.nsuper; s++) {
-            const int w = P.sn_first[s + 1] - P.sn_first[s];
-            if (w > 16 && w <= 64) wide.push_back(s);
-            else { small.push_back(s); S->inv_wsmall = std::max(S->inv_wsmall, w); }
-        }
-        S->inv_nsmall = (int)small.size();
-        S->inv_nwide = (int)wide.size();
-        small.insert(small.end(), wide.begin(), wide.end());
-        D.inv_list = S->upload(small);
-    }
-    D.fac_items = S->upload(P.fac_items);
-    {
-        std::vector<FacRec> recs(P.fac_items.size());
-        for (size_t q = 0; q < recs.size(); q++) {
-            const int s = P.fac_items[q].sn;
-            recs[q] = {P.sn_panel[s], P.sn_diag[s], P.lt_off[s], P.sn_first[s], P.sn_first[s + 1] - P.sn_first[s],
-                       (int32_t)(P.sn_rowptr[s + 1] - P.sn_rowptr[s]), P.fac_items[q].blk};
-        }
-        D.fac_recs = S->upload(recs);
-    }
-    D.slv_items = S->upload(S->slv_items);
-    D.rel = S->upload(P.rel);
-    D.upd_tasks = S->upload(P.upd_tasks);
-    D.upd_groups = S->upload(P.upd_groups);
-    std::vector<DenseGroup> dg(P.upd_groups.size());       // uploaded after the front batches are known (plan_split_k appends to it)
-    {
-        const bool no_full_tiles = !debug_opts().full_tiles;   // bit-identity test of the full-tile core
-        for (size_t q = 0; q < dg.size(); q++) {
-            const UpdGroup &G = P.upd_groups[q];
-            const int t = G.tgt;
-            const int rt = (int)(P.sn_rowptr[t + 1] - P.sn_rowptr[t]);
-            // pad bit 0: a FULL tile (dense_tile.h dense_tile_core_full): 64 x 64, every task lands contiguously on all of it
-            bool full = G.dense == 1 && rt - G.row_base >= kUpdRows && P.sn_first[t + 1] - P.sn_first[t] == 64 && !no_full_tiles;
-            for (int u = G.task_begin; u < G.task_end && full; u++) {
-                const UpdTask &T = P.upd_tasks[u];
-                const int K = P.sn_first[T.src + 1] - P.sn_first[T.src];
-                full = !(T.geom & (1 << 17)) && (T.geom & 0xFFFF) == 0 && T.nrows >= 64 && T.ncols >= 64 && K >= 8 && (K & 7) == 0;
-            }
-            dg[q] = {P.sn_panel[t] + G.row_base, rt, std::min(kUpdRows, rt - G.row_base), P.sn_first[t + 1] - P.sn_first[t],
-                     G.task_begin, G.task_end, full ? 1 : 0};
-        }
-    }
-    // (never empty: the dense tile core requests "the next task's map" unconditionally and reads map 0 for tasks without one)
-    D.upd_tmap = P.upd_tmap.size() >= 128 ? S->upload(P.upd_tmap) : S->upload(std::vector<int16_t>(128, (int16_t)-1));
-    {
-        std::vector<DenseTask> dt(P.upd_tasks.size());
-        for (size_t q = 0; q < dt.size(); q++) {
-            const UpdTask &T = P.upd_tasks[q];
-            const int s = T.src;
-            dt[q] = {P.sn_panel[s], (int32_t)((P.sn_rowptr[s + 1] - P.sn_rowptr[s]) * 8), P.sn_first[s + 1] - P.sn_first[s],
-                     P.sn_first[s], T.row_lo, T.nrows, T.col_lo, T.ncols, T.geom, T.vt_begin, 0};
-        }
-        D.dtasks = S->upload(dt);
-    }
-    D.gath_tgt = S->upload(P.gath_tgt);
-    D.gath_pptr = S->upload(P.gath_pptr);
-    {
-        std::vector<GathPair> gp(P.gath_src.size());
-        for (size_t q = 0; q < gp.size(); q++) {
-            const int s = P.gath_sn[q];
-            gp[q] = {P.gath_src[q], P.gath_dj[q], (int32_t)(P.sn_rowptr[s + 1] - P.sn_rowptr[s]), P.sn_first[s + 1] - P.sn_first[s], P.sn_first[s]};
-        }
-        D.gath_pairs = S->upload(gp);
-        std::vector<int64_t> heavy;
-        S->gath_heavy_ptr.assign(P.nlevels + 1, 0);
-        S->gath_heavy_split.assign(std::max(P.nlevels, 1), 0);
-        for (int l = 0; l < P.nlevels; l++) {
-            const int64_t e_split = S->gath_split[l] >= 0 ? P.gath_stage_ptr[l] + S->gath_split[l] : P.gath_stage_ptr[l + 1];
-            for (int64_t e = P.gath_stage_ptr[l]; e < P.gath_stage_ptr[l + 1]; e++)
-                if (P.gath_pptr[e + 1] - P.gath_pptr[e] > kGathHeavy) {
-                    heavy.push_back(e);
-                    if (e < e_split) S->gath_heavy_split[l]++;
-                }
-            S->gath_heavy_ptr[l + 1] = (int64_t)heavy.size();
-        }
-        D.gath_heavy = S->upload(heavy);
-    }
-    D.g_ptr = S->upload(P.g_ptr);
-    D.g_idx = S->upload(P.g_idx);
-    D.kmap = S->upload(P.kmap);
-    D.kdiag_sign = S->upload(kdiag);
-    D.sym_rowptr = S->upload(P.sym_rowptr);
-    D.sym_col = S->upload(P.sym_col);
-    D.sym_q = S->upload(P.sym_q);
-    {
-        std::vector<int> lr;
-        const int thr = long_row_threshold();
-        for (int i = 0; i < N; i++)
-            if (P.sym_rowptr[i + 1] - P.sym_rowptr[i] > thr) lr.push_back(i);
-        D.long_rows = S->upload(lr);
-        D.n_long_rows = (int)lr.size();
-    }
-    {
-        // dense triangles of K (symbolic.h HostPlan::dtri): one workgroup of k_spmv_dense_tri per 64 rows of a triangle
-        std::vector<DenseTriStrip> strips;
-        for (const DenseTri &T : P.dtri)
-            for (int i0 = 0; i0 < T.d; i0 += 64) strips.push_back(DenseTriStrip{T.c0, T.d, i0, 0, T.col0});
-        D.dtri_strips = S->upload(strips);
-        D.n_dtri_strips = (int)strips.size();
-        D.dtri_col = S->upload(P.dtri_col);
-        D.dense_acc = nullptr;                 // per solve context (below)
-    }
-    D.front_panels = S->upload(P.front_panels);
-    D.front_gptr = S->upload(P.front_gptr);
-    D.front_gidx = S->upload(P.front_gidx);
-    D.pbwd_items = S->upload(S->pbwd_items);
-    {
-        std::vector<int> dep_total(P.nsuper, 0);
-        for (int s = 0; s < P.nsuper; s++)
-            for (int q = dep_ptr[s]; q < dep_ptr[s + 1]; q++) dep_total[s] += sn_nitems[dep_idx[q]];
-        D.dep_total = S->upload(dep_total);
-    }
-    D.sn_nitems = S->upload(sn_nitems);
-    D.sn_bparent = S->upload(sn_bparent);
-    D.nseg = S->nseg;
-    {
-        D.seg_ticket = 3;                                  // bit 0: forward sweep, bit 1: backward sweep take their items by atomic ticket
-        D.spin_limit = debug_opts().spin_limit >= 0 ? (unsigned)debug_opts().spin_limit : (1u << 20);   // tests force a sweep time-out with a tiny bound
-#ifdef HIPKKT_TESTING
-        D.dbg = debug_opts().debug_flags;                  // timing experiments only: results are WRONG when set (device_plan.h DevPlan::dbg)
-        if (D.dbg) fprintf(stderr, "hipkkt: DEBUG_FLAGS = %d: timing experiment, the results of this handle are WRONG\n", D.dbg);
-#else
-        D.dbg = 0;
-#endif
-        D.sn_polish = S->dalloc<int>((size_t)std::max(P.nsuper, 1));
-        fill_async(S->stream, D.sn_polish, 0, (size_t)std::max(P.nsuper, 1) * sizeof(int));
-        D.polish_tau = S->accurate_threshold;
-    }
-    {
-        const size_t nsync = seg_sync_ints(S->nseg, P.nsuper);
-        D.seg_sync = S->dalloc<int>(nsync);
-        fill_async(S->stream, D.seg_sync, 0, nsync * sizeof(int));
-    }
-    D.front_sync = S->dalloc<int>(std::max(P.front_sync_ints, 16));
-    fill_async(S->stream, D.front_sync, 0, (size_t)std::max(P.front_sync_ints, 16) * sizeof(int));
-    build_front_batches(S);
-    const int64_t split_scratch = plan_split_k(S, dg);
-    S->split_scratch_doubles = split_scratch;
-    D.dgroups = S->upload(dg);
-    D.kval = S->upload(S->img.nzval);
-    D.Lx = S->dalloc<double>(P.panel_doubles + split_scratch);
-    if (split_scratch) fill_async(S->stream, D.Lx + P.panel_doubles, 0, (size_t)split_scratch * sizeof(double));
-    D.Ldiag = S->dalloc<double>(P.diag_doubles);
-    D.Linv = S->dalloc<double>(P.diag_doubles);
-    D.LinvT = S->dalloc<double>(P.diag_doubles);
-    D.LT = S->dalloc<double>(P.lt_off[P.nsuper]);
-    D.SbInv = S->dalloc<double>(P.sbinv_doubles);
-    fill_async(S->stream, D.SbInv, 0, (size_t)std::max<int64_t>(P.sbinv_doubles, 1) * sizeof(double));
-    D.D = S->dalloc<double>(N);
-    D.Dinv = S->dalloc<double>(N);
-    D.ubuf = S->dalloc<double>(P.ubuf_len);
-    D.pbuf = S->dalloc<double>(S->p_off[P.nsuper]);
-    {
-        // slots start out all-zero = invalid in every epoch
-        const size_t nx = (size_t)std::max(N, 1), np_ = (size_t)std::max<int64_t>(S->p_off[P.nsuper], 1);
-        D.xseg = (FrontSlot *)S->dalloc<double>(2 * nx);
-        D.pseg = (FrontSlot *)S->dalloc<double>(2 * np_);
-        fill_async(S->stream, D.xseg, 0, 16 * nx);
-        fill_async(S->stream, D.pseg, 0, 16 * np_);
-        D.seg_epoch = S->dalloc<int>(4);
-        fill_async(S->stream, D.seg_epoch, 0, 4 * sizeof(int));
-        D.rows_seg = S->upload(rows_seg);
-    }
-    D.scal = S->dalloc<double>(SC_COUNT);
-    D.flags = S->dalloc<int>(FL_COUNT);
-    fill_async(S->stream, D.scal, 0, SC_COUNT * sizeof(double));
-    fill_async(S->stream, D.flags, 0, FL_COUNT * sizeof(int));
-    fill_async(S->stream, D.Dinv, 0, (size_t)std::max(N, 1) * sizeof(double));
-    fill_async(S->stream, D.Ldiag, 0, (size_t)std::max<int64_t>(P.diag_doubles, 1) * sizeof(double));
-
-    S->d_diag_full = S->upload(S->img.diag_full);
-    if (S->l1) {
-        S->d_mapHs = S->upload(S->img.mapHs);
-        S->d_mapP = S->upload(S->img.mapP);
-        S->d_mapA = S->upload(S->img.mapA);
-        // concatenated SOC expansion maps
-        std::vector<int64_t> uidx, vidx, didx;
-        std::vector<int> coneof;
-        S->soc_of_sparse.assign(S->img.smaps.size(), -1);
-        for (size_t i = 0; i < S->img.smaps.size(); i++) {
-            const SparseMap &sm = S->img.smaps[i];
-            if (sm.kind != 1) continue;
-            S->soc_of_sparse[i] = S->nsoc;
-            S->soc_off.push_back((int64_t)uidx.size());
-            for (size_t q = 0; q < sm.vec[0].size(); q++) {
-                uidx.push_back(sm.vec[0][q]);
-                vidx.push_back(sm.vec[1][q]);
-                coneof.push_back(S->nsoc);
-            }
-            didx.push_back(sm.D[0]);
-            didx.push_back(sm.D[1]);
-            S->nsoc++;
-        }
-        S->soc_off.push_back((int64_t)uidx.size());
-        S->soc_total = (int64_t)uidx.size();
-        S->d_soc_uidx = S->upload(uidx);
-        S->d_soc_vidx = S->upload(vidx);
-        S->d_soc_didx = S->upload(didx);
-        S->d_soc_cone = S->upload(coneof);
-        S->d_soc_u = S->dalloc<double>(S->soc_total);
-        S->d_soc_v = S->dalloc<double>(S->soc_total);
-        S->d_soc_eta2 = S->dalloc<double>(S->nsoc);
-    }
-    for (int c = 0; c < kNumCtx; c++) {
-        SolveCtx &C = S->ctx[c];
-        for (double **v : {&C.d_b, &C.d_x0, &C.d_x1, &C.d_e, &C.d_corr, &C.d_y, &C.d_z, &C.d_xp}) {
-            *v = S->dalloc<double>(N);
-            fill_async(S->stream, *v, 0, (size_t)std::max(N, 1) * sizeof(double));
-        }
-        C.d_rs = (RefineState *)S->dalloc<double>(sizeof(RefineState) / sizeof(double) + 1);
-        fill_async(S->stream, C.d_rs, 0, sizeof(RefineState));
-        C.dp = D;
-        if (D.n_dtri_strips > 0) {
-            C.dp.dense_acc = S->dalloc<double>(N);     // rows outside the triangles stay 0 for ever, the others are rewritten by every SpMV
-            fill_async(S->stream, C.dp.dense_acc, 0, (size_t)std::max(N, 1) * sizeof(double));
-        }
-        if (c > 0) {   // private copies of everything a solve writes besides its vectors
-            const size_t nx = (size_t)std::max(N, 1), np_ = (size_t)std::max<int64_t>(S->p_off[P.nsuper], 1);
-            const size_t nsync = seg_sync_ints(S->nseg, P.nsuper), nfs = (size_t)std::max(P.front_sync_ints, 16);
-            C.dp.ubuf = S->dalloc<double>(P.ubuf_len);
-            C.dp.pbuf = S->dalloc<double>(S->p_off[P.nsuper]);
-            C.dp.xseg = (FrontSlot *)S->dalloc<double>(2 * nx);
-            C.dp.pseg = (FrontSlot *)S->dalloc<double>(2 * np_);
-            fill_async(S->stream, C.dp.xseg, 0, 16 * nx);
-            fill_async(S->stream, C.dp.pseg, 0, 16 * np_);
-            C.dp.seg_epoch = S->dalloc<int>(4);
-            fill_async(S->stream, C.dp.seg_epoch, 0, 4 * sizeof(int));
-            C.dp.seg_sync = S->dalloc<int>(nsync);
-            fill_async(S->stream, C.dp.seg_sync, 0, nsync * sizeof(int));
-            C.dp.front_sync = S->dalloc<int>(nfs);
-            fill_async(S->stream, C.dp.front_sync, 0, nfs * sizeof(int));
-            C.dp.scal = S->dalloc<double>(SC_COUNT);
-            C.dp.flags = S->dalloc<int>(FL_COUNT);
-            fill_async(S->stream, C.dp.scal, 0, SC_COUNT * sizeof(double));
-            fill_async(S->stream, C.dp.flags, 0, FL_COUNT * sizeof(int));
-        }
-        C.ir_used = false;
-        C.h_rs->cur = 0;
-    }
-    // legacy names = context 0
-    S->d_b = S->ctx[0].d_b; S->d_x = S->ctx[0].d_x0; S->d_dx = S->ctx[0].d_x1; S->d_e = S->ctx[0].d_e;
-    S->d_sin = S->ctx[0].d_b; S->d_sout = S->ctx[0].d_corr; S->d_y = S->ctx[0].d_y; S->d_z = S->ctx[0].d_z; S->d_xp = S->ctx[0].d_xp;
-    S->ensure_stage(std::max<int64_t>(1024, std::max<int64_t>(S->img.nHs, N)));
-    HK_CHECK(hipStreamSynchronize(S->stream));
+// device array of n elements (at least one), cleared on the handle's stream
+template <class T>
+static T *zeroed(hipkkt_solver *S, size_t n) {
+    T *p = S->dalloc<T>(n);
+    fill_async(S->stream, p, 0, std::max<size_t>(n, 1) * sizeof(T));
+    return p;
 }
 
 // Far stage of every front batch whose successor (the next batch of the same front) follows at once: its dense tiles are reordered
@@ -576,15 +113,15 @@ static void order_far_stages(hipkkt_solver *S) {
     const HostPlan &P = S->plan;
     const auto hb = front_batches(P, S->plan_opts.update_policy, kFbMax);
     const size_t nbh = hb.size();
-    S->next_batch.assign(nbh, hipkkt_solver::NextBatch());
-    if (!S->fb_extra || !debug_opts().front_block) return;
+    S->fb.next.assign(nbh, NextBatch());
+    if (!S->fb.sw.extra || !debug_opts().front_block) return;
     std::vector<std::vector<int>> panel_batch(P.fronts.size());
     for (size_t fi = 0; fi < P.fronts.size(); fi++) panel_batch[fi].assign((size_t)P.fronts[fi].np, -1);
     for (size_t q = 0; q < nbh; q++)
         for (int t = 0; t < hb[q].nb; t++) panel_batch[(size_t)hb[q].front][(size_t)(hb[q].p0 + t)] = (int)q;
     for (size_t b = 0; b < nbh; b++) {
         const bool next = b + 1 < nbh && hb[b + 1].front == hb[b].front && hb[b + 1].p0 == hb[b].p0 + hb[b].nb;
-        hipkkt_solver::NextBatch &A = S->next_batch[b];
+        NextBatch &A = S->fb.next[b];
         const int l = hb[b].level_last, g0 = P.upd_stage_ptr[l], nd = P.upd_stage_ndense[l];
         const FrontDesc &F = P.fronts[(size_t)hb[b].front];
         auto near = [&](const UpdGroup &G) {
@@ -620,7 +157,7 @@ constexpr int64_t kGatherSplitMin = 1000000;   // (200 000 at first: a batch of 
 constexpr int64_t kGatherSortMin = 50000;
 static void split_gather_stages(hipkkt_solver *S) {
     HostPlan &P = S->plan;
-    S->gath_split.assign(std::max(P.nlevels, 1), -1);
+    S->split.gath.assign(std::max(P.nlevels, 1), -1);
     const int B = P.update_batch_used;
     const bool may_split = S->plan_opts.update_policy == 2 && B >= 2 && debug_opts().gather_overlap;
     for (int l = 0; l < P.nlevels; l++) {
@@ -661,7 +198,7 @@ static void split_gather_stages(hipkkt_solver *S) {
         std::copy(src.begin(), src.end(), P.gath_src.begin() + p0);
         std::copy(dj.begin(), dj.end(), P.gath_dj.begin() + p0);
         std::copy(sn.begin(), sn.end(), P.gath_sn.begin() + p0);
-        if (nfar > 0) S->gath_split[l] = ne - nfar;
+        if (nfar > 0) S->split.gath[l] = ne - nfar;
         if (verbose()) fprintf(stderr, "hipkkt: gather stage %d: %lld entries sorted by source, %lld of them deferred to the side stream (targets beyond level %d)\n", l, (long long)ne, (long long)nfar, l + B);
     }
 }
@@ -675,16 +212,16 @@ static void split_gather_stages(hipkkt_solver *S) {
 // scratch doubles needed.
 static int64_t plan_split_k(hipkkt_solver *S, std::vector<DenseGroup> &dg) {
     const HostPlan &P = S->plan;
-    S->split_group_begin.assign(std::max(P.nlevels, 1), 0);
-    S->split_group_count.assign(std::max(P.nlevels, 1), 0);
-    S->split_rec_ptr.assign(P.nlevels + 1, 0);
+    S->split.group_begin.assign(std::max(P.nlevels, 1), 0);
+    S->split.group_count.assign(std::max(P.nlevels, 1), 0);
+    S->split.rec_ptr.assign(P.nlevels + 1, 0);
     std::vector<SplitRec> recs;
     int64_t scratch_max = 0;
-    if (!debug_opts().split_k) { S->d_split_recs = S->upload(recs); return 0; }   // (A/B timing, comparison test)
+    if (!debug_opts().split_k) { S->split.d_recs = S->upload(recs); return 0; }   // (A/B timing, comparison test)
     for (int l = 0; l < P.nlevels; l++) {
-        S->split_rec_ptr[l + 1] = S->split_rec_ptr[l];
+        S->split.rec_ptr[l + 1] = S->split.rec_ptr[l];
         const int g0 = P.upd_stage_ptr[l], nd = P.upd_stage_ndense[l];
-        if (nd == 0 || S->lvl_fb[l] != -1) continue;
+        if (nd == 0 || S->fb.lvl[l] != -1) continue;
         int64_t ntasks = 0;
         for (int g = g0; g < g0 + nd; g++) ntasks += dg[g].task_end - dg[g].task_begin;
         // chunk size = the stage's typical tile (average contributions per tile, at least 4).  Only launches of the one-wavefront-
@@ -696,7 +233,7 @@ static int64_t plan_split_k(hipkkt_solver *S, std::vector<DenseGroup> &dg) {
         for (int g = g0; g < g0 + nd; g++) max_nt = std::max(max_nt, dg[g].task_end - dg[g].task_begin);
         if (nd <= 384 || max_nt < 2 * chunk + 6) continue;
         int64_t scratch = 0;
-        S->split_group_begin[l] = (int)dg.size();
+        S->split.group_begin[l] = (int)dg.size();
         for (int g = g0; g < g0 + nd; g++) {
             const int nt = dg[g].task_end - dg[g].task_begin;
             const int parts = std::min(16, nt / chunk);
@@ -709,11 +246,11 @@ static int64_t plan_split_k(hipkkt_solver *S, std::vector<DenseGroup> &dg) {
             }
             dg[g].wt = 0;                                   // switched off
         }
-        S->split_group_count[l] = (int)dg.size() - S->split_group_begin[l];
-        S->split_rec_ptr[l + 1] = (int)recs.size();
+        S->split.group_count[l] = (int)dg.size() - S->split.group_begin[l];
+        S->split.rec_ptr[l + 1] = (int)recs.size();
         scratch_max = std::max(scratch_max, scratch);
     }
-    S->d_split_recs = S->upload(recs);
+    S->split.d_recs = S->upload(recs);
     if (verbose() && !recs.empty())
         fprintf(stderr, "hipkkt: split-K: %zu target tiles cut into %zu chunks, %.1f MB of partial tiles\n", recs.size(), dg.size() - P.upd_groups.size(), scratch_max * 8e-6);
     return scratch_max;
@@ -722,10 +259,9 @@ static int64_t plan_split_k(hipkkt_solver *S, std::vector<DenseGroup> &dg) {
 // One launch of k_front_block per qualifying update batch of a front (symbolic.cpp front_batches).  HIPKKT_FRONT_BLOCK=0: never.
 static void build_front_batches(hipkkt_solver *S) {
     const HostPlan &P = S->plan;
-    S->fbatches.clear(); S->fb_last_level.clear();
-    S->lvl_fb.assign(std::max(P.nlevels, 1), -1);
-    if (!debug_opts().front_block) S->use_front_block = false;
-    if (S->use_front_block)
+    S->fb.lvl.assign(std::max(P.nlevels, 1), -1);
+    if (!debug_opts().front_block) S->fb.sw.use = false;
+    if (S->fb.sw.use)
         for (const FrontBatchHost &H : front_batches(P, S->plan_opts.update_policy, kFbMax)) {
             const FrontDesc &F = P.fronts[H.front];
             FrontBatch B;
@@ -734,25 +270,310 @@ static void build_front_batches(hipkkt_solver *S) {
             B.r0 = P.front_panels[F.fp_off + H.p0].r;
             B.nblk = (B.r0 + 63) / 64;
             B.i_base = 0; B.i_end = B.nblk; B.tick = 0; B.pad = 0; B.x_begin = 0; B.x_count = 0;
-            B.sync_off = 128 * (int)S->fbatches.size();
-            B.scratch_off = kFbScratch * (int64_t)S->fbatches.size();
-            B.stream_off = kFbStream * (int64_t)S->fbatches.size();
-            S->lvl_fb[H.level_first] = (int)S->fbatches.size();
-            for (int l = H.level_first + 1; l <= H.level_last; l++) S->lvl_fb[l] = -2;
-            S->fbatches.push_back(B);
-            S->fb_last_level.push_back(H.level_last);
+            B.sync_off = 128 * (int)S->fb.batches.size();
+            B.scratch_off = kFbScratch * (int64_t)S->fb.batches.size();
+            B.stream_off = kFbStream * (int64_t)S->fb.batches.size();
+            S->fb.lvl[H.level_first] = (int)S->fb.batches.size();
+            for (int l = H.level_first + 1; l <= H.level_last; l++) S->fb.lvl[l] = -2;
+            S->fb.batches.push_back(B);
+            S->fb.last_level.push_back(H.level_last);
         }
-    if (verbose()) fprintf(stderr, "hipkkt: %zu front batch(es) factored by one launch each (fronts %zu, update batch %d)\n", S->fbatches.size(), P.fronts.size(), P.update_batch_used);
-    const size_t nb_ = std::max<size_t>(S->fbatches.size(), 1);
-    S->d_fb_sync = S->dalloc<int>(128 * nb_);
-    S->d_fb_scratch = S->dalloc<double>((size_t)kFbScratch * nb_);
-    fill_async(S->stream, S->d_fb_sync, 0, 128 * nb_ * sizeof(int));
-    S->fb_stream_doubles = (S->fb_streamed || S->fb_v2) ? (int64_t)kFbStream * (int64_t)nb_ : 0;
-    S->d_fb_stream = S->dalloc<double>((size_t)std::max<int64_t>(S->fb_stream_doubles, 1));
-    if (getenv("HIPKKT_FB_TRACE")) {
-        S->d_fb_trace = (long long *)S->dalloc<double>(nb_ * 128);
-        fill_async(S->stream, S->d_fb_trace, 0, nb_ * 128 * sizeof(double));
+    if (verbose()) fprintf(stderr, "hipkkt: %zu front batch(es) factored by one launch each (fronts %zu, update batch %d)\n", S->fb.batches.size(), P.fronts.size(), P.update_batch_used);
+    const size_t nb_ = std::max<size_t>(S->fb.batches.size(), 1);
+    S->fb.d_sync = zeroed<int>(S, 128 * nb_);
+    S->fb.d_scratch = S->dalloc<double>((size_t)kFbScratch * nb_);
+    S->fb.stream_doubles = (S->fb.sw.streamed || S->fb.sw.v2) ? (int64_t)kFbStream * (int64_t)nb_ : 0;
+    S->fb.d_stream = S->dalloc<double>((size_t)std::max<int64_t>(S->fb.stream_doubles, 1));
+    if (getenv("HIPKKT_FB_TRACE")) S->fb.d_trace = (long long *)zeroed<double>(S, nb_ * 128);
+}
+
+// ---- setup_device, step by step.  The order of the dalloc / upload calls is part of how the kernels hit memory channels: the steps
+//      that only BUILD host records are functions of their own, the uploads keep the order they always had.
+// What an earlier set-up left: graphs, slabs, every part of the handle that describes them (hipkkt_parts.h says what a part keeps)
+static void reset_device_state(hipkkt_solver *S) {
+    S->for_each_graph_slot([](GraphSlot &g) { if (g.exec) (void)hipGraphExecDestroy(g.exec); g = GraphSlot(); });
+    if (!S->allocs.empty() && S->stream) (void)hipStreamSynchronize(S->stream);   // hipFree used to wait implicitly
+    for (auto &a : S->allocs) RuntimePool::get().dev_free(S->device, a.first, a.second);
+    S->allocs.clear();
+    S->slab_cur = nullptr; S->slab_left = 0;
+    S->stage_cap = 0; S->d_stage = nullptr; S->d_stage_idx = nullptr;
+    S->persist.rearm(!debug_opts().no_persist);
+    S->fb.reset();
+    S->split = UpdateSplit();
+    S->soc = SocTables();
+    S->res = ResidualBuffers();
+    S->red = ReducedSolve();
+    S->cones = ConeState();   // (slab memory of an earlier set-up is gone: the device tables, the resident step, so the registration too)
+}
+
+// diagonal blocks of 17 .. 64 columns are inverted by k_invert_diag_wide, the rest by the one-wave kernel (LDS for the widest): [small | wide]
+static std::vector<int> inversion_list(hipkkt_solver *S) {
+    const HostPlan &P = S->plan;
+    std::vector<int> small, wide;
+    S->inv_wsmall = 1;
+    for (int s = 0; s < P.nsuper; s++) {
+        const int w = P.sn_first[s + 1] - P.sn_first[s];
+        if (w > 16 && w <= 64) wide.push_back(s);
+        else { small.push_back(s); S->inv_wsmall = std::max(S->inv_wsmall, w); }
     }
+    S->inv_nsmall = (int)small.size();
+    S->inv_nwide = (int)wide.size();
+    small.insert(small.end(), wide.begin(), wide.end());
+    return small;
+}
+
+static std::vector<FacRec> fac_records(const HostPlan &P) {
+    std::vector<FacRec> recs(P.fac_items.size());
+    for (size_t q = 0; q < recs.size(); q++) {
+        const int s = P.fac_items[q].sn;
+        recs[q] = {P.sn_panel[s], P.sn_diag[s], P.lt_off[s], P.sn_first[s], P.sn_first[s + 1] - P.sn_first[s],
+                   (int32_t)(P.sn_rowptr[s + 1] - P.sn_rowptr[s]), P.fac_items[q].blk};
+    }
+    return recs;
+}
+
+static std::vector<DenseGroup> dense_groups(const HostPlan &P) {
+    std::vector<DenseGroup> dg(P.upd_groups.size());
+    const bool no_full_tiles = !debug_opts().full_tiles;   // bit-identity test of the full-tile core
+    for (size_t q = 0; q < dg.size(); q++) {
+        const UpdGroup &G = P.upd_groups[q];
+        const int t = G.tgt;
+        const int rt = (int)(P.sn_rowptr[t + 1] - P.sn_rowptr[t]);
+        // pad bit 0: a FULL tile (dense_tile.h dense_tile_core_full): 64 x 64, every task lands contiguously on all of it
+        bool full = G.dense == 1 && rt - G.row_base >= kUpdRows && P.sn_first[t + 1] - P.sn_first[t] == 64 && !no_full_tiles;
+        for (int u = G.task_begin; u < G.task_end && full; u++) {
+            const UpdTask &T = P.upd_tasks[u];
+            const int K = P.sn_first[T.src + 1] - P.sn_first[T.src];
+            full = !(T.geom & (1 << 17)) && (T.geom & 0xFFFF) == 0 && T.nrows >= 64 && T.ncols >= 64 && K >= 8 && (K & 7) == 0;
+        }
+        dg[q] = {P.sn_panel[t] + G.row_base, rt, std::min(kUpdRows, rt - G.row_base), P.sn_first[t + 1] - P.sn_first[t],
+                 G.task_begin, G.task_end, full ? 1 : 0};
+    }
+    return dg;
+}
+
+static std::vector<DenseTask> dense_tasks(const HostPlan &P) {
+    std::vector<DenseTask> dt(P.upd_tasks.size());
+    for (size_t q = 0; q < dt.size(); q++) {
+        const UpdTask &T = P.upd_tasks[q];
+        const int s = T.src;
+        dt[q] = {P.sn_panel[s], (int32_t)((P.sn_rowptr[s + 1] - P.sn_rowptr[s]) * 8), P.sn_first[s + 1] - P.sn_first[s],
+                 P.sn_first[s], T.row_lo, T.nrows, T.col_lo, T.ncols, T.geom, T.vt_begin, 0};
+    }
+    return dt;
+}
+
+static std::vector<GathPair> gather_pairs(const HostPlan &P) {
+    std::vector<GathPair> gp(P.gath_src.size());
+    for (size_t q = 0; q < gp.size(); q++) {
+        const int s = P.gath_sn[q];
+        gp[q] = {P.gath_src[q], P.gath_dj[q], (int32_t)(P.sn_rowptr[s + 1] - P.sn_rowptr[s]), P.sn_first[s + 1] - P.sn_first[s], P.sn_first[s]};
+    }
+    return gp;
+}
+
+// gather entries with long pair lists (k_update_gather_heavy), per stage and per part of a split stage
+static std::vector<int64_t> heavy_gathers(hipkkt_solver *S) {
+    const HostPlan &P = S->plan;
+    std::vector<int64_t> heavy;
+    S->split.heavy_ptr.assign(P.nlevels + 1, 0);
+    S->split.gath_heavy.assign(std::max(P.nlevels, 1), 0);
+    for (int l = 0; l < P.nlevels; l++) {
+        const int64_t e_split = S->split.gath[l] >= 0 ? P.gath_stage_ptr[l] + S->split.gath[l] : P.gath_stage_ptr[l + 1];
+        for (int64_t e = P.gath_stage_ptr[l]; e < P.gath_stage_ptr[l + 1]; e++)
+            if (P.gath_pptr[e + 1] - P.gath_pptr[e] > kGathHeavy) {
+                heavy.push_back(e);
+                if (e < e_split) S->split.gath_heavy[l]++;
+            }
+        S->split.heavy_ptr[l + 1] = (int64_t)heavy.size();
+    }
+    return heavy;
+}
+
+// the plan's tables, the schedule and the records derived from them; `dg` goes up later (plan_split_k appends to it)
+static void upload_plan(hipkkt_solver *S) {
+    const HostPlan &P = S->plan;
+    const SolveSchedule &H = S->sched;
+    const int N = P.N;
+    std::vector<signed char> sgn_perm(N), kdiag(S->nnzK, 0);
+    for (int k = 0; k < N; k++) sgn_perm[k] = (signed char)(S->img.dsigns[P.perm[k]] >= 0 ? 1 : -1);
+    for (int j = 0; j < N; j++)
+        for (int64_t q = S->img.colptr[j]; q < S->img.colptr[j + 1]; q++)
+            if (S->img.rowval[q] == j) kdiag[q] = (signed char)(S->img.dsigns[j] >= 0 ? 1 : -1);
+    DevPlan &D = S->dp;
+    D.sn_first = S->upload(P.sn_first);
+    D.sn_rowptr = S->upload(P.sn_rowptr);
+    D.sn_rows = S->upload(P.sn_rows);
+    D.sn_panel = S->upload(P.sn_panel);
+    D.sn_diag = S->upload(P.sn_diag);
+    D.u_off = S->upload(P.u_off);
+    D.p_off = S->upload(H.p_off);
+    D.lt_off = S->upload(P.lt_off);
+    D.bwd_items = S->upload(H.bwd_items);
+    D.lvl_sn = S->upload(H.lvl_sn);
+    D.perm = S->upload(P.perm);
+    D.sgn_perm = S->upload(sgn_perm);
+    D.inv_list = S->upload(inversion_list(S));
+    D.fac_items = S->upload(P.fac_items);
+    D.fac_recs = S->upload(fac_records(P));
+    D.slv_items = S->upload(H.slv_items);
+    D.rel = S->upload(P.rel);
+    D.upd_tasks = S->upload(P.upd_tasks);
+    D.upd_groups = S->upload(P.upd_groups);
+    // (never empty: the dense tile core requests "the next task's map" unconditionally and reads map 0 for tasks without one)
+    D.upd_tmap = P.upd_tmap.size() >= 128 ? S->upload(P.upd_tmap) : S->upload(std::vector<int16_t>(128, (int16_t)-1));
+    D.dtasks = S->upload(dense_tasks(P));
+    D.gath_tgt = S->upload(P.gath_tgt);
+    D.gath_pptr = S->upload(P.gath_pptr);
+    D.gath_pairs = S->upload(gather_pairs(P));
+    D.gath_heavy = S->upload(heavy_gathers(S));
+    D.g_ptr = S->upload(P.g_ptr);
+    D.g_idx = S->upload(P.g_idx);
+    D.kmap = S->upload(P.kmap);
+    D.kdiag_sign = S->upload(kdiag);
+    D.sym_rowptr = S->upload(P.sym_rowptr);
+    D.sym_col = S->upload(P.sym_col);
+    D.sym_q = S->upload(P.sym_q);
+    std::vector<int> lr;
+    const int thr = long_row_threshold();
+    for (int i = 0; i < N; i++)
+        if (P.sym_rowptr[i + 1] - P.sym_rowptr[i] > thr) lr.push_back(i);
+    D.long_rows = S->upload(lr);
+    D.n_long_rows = (int)lr.size();
+    // dense triangles of K (symbolic.h HostPlan::dtri): one workgroup of k_spmv_dense_tri per 64 rows of a triangle
+    std::vector<DenseTriStrip> strips;
+    for (const DenseTri &T : P.dtri)
+        for (int i0 = 0; i0 < T.d; i0 += 64) strips.push_back(DenseTriStrip{T.c0, T.d, i0, 0, T.col0});
+    D.dtri_strips = S->upload(strips);
+    D.n_dtri_strips = (int)strips.size();
+    D.dtri_col = S->upload(P.dtri_col);
+    D.dense_acc = nullptr;                 // per solve context (alloc_contexts)
+    D.front_panels = S->upload(P.front_panels);
+    D.front_gptr = S->upload(P.front_gptr);
+    D.front_gidx = S->upload(P.front_gidx);
+    D.pbwd_items = S->upload(H.pbwd_items);
+    D.dep_total = S->upload(H.dep_total);
+    D.sn_nitems = S->upload(H.sn_nitems);
+    D.sn_bparent = S->upload(H.sn_bparent);
+    D.nseg = H.nseg;
+    D.seg_ticket = 3;                                  // bit 0: forward sweep, bit 1: backward sweep take their items by atomic ticket
+    D.spin_limit = debug_opts().spin_limit >= 0 ? (unsigned)debug_opts().spin_limit : (1u << 20);   // tests force a sweep time-out with a tiny bound
+#ifdef HIPKKT_TESTING
+    D.dbg = debug_opts().debug_flags;                  // timing experiments only: results are WRONG when set (device_plan.h DevPlan::dbg)
+    if (D.dbg) fprintf(stderr, "hipkkt: DEBUG_FLAGS = %d: timing experiment, the results of this handle are WRONG\n", D.dbg);
+#else
+    D.dbg = 0;
+#endif
+    D.sn_polish = zeroed<int>(S, (size_t)P.nsuper);
+    D.polish_tau = S->accurate_threshold;
+}
+
+// everything a solve writes besides its vectors, for one solve context (context 0: S->dp); all-zero slots = invalid in every epoch
+static void alloc_solve_scratch(hipkkt_solver *S, DevPlan &D) {
+    const HostPlan &P = S->plan;
+    const int64_t np0 = S->sched.p_off[P.nsuper];
+    const size_t nx = (size_t)std::max(P.N, 1), np_ = (size_t)std::max<int64_t>(np0, 1);
+    const SyncWords nw = sync_words(S);
+    D.ubuf = S->dalloc<double>(P.ubuf_len);
+    D.pbuf = S->dalloc<double>(np0);
+    D.xseg = (FrontSlot *)zeroed<double>(S, 2 * nx);
+    D.pseg = (FrontSlot *)zeroed<double>(S, 2 * np_);
+    D.seg_epoch = zeroed<int>(S, 4);
+    D.seg_sync = zeroed<int>(S, nw.seg);
+    D.front_sync = zeroed<int>(S, nw.front);
+    D.scal = zeroed<double>(S, SC_COUNT);
+    D.flags = zeroed<int>(S, FL_COUNT);
+}
+
+// front batches, the dense groups (split-K appends to them), the values of K and the factor itself
+static void alloc_factor_storage(hipkkt_solver *S) {
+    const HostPlan &P = S->plan;
+    DevPlan &D = S->dp;
+    const int N = P.N;
+    std::vector<DenseGroup> dg = dense_groups(P);
+    build_front_batches(S);
+    const int64_t split_scratch = S->split.scratch_doubles = plan_split_k(S, dg);
+    D.dgroups = S->upload(dg);
+    D.kval = S->upload(S->img.nzval);
+    D.Lx = S->dalloc<double>(P.panel_doubles + split_scratch);
+    if (split_scratch) fill_async(S->stream, D.Lx + P.panel_doubles, 0, (size_t)split_scratch * sizeof(double));
+    D.Ldiag = zeroed<double>(S, (size_t)P.diag_doubles);
+    D.Linv = S->dalloc<double>(P.diag_doubles);
+    D.LinvT = S->dalloc<double>(P.diag_doubles);
+    D.LT = S->dalloc<double>(P.lt_off[P.nsuper]);
+    D.SbInv = zeroed<double>(S, (size_t)P.sbinv_doubles);
+    D.D = S->dalloc<double>(N);
+    D.Dinv = zeroed<double>(S, (size_t)N);
+}
+
+// index arrays of the value updates; all sparse SOC cones concatenated
+static void upload_value_maps(hipkkt_solver *S) {
+    S->d_diag_full = S->upload(S->img.diag_full);
+    if (!S->l1) return;
+    SocTables &T = S->soc;
+    S->d_mapHs = S->upload(S->img.mapHs);
+    S->d_mapP = S->upload(S->img.mapP);
+    S->d_mapA = S->upload(S->img.mapA);
+    std::vector<int64_t> uidx, vidx, didx;
+    std::vector<int> coneof;
+    T.of_sparse.assign(S->img.smaps.size(), -1);
+    for (size_t i = 0; i < S->img.smaps.size(); i++) {
+        const SparseMap &sm = S->img.smaps[i];
+        if (sm.kind != 1) continue;
+        T.of_sparse[i] = T.n;
+        T.off.push_back((int64_t)uidx.size());
+        for (size_t q = 0; q < sm.vec[0].size(); q++) {
+            uidx.push_back(sm.vec[0][q]);
+            vidx.push_back(sm.vec[1][q]);
+            coneof.push_back(T.n);
+        }
+        didx.push_back(sm.D[0]);
+        didx.push_back(sm.D[1]);
+        T.n++;
+    }
+    T.off.push_back((int64_t)uidx.size());
+    T.total = (int64_t)uidx.size();
+    T.d_uidx = S->upload(uidx);
+    T.d_vidx = S->upload(vidx);
+    T.d_didx = S->upload(didx);
+    T.d_cone = S->upload(coneof);
+    T.d_u = S->dalloc<double>(T.total);
+    T.d_v = S->dalloc<double>(T.total);
+    T.d_eta2 = S->dalloc<double>(T.n);
+}
+
+// the vectors and the refinement state of every solve context; contexts > 0 get private scratch as well
+static void alloc_contexts(hipkkt_solver *S) {
+    const int N = S->N;
+    for (int c = 0; c < kNumCtx; c++) {
+        SolveCtx &C = S->ctx[c];
+        for (double **v : {&C.d_b, &C.d_x0, &C.d_x1, &C.d_e, &C.d_corr, &C.d_y, &C.d_z, &C.d_xp}) *v = zeroed<double>(S, (size_t)N);
+        C.d_rs = (RefineState *)zeroed<double>(S, sizeof(RefineState) / sizeof(double) + 1);
+        C.dp = S->dp;
+        // rows outside the triangles stay 0 for ever, the others are rewritten by every SpMV
+        if (S->dp.n_dtri_strips > 0) C.dp.dense_acc = zeroed<double>(S, (size_t)N);
+        if (c > 0) alloc_solve_scratch(S, C.dp);
+        C.ir_used = false;
+        C.h_rs->cur = 0;
+    }
+}
+
+// (re)builds every device-resident structure from S->plan and S->img (values included)
+void setup_device(hipkkt_solver *S) {
+    HK_CHECK(hipSetDevice(S->device));
+    reset_device_state(S);
+    order_far_stages(S);
+    split_gather_stages(S);
+    S->N = S->plan.N; S->nnzK = S->plan.nnzK;
+    S->sched = build_solve_schedule(S->plan);
+    upload_plan(S);
+    alloc_factor_storage(S);
+    S->dp.rows_seg = S->upload(S->sched.rows_seg);
+    alloc_solve_scratch(S, S->dp);
+    upload_value_maps(S);
+    alloc_contexts(S);
+    S->ensure_stage(std::max<int64_t>(1024, std::max<int64_t>(S->img.nHs, S->N)));
+    HK_CHECK(hipStreamSynchronize(S->stream));
 }
 
 int32_t finish_create(hipkkt_solver *S, const hipkkt_opts *opts, hipkkt_handle *out) {
@@ -764,20 +585,12 @@ int32_t finish_create(hipkkt_solver *S, const hipkkt_opts *opts, hipkkt_handle *
     po.amd_dense_scale = opts->amd_dense_scale > 0 ? opts->amd_dense_scale : 1.5;
     po.front_min_panels = opts->front_min_panels == 0 ? 4 : std::max(0, opts->front_min_panels);
     po.n_hold = S->l1 ? (int)S->img.n : 0;
-    {
-        // debug switch DENSE_TRI=0: dense Hs triangles stay in the symmetric view (A/B timing, parity test of k_spmv_dense_tri)
-        po.dense_tri_first_col = (S->l1 && debug_opts().dense_tri) ? (int)S->img.n : -1;
-    }
-    {
-        if (debug_opts().front_block_min_rows >= 0) po.front_block_min_width = debug_opts().front_block_min_rows;   // tests: 0, so that small fronts take the front-batch kernel too
-        if (debug_opts().superhop >= 0) po.superhop = debug_opts().superhop;   // 0: one hop per panel in the front sweeps; N: fronts of >= N panels go super-block by super-block
-    }
-    {
-        if (debug_opts().ordering_amd) po.n_hold = 0;   // minimum degree on K only
-    }
-    {
-        if (debug_opts().no_front) po.front_min_panels = 0;
-    }
+    // debug switch DENSE_TRI=0: dense Hs triangles stay in the symmetric view (A/B timing, parity test of k_spmv_dense_tri)
+    po.dense_tri_first_col = (S->l1 && debug_opts().dense_tri) ? (int)S->img.n : -1;
+    if (debug_opts().front_block_min_rows >= 0) po.front_block_min_width = debug_opts().front_block_min_rows;   // tests: 0, so that small fronts take the front-batch kernel too
+    if (debug_opts().superhop >= 0) po.superhop = debug_opts().superhop;   // 0: one hop per panel in the front sweeps; N: fronts of >= N panels go super-block by super-block
+    if (debug_opts().ordering_amd) po.n_hold = 0;   // minimum degree on K only
+    if (debug_opts().no_front) po.front_min_panels = 0;
     std::vector<int64_t> up;
     const int64_t *uperm = nullptr;
     if (opts->user_perm) {
@@ -802,15 +615,15 @@ int32_t finish_create(hipkkt_solver *S, const hipkkt_opts *opts, hipkkt_handle *
                 PlanOptions po2 = po;
                 po2.n_hold = 0;
                 po2.on_alternative_order = nullptr;
-                S->twin_cancel = std::make_shared<std::atomic<bool>>(false);
-                po2.cancel = S->twin_cancel.get();
+                S->twin.cancel = std::make_shared<std::atomic<bool>>(false);
+                po2.cancel = S->twin.cancel.get();
                 T->plan_opts = po2;
                 hipkkt_solver *Tp = T.get();
                 std::vector<int64_t> pv(perm_md.begin(), perm_md.end());
-                S->twin_pending = std::move(T);
-                S->twin_go = std::make_shared<std::atomic<int>>(0);
-                std::shared_ptr<std::atomic<int>> go = S->twin_go;
-                S->twin_future = std::async(std::launch::async, [Tp, pv, po2, go]() {
+                S->twin.pending = std::move(T);
+                S->twin.go = std::make_shared<std::atomic<int>>(0);
+                std::shared_ptr<std::atomic<int>> go = S->twin.go;
+                S->twin.future = std::async(std::launch::async, [Tp, pv, po2, go]() {
                     std::string err = build_plan((int)Tp->img.N, Tp->img.colptr.data(), Tp->img.rowval.data(), pv.data(), po2, Tp->plan);
                     if (!err.empty()) return err;
                     // Round 6: the twin's device residency too (its work lists are hundreds of MB on the problems that take this path:
@@ -829,7 +642,7 @@ int32_t finish_create(hipkkt_solver *S, const hipkkt_opts *opts, hipkkt_handle *
                     try {
                         init_runtime(Tp);
                         setup_device(Tp);
-                        Tp->device_ready = true;
+                        Tp->twin.device_ready = true;
                     } catch (const DeviceError &e) {
                         return std::string("twin device set-up: ") + e.msg;       // (the failing factorisation will try again, synchronously)
                     } catch (const std::bad_alloc &) {
@@ -866,8 +679,8 @@ int32_t finish_create(hipkkt_solver *S, const hipkkt_opts *opts, hipkkt_handle *
     }
     po.on_alternative_order = nullptr;
     if (!err.empty()) { g_create_error = err; delete S; return HIPKKT_ERR_ARGUMENT; }
-    if (S->plan.ordering_used != 1 && S->twin_cancel) S->twin_cancel->store(true);   // speculative twin not needed: the thread stops at its next phase
-    if (S->twin_go) S->twin_go->store((S->plan.ordering_used == 1 && err.empty()) ? 1 : 2, std::memory_order_release);   // ... or goes on to its device set-up
+    if (S->plan.ordering_used != 1 && S->twin.cancel) S->twin.cancel->store(true);   // speculative twin not needed: the thread stops at its next phase
+    if (S->twin.go) S->twin.go->store((S->plan.ordering_used == 1 && err.empty()) ? 1 : 2, std::memory_order_release);   // ... or goes on to its device set-up
     S->plan_opts = po;
     const auto t_b = std::chrono::steady_clock::now();
     try {
@@ -877,7 +690,7 @@ int32_t finish_create(hipkkt_solver *S, const hipkkt_opts *opts, hipkkt_handle *
         if (verbose())
             fprintf(stderr, "hipkkt: N %d nnzL %lld levels %d ordering %d: symbolic %.2f ms (%s), device set-up %.2f ms, runtime objects %.2f ms\n", S->plan.N, (long long)S->plan.nnzL,
                     S->plan.nlevels, S->plan.ordering_used, 1e3 * std::chrono::duration<double>(t_b - t_a).count(), S->plan.timing_note.c_str(),
-                    1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t_b).count(), 1e3 * S->t_init_runtime);
+                    1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t_b).count(), 1e3 * S->stats.t_init_runtime);
     } catch (const DeviceError &e) {
         g_create_error = e.msg; delete S; return HIPKKT_ERR_DEVICE;
     } catch (const std::bad_alloc &) {

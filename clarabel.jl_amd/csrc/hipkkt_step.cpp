@@ -163,8 +163,7 @@ struct StepScalars { double tau, kappa, rhs_tau, rhs_kappa; };
 // term of ds.  The solve and its reduction are hipkkt_kkt_solve_reduced_dev's; ds = -(Hs dz + addc) (:203-207) and the step length of
 // the cones (alpha_max = 1) are enqueued behind every reduction, so the host still synchronises once.
 static int32_t fused_solve(hipkkt_solver *S, const StepScalars &sc, const double *addc, int32_t const_pending, double step_fraction,
-                           double *scal_out15, int32_t ir_enable, double reltol, double abstol, int64_t max_iter, double stop_ratio,
-                           int64_t *ir_steps2) {
+                           double *scal_out15, const RefineOpts &ir, int64_t *ir_steps2) {
     const int64_t n = S->img.n, m = S->img.m;
     ConeState &C = S->cones;
     const ConeTables T = tables(S);
@@ -176,14 +175,15 @@ static int32_t fused_solve(hipkkt_solver *S, const StepScalars &sc, const double
         op_mulhs(st, T, dz, addc, ds);
         // (with Exponential / Power cones the line search starts from min(alpha_tau, alpha_kappa, 1): dtau is the reduction's first scalar)
         double *out2 = C.step.out + (T.line_search() ? kStOutLen : kStOutSym);
-        op_length(S, st, T, dz, ds, 1.0, S->d_red + 3 * (size_t)S->N + n, sc.tau, sc.kappa, sc.rhs_kappa, out2);
+        op_length(S, st, T, dz, ds, 1.0, S->red.d + 3 * (size_t)S->N + n, sc.tau, sc.kappa, sc.rhs_kappa, out2);
         HK_CHECK(hipMemcpyAsync(h2, out2, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
     };
     const double scal_in[4] = {sc.tau, sc.kappa, sc.rhs_tau, sc.rhs_kappa};
     double red[10];
     C.step.have_step = false;
-    const int32_t rc = kkt_solve_reduced_impl(S, nullptr, nullptr, nullptr, C.step.in, scal_in, const_pending, nullptr, nullptr, nullptr, red,
-                                              ir_enable, reltol, abstol, max_iter, stop_ratio, ir_steps2, &after);
+    ReducedOut out;
+    out.scal_out = red; out.ir_steps = ir_steps2; out.after_reduce = &after;
+    const int32_t rc = kkt_solve_reduced_impl(S, ReducedIn::device(C.step.in), {scal_in, const_pending}, out, ir);
     if (rc != HIPKKT_OK) return rc;
     C.step.have_step = true;
     // variables.jl:14-43 (the cones' part ran with alpha_max = 1: the minimum is exact in any order), kktsystem.jl:209
@@ -422,14 +422,14 @@ int32_t hipkkt_step_affine_dev(hipkkt_handle h, const double *xzs_dev, const dou
     HK_ENTER(h)
     ConeState &C = S->cones;
     if (!step_ready(S, "step_affine_dev")) return HIPKKT_ERR_ARGUMENT;
-    if (!S->d_qb || !xzs_dev || !res_dev || !scal_in3 || !scal_out15) { S->err = "step_affine_dev: call hipkkt_set_qb first / bad arguments"; return HIPKKT_ERR_ARGUMENT; }
+    if (!S->res.d_qb || !xzs_dev || !res_dev || !scal_in3 || !scal_out15) { S->err = "step_affine_dev: call hipkkt_set_qb first / bad arguments"; return HIPKKT_ERR_ARGUMENT; }
     const int64_t n = S->img.n, m = S->img.m;
     ensure_step_buffers(S);
     const double tau = scal_in3[0], kappa = scal_in3[1], r_tau = scal_in3[2];
     // variables_affine_step_rhs!, variables.jl:107-121; ds_const = s (kktsystem.jl:152-156)
     launch_step_rhs(S->stream, C.step.in, xzs_dev, res_dev, nullptr, 1.0, n, m);
     const StepScalars sc{tau, kappa, r_tau, tau * kappa};
-    return fused_solve(S, sc, xzs_dev + n + m, const_pending, 1.0, scal_out15, ir_enable, reltol, abstol, max_iter, stop_ratio, ir_steps2);
+    return fused_solve(S, sc, xzs_dev + n + m, const_pending, 1.0, scal_out15, RefineOpts{ir_enable, reltol, abstol, max_iter, stop_ratio}, ir_steps2);
     HK_LEAVE
 }
 
@@ -439,7 +439,7 @@ int32_t hipkkt_step_combined_dev(hipkkt_handle h, const double *xzs_dev, const d
     HK_ENTER(h)
     ConeState &C = S->cones;
     if (!step_ready(S, "step_combined_dev")) return HIPKKT_ERR_ARGUMENT;
-    if (!S->d_qb || !xzs_dev || !res_dev || !scal_in9 || !scal_out15) { S->err = "step_combined_dev: call hipkkt_set_qb first / bad arguments"; return HIPKKT_ERR_ARGUMENT; }
+    if (!S->res.d_qb || !xzs_dev || !res_dev || !scal_in9 || !scal_out15) { S->err = "step_combined_dev: call hipkkt_set_qb first / bad arguments"; return HIPKKT_ERR_ARGUMENT; }
     if (!C.step.have_step) { S->err = "step_combined_dev: no affine step resident (hipkkt_step_affine_dev comes first)"; return HIPKKT_ERR_ARGUMENT; }
     const int64_t n = S->img.n, m = S->img.m;
     const double tau = scal_in9[0], kappa = scal_in9[1], r_tau = scal_in9[2], dtau_aff = scal_in9[3], dkappa_aff = scal_in9[4];
@@ -458,7 +458,7 @@ int32_t hipkkt_step_combined_dev(hipkkt_handle h, const double *xzs_dev, const d
     op_offset(st, T, w_rhs_s, w_dsc);                                                                   // kktsystem.jl:157-163
     launch_step_rhs(st, C.step.in, xzs_dev, res_dev, w_dsc, oms, n, m);
     const StepScalars sc{tau, kappa, oms * r_tau, rhs_kappa};
-    return fused_solve(S, sc, w_dsc, const_pending, step_fraction, scal_out15, ir_enable, reltol, abstol, max_iter, stop_ratio, ir_steps2);
+    return fused_solve(S, sc, w_dsc, const_pending, step_fraction, scal_out15, RefineOpts{ir_enable, reltol, abstol, max_iter, stop_ratio}, ir_steps2);
     HK_LEAVE
 }
 

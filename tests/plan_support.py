@@ -18,7 +18,7 @@ def lib():
         L = C.CDLL(os.path.join(_HERE, "libplan_check.so"))
         L.plan_check_run.restype = C.c_int
         L.plan_check_run.argtypes = [C.c_int64, _i64p, _i64p, _f64p, _i64p, C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                     C.c_double, C.c_double, _f64p, _f64p, _i64p, _f64p, C.c_int]
+                                     C.c_double, C.c_double, _f64p, _f64p, _i64p, _f64p, C.c_int, C.c_int]
         L.plan_check_symmetric_product.restype = C.c_int
         L.plan_check_symmetric_product.argtypes = [C.c_int64, _i64p, _i64p, _f64p, C.c_int, C.c_int, _f64p, _f64p, _f64p]
         _lib = L
@@ -41,7 +41,9 @@ STAT_NAMES = ["nsuper", "nlevels", "nnzL", "panel_doubles", "ntasks", "ngroups",
 
 
 def run(N, colptr, rowval, nzval, dsigns, b=None, perm=None, max_width=64, relax=1, policy=0,
-        reg_eps=1e-13, reg_delta=2e-7, symbolic_only=False):
+        reg_eps=1e-13, reg_delta=2e-7, symbolic_only=False, schedule=0):
+    """schedule: the order of the solve.  0 = the plan's own level lists; 1 = the lists the solve kernels consume (own-launch levels,
+    segment items, fronts: csrc/solve_schedule.h); 2 = its level lists over every supernode, without front sweeps"""
     L = lib()
     x = np.zeros(N)
     perm_out = np.zeros(N, dtype=np.int64)
@@ -55,5 +57,5 @@ def run(N, colptr, rowval, nzval, dsigns, b=None, perm=None, max_width=64, relax
     rc = L.plan_check_run(N, np.ascontiguousarray(colptr, dtype=np.int64), np.ascontiguousarray(rowval, dtype=np.int64),
                           np.ascontiguousarray(nzval, dtype=np.float64), np.ascontiguousarray(dsigns, dtype=np.int64),
                           pp, max_width, relax, policy, reg_eps, reg_delta,
-                          np.ascontiguousarray(b, dtype=np.float64), x, perm_out, stats, int(symbolic_only))
+                          np.ascontiguousarray(b, dtype=np.float64), x, perm_out, stats, int(symbolic_only), int(schedule))
     return rc, x, perm_out, dict(zip(STAT_NAMES, stats))

@@ -11,7 +11,7 @@
 #include <string>
 #include <vector>
 
-#include "../../clarabel.jl_amd/csrc/symbolic.h"
+#include "../../clarabel.jl_amd/csrc/solve_schedule.h"
 
 using namespace hipkkt;
 
@@ -209,7 +209,7 @@ int plan_check_symmetric_product(int64_t N, const int64_t *Ap, const int64_t *Ai
 int plan_check_run(int64_t N, const int64_t *Ap, const int64_t *Ai, const double *Ax, const int64_t *dsigns,
                    const int64_t *user_perm, int max_width, int relax, int policy, double reg_eps,
                    double reg_delta, const double *b, double *x, int64_t *perm_out, double *stats,
-                   int symbolic_only) {
+                   int symbolic_only, int schedule) {
     HostPlan P;
     PlanOptions opt;
     opt.max_width = max_width; opt.relax = relax != 0; opt.update_policy = policy & 15; if (policy >> 4) opt.update_batch = policy >> 4;
@@ -401,77 +401,188 @@ int plan_check_run(int64_t N, const int64_t *Ap, const int64_t *Ai, const double
         }
         for (int i = 0; i < w_; i++) v[i] = t[i];
     };
-    for (int lvl = 0; lvl < P.nlevels; lvl++) {
-        for (int q = P.lvl_ptr[lvl]; q < P.lvl_ptr[lvl + 1]; q++) {
-            int s = P.lvl_sn[q], w = W(s), r = R(s), f = P.sn_first[s];
-            if (P.sn_front[s] >= 0) continue;   // handled by the front sweep below (k_front_fwd)
-            const double *pan = &Lx[P.sn_panel[s]];
-            const double *ld = &Ld[P.sn_diag[s]];
-            const int64_t slot0 = P.sn_rowptr[s];
-            for (int k = 0; k < w; k++) {
-                double v = 0;
-                for (int64_t g = P.g_ptr[slot0 + k]; g < P.g_ptr[slot0 + k + 1]; g++) v += ub[P.g_idx[g]];
-                y[f + k] -= v;
-            }
-            if (xinv) inv_apply(s, w, &y[f], false);        // the kernels' form (k_fwd_level): y_J = Linv * rhs, a lower-triangular GEMV
+    // ---- the pieces of a solve: one regular supernode forward / backward, one front forward / backward.  Which of them runs when
+    //      is decided below: by the plan's own level lists (schedule 0) or by the lists the solve kernels consume (solve_schedule.h)
+    std::vector<int> seen_f(P.nsuper, 0), seen_b(P.nsuper, 0);
+    auto fwd_sn = [&](int s) {
+        const int w = W(s), r = R(s), f = P.sn_first[s];
+        seen_f[s]++;
+        const double *pan = &Lx[P.sn_panel[s]];
+        const double *ld = &Ld[P.sn_diag[s]];
+        const int64_t slot0 = P.sn_rowptr[s];
+        for (int k = 0; k < w; k++) {
+            double v = 0;
+            for (int64_t g = P.g_ptr[slot0 + k]; g < P.g_ptr[slot0 + k + 1]; g++) v += ub[P.g_idx[g]];
+            y[f + k] -= v;
+        }
+        if (xinv) inv_apply(s, w, &y[f], false);        // the kernels' form (k_fwd_level): y_J = Linv * rhs, a lower-triangular GEMV
+        else
+        for (int k = 0; k < w; k++)
+            for (int i = k + 1; i < w; i++) y[f + i] -= ld[i + (size_t)k * w] * y[f + k];
+        for (int i = w; i < r; i++) {
+            double a = 0;
+            for (int64_t g = P.g_ptr[slot0 + i]; g < P.g_ptr[slot0 + i + 1]; g++) a += ub[P.g_idx[g]];
+            for (int k = 0; k < w; k++) a += pan[i + (size_t)k * r] * y[f + k];
+            ub[P.u_off[s] + (i - w)] = a;
+        }
+    };
+    // the persistent sweep of a front (external gathers + panel-ordered accumulation)
+    auto front_fwd = [&](const FrontDesc &F) {
+        for (int p = 0; p < F.np; p++) seen_f[F.s0 + p]++;
+        if (F.sb_g > 0 && !sb_subst) { sbe.invert_super(F); sbe.fwd(F, y, ub); return 0; }   // front_sweep.hip
+        const FrontPanel *fp = &P.front_panels[F.fp_off];
+        std::vector<double> acc(F.rF, 0.0);
+        for (int i = 0; i < F.rF; i++)
+            for (int64_t g = P.front_gptr[F.gptr_off + i]; g < P.front_gptr[F.gptr_off + i + 1]; g++) acc[i] += ub[P.front_gidx[g]];
+        for (int p = 0; p < F.np; p++) {
+            const FrontPanel &me = fp[p];
+            if (me.sn != F.s0 + p || me.f != P.sn_first[me.sn] || me.w != W(me.sn) || me.r != R(me.sn)) return -10;
+            const double *ld = &Ld[P.sn_diag[me.sn]];
+            const double *pan = &Lx[me.panel_off];
+            for (int k = 0; k < me.w; k++) y[me.f + k] -= acc[F.cw * p + k];
+            if (xinv) inv_apply(me.sn, me.w, &y[me.f], false);
             else
-            for (int k = 0; k < w; k++)
-                for (int i = k + 1; i < w; i++) y[f + i] -= ld[i + (size_t)k * w] * y[f + k];
-            for (int i = w; i < r; i++) {
+            for (int k = 0; k < me.w; k++)
+                for (int i = k + 1; i < me.w; i++) y[me.f + i] -= ld[i + (size_t)k * me.w] * y[me.f + k];
+            for (int j = me.w; j < me.r; j++) {      // local row j = front row cw*p + j
                 double a = 0;
-                for (int64_t g = P.g_ptr[slot0 + i]; g < P.g_ptr[slot0 + i + 1]; g++) a += ub[P.g_idx[g]];
-                for (int k = 0; k < w; k++) a += pan[i + (size_t)k * r] * y[f + k];
-                ub[P.u_off[s] + (i - w)] = a;
+                for (int k = 0; k < me.w; k++) a += pan[j + (size_t)k * me.r] * y[me.f + k];
+                acc[F.cw * p + j] += a;
             }
         }
-        // fronts that end at this level: the persistent sweep (external gathers + panel-ordered accumulation)
-        for (const FrontDesc &F : P.fronts) {
-            if (F.level_last != lvl) continue;
-            if (F.sb_g > 0 && !sb_subst) { sbe.invert_super(F); sbe.fwd(F, y, ub); continue; }   // front_sweep.hip
-            const FrontPanel *fp = &P.front_panels[F.fp_off];
-            std::vector<double> acc(F.rF, 0.0);
-            for (int i = 0; i < F.rF; i++)
-                for (int64_t g = P.front_gptr[F.gptr_off + i]; g < P.front_gptr[F.gptr_off + i + 1]; g++) acc[i] += ub[P.front_gidx[g]];
-            for (int p = 0; p < F.np; p++) {
-                const FrontPanel &me = fp[p];
-                if (me.sn != F.s0 + p || me.f != P.sn_first[me.sn] || me.w != W(me.sn) || me.r != R(me.sn)) return -10;
-                const double *ld = &Ld[P.sn_diag[me.sn]];
-                const double *pan = &Lx[me.panel_off];
-                for (int k = 0; k < me.w; k++) y[me.f + k] -= acc[F.cw * p + k];
-                if (xinv) inv_apply(me.sn, me.w, &y[me.f], false);
-                else
-                for (int k = 0; k < me.w; k++)
-                    for (int i = k + 1; i < me.w; i++) y[me.f + i] -= ld[i + (size_t)k * me.w] * y[me.f + k];
-                for (int j = me.w; j < me.r; j++) {      // local row j = front row cw*p + j
-                    double a = 0;
-                    for (int k = 0; k < me.w; k++) a += pan[j + (size_t)k * me.r] * y[me.f + k];
-                    acc[F.cw * p + j] += a;
-                }
-            }
-            for (int i = F.W; i < F.rF; i++) ub[F.ubelow_off + (i - F.W)] = acc[i];
+        for (int i = F.W; i < F.rF; i++) ub[F.ubelow_off + (i - F.W)] = acc[i];
+        return 0;
+    };
+    auto bwd_sn = [&](int s) {
+        const int w = W(s), r = R(s), f = P.sn_first[s];
+        seen_b[s]++;
+        const double *pan = &Lx[P.sn_panel[s]];
+        const double *ld = &Ld[P.sn_diag[s]];
+        const int *rows = &P.sn_rows[P.sn_rowptr[s]];
+        for (int k = 0; k < w; k++) {
+            double a = 0;
+            for (int i = w; i < r; i++) a += pan[i + (size_t)k * r] * y[rows[i]];
+            y[f + k] -= a;
         }
+        if (xinv) inv_apply(s, w, &y[f], true);        // k_bwd_final: x_J = Linv^T t
+        else
+        for (int k = w - 1; k >= 0; k--)
+            for (int i = k + 1; i < w; i++) y[f + k] -= ld[i + (size_t)k * w] * y[f + i];
+    };
+    auto front_bwd = [&](const FrontDesc &F) {
+        if (F.sb_g > 0 && !sb_subst) {                  // k_front_bwd_sb
+            for (int p = 0; p < F.np; p++) seen_b[F.s0 + p]++;
+            const std::vector<double> zc(y);
+            sbe.bwd(F, zc, y);
+        } else
+            for (int p = F.np - 1; p >= 0; p--) bwd_sn(F.s0 + p);
+    };
+    auto scale_by_dinv = [&] { for (int k = 0; k < N; k++) y[k] *= Dinv[k]; };
+    if (schedule == 0) {
+        for (int lvl = 0; lvl < P.nlevels; lvl++) {
+            for (int q = P.lvl_ptr[lvl]; q < P.lvl_ptr[lvl + 1]; q++)
+                if (P.sn_front[P.lvl_sn[q]] < 0) fwd_sn(P.lvl_sn[q]);   // (the others: by the front sweep below, k_front_fwd)
+            for (const FrontDesc &F : P.fronts)         // fronts that end at this level
+                if (F.level_last == lvl && front_fwd(F)) return -10;
+        }
+        scale_by_dinv();
+        for (int lvl = P.nlevels - 1; lvl >= 0; lvl--) {
+            for (const FrontDesc &F : P.fronts)
+                if (F.sb_g > 0 && !sb_subst && F.level_last == lvl) front_bwd(F);
+            for (int q = P.lvl_ptr[lvl]; q < P.lvl_ptr[lvl + 1]; q++) {
+                const int s = P.lvl_sn[q];
+                if (!(P.sn_front[s] >= 0 && P.fronts[P.sn_front[s]].sb_g > 0 && !sb_subst)) bwd_sn(s);
+            }
+        }
+    } else {
+        // the order of enqueue_ldl_solve (hipkkt_solve.cpp) over the lists of build_solve_schedule: 1 = persistent kernels
+        // (own-launch levels, segment items, fronts), 2 = the level lists over every supernode, no front sweep
+        const SolveSchedule H = build_solve_schedule(P);
+        const LevelLists &L = schedule == 1 ? H.regular : H.all;
+        auto nitems = [&](int s) { return std::max(1, (R(s) - W(s) + 63) / 64); };
+        // which segment launch solves a supernode, read off the forward item ranges (-1: a launch of its own level, or a front)
+        std::vector<int> launch_of(P.nsuper, -1);
+        for (int g = 0; g < H.nseg; g++)
+            for (int q = H.fseg_ptr[2 * g]; q < H.fseg_ptr[2 * g + 1]; q++) launch_of[H.slv_items[q].sn] = g;
+        int bad = 0;
+        // items [a, b) of one launch: every supernode's blocks 0 .. nitems - 1 in order; the supernode is solved at its block 0
+        auto fwd_items = [&](int a, int b) {
+            std::vector<int> nb(P.nsuper, 0);
+            for (int q = a; q < b; q++) {
+                const FacItem it = H.slv_items[q];
+                if (it.blk != nb[it.sn]++) bad = -20;
+                if (it.blk == 0) fwd_sn(it.sn);
+            }
+            for (int q = a; q < b; q++)
+                if (nb[H.slv_items[q].sn] != nitems(H.slv_items[q].sn)) bad = -20;
+        };
+        // partial blocks of a backward launch: none for a supernode of one block, otherwise all of them
+        auto bwd_blocks = [&](const std::vector<FacItem> &items, int a, int b, const std::vector<int> &fin) {
+            std::vector<int> nb(P.nsuper, 0);
+            for (int q = a; q < b; q++)
+                if (items[q].blk >= 0 && items[q].blk != nb[items[q].sn]++) bad = -21;
+            for (int s : fin)
+                if (nb[s] != (nitems(s) > 1 ? nitems(s) : 0)) bad = -21;
+        };
+        auto fwd_level = [&](int l) {
+            for (int q = L.reg_ptr[l]; q < L.reg_ptr[l] + L.nnarrow[l]; q++) fwd_sn(H.lvl_sn[q]);      // k_fwd_narrow
+            fwd_items(L.slv_ptr[l], L.slv_ptr[l + 1]);
+        };
+        auto bwd_level = [&](int l) {
+            const std::vector<int> fin(H.lvl_sn.begin() + L.reg_ptr[l] + L.nnarrow[l], H.lvl_sn.begin() + L.reg_ptr[l + 1]);
+            bwd_blocks(H.bwd_items, L.bwd_ptr[l], L.bwd_ptr[l + 1], fin);
+            for (int s : fin) bwd_sn(s);
+            for (int q = L.reg_ptr[l]; q < L.reg_ptr[l] + L.nnarrow[l]; q++) bwd_sn(H.lvl_sn[q]);      // k_bwd_narrow
+        };
+        if (schedule == 1) {
+            for (int g = 0; g < H.nseg; g++) {
+                const int lend = std::min(H.seg_lstar[g], H.seg_hi[g] + 1);
+                for (int l = H.seg_lo[g]; l < lend; l++) fwd_level(l);
+                fwd_items(H.fseg_ptr[2 * g], H.fseg_ptr[2 * g + 1]);
+                for (const FrontDesc &F : P.fronts)
+                    if (H.seg_of_level[F.level_last] == g && front_fwd(F)) return -10;
+            }
+            scale_by_dinv();
+            for (int g = H.nseg - 1; g >= 0; g--) {
+                for (const FrontDesc &F : P.fronts)
+                    if (H.seg_of_level[F.level_last] == g) front_bwd(F);
+                const int k = H.nseg - 1 - g;     // launch order index
+                std::vector<int> fin;
+                for (int q = H.bseg_ptr[k]; q < H.bseg_ptr[k + 1]; q++)
+                    if (H.pbwd_items[q].blk == -1) {
+                        const int s = H.pbwd_items[q].sn;
+                        if (launch_of[s] != g) bad = -22;      // both sweeps of a segment hold the same supernodes
+                        fin.push_back(s);
+                        bwd_sn(s);
+                    }
+                bwd_blocks(H.pbwd_items, H.bseg_ptr[k], H.bseg_ptr[k + 1], fin);
+                for (int l = std::min(H.seg_lstar[g], H.seg_hi[g] + 1) - 1; l >= H.seg_lo[g]; l--) bwd_level(l);
+            }
+        } else {
+            for (int l = 0; l < P.nlevels; l++) fwd_level(l);
+            scale_by_dinv();
+            for (int l = P.nlevels - 1; l >= 0; l--) bwd_level(l);
+        }
+        // the tables of the segment kernels against the launches found above
+        std::vector<int> dep(P.nsuper, 0), col_sn(N, -1);
+        for (int c = 0; c < P.nsuper; c++) {
+            const int p = P.sn_parent[c];
+            if (launch_of[c] >= 0 && H.sn_nitems[c] != nitems(c)) bad = -23;
+            if (p >= 0 && launch_of[c] >= 0 && launch_of[p] == launch_of[c]) dep[p] += H.sn_nitems[c];
+            for (int k = P.sn_first[c]; k < P.sn_first[c + 1]; k++) col_sn[k] = c;
+        }
+        for (int s = 0; s < P.nsuper; s++) {
+            if (H.dep_total[s] != dep[s]) bad = -23;
+            for (int64_t slot = P.sn_rowptr[s]; slot < P.sn_rowptr[s + 1]; slot++) {
+                const int a = col_sn[P.sn_rows[slot]];
+                const bool same = a != s && launch_of[s] >= 0 && launch_of[a] == launch_of[s];
+                if (H.rows_seg[(size_t)slot] != (same ? (P.sn_rows[slot] | kSegRowTagHost) : P.sn_rows[slot])) bad = -24;
+            }
+        }
+        if (bad) return bad;
     }
-    for (int k = 0; k < N; k++) y[k] *= Dinv[k];
-    for (int lvl = P.nlevels - 1; lvl >= 0; lvl--) {
-        for (const FrontDesc &F : P.fronts)
-            if (F.sb_g > 0 && !sb_subst && F.level_last == lvl) { const std::vector<double> zc(y); sbe.bwd(F, zc, y); }   // k_front_bwd_sb
-        for (int q = P.lvl_ptr[lvl]; q < P.lvl_ptr[lvl + 1]; q++) {
-            int s = P.lvl_sn[q], w = W(s), r = R(s), f = P.sn_first[s];
-            if (P.sn_front[s] >= 0 && P.fronts[P.sn_front[s]].sb_g > 0 && !sb_subst) continue;
-            const double *pan = &Lx[P.sn_panel[s]];
-            const double *ld = &Ld[P.sn_diag[s]];
-            const int *rows = &P.sn_rows[P.sn_rowptr[s]];
-            for (int k = 0; k < w; k++) {
-                double a = 0;
-                for (int i = w; i < r; i++) a += pan[i + (size_t)k * r] * y[rows[i]];
-                y[f + k] -= a;
-            }
-            if (xinv) inv_apply(s, w, &y[f], true);        // k_bwd_final: x_J = Linv^T t
-            else
-            for (int k = w - 1; k >= 0; k--)
-                for (int i = k + 1; i < w; i++) y[f + k] -= ld[i + (size_t)k * w] * y[f + i];
-        }
-    }
+    for (int s = 0; s < P.nsuper; s++)
+        if (seen_f[s] != 1 || seen_b[s] != 1) return -25;     // a supernode visited twice or never
     for (int k = 0; k < N; k++) x[P.perm[k]] = y[k];
     if (xmode >= 2) stats[11] = (double)nflag;   // (diagnostic: block solves that took the refinement step)
     return 0;

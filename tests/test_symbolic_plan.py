@@ -37,14 +37,15 @@ def _kkt(prob, rng):
 
 @pytest.mark.parametrize("policy", [0, 1, 2 + 16 * 4, 2 + 16 * 2])
 @pytest.mark.parametrize("maxw,relax", [(64, 1), (8, 1), (3, 0), (1, 0)])
-def test_plan_reproduces_dense_solve(policy, maxw, relax):
+@pytest.mark.parametrize("schedule", [0, 1, 2])
+def test_plan_reproduces_dense_solve(policy, maxw, relax, schedule):
     rng = np.random.default_rng(5)
     probs = [problems.random_sparse_qp(60, 100, 3, 3, 1), problems.random_sparse_qp(200, 300, 4, 4, 2, window=10),
              problems.portfolio_socp(n=40, nsoc=3, socdim=9, seed=1), problems.sdp_blocks(n=12, ncones=2, dim=4, seed=2)]
     for prob in probs:
         k, nz, ds = _kkt(prob, rng)
         b = rng.standard_normal(k.N)
-        rc, x, perm, st = ps.run(k.N, k.colptr, k.rowval, nz, ds, b, max_width=maxw, relax=relax, policy=policy)
+        rc, x, perm, st = ps.run(k.N, k.colptr, k.rowval, nz, ds, b, max_width=maxw, relax=relax, policy=policy, schedule=schedule)
         assert rc == 0
         assert sorted(perm) == list(range(k.N))
         K = sp.csc_matrix((nz, k.rowval, k.colptr), shape=(k.N, k.N)).toarray()
@@ -54,7 +55,8 @@ def test_plan_reproduces_dense_solve(policy, maxw, relax):
         assert st["nreg"] == 0
 
 
-def test_device_work_lists_are_exercised_and_correct():
+@pytest.mark.parametrize("schedule", [0, 1, 2])
+def test_device_work_lists_are_exercised_and_correct(schedule):
     """The host interpreter applies the plan the way the device kernels do (dense tiles in tile coordinates
     incl. tile maps, per-entry gather lists, persistent front sweep with its external gather lists).  A larger
     problem makes sure every kind of work list is present, and the result still equals the dense solve."""
@@ -63,7 +65,7 @@ def test_device_work_lists_are_exercised_and_correct():
     b = rng.standard_normal(k.N)
     seen = dict(nfronts=0, ngather_entries=0, ndense_groups=0, nmapped_tasks=0)
     for maxw in (64, 16):
-        rc, x, perm, st = ps.run(k.N, k.colptr, k.rowval, nz, ds, b, max_width=maxw, relax=1, policy=2 + 16 * 4)
+        rc, x, perm, st = ps.run(k.N, k.colptr, k.rowval, nz, ds, b, max_width=maxw, relax=1, policy=2 + 16 * 4, schedule=schedule)
         assert rc == 0
         K = sp.csc_matrix((nz, k.rowval, k.colptr), shape=(k.N, k.N)).toarray()
         K = K + K.T - np.diag(np.diag(K))
