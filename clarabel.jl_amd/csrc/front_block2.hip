@@ -198,38 +198,63 @@ k_front_block2(DevPlan P, FrontBatch B, int *sync_all, double *scratch_all, doub
     //      the sentinel and polls).  Fully unrolled: the strip / register of a block's columns is static.  The loop is instruction-
     //      issue bound (one wavefront issues every ~5 cycles): uniform base + lane offset addressing, one negation per record (the B
     //      operand), the freshness test by unsigned maxima, the panel stores elsewhere.
-    auto consume = [&](auto with_tr_tag, int jt, v4f64 (&t)[4], double (&dcol)[4][4]) -> bool {
-        constexpr bool WITH_TR = decltype(with_tr_tag)::value;
-        const double *rec0 = stream + (int64_t)jt * 8 * kFbRec;
-        double *ldx = S0 + 4096;                          // [2 buffers][4 waves][2][64 lanes]
-        double rc[3][4][2], rt[3][2], rd[3][2];
-        double pn0 = 0.0, pn1 = 0.0;                      // -l of the record before (WITH_TR: its diagonal-tile update trails by one record)
+    //      The ring is filled in two parts: request_head(jt) issues the loads of records 0 - 2 of tile jt, consume(jt) starts from those
+    //      registers.  A diagonal workgroup requests the NEXT panel's head at the end of a step (the ring is dead between two calls
+    //      of consume(), and so are the operands of the step's staged products: requested any earlier, inside the step's last
+    //      product, the ring spills 250 registers) and awaits it at the head of the next step, see head() below.
+    double rc[3][4][2], rt[3][2], rd[3][2];
 #define F2_REQUEST(slot, Bq) do { \
             const double *rq_ = rec0 + (int64_t)(Bq) * kFbRec; \
             _Pragma("unroll") for (int q = (Bq) >> 1; q < 4; q++) { \
                 rc[slot][q][0] = f2_ldo(rq_, lane8 + (q * 2) * 512); rc[slot][q][1] = f2_ldo(rq_, lane8 + (q * 2 + 1) * 512); } \
             rt[slot][0] = f2_ldo(rq_ + 512, lane8); rt[slot][1] = f2_ldo(rq_ + 512, lane8 + 512); \
             rd[slot][0] = f2_ldo(rq_ + 512, lane8 + 1024); rd[slot][1] = f2_ldo(rq_ + 512, lane8 + 1536); } while (0)
+    auto request_head = [&](int jt) {
+        const double *rec0 = stream + (int64_t)jt * 8 * kFbRec;
         F2_REQUEST(0, 0); F2_REQUEST(1, 1); F2_REQUEST(2, 2);
+    };
+    // the head records have arrived: an empty statement that reads the ring, so the wait for these loads stands here (and leaves
+    // nothing in flight) instead of in front of their first use
+    auto await_head = [&]() {
+        asm volatile("" :: "v"(rc[0][0][0]), "v"(rc[0][0][1]), "v"(rc[0][1][0]), "v"(rc[0][1][1]), "v"(rc[0][2][0]), "v"(rc[0][2][1]),
+                     "v"(rc[0][3][0]), "v"(rc[0][3][1]), "v"(rt[0][0]), "v"(rt[0][1]), "v"(rd[0][0]), "v"(rd[0][1]) : "memory");
+        asm volatile("" :: "v"(rc[1][0][0]), "v"(rc[1][0][1]), "v"(rc[1][1][0]), "v"(rc[1][1][1]), "v"(rc[1][2][0]), "v"(rc[1][2][1]),
+                     "v"(rc[1][3][0]), "v"(rc[1][3][1]), "v"(rt[1][0]), "v"(rt[1][1]), "v"(rd[1][0]), "v"(rd[1][1]) : "memory");
+        asm volatile("" :: "v"(rc[2][1][0]), "v"(rc[2][1][1]), "v"(rc[2][2][0]), "v"(rc[2][2][1]), "v"(rc[2][3][0]), "v"(rc[2][3][1]),
+                     "v"(rt[2][0]), "v"(rt[2][1]), "v"(rd[2][0]), "v"(rd[2][1]) : "memory");
+    };
+    auto consume = [&](auto with_tr_tag, int jt, v4f64 (&t)[4], double (&dcol)[4][4]) -> bool {   // after request_head(jt)
+        constexpr bool WITH_TR = decltype(with_tr_tag)::value;
+        const double *rec0 = stream + (int64_t)jt * 8 * kFbRec;
+        double *ldx = S0 + 4096;                          // [2 buffers][4 waves][2][64 lanes]
+        double pn0 = 0.0, pn1 = 0.0;                      // -l of the record before (WITH_TR: its diagonal-tile update trails by one record)
 #pragma unroll
         for (int Bk = 0; Bk < 8; Bk++) {
             const int sb = Bk >> 1, par = Bk & 1, sl = Bk % 3;
-            for (unsigned spins = 0;; spins++) {               // level with the producer: poll (bounded)
+            auto complete = [&]() -> bool {
                 unsigned m = f2_max3(f2_hi(rt[sl][0]), f2_hi(rt[sl][1]), f2_hi(rd[sl][0]));
                 m = max(m, f2_hi(rd[sl][1]));
 #pragma unroll
                 for (int q = sb; q < 4; q++) m = f2_max3(m, f2_hi(rc[sl][q][0]), f2_hi(rc[sl][q][1]));
-                if (__builtin_amdgcn_readfirstlane((int)(__ballot(m != 0xFFFFFFFFu) == ~0ull)) != 0) break;
-                if ((spins & 63u) == 63u || lim < 64u) {
-                    if (spins > lim) {
-                        __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        if (lane == 0) atomicOr(failflag, 1);
-                        return false;
+                return __builtin_amdgcn_readfirstlane((int)(__ballot(m != 0xFFFFFFFFu) == ~0ull)) != 0;
+            };
+            // level with the producer: poll (bounded).  The first test stands in front of the loop: as the loop's first statement it
+            // shares its wait with the tests behind a re-request, whose loads are the youngest on the counter -- the compiler then
+            // waits for everything in flight (the ring's other records, the panel stores of a step's head) instead of for this record
+            if (!complete()) {
+                for (unsigned spins = 0;; spins++) {
+                    if ((spins & 63u) == 63u || lim < 64u) {
+                        if (spins > lim) {
+                            __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            if (lane == 0) atomicOr(failflag, 1);
+                            return false;
+                        }
+                        if (__builtin_amdgcn_readfirstlane(f2_ldi(err)) != 0) return false;
                     }
-                    if (__builtin_amdgcn_readfirstlane(f2_ldi(err)) != 0) return false;
+                    __builtin_amdgcn_s_sleep(1);
+                    F2_REQUEST(sl, Bk);
+                    if (complete()) break;
                 }
-                __builtin_amdgcn_s_sleep(1);
-                F2_REQUEST(sl, Bk);
             }
             if (WITH_TR && Bk == 0) F2_T(3);
             double cr[4][2], tv[2], dv[2];
@@ -294,9 +319,9 @@ k_front_block2(DevPlan P, FrontBatch B, int *sync_all, double *scratch_all, doub
                 tr[so] = __builtin_amdgcn_mfma_f64_16x16x4f64(la[so][1], pn1, tr[so], 0, 0, 0);
             }
         }
-#undef F2_REQUEST
         return true;
     };
+#undef F2_REQUEST
 
     // ---- the panels left of this block: X_j^T = Minv_j^T A_j^T, then A_k^T -= (L(k,j) D_j) X_j^T for the tiles right of it
     double *STG = S1;                                     // staging tile of the shared operand (S1 holds L11 only from the pivots on)
@@ -418,6 +443,7 @@ k_front_block2(DevPlan P, FrontBatch B, int *sync_all, double *scratch_all, doub
                 if (k == nb - 1) x[sub] = acc[k][sub];
         }
         double dj[4][4];
+        request_head(nb - 1);
         if (!consume(std::false_type{}, nb - 1, x, dj)) return;
         f2_settle();
         if (rowok) {
@@ -439,6 +465,38 @@ k_front_block2(DevPlan P, FrontBatch B, int *sync_all, double *scratch_all, doub
     //      no step waits for the inverse of a tile, which is published 4 - 5 us after its pivots.  Then the step's hand-off and
     //      updates as in the regular steps.  One copy of the code, rolled over j2; the tiles are selected by run-time index.
     const bool early_store = FB_EARLY_STORE && i == nb - 1 && B.nblk > nb;
+    // The head of a step over panel jt.  Its first records were requested at the END of the step before (request_head(jt) below, in
+    // front of that step's last register shuffles, which cover most of the round trip) and are awaited here, so nothing is in
+    // flight when -- in the batch's LAST diagonal workgroup only (round 6: the launch ends with ITS panel stores, four tiles, ~10 us
+    // after its last pivot, so it stores a panel as soon as the panel is final) -- the stores of panel jt - 1, finished by the step
+    // before, are issued.  A store sits on the same in-order counter as the record loads.  Issued at the end of its own step, in
+    // front of the request (round 6), it made the first records of the next panel wait for 32 write-through acknowledgements on the
+    // one workgroup of the chain that has no slack (last hop 23 - 25 us against 15).  Issued BEHIND records that have arrived it is
+    // harmless: records 0 - 2 need no wait at all, and the first load younger than the stores (record 3, requested after record 0) is
+    // needed three records (~2.3 us) later.  [The wait has to stand in front of the stores explicitly: left to the first use of a
+    // record, it is placed behind the join of the storing and the non-storing path and counts as if no store were in flight -- it
+    // then waits for 10 of the 32 stores at record 0, 23 at record 1, all at record 2 (measured: last hop unchanged).]
+    FrontPanel pe = fp[0];                                // panel jt - 1 of the next head (a vector load: issued a step ahead of its use)
+    auto head = [&](int jt, bool store) {
+        await_head();
+        if (early_store && store && rowok) {
+            double *dst = P.Lx + pe.panel_off + 64 * (i - (jt - 1));
+            double *lt2 = P.LT + pe.lt_off + (int64_t)(64 * (i - (jt - 1)) - 64) * 64;
+            const unsigned o1 = 8u * (unsigned)(n + lk * pe.r), o2 = 8u * (unsigned)(n * 64 + lk);
+#pragma unroll
+            for (int sub = 0; sub < 4; sub++)
+#pragma unroll
+                for (int reg = 0; reg < 4; reg++) {
+                    double v = 0.0;
+#pragma unroll
+                    for (int k = 0; k < kFbMax - 1; k++)
+                        if (k == jt - 1) v = acc[k][sub][reg];
+                    st_off(dst + (int64_t)(16 * sub + 4 * reg) * pe.r, o1, v);
+                    st_off(lt2, o2 + 8u * (unsigned)(16 * sub + 4 * reg), v);
+                }
+        }
+    };
+    if (i > 0) request_head(0);
 #pragma unroll 1
     for (int j2 = 0; j2 < i - 1; j2++) {
         v4f64 x[4];
@@ -450,8 +508,10 @@ k_front_block2(DevPlan P, FrontBatch B, int *sync_all, double *scratch_all, doub
                 if (k == j2) x[sub] = acc[k][sub];
         }
         double dj[4][4];
+        head(j2, j2 > 0);
         if (!consume(std::false_type{}, j2, x, dj)) return;
         if (j2 == i - 2) F2_T(9);
+        const FrontPanel pn = fp[j2];                     // (awaited with this step's hand-off stores below)
         {
             double *lt = ltiles + (int64_t)(i * (i - 1) / 2 + j2) * 4096 + (wv * 16) * 64;
             double *xd = S0 + (j2 & 1) * 4096;
@@ -478,6 +538,7 @@ k_front_block2(DevPlan P, FrontBatch B, int *sync_all, double *scratch_all, doub
             f2_settle();
             if (j2 == i - 2) F2_T(11);
             f2_wave_done(fl_L + 8 * i + j2);
+            pe = pn;
         }
         // the tiles between panel j2 and the own one need L(k, j2) D of the diagonal workgroups above (raised after THEIR step j2)
 #pragma unroll 1
@@ -508,30 +569,14 @@ k_front_block2(DevPlan P, FrontBatch B, int *sync_all, double *scratch_all, doub
                 for (int kk = 0; kk < kFbMax; kk++)
                     if (kk == k) acc[kk][sub] = t[sub];
         }
-        // the finished rows stay in the tile's registers (x holds -X); they go to the panel at the very end -- a store here would
-        // sit in front of the next step's record loads on the memory counter
+        // the next panel's first records, then the finished rows: they stay in the tile's registers (x holds -X) and go to the panel at
+        // the very end (the batch's last diagonal workgroup: at the head of the next step, behind these records, see head())
+        request_head(j2 + 1);
 #pragma unroll
         for (int sub = 0; sub < 4; sub++)
 #pragma unroll
             for (int kk = 0; kk < kFbMax; kk++)
                 if (kk == j2) acc[kk][sub] = -x[sub];
-        // ... except in the batch's LAST diagonal workgroup (round 6): the launch ends with ITS panel stores (four tiles, ~10 us after
-        // its last pivot), and it spends most of the launch waiting for the workgroups before it -- its stores of a finished panel
-        // wait in front of flag polls that are not due yet
-        if (early_store && rowok) {
-            const FrontPanel pk = fp[j2];
-            double *dst = P.Lx + pk.panel_off + 64 * (i - j2);
-            double *lt2 = P.LT + pk.lt_off + (int64_t)(64 * (i - j2) - 64) * 64;
-            const unsigned o1 = 8u * (unsigned)(n + lk * pk.r), o2 = 8u * (unsigned)(n * 64 + lk);
-#pragma unroll
-            for (int sub = 0; sub < 4; sub++)
-#pragma unroll
-                for (int reg = 0; reg < 4; reg++) {
-                    const double v = -x[sub][reg];
-                    st_off(dst + (int64_t)(16 * sub + 4 * reg) * pk.r, o1, v);
-                    st_off(lt2, o2 + 8u * (unsigned)(16 * sub + 4 * reg), v);
-                }
-        }
     }
     v4f64 xr[4];                                          // the tile of panel i - 1, L(i, i-1) after the streamed step
 #pragma unroll
@@ -545,6 +590,7 @@ k_front_block2(DevPlan P, FrontBatch B, int *sync_all, double *scratch_all, doub
     if (i > 0) {
         double dl[4][4];
         f2_bar();                                         // the X D buffers of the steps before are free
+        head(i - 1, i > 1);
         if (!consume(std::true_type{}, i - 1, xr, dl)) return;
         // L(i, i-1) D for the workgroups below (operand order); the flag follows during the first pivot block
         double *lt = ltiles + (int64_t)(i * (i - 1) / 2 + i - 1) * 4096 + (wv * 16) * 64;

@@ -89,7 +89,8 @@ void enqueue_updates(hipkkt_solver *S, int l, int dense_skip_tail = 0) {
 }
 
 // How many of a front batch's far tiles ride in the next k_front_block launch (enqueue_factor; HIPKKT_FB_EXTRA=0: none).  That launch
-// has `next_blk` workgroups of its own, one per compute unit (100 KB of LDS), and lasts ~112 us: every other compute unit can take one
+// has `next_blk` workgroups of its own, one per compute unit (100 KB of LDS), and lasts ~86 us (five panels, cfg 2a; 112 us when the
+// tile counts below were measured, in round 4): every other compute unit can take one
 // extra workgroup = four wavefronts, each alone on its SIMD, with one tile (launch +10 us) or two tiles one after the other (+28 us)
 // per wavefront.  The stage's own launch then holds M = nd - r tiles; its cost is a step function of M (rounds of one tile per SIMD;
 // measured on MI355X at K = 320: 1024 tiles 77 us, 2048 130, 3072 194; a remainder of <= 256 tiles as strips +13, <= 512 as halves

@@ -22,12 +22,30 @@ raw = hk.h.debug_dump(9).view(np.int64).reshape(-1, 8, 16)
 t = raw * 0.01   # microseconds
 names = ["start", "loaded", "steps done", "first record", "streamed", "pivots start", "pivots end", "minv published", "end",
          "last step: minv seen", "X done", "diag tile done", "L flag raised", "L(i-1, j) seen"]
-periods = []
+periods, hop_rows = [], []
+
+
+def hops_of(bi):
+    """hop h = pivot start of workgroup h minus that of workgroup h - 1; tail = last pivot block of the last diagonal workgroup to its end"""
+    piv = [t[bi, i, 5] for i in range(5) if t[bi, i, 5] > 0]
+    if len(piv) < 2:
+        return None
+    last = len(piv) - 1
+    return np.diff(piv), t[bi, last, 8] - t[bi, last, 6]
+
+
+def hop_line(hops, tail):
+    before = f"{np.mean(hops[:-1]):.2f}" if len(hops) > 1 else "-"
+    return (f"hops {' / '.join(f'{h:.2f}' for h in hops)} us; last hop {hops[-1]:.2f} against {before} (mean of the hops before it); "
+            f"tail {tail:.2f} us")
+
+
 for bi in range(len(t)):
     t0 = t[bi, 0, 0]
     piv = [t[bi, i, 5] - t0 for i in range(5) if t[bi, i, 5] > 0]
     if len(piv) > 1:
         periods.append(np.mean(np.diff(piv)))
+        hop_rows.append(hops_of(bi))
     if bi not in (1, 8, 15):
         continue
     print(f"batch {bi}: stamps relative to workgroup 0's start (us)")
@@ -44,9 +62,17 @@ for bi in range(len(t)):
     if len(piv) > 1:
         print(f"  chain: pivots start at {[round(float(v), 2) for v in piv]} -> {np.mean(np.diff(piv)):.2f} us per panel; pivots themselves "
               f"{np.mean([t[bi, i, 6] - t[bi, i, 5] for i in range(len(piv))]):.2f} us")
+        print("  " + hop_line(*hops_of(bi)))
         for i in range(1, len(piv)):
             if t[bi, i, 3] > 0 and t[bi, i, 4] > 0:
                 print(f"    wg {i}: first record {t[bi, i, 3] - t[bi, i - 1, 5]:5.2f} us after wg {i-1}'s pivot start, {(t[bi, i, 4] - t[bi, i, 3]) / 8.0:4.2f} us per record, "
                       f"streamed step done {t[bi, i, 4] - t[bi, i - 1, 6]:5.2f} us after wg {i-1}'s last pivot block (incl. its T and publish)")
 if periods:
     print(f"all {len(periods)} batches: mean chain period {np.mean(periods):.2f} us per panel (min {np.min(periods):.2f}, max {np.max(periods):.2f})")
+    # batches of the full length only: hop h of a shorter batch is another workgroup's hop
+    nfull = max(len(h) for h, _ in hop_rows)
+    full = [(h, tl) for h, tl in hop_rows if len(h) == nfull]
+    print(f"  {len(full)} batches of {nfull + 1} panels, mean: " + hop_line(np.mean([h for h, _ in full], axis=0), np.mean([tl for _, tl in full])))
+    lasts, befores = [h[-1] for h, _ in hop_rows], [np.mean(h[:-1]) for h, _ in hop_rows if len(h) > 1]
+    print(f"  all {len(hop_rows)} batches, mean: last hop {np.mean(lasts):.2f} us against {np.mean(befores):.2f} (hops before it); "
+          f"tail {np.mean([tl for _, tl in hop_rows]):.2f} us")
