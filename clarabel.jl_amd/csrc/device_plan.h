@@ -9,13 +9,13 @@ namespace hipkkt {
 enum { SC_MAXDIAG = 0, SC_NORMB = 1, SC_NORME = 2, SC_COUNT = 8 };  // 64-bit scalar slots
 enum { FL_NONFINITE = 0, FL_NREG = 1, FL_FRONTFAIL = 2, FL_FACFAIL = 3, FL_NPOLISH = 4, FL_COUNT = 8 };   // int flags (FL_FACFAIL: k_front_block gave up)
 
-// hand-off slot of the persistent sweeps: a value and its self-validating tag (kernels.hip front_slot_* / seg_slot_*)
+// hand-off slot of the persistent sweeps: a value and its self-validating tag (sweep_common.h front_slot_*, solve_sweep.hip seg_slot_st)
 struct __attribute__((aligned(16))) FrontSlot {
     double v;
     unsigned long long h;
 };
 
-// Device-resident state of one refined solve (kernels.hip k_refine_*): the control flow of the reference's
+// Device-resident state of one refined solve (refine.hip k_refine_*): the control flow of the reference's
 // _iterative_refinement (kktsolver_directldl.jl:389-449) is decided ON THE DEVICE, so a refined solve needs one host
 // synchronisation (at its end) instead of one per refinement step.  The current iterate is xbuf[cur], the candidate
 // xbuf[1 - cur] (the reference swaps x and dx).
@@ -36,7 +36,7 @@ struct GathPair {
     int32_t K;                    // its width
     int32_t dfirst;               // first pivot of the source in D
 };
-// 64 rows of a dense triangle of K (k_spmv_dense_tri, kernels.hip)
+// 64 rows of a dense triangle of K (k_spmv_dense_tri, refine.hip)
 struct DenseTriStrip {
     int c0, d, i0, pad;   // the triangle's first row / column, its dimension; first row of the strip inside it
     int64_t col0;         // the triangle's first entry in DevPlan::dtri_col
@@ -62,6 +62,23 @@ constexpr int kFbRec = 768;       // one streamed block of 8 pivots.  front_bloc
                                   // operand order, 2 of T = L_bb^-T D_b^-1, 2 of the pivots); front_block.hip uses the first 528: [8][64] raw columns, d, 1/d
 constexpr int64_t kFbStream = (int64_t)kFbMax * 8 * kFbRec;   // doubles per batch
 constexpr int kGathHeavy = 24;    // target entries with more pairs than this get a wavefront of their own
+
+// What the solve kernels (solve_sweep.hip) and their host side (solve_schedule.cpp, hipkkt_internal.h sync_words()) agree on:
+constexpr int kSlvRows = 64;             // off-diagonal rows of one solve item (solve_sweep.hip gives the latency model behind it)
+constexpr int kSegSub = 8;               // fdone sub-counters of a supernode that waits for >= kSegSubMin blocks (solve_sweep.hip: why)
+constexpr int kSegSubMin = 64;
+constexpr int kSegRowTag = 0x40000000;   // rows_seg: the row's x comes from an item of the same launch
+// DevPlan::seg_sync, in ints: [forward tickets | backward tickets], one per segment, padded to whole 128-byte lines (k_permute_in
+// clears them with plain stores, which must not share a line with words under atomic increment); fdone, kSegSub arrays of nsuper
+// counters; the error word; `words` = what the host allocates and re-arms (16 trailing words from the error word on).
+struct SegSyncLayout { int ftick, btick, fdone; int64_t err, words; };
+constexpr SegSyncLayout seg_sync_layout(int nseg, int nsuper) {
+    const int fdone = (2 * nseg + 31) & ~31;
+    const int64_t err = fdone + (int64_t)kSegSub * nsuper;
+    return {0, nseg, fdone, err, err + 16};
+}
+static_assert(seg_sync_layout(3, 5).btick == 3 && seg_sync_layout(3, 5).fdone == 32 && seg_sync_layout(3, 5).err == 32 + 8 * 5 &&
+              seg_sync_layout(3, 5).words == 88, "seg_sync: tickets padded to 32 ints, then 8 * nsuper counters, then the error word");
 
 struct DevPlan {
     // structure (read-only after setup)
@@ -107,20 +124,19 @@ struct DevPlan {
     const FrontPanel *front_panels;
     const int64_t *front_gptr;
     const int *front_gidx;
-    int *front_sync;
+    int *front_sync;             // per front and sweep direction: {ticket, error word}, then the hand-off slots (sweep_common.h front_slots())
     // persistent level-free sweeps over the regular (non-front) supernodes: dependency counters and lists
     const FacItem *pbwd_items;   // backward order: per level (descending) partial items, then finals (blk = -1)
     const int *dep_total;        // [nsuper] forward items of all same-segment regular children (what fdone[s] must reach)
     const int *sn_nitems;        // forward items (64-row blocks) of a supernode
     const int *sn_bparent;       // same-segment regular parent, or -1
-    int *seg_sync;               // [0,nseg) forward tickets, [nseg,2nseg) backward tickets, then per-supernode counters:
-    int seg_ticket;              // bit 0 / bit 1: forward / backward segment-sweep items are atomic tickets (default 3); 0: blockIdx
-    unsigned spin_limit;         // bound of every spin loop of the persistent sweeps (default 2^20; HIPKKT_SPIN_LIMIT)
+    int *seg_sync;               // tickets, completion counters and error word of the segment sweeps: seg_sync_layout(nseg, nsuper)
+    unsigned spin_limit;        // bound of every spin loop of the persistent sweeps (default 2^20; HIPKKT_SPIN_LIMIT)
     int *sn_polish;              // [nsuper] 1: the block solves with this supernode take one refinement step (written by k_invert_diag_wide per factorisation)
     double polish_tau;           // threshold on the largest |entry| of a wide block's explicit inverse (64; HIPKKT_ACCURATE)
     int dbg;                     // timing experiments only (HIPKKT_DEBUG_FLAGS; results are WRONG when set): bit 0 = the super-block sweeps skip
                                  // their L tile loads (what remains is the hand-off chain)
-    int nseg;                    //   fdone[8][nsuper] (kernels.hip kSegSub); error word last   // per front: {ticket, error, flags[np]} (zeroed before every front kernel)
+    int nseg;                    // segments of the persistent sweeps (SolveSchedule::nseg)
     // numeric state
     double *kval;    // resident, UNREGULARISED triu KKT values (original nz order)
     double *Lx;      // supernodal panels
@@ -132,7 +148,7 @@ struct DevPlan {
     double *D;
     double *Dinv;
     double *ubuf;    // forward-solve update vectors
-    // tagged hand-off of the backward segment sweep (kernels.hip seg_slot_*): 16-byte slots parallel to x / pbuf, the
+    // tagged hand-off of the backward segment sweep (solve_sweep.hip seg_slot_st): 16-byte slots parallel to x / pbuf, the
     // solve epoch, and the copy of sn_rows that marks the rows whose x is produced inside the same launch
     FrontSlot *xseg, *pseg;
     int *seg_epoch;

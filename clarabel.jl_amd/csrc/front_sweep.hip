@@ -1,4 +1,6 @@
-// K5 over a FRONT, super-block sweeps (round 3; VERDICT r2 task 1): the per-panel sweeps of kernels.hip (k_front_fwd / k_front_bwd)
+// K5 over a FRONT: both forms of the persistent front sweeps and the choice between them (launch_front_fwd / launch_front_bwd).
+// The per-panel sweeps (k_front_fwd / k_front_bwd, at the end of this file with the protocol both forms share) come first in time;
+// the super-block sweeps (round 3; VERDICT r2 task 1) answer their cost: the per-panel sweeps
 // pay one inter-workgroup hand-off per 64-column panel -- 88 dependent hops of ~1.7 us on the 5617-column root of a random sparse
 // QP, at 14 % of the HBM roofline.  Here the np panels of a front are grouped into super-blocks of kSbG = 8 consecutive panels and
 // the explicit inverse of every super-block's unit-lower diagonal block (8 x 8 tiles of 64 x 64, formed after each factorisation by
@@ -578,11 +580,262 @@ k_front_bwd_sb(DevPlan P, FrontDesc F, const double *__restrict__ z, double *__r
     }
 }
 
-void launch_front_fwd_sb(hipStream_t st, const DevPlan &P, const FrontDesc &F, double *y, double *z) {
-    hipLaunchKernelGGL(k_front_fwd_sb, dim3(2 * F.nb), dim3(kSbThreads), 0, st, P, F, y, z);
+// ------------------------------------------------------------------------------------------
+// K5 over a FRONT (a chain of np panels cut from one wide supernode, e.g. the dense root of a random
+// sparse QP): ONE persistent launch per sweep instead of np dependent launches.  Workgroup b owns the
+// b-th row block of the front, accumulates  sum_q L[b,q] y_q  over the panels q in order while the
+// y_q are published by their owners through self-validating hand-off slots (below), then solves its
+// own diagonal block and publishes.  The L blocks of step q+1 are prefetched while the workgroup
+// waits for y_q, so a hop costs one hand-off + two 64x64 GEMVs (1.6 us measured; the sweep reads L
+// once, 126 MB on cfg 2a, i.e. it also runs at ~0.9 TB/s of HBM traffic).
+// Deadlock freedom: block indices are tickets taken in arrival order (a workgroup only ever waits for
+// lower tickets, whose owners are already running); every spin is bounded and aborts through the
+// front's error word, which makes the solve report a failure instead of hanging.
+// Summation order is fixed (panel order, then a fixed 4-way tree): results are deterministic.
+// ------------------------------------------------------------------------------------------
+// (front_ld_flag / front_ld / front_st, the self-validating hand-off slots and front_slots(): sweep_common.h)
+
+__global__ void __launch_bounds__(256)
+k_front_fwd(DevPlan P, FrontDesc F, double *__restrict__ y, double *__restrict__ z) {
+    __shared__ double red[4][64];
+    __shared__ double tv[64];
+    __shared__ double ybuf[2][64];
+    __shared__ int sb, okflag;
+    int *sync = P.front_sync + F.sync_off;
+    if (threadIdx.x == 0) sb = atomicAdd(sync, 1);
+    __syncthreads();
+    const int b = sb;
+    if (b >= F.nb) return;
+    // re-arm the backward sweep's block (idle during this launch), every workgroup a share
+    for (int q = b * 256 + threadIdx.x; q < F.sync_blk; q += F.nb * 256) sync[F.sync_blk + q] = 0;
+    FrontSlot *slots = front_slots(sync, F.np);
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const FrontPanel *fps = P.front_panels + F.fp_off;
+    const bool own = b < F.np;
+    FrontPanel me = fps[own ? b : 0];
+    const int i0 = own ? F.cw * b : F.W + 64 * (b - F.np);
+    const int nrows = own ? me.w : min(64, F.rF - i0);
+    const int i = i0 + lane;
+    const bool valid = lane < nrows;
+    // this row's start value: own rows  b_i - (external children), rows below the front  + (external children)
+    double base = 0.0;
+    if (wv == 0 && valid) {
+        double G = 0.0;
+        const int64_t g0 = P.front_gptr[F.gptr_off + i], g1 = P.front_gptr[F.gptr_off + i + 1];
+        for (int64_t g = g0; g < g1; g++) G += P.ubuf[P.front_gidx[g]];
+        base = own ? y[me.f + lane] - G : G;
+    }
+    const double dinv_own = (own && valid) ? P.Dinv[me.f + lane] : 0.0;   // static: fetched before any wait
+    // own diagonal block: row `lane` of Linv, columns j = wv + 4t (lower triangle)
+    double li[16];
+#pragma unroll
+    for (int t = 0; t < 16; t++) {
+        const int j = wv + 4 * t;
+        li[t] = (own && valid && j <= lane) ? P.Linv[me.diag_off + lane + j * me.w] : 0.0;
+    }
+    const int nq = own ? b : F.np;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    FrontPanel fq = fps[0];
+    double lv[16];
+#pragma unroll
+    for (int t = 0; t < 16; t++) {
+        const int k = wv + 4 * t;
+        lv[t] = (nq > 0 && valid && k < fq.w) ? P.Lx[fq.panel_off + i + (int64_t)k * fq.r] : 0.0;
+    }
+    bool ok = true;
+    for (int q = 0; q < nq; q++) {
+        FrontPanel fn = fq;
+        double ln[16];
+        if (q + 1 < nq) {                      // prefetch the next panel's block before waiting
+            fn = fps[q + 1];
+            const int jl = i - F.cw * (q + 1);
+#pragma unroll
+            for (int t = 0; t < 16; t++) {
+                const int k = wv + 4 * t;
+                ln[t] = (valid && k < fn.w) ? P.Lx[fn.panel_off + jl + (int64_t)k * fn.r] : 0.0;
+            }
+        } else {
+#pragma unroll
+            for (int t = 0; t < 16; t++) ln[t] = 0.0;
+        }
+        // ONE wave polls the panel's hand-off slots (value and validity in one 16-byte load per lane); the
+        // workgroup reads y_q from LDS (double buffered by hop parity: one barrier per hop)
+        double *yb = ybuf[q & 1];
+        if (wv == 0) {
+            double yv = 0.0;
+            ok = front_slot_wait(slots + q * 64 + lane, yv, sync + 1, P.flags + FL_FRONTFAIL, P.spin_limit);
+            yb[lane] = ok ? yv : 0.0;
+            if (lane == 0) okflag = ok ? 1 : 0;
+        }
+        __syncthreads();
+        if (!okflag) { ok = false; break; }
+#pragma unroll
+        for (int t = 0; t < 16; t += 4) {
+            a0 = fma(lv[t], yb[(wv + 4 * t) & 63], a0);
+            a1 = fma(lv[t + 1], yb[(wv + 4 * t + 4) & 63], a1);
+            a2 = fma(lv[t + 2], yb[(wv + 4 * t + 8) & 63], a2);
+            a3 = fma(lv[t + 3], yb[(wv + 4 * t + 12) & 63], a3);
+        }
+        fq = fn;
+#pragma unroll
+        for (int t = 0; t < 16; t++) lv[t] = ln[t];
+    }
+    red[wv][lane] = (a0 + a1) + (a2 + a3);
+    __syncthreads();
+    const double tot = ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
+    if (!own) {
+        if (wv == 0 && valid && ok) P.ubuf[F.ubelow_off + (i - F.W)] = base + tot;
+        return;
+    }
+    if (wv == 0) tv[lane] = valid ? base - tot : 0.0;
+    __syncthreads();
+    {   // y_J = Linv * t  (lower-triangular GEMV, 4-way split over j)
+        double s0 = 0.0, s1 = 0.0;
+#pragma unroll
+        for (int t = 0; t < 16; t += 2) {
+            s0 = fma(li[t], tv[wv + 4 * t], s0);
+            s1 = fma(li[t + 1], tv[wv + 4 * t + 4], s1);
+        }
+        red[wv][lane] = s0 + s1;
+    }
+    __syncthreads();
+    if (wv == 0) {
+        const double v = valid ? ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane] : 0.0;
+        if (ok) front_slot_st(slots + b * 64 + lane, v);     // first: the next panel's owner is waiting for it
+        if (valid && ok) z[me.f + lane] = v * dinv_own;
+    }
 }
-void launch_front_bwd_sb(hipStream_t st, const DevPlan &P, const FrontDesc &F, const double *z, double *x, double *xout) {
-    hipLaunchKernelGGL(k_front_bwd_sb, dim3(2 * F.np), dim3(kSbThreads), 0, st, P, F, z, x, xout);
+
+// backward sweep over a front: ticket t owns panel p = np-1-t:  x_J = L_JJ^-T (z_J - L_RJ^T x_R), where R
+// = the rows below the front (final before the launch) followed by the later panels' columns in
+// descending panel order (published inside the launch).  lane = column, wave = 16-row slice.
+__global__ void __launch_bounds__(256)
+k_front_bwd(DevPlan P, FrontDesc F, const double *__restrict__ z, double *__restrict__ x, double *__restrict__ xout) {
+    __shared__ double red[4][64];
+    __shared__ double tv[64];
+    __shared__ double xbuf[2][64];
+    __shared__ int sb, okflag;
+    int *sync = P.front_sync + F.sync_off + F.sync_blk;
+    if (threadIdx.x == 0) sb = atomicAdd(sync, 1);
+    __syncthreads();
+    if (sb >= F.np) return;
+    // re-arm the forward sweep's block for the next solve (idle during this launch), every workgroup a share
+    for (int q = sb * 256 + threadIdx.x; q < F.sync_blk; q += F.np * 256) sync[q - F.sync_blk] = 0;
+    FrontSlot *slots = front_slots(sync, F.np);
+    const int p = F.np - 1 - sb;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const FrontPanel *fps = P.front_panels + F.fp_off;
+    const FrontPanel me = fps[p];
+    const int w = me.w;
+    const bool cvalid = lane < w;
+    const double *lt = P.LT + me.lt_off;            // row-major: lt[(j - w) * w + k], j = local panel row
+    const int perm_own = cvalid ? P.perm[me.f + lane] : 0;                // static: fetched before any wait
+    // own diagonal block: column `lane` of Linv (as stored transposed), rows i2 = wv + 4t >= lane
+    double lit[16];
+#pragma unroll
+    for (int t = 0; t < 16; t++) {
+        const int i2 = wv + 4 * t;
+        lit[t] = (cvalid && i2 >= lane && i2 < w) ? P.LinvT[me.diag_off + lane + i2 * w] : 0.0;
+    }
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    // (A) rows below the front: x is final
+    {
+        const int *rows = P.sn_rows + F.rows_off;
+        for (int ib = F.W; ib < F.rF; ib += 64) {
+            const int lo = ib + 16 * wv;
+            double xv[16], l[16];
+#pragma unroll
+            for (int t = 0; t < 16; t++) {
+                const int i = lo + t;
+                const bool in = i < F.rF && i < ib + 64;
+                xv[t] = in ? x[rows[in ? i : F.W]] : 0.0;
+                l[t] = (in && cvalid) ? lt[(int64_t)(i - F.cw * p - w) * w + lane] : 0.0;
+            }
+#pragma unroll
+            for (int t = 0; t < 16; t += 4) {
+                a0 = fma(l[t], xv[t], a0);
+                a1 = fma(l[t + 1], xv[t + 1], a1);
+                a2 = fma(l[t + 2], xv[t + 2], a2);
+                a3 = fma(l[t + 3], xv[t + 3], a3);
+            }
+        }
+    }
+    // (B) later panels, descending
+    bool ok = true;
+    double lv[16];
+    {
+        const int q = F.np - 1;
+        const FrontPanel fq = fps[q];
+#pragma unroll
+        for (int t = 0; t < 16; t++) {
+            const int jr = 16 * wv + t;
+            lv[t] = (q > p && cvalid && jr < fq.w) ? lt[(int64_t)(F.cw * (q - p) + jr - w) * w + lane] : 0.0;
+        }
+    }
+    for (int q = F.np - 1; q > p; q--) {
+        double ln[16];
+        if (q - 1 > p) {
+            const FrontPanel fn = fps[q - 1];
+#pragma unroll
+            for (int t = 0; t < 16; t++) {
+                const int jr = 16 * wv + t;
+                ln[t] = (cvalid && jr < fn.w) ? lt[(int64_t)(F.cw * (q - 1 - p) + jr - w) * w + lane] : 0.0;
+            }
+        } else {
+#pragma unroll
+            for (int t = 0; t < 16; t++) ln[t] = 0.0;
+        }
+        double *xb = xbuf[q & 1];
+        if (wv == 0) {   // one polling wave, broadcast through LDS (see k_front_fwd)
+            double xv = 0.0;
+            ok = front_slot_wait(slots + q * 64 + lane, xv, sync + 1, P.flags + FL_FRONTFAIL, P.spin_limit);
+            xb[lane] = ok ? xv : 0.0;
+            if (lane == 0) okflag = ok ? 1 : 0;
+        }
+        __syncthreads();
+        if (!okflag) { ok = false; break; }
+#pragma unroll
+        for (int t = 0; t < 16; t += 4) {
+            a0 = fma(lv[t], xb[16 * wv + t], a0);
+            a1 = fma(lv[t + 1], xb[16 * wv + t + 1], a1);
+            a2 = fma(lv[t + 2], xb[16 * wv + t + 2], a2);
+            a3 = fma(lv[t + 3], xb[16 * wv + t + 3], a3);
+        }
+#pragma unroll
+        for (int t = 0; t < 16; t++) lv[t] = ln[t];
+    }
+    red[wv][lane] = (a0 + a1) + (a2 + a3);
+    __syncthreads();
+    if (wv == 0) tv[lane] = cvalid ? z[me.f + lane] - (((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane]) : 0.0;
+    __syncthreads();
+    {   // x_J = Linv^T t :  x_k = sum_{i >= k} Linv[i][k] t_i
+        double s0 = 0.0, s1 = 0.0;
+#pragma unroll
+        for (int t = 0; t < 16; t += 2) {
+            s0 = fma(lit[t], tv[wv + 4 * t], s0);
+            s1 = fma(lit[t + 1], tv[wv + 4 * t + 4], s1);
+        }
+        red[wv][lane] = s0 + s1;
+    }
+    __syncthreads();
+    if (wv == 0) {
+        const double v = cvalid ? ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane] : 0.0;
+        if (ok) front_slot_st(slots + p * 64 + lane, v);     // first: the previous panel's owner is waiting for it
+        if (cvalid && ok) {
+            x[me.f + lane] = v;
+            xout[perm_own] = v;
+        }
+    }
+}
+
+// the choice between the two forms: super-blocks where the plan formed them (FrontDesc::sb_g > 0), one hop per panel otherwise
+void launch_front_fwd(hipStream_t st, const DevPlan &P, const FrontDesc &F, double *y, double *z) {
+    if (F.sb_g > 0) hipLaunchKernelGGL(k_front_fwd_sb, dim3(2 * F.nb), dim3(kSbThreads), 0, st, P, F, y, z);
+    else hipLaunchKernelGGL(k_front_fwd, dim3(F.nb), dim3(256), 0, st, P, F, y, z);
+}
+void launch_front_bwd(hipStream_t st, const DevPlan &P, const FrontDesc &F, const double *z, double *x, double *xout) {
+    if (F.sb_g > 0) hipLaunchKernelGGL(k_front_bwd_sb, dim3(2 * F.np), dim3(kSbThreads), 0, st, P, F, z, x, xout);
+    else hipLaunchKernelGGL(k_front_bwd, dim3(F.np), dim3(256), 0, st, P, F, z, x, xout);
 }
 void launch_invert_super(hipStream_t st, const DevPlan &P, const FrontDesc &F) {
     if (F.sb_g <= 0 || F.nsb <= 0) return;

@@ -142,7 +142,7 @@ static void enqueue_factor(hipkkt_solver *S, int static_enable, double eps_const
     const HostPlan &P = S->plan;
     hipStream_t st = S->stream;
     S->side_join_level = -1;
-    launch_zero_words(st, S->dp.scal, 2);                 // SC_MAXDIAG  (kernels.hip: why not hipMemsetAsync)
+    launch_zero_words(st, S->dp.scal, 2);                 // SC_MAXDIAG  (values.hip: why not hipMemsetAsync)
     launch_zero_words(st, S->dp.flags, FL_COUNT);
     launch_maxabs_gather(st, S->dp.kval, S->d_diag_full, S->N, (unsigned long long *)S->dp.scal + SC_MAXDIAG);
     HK_CHECK(hipMemsetAsync(S->dp.Lx, 0, (size_t)(P.panel_doubles + S->split.scratch_doubles) * sizeof(double), st));   // (incl. the split-K partial tiles: a factorisation that aborted between a chunk launch and its reduce must not leave sums behind)

@@ -7,7 +7,8 @@
 //   hipkkt_solve.cpp   LDL solves, device-side iterative refinement, the solve entry points
 //   hipkkt_step.cpp    the cone algebra of an interior-point step around the reduced solve (hipkkt_cone_* / hipkkt_step_*)
 // hipkkt_parts.h holds the parts a handle is made of besides its cones (hipkkt_cones.h).
-// Host orchestration only; all numeric work is in kernels.hip / front_block.hip / assemble_dev.hip / scaling.hip / step.hip.
+// Host orchestration only; all numeric work is in the .hip files: values / kernels / front_block2 (front_block: testing build) /
+// solve_sweep / front_sweep / refine / assemble_dev / scaling / step, step_cone3, step_genpow, step_psd; kernels.h lists their launchers.
 #pragma once
 #include "../../include/hipkkt.h"
 
@@ -274,11 +275,10 @@ struct hipkkt_solver {
 namespace hipkkt_host {
 
 // The words a sweep time-out leaves in an undefined state, per solve context (recover_from_sweep_failure re-arms what
-// alloc_solve_scratch cleared).  seg_sync = [forward tickets | backward tickets] padded to whole 128-byte lines, then fdone
-// [kSegSub = 8 arrays of nsuper], then the error word (kernels.hip seg_sync())
+// alloc_solve_scratch cleared): the whole of seg_sync (device_plan.h seg_sync_layout) and of front_sync
 struct SyncWords { size_t seg, front; };
 inline SyncWords sync_words(const hipkkt_solver *S) {
-    return {(size_t)((2 * S->sched.nseg + 31) & ~31) + 8 * (size_t)S->plan.nsuper + 16, (size_t)std::max(S->plan.front_sync_ints, 16)};
+    return {(size_t)seg_sync_layout(S->sched.nseg, S->plan.nsuper).words, (size_t)std::max(S->plan.front_sync_ints, 16)};
 }
 
 // hipkkt_setup.cpp

@@ -456,7 +456,6 @@ static void upload_plan(hipkkt_solver *S) {
     D.sn_nitems = S->upload(H.sn_nitems);
     D.sn_bparent = S->upload(H.sn_bparent);
     D.nseg = H.nseg;
-    D.seg_ticket = 3;                                  // bit 0: forward sweep, bit 1: backward sweep take their items by atomic ticket
     D.spin_limit = debug_opts().spin_limit >= 0 ? (unsigned)debug_opts().spin_limit : (1u << 20);   // tests force a sweep time-out with a tiny bound
 #ifdef HIPKKT_TESTING
     D.dbg = debug_opts().debug_flags;                  // timing experiments only: results are WRONG when set (device_plan.h DevPlan::dbg)

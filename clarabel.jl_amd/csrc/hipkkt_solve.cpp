@@ -28,15 +28,13 @@ static void enqueue_ldl_solve(hipkkt_solver *S, SolveCtx &C, const double *in, d
     };
     if (S->persist.use) {
         // one persistent launch per segment of regular levels, front kernels in between
-        bool first = true;
         for (int g = 0; g < H.nseg; g++) {
             for (int l = H.seg_lo[g]; l < std::min(H.seg_lstar[g], H.seg_hi[g] + 1); l++) fwd_level(l);   // wide bottom levels
-            const int n = H.fseg_ptr[2 * g + 1] - H.fseg_ptr[2 * g];
-            if (n > 0) { launch_fwd_seg(st, D, g, H.fseg_ptr[2 * g], n, P.nsuper, first ? 1 : 0, C.d_y, C.d_z); first = false; }
+            launch_fwd_seg(st, D, g, H.fseg_ptr[2 * g], H.fseg_ptr[2 * g + 1] - H.fseg_ptr[2 * g], P.nsuper, C.d_y, C.d_z);
             for (const FrontDesc &F : P.fronts)
                 if (H.seg_of_level[F.level_last] == g) launch_front_fwd(st, D, F, C.d_y, C.d_z);
         }
-        first = true;
+        bool first = true;    // the first backward launch of a solve re-arms the forward sweeps' counters
         for (int g = H.nseg - 1; g >= 0; g--) {
             for (const FrontDesc &F : P.fronts)
                 if (H.seg_of_level[F.level_last] == g) launch_front_bwd(st, D, F, C.d_z, C.d_xp, out);
@@ -69,7 +67,7 @@ static void enqueue_refine_step(hipkkt_solver *S, SolveCtx &C, const RefineOpts 
     hipStream_t st = C.stream;
     enqueue_ldl_solve(S, C, C.d_e, C.d_corr, (int *)(C.dp.scal + SC_NORME), 2);   // (||e|| of the candidate starts from zero)
     launch_refine_add(st, C.d_rs, C.d_x0, C.d_x1, C.d_corr, S->N);
-    launch_spmv_residual_cand(st, C.dp, C.d_b, C.d_rs, C.d_x0, C.d_x1, C.d_e, S->N, (unsigned long long *)C.dp.scal + SC_NORME);
+    launch_spmv_residual(st, C.dp, C.d_b, C.d_rs, C.d_x0, C.d_x1, C.d_e, S->N, (unsigned long long *)C.dp.scal + SC_NORME);
     launch_refine_decide(st, C.d_rs, C.dp.scal, 1, ir.reltol, ir.abstol, (int)std::min<int64_t>(ir.max_iter, 1 << 30), ir.stop_ratio);
 }
 
@@ -154,7 +152,7 @@ static void solve_begin(hipkkt_solver *S, SolveCtx &C, const RefineOpts &ir) {
         run_graphed(S, st, C.g_first, same, [&] {
             enqueue_ldl_solve(S, C, C.d_b, C.d_x0, (int *)(C.dp.scal + SC_NORMB), 4);       // (||b||, ||e|| start from zero)
             launch_norm_inf(st, C.d_b, S->N, (unsigned long long *)C.dp.scal + SC_NORMB);
-            launch_spmv_residual(st, C.dp, C.d_b, C.d_x0, C.d_e, S->N, (unsigned long long *)C.dp.scal + SC_NORME);
+            launch_spmv_residual(st, C.dp, C.d_b, nullptr, C.d_x0, C.d_x0, C.d_e, S->N, (unsigned long long *)C.dp.scal + SC_NORME);
             launch_refine_decide(st, C.d_rs, C.dp.scal, 0, ir.reltol, ir.abstol, (int)std::min<int64_t>(ir.max_iter, 1 << 30), ir.stop_ratio);
             if (ir.max_iter > 0) enqueue_refine_step(S, C, ir);
         });

@@ -2,10 +2,15 @@
 // memory-bound ones do not -- the shader clock a single busy wavefront really gets, and the round trip of a flag between two
 // workgroups on the same XCD and on different XCDs (relaxed agent-scope atomics, what the hand-offs of front_block.hip /
 // front_sweep.hip are made of).  bench.py puts the result into its JSON line so that a slow line names its cause.
+// Also the self test's matrix-core probe (k_mfma_probe, at the end).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "kernels.h"
+
 namespace hipkkt {
+
+typedef double v4f64 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ int pb_ld(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void pb_st(int *p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -139,6 +144,19 @@ int box_probe(int device, double *out) {
     if (st) (void)hipStreamDestroy(st);
     if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
     return rc;
+}
+
+// probe used by hipkkt's self test: D = A(16x4) * B(4x16) through the same MFMA form and the
+// same lane maps as k_update_stage; out[i*16+j] receives D[i][j].
+__global__ void k_mfma_probe(const double *__restrict__ A, const double *__restrict__ B, double *__restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int l15 = lane & 15, lk = lane >> 4;
+    v4f64 acc = {0.0, 0.0, 0.0, 0.0};
+    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(A[l15 * 4 + lk], B[lk * 16 + l15], acc, 0, 0, 0);
+    for (int reg = 0; reg < 4; reg++) out[(lk + 4 * reg) * 16 + l15] = acc[reg];
+}
+void launch_mfma_probe(hipStream_t st, const double *A, const double *B, double *out) {
+    hipLaunchKernelGGL(k_mfma_probe, dim3(1), dim3(64), 0, st, A, B, out);
 }
 
 }  // namespace hipkkt

@@ -4,7 +4,7 @@
 //   Nonnegative   lambda = sqrt(s z), w = sqrt(s / z), Hs = w^2                (coneops_nncone.jl:77-101)          bit-exact
 //   SecondOrder   eta, w, lambda, sparse (d, u, v) or the dense <= 4 block     (coneops_socone.jl:75-192)          sums are tree sums
 //   PSDTriangle   W = R R^T from the caller's R (the Cholesky / SVD of :78-143 stay with the caller), then the skron block of
-//                 k_psd_hs (kernels.hip)                                       (coneops_psdtrianglecone.jl:145-161)
+//                 k_psd_hs (values.hip)                                        (coneops_psdtrianglecone.jl:145-161)
 // Expressions keep the reference's association; this file is compiled with -ffp-contract=off so that a*x + b*y is two rounded
 // products and a sum like Julia's, not an FMA.  Everything is HBM / latency bound: 2 m doubles in, (w, lambda) out, O(m) K entries.
 #include <hip/hip_runtime.h>

@@ -8,8 +8,8 @@ namespace hipkkt {
 namespace {
 inline int width_of(const HostPlan &P, int s) { return P.sn_first[s + 1] - P.sn_first[s]; }
 inline int64_t rows_of(const HostPlan &P, int s) { return P.sn_rowptr[s + 1] - P.sn_rowptr[s]; }
-// forward items of a supernode: 64-row blocks below its diagonal block
-inline int nitems_of(const HostPlan &P, int s) { return (int)std::max<int64_t>(1, (rows_of(P, s) - width_of(P, s) + 63) / 64); }
+// forward items of a supernode: blocks of kSlvRows rows below its diagonal block
+inline int nitems_of(const HostPlan &P, int s) { return (int)std::max<int64_t>(1, (rows_of(P, s) - width_of(P, s) + kSlvRows - 1) / kSlvRows); }
 
 // Segments of the persistent sweeps = level ranges between two front kernels; inside a segment the wide bottom levels (thousands of
 // leaf supernodes) are cheaper as one launch per level, the persistent kernels take over from the first level with fewer than
@@ -102,7 +102,7 @@ void build_segment_sweeps(const HostPlan &P, SolveSchedule &H) {
         if (!in_seg_kernel(s)) continue;
         for (int64_t slot = P.sn_rowptr[s]; slot < P.sn_rowptr[s + 1]; slot++) {
             const int a = col_sn[P.sn_rows[slot]];
-            if (a != s && a >= 0 && in_seg_kernel(a) && seg_of(a) == seg_of(s)) H.rows_seg[(size_t)slot] = P.sn_rows[slot] | kSegRowTagHost;
+            if (a != s && a >= 0 && in_seg_kernel(a) && seg_of(a) == seg_of(s)) H.rows_seg[(size_t)slot] = P.sn_rows[slot] | kSegRowTag;
         }
     }
     // forward segments: slv_items is level-ordered, a segment is a level range

@@ -1,6 +1,7 @@
 // The schedule of one LDL solve: which supernodes go to which launch, in which order.  Plain host arithmetic on a HostPlan (no HIP):
 // hipkkt_setup.cpp uploads it, hipkkt_solve.cpp walks it, tests/support/plan_check.cpp interprets it on the CPU.
 #pragma once
+#include "device_plan.h"   // kSlvRows, kSegRowTag: what the schedule shares with the solve kernels
 #include "symbolic.h"
 
 namespace hipkkt {
@@ -11,7 +12,7 @@ constexpr int kPersistMaxItems = 1024;     // a segment's persistent kernels tak
 // w x (r - w) panel entries one strided load after the other: at most kNarrowMaxPanel of them.
 constexpr unsigned kNarrowMinTiny = 256, kNarrowMinLeaves = 2048;
 constexpr int kNarrowMaxPanel = 128;
-constexpr int kSegRowTagHost = 0x40000000; // rows_seg: the row's x comes from an item of the same launch (= kSegRowTag, kernels.hip)
+constexpr int kSegRowTagHost = kSegRowTag;   // the name the plan interpreter of tests/support knows the tag by
 
 // Level lists of the per-level solve kernels: ranges into slv_items / bwd_items / lvl_sn.  The first nnarrow[l] supernodes of a
 // level's lvl_sn range are NARROW (one thread each, no items); wnarrow[l] is the widest of them.
@@ -20,7 +21,7 @@ struct LevelLists { std::vector<int> slv_ptr, bwd_ptr, reg_ptr, nnarrow, wnarrow
 struct SolveSchedule {
     LevelLists regular;   // without the panels of the fronts (the persistent front kernels solve those)
     LevelLists all;       // EVERY supernode: the path without any persistent kernel, taken after a sweep time-out
-    std::vector<FacItem> slv_items, bwd_items;   // 64-row blocks (kSlvRows in kernels.hip), both families appended
+    std::vector<FacItem> slv_items, bwd_items;   // blocks of kSlvRows rows (device_plan.h), both families appended
     std::vector<int> lvl_sn;
     std::vector<FacItem> pbwd_items;             // persistent backward sweep: blk == -1 is a supernode's finaliser
     std::vector<int64_t> p_off;                  // [nsuper + 1] partial sums of the backward blocks

@@ -1,5 +1,6 @@
-// Hand-off primitives of the persistent front sweeps, shared by kernels.hip (one hop per panel) and front_sweep.hip (super-block
-// sweeps).  See the comment block above k_front_fwd in kernels.hip for the protocol.
+// Hand-off primitives of the persistent sweeps, shared by front_sweep.hip (fronts: one hop per panel, and super-blocks) and
+// solve_sweep.hip (segment sweeps over the regular supernodes).  See the comment block above k_front_fwd in front_sweep.hip for
+// the protocol.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -41,20 +42,30 @@ __device__ __forceinline__ void front_slot_st(FrontSlot *p, double v) {
     // compiler's hazard recogniser does not look inside inline asm)
     asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 2" : : "v"(p), "v"(r) : "memory");
 }
+// The give-up rule of every bounded spin of the sweeps, called after a poll that was not satisfied; false = stop waiting.
+// n = unsatisfied polls of this wait, this one included: the rule is looked at on every 128th, on every one when the limit is
+// below 128 (a test's HIPKKT_SPIN_LIMIT).  `waited` past the limit: the sweep's error word and the handle's fail flag are set;
+// otherwise give up when another workgroup has set the error word.  Loops that count `for (spins = 0;; spins++)` pass
+// (spins + 1, spins); the poll loops of k_bwd_seg count the poll first and pass (spins, spins): one poll earlier when the limit
+// is below 128, at the first unsatisfied poll for a limit of 0.
+__device__ __forceinline__ bool spin_go_on(unsigned n, unsigned waited, int *err, int *failflag, unsigned lim) {
+    if ((n & 127u) == 0u || lim < 128u) {
+        if (waited > lim) {
+            __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            atomicOr(failflag, 1);
+            return false;
+        }
+        if (front_ld_flag(err) != 0) return false;
+    }
+    return true;
+}
 // whole-wave wait for the 64 slots of one panel (lane = slot); false = timed out / another workgroup failed
 __device__ __forceinline__ bool front_slot_wait(const FrontSlot *p, double &v, int *err, int *failflag, unsigned lim) {
     for (unsigned spins = 0;; spins++) {
         const FrontSlot s = front_slot_ld(p);
         const bool okl = ((unsigned long long)__double_as_longlong(s.v) ^ s.h) == kSlotKey;
         if (__ballot(okl) == ~0ull) { v = s.v; return true; }
-        if ((spins & 127u) == 127u || lim < 128u) {
-            if (spins > lim) {
-                __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                atomicOr(failflag, 1);
-                return false;
-            }
-            if (front_ld_flag(err) != 0) return false;
-        }
+        if (!spin_go_on(spins + 1u, spins, err, failflag, lim)) return false;
     }
 }
 __device__ __forceinline__ FrontSlot *front_slots(int *sync_block, int np) {

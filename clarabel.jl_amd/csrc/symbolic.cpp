@@ -790,7 +790,7 @@ std::string build_plan(int N, const int64_t *Ap, const int64_t *Ai, const int64_
             F.rows_off = P.sn_rowptr[s0];
             F.sync_off = sync_ints;
             // two blocks (forward sweep, backward sweep): {ticket, error, flags[np]} padded to 32 ints (128 B), then np x 64
-            // hand-off slots of 16 bytes (value, self-validating tag: kernels.hip front_slot_*)
+            // hand-off slots of 16 bytes (value, self-validating tag: sweep_common.h front_slot_*)
             // (super-block sweeps use a second set of np x 64 slots per block: the partial right-hand sides r / s)
             F.sync_blk = ((2 + np + 31) & ~31) + 2 * np * 64 * 4;   // multiple of 32 ints: the two blocks share no cache line
             sync_ints += 2 * F.sync_blk;

@@ -95,7 +95,7 @@ struct FrontDesc {
     int64_t rows_off;             // sn_rowptr[s0]: global (permuted) index of every front row
     int32_t sync_off, sync_blk;   // sync area of this front: two blocks of sync_blk ints {ticket, error, flags[np], slots},
                                   // one per sweep; each sweep's kernel re-zeroes the OTHER block for the next solve
-    // super-block sweeps (kernels.hip k_front_fwd_sb / k_front_bwd_sb): the np panels are grouped into nsb super-blocks of sb_g
+    // super-block sweeps (front_sweep.hip k_front_fwd_sb / k_front_bwd_sb): the np panels are grouped into nsb super-blocks of sb_g
     // consecutive panels; the off-diagonal 64 x 64 tiles of every super-block's INVERSE are formed after each factorisation
     // (k_invert_super) at sbinv_off: tile (B, bl > cl) at ((B * sb_g (sb_g - 1) / 2 + bl (bl - 1) / 2 + cl) * 8192: 4096 doubles
     // column-major (forward sweep), then 4096 row-major (backward sweep).  sb_g = 0: one hop per panel (k_front_fwd / _bwd).

@@ -173,7 +173,7 @@ struct SbEmu {
 extern "C" {
 
 // y = K x of the symmetric K the way the refinement's SpMV kernels take it: the symmetric view (without the dense triangles) row by row
-// plus, per dense triangle, the row part and the column part of k_spmv_dense_tri (kernels.hip) from the packed columns alone.
+// plus, per dense triangle, the row part and the column part of k_spmv_dense_tri (refine.hip) from the packed columns alone.
 // stats: [0] triangles found [1] entries left in the view [2] sum of the triangles' dimensions
 int plan_check_symmetric_product(int64_t N, const int64_t *Ap, const int64_t *Ai, const double *Ax, int first_col, int min_dim,
                                  const double *x, double *y, double *stats) {

@@ -1,4 +1,4 @@
-"""CPU-side evidence for the refined block solves of the HIP path (kernels.hip k_invert_diag_wide / polish_fwd / polish_bwd, round 5).
+"""CPU-side evidence for the refined block solves of the HIP path (kernels.hip k_invert_diag_wide, solve_sweep.hip polish_fwd / polish_bwd, round 5).
 
 Batch seed 324 was the one problem of cfg 4 whose HIP-vs-oracle difference exceeded 1e-10 (rounds 3 - 4: |dobj| 1.3e-5, iterations 24 vs
 23): at IPM iteration 19 the first, unrefined LDL solve of the HIP path left a residual 1.6x the oracle's and the stop-ratio branch of the

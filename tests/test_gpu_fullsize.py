@@ -487,7 +487,7 @@ def test_split_k_of_long_tiles_equals_unsplit_updates(monkeypatch):
 
 
 def test_dense_triangle_spmv_matches_host_product(monkeypatch):
-    """kernels.hip k_spmv_dense_tri (round 4): the packed upper triangles of PSD-cone Hs blocks leave the symmetric CSR view of the
+    """refine.hip k_spmv_dense_tri (round 4): the packed upper triangles of PSD-cone Hs blocks leave the symmetric CSR view of the
     refinement's SpMV and are multiplied from their values alone.  The residual e = b - K x the device computes (debug_dump 18, right
     after an unrefined solve: max_iter = 0) against the host product with the K the handle holds, entry by entry at the rounding level
     of the row's terms -- with the triangles in their own kernel and (HIPKKT_DENSE_TRI=0) inside the view; the refined solves of the

@@ -1,4 +1,4 @@
-"""CPU check of the index arithmetic of k_psd_hs (clarabel.jl_amd/csrc/kernels.hip): entry e of the packed upper
+"""CPU check of the index arithmetic of k_psd_hs (clarabel.jl_amd/csrc/values.hip): entry e of the packed upper
 triangle of W (x)_s W  <->  (a <= b)  <->  ((i <= j), (k <= l)), evaluated with the kernel's four cases and order of
 operations, must reproduce a literal restatement of the reference's skron! loop + pack_triu
 (coneops_psdtrianglecone.jl:153-161, 502-540) bit for bit, and so must the vectorised host stand-in.  The GPU side of the same statement is
