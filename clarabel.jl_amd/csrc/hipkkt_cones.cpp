@@ -36,6 +36,8 @@ static int32_t set_cone_types_impl(hipkkt_handle h, int64_t ncones, const int32_
     C.reg.nonsym = false;
     C.step.scaled = false;
     C.step.psd_fresh = false;
+    C.step.psd_scaling = false;
+    C.step.psd_resident = false;
     C.reg.cls = cone_class(ncones, kinds, ex);      // what the enables of hipkkt_step.cpp may switch on: per registration
     C.step.mode = C.reg.cls == ConeClass::Symmetric ? StepMode::Symmetric : StepMode::Off;
     // the non-symmetric cones: three-row cones in two lists (joined [Exponential | Power] below), GenPower descriptors (cone_layout.h)
@@ -187,7 +189,8 @@ int32_t hipkkt_get_nonsym_len(hipkkt_handle h, int64_t *len) {
     return HIPKKT_OK;
 }
 
-// s, z (length m), psd_R (concatenated n x n column-major R factors, NULL = leave the PSD blocks to hipkkt_set_hs_psd) and the three
+// s, z (length m), psd_R (concatenated n x n column-major R factors, NULL = leave the PSD blocks to hipkkt_set_hs_psd or, after
+// hipkkt_psd_scaling_enable, compute the factors on the device: scaling_psd.hip) and the three
 // outputs (w and lambda of length m, eta per second-order cone; any may be NULL) are host pointers, or device pointers when `dev`
 // ex: hipkkt_update_scaling_ex[_dev] -- the same launches in the same order, then the non-symmetric cones of the registration with
 // (mu, strategy); nonsym_out (may be NULL) receives their output vector.  One host synchronisation per call, whatever the cone count.
@@ -202,8 +205,11 @@ static int32_t update_scaling_impl(hipkkt_handle h, const double *s, const doubl
     if (ex && strategy != 0 && strategy != 1) { S->err = "update_scaling_ex: strategy is 0 (PrimalDual) or 1 (Dual)"; return HIPKKT_ERR_ARGUMENT; }
     const int64_t m = S->img.m;
     if (m && (!s || !z)) { S->err = "update_scaling: null s / z"; return HIPKKT_ERR_ARGUMENT; }
-    if (psd_step && (!psd_R || !C.step.psd_fresh)) {
+    // hipkkt_psd_scaling_enable: without psd_R and without staged factors the PSD cones' (R, Rinv, lambda) come from scaling_psd.hip
+    const bool psd_nt = psd_step && C.step.psd_scaling && !psd_R && !C.step.psd_fresh;
+    if (psd_step && !psd_nt && (!psd_R || !C.step.psd_fresh)) {
         C.step.scaled = false;
+        C.step.psd_resident = false;
         S->err = "update_scaling: after hipkkt_step_enable_psd the call needs psd_R and the factors of a hipkkt_psd_set_factors[_dev] since the last scaling";
         return HIPKKT_ERR_ARGUMENT;
     }
@@ -222,7 +228,7 @@ static int32_t update_scaling_impl(hipkkt_handle h, const double *s, const doubl
         HK_CHECK(hipMemcpyAsync(C.tab.sz, s, m * sizeof(double), hipMemcpyDeviceToDevice, S->stream));
         HK_CHECK(hipMemcpyAsync(C.tab.sz + m, z, m * sizeof(double), hipMemcpyDeviceToDevice, S->stream));
     }
-    if (psd_step) {      // the PSD step reads the resident (R, Rinv, lambda): R next to the staged pair
+    if (psd_step && !psd_nt) {      // the PSD step reads the resident (R, Rinv, lambda): R next to the staged pair
         if (dev) {
             HK_CHECK(hipMemcpyAsync(C.tab.R, psd_R, (size_t)C.reg.psd_total * sizeof(double), hipMemcpyDeviceToDevice, S->stream));
             dR = C.tab.R;
@@ -234,6 +240,11 @@ static int32_t update_scaling_impl(hipkkt_handle h, const double *s, const doubl
     }
     double *dw = C.tab.wl, *dl = C.tab.wl + m;
     launch_zero_words(S->stream, C.tab.fail, 1);
+    if (psd_nt) {
+        launch_psd_nt_scaling(S->stream, (int)C.reg.psd_n.size(), C.tab.psdtab, ds, dz, C.tab.R, C.tab.psd_rinv, C.tab.psd_lam,
+                              C.tab.psd_bad, C.tab.fail);
+        dR = C.tab.R;
+    }
     if (psd_step) launch_psd_step_check(S->stream, C.tab.psd_lam, C.reg.psd_lam_total, C.tab.fail);
     launch_scaling_diag(S->stream, C.tab.kind, C.tab.rowhs, S->d_mapHs, ds, dz, dw, dl, S->dp.kval, m);
     launch_scaling_soc(S->stream, C.reg.nsoc, C.tab.socdesc, S->d_mapHs, ds, dz, dw, dl, C.tab.eta, S->soc.d_u, S->soc.d_v,
@@ -246,7 +257,7 @@ static int32_t update_scaling_impl(hipkkt_handle h, const double *s, const doubl
         for (size_t c = 0; c < C.reg.psd_n.size(); c++) {
             const int n = (int)C.reg.psd_n[c];
             launch_psd_rrt(S->stream, dR + off, C.tab.W + off, n);
-            launch_psd_hs(S->stream, S->dp.kval, S->d_mapHs, C.reg.psd_hs[c], C.tab.W + off, n);
+            launch_psd_hs(S->stream, S->dp.kval, S->d_mapHs, C.reg.psd_hs[c], C.tab.W + off, n, psd_nt ? C.tab.psd_bad + c : nullptr);
             off += (int64_t)n * n;
         }
     }
@@ -267,6 +278,7 @@ static int32_t update_scaling_impl(hipkkt_handle h, const double *s, const doubl
     copy_sync(S->stream, &fail, C.tab.fail, sizeof(int), hipMemcpyDeviceToHost);
     if (scaling_ok) *scaling_ok = fail ? 0 : 1;
     C.step.scaled = fail == 0;
+    C.step.psd_resident = psd_step;
     return HIPKKT_OK;
     HK_LEAVE
 }

@@ -49,6 +49,7 @@ struct ConeState {
         int64_t cap_psd_cones = 0, cap_psd_mat = 0, cap_psd_lam = 0;
         int64_t *psdtab = nullptr;
         double *psd_rinv = nullptr, *psd_lam = nullptr, *psd_stage = nullptr;
+        int *psd_bad = nullptr;                            // per PSD cone: its device-side scaling failed (scaling_psd.hip)
     } tab;
     // what the step entry points work on between the calls
     struct Step {
@@ -56,6 +57,8 @@ struct ConeState {
         bool scaled = false;                               // the last hipkkt_update_scaling[_dev] since the registration / enable succeeded
         bool have_step = false;                            // [dx | dz | ds] of a fused step call is resident
         bool psd_fresh = false;                            // factors staged since the last scaling
+        bool psd_scaling = false;                          // hipkkt_psd_scaling_enable: a scaling without psd_R computes the factors
+        bool psd_resident = false;                         // a scaling since the enable left (R, Rinv, lambda) resident (hipkkt_psd_get_factors)
         double ls_step = 0.0, ls_amin = 0.0;               // linesearch_backtrack_step, min_terminate_step_length (Cone3 / GenPow)
         int ls_trips = 0;                                  // bound of the backtracking loop: ceil(log amin / log step) + 2
         double mu = 0.0;                                   // mu of the last hipkkt_update_scaling_ex[_dev] (mul_Hs of the GenPower cones)

@@ -315,7 +315,10 @@ int32_t hipkkt_step_enable_genpow(hipkkt_handle h, int32_t enable, double linese
 int32_t hipkkt_step_enable_psd(hipkkt_handle h, int32_t enable) {
     HK_ENTER(h)
     ConeState &C = S->cones;
-    if (!enable) { if (C.step.mode == StepMode::Psd) C.step.mode = StepMode::Off; return HIPKKT_OK; }
+    if (!enable) {
+        if (C.step.mode == StepMode::Psd) { C.step.mode = StepMode::Off; C.step.psd_scaling = C.step.psd_resident = false; }
+        return HIPKKT_OK;
+    }
     bool ok = S->l1 && C.reg.ready && C.reg.cls == ConeClass::Psd;
     for (size_t c = 0; ok && c < C.reg.psd_n.size(); c++) ok = C.reg.psd_n[c] <= HIPKKT_PSD_STEP_MAX_DIM;
     if (!ok) {
@@ -333,7 +336,9 @@ int32_t hipkkt_step_enable_psd(hipkkt_handle h, int32_t enable) {
         t[kPsdRow0] = C.reg.psd_row[c]; t[kPsdN] = n; t[kPsdFactor0] = foff; t[kPsdLambda0] = loff;
         foff += n * n; loff += n;
     }
-    if (npsd > C.tab.cap_psd_cones) { C.tab.psdtab = S->dalloc<int64_t>(kPsdTab * npsd); C.tab.cap_psd_cones = npsd; }
+    if (npsd > C.tab.cap_psd_cones) {
+        C.tab.psdtab = S->dalloc<int64_t>(kPsdTab * npsd); C.tab.psd_bad = S->dalloc<int>(npsd); C.tab.cap_psd_cones = npsd;
+    }
     if (foff > C.tab.cap_psd_mat || loff > C.tab.cap_psd_lam) {
         C.tab.psd_rinv = S->dalloc<double>(foff); C.tab.psd_lam = S->dalloc<double>(loff); C.tab.psd_stage = S->dalloc<double>(foff + loff);
         C.tab.cap_psd_mat = foff; C.tab.cap_psd_lam = loff;
@@ -341,6 +346,7 @@ int32_t hipkkt_step_enable_psd(hipkkt_handle h, int32_t enable) {
     copy_sync(S->stream, C.tab.psdtab, tab.data(), tab.size() * sizeof(int64_t), hipMemcpyHostToDevice);
     C.step.mode = StepMode::Psd;
     C.step.psd_fresh = false;
+    C.step.psd_scaling = C.step.psd_resident = false;
     C.step.scaled = false;      // the step reads the factors of a scaling that ran with the enable in place
     C.step.have_step = false;
     return HIPKKT_OK;
@@ -367,6 +373,38 @@ int32_t hipkkt_psd_set_factors(hipkkt_handle h, const double *Rinv_all, const do
 }
 int32_t hipkkt_psd_set_factors_dev(hipkkt_handle h, const double *Rinv_all, const double *lambda_all) {
     return psd_set_factors_impl(h, Rinv_all, lambda_all, true);
+}
+
+// the Cholesky / SVD of the PSD cones' scaling on the device (scaling_psd.hip): hipkkt_update_scaling[_ex][_dev] without psd_R
+int32_t hipkkt_psd_scaling_enable(hipkkt_handle h, int32_t enable) {
+    HK_ENTER(h)
+    ConeState &C = S->cones;
+    if (C.step.mode != StepMode::Psd) {
+        S->err = "psd_scaling_enable: needs hipkkt_step_enable_psd first";
+        return HIPKKT_ERR_ARGUMENT;
+    }
+    C.step.psd_scaling = enable != 0;
+    C.step.scaled = false;      // as the other enables: the step reads the factors of a scaling that ran with this setting in place
+    C.step.have_step = false;
+    C.step.psd_resident = false;
+    return HIPKKT_OK;
+    HK_LEAVE
+}
+
+int32_t hipkkt_psd_get_factors(hipkkt_handle h, double *R_out, double *Rinv_out, double *lambda_out) {
+    HK_ENTER(h)
+    ConeState &C = S->cones;
+    if (C.step.mode != StepMode::Psd || !C.step.psd_resident) {
+        S->err = "psd_get_factors: no PSD scaling is resident (hipkkt_step_enable_psd, then a hipkkt_update_scaling[_ex][_dev])";
+        return HIPKKT_ERR_ARGUMENT;
+    }
+    const size_t nr = (size_t)C.reg.psd_total * sizeof(double), nl = (size_t)C.reg.psd_lam_total * sizeof(double);
+    if (R_out) HK_CHECK(hipMemcpyAsync(R_out, C.tab.R, nr, hipMemcpyDeviceToHost, S->stream));
+    if (Rinv_out) HK_CHECK(hipMemcpyAsync(Rinv_out, C.tab.psd_rinv, nr, hipMemcpyDeviceToHost, S->stream));
+    if (lambda_out) HK_CHECK(hipMemcpyAsync(lambda_out, C.tab.psd_lam, nl, hipMemcpyDeviceToHost, S->stream));
+    HK_CHECK(hipStreamSynchronize(S->stream));
+    return HIPKKT_OK;
+    HK_LEAVE
 }
 
 int32_t hipkkt_cone_barrier(hipkkt_handle h, const double *dz, const double *ds, const double *alphas, int64_t nalpha, double *out) {

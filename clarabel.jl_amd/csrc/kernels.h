@@ -10,7 +10,8 @@ void launch_scatter_values(hipStream_t st, double *kval, const int64_t *idx, con
 void launch_scale_values(hipStream_t st, double *kval, const int64_t *idx, int64_t n, double scale);
 void launch_soc_batch(hipStream_t st, double *kval, const int64_t *uidx, const int64_t *vidx, const int *cone_of,
                       const double *u, const double *v, const double *eta2, int64_t n, const int64_t *didx, int nsoc);
-void launch_psd_hs(hipStream_t st, double *kval, const int64_t *map_hs, int64_t hs_off, const double *W, int n);
+// skip != NULL: the launch writes nothing when *skip != 0 (the word of a cone whose device-side scaling failed, scaling_psd.hip)
+void launch_psd_hs(hipStream_t st, double *kval, const int64_t *map_hs, int64_t hs_off, const double *W, int n, const int *skip = nullptr);
 void launch_zero_words(hipStream_t st, void *p, int nwords);
 // kernels.hip: the numeric factorisation
 void launch_maxabs_gather(hipStream_t st, const double *v, const int64_t *idx, int64_t n, unsigned long long *slot);
@@ -161,4 +162,9 @@ void launch_psd_step_offset(hipStream_t st, int npsd, const int64_t *tab, const 
 void launch_psd_step_length(hipStream_t st, int npsd, const int64_t *tab, const double *R, const double *Rinv, const double *lam,
                             const double *dz, const double *ds, double alpha_max, const double *sym2, double *part, double *out2);
 void launch_psd_step_check(hipStream_t st, const double *lam, int64_t len, int *fail);
+// scaling_psd.hip: update_scaling!(::PSDTriangleCone) for the cones of the same table, one workgroup per cone: Cholesky factors of
+// svec_to_mat of the cone's rows of (s, z), the SVD of L2' L1 by one-sided Jacobi sweeps, (R, Rinv, lam) in the layout above.  A cone
+// that fails sets *fail and bad[cone] (0 otherwise) and gets NaN factors.
+void launch_psd_nt_scaling(hipStream_t st, int npsd, const int64_t *tab, const double *s, const double *z, double *R, double *Rinv,
+                           double *lam, int *bad, int *fail);
 }  // namespace hipkkt

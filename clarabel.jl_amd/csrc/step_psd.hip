@@ -22,45 +22,23 @@
 #include "cone_layout.h"
 #include "cone_reduce.h"
 #include "kernels.h"
+#include "psd_cone.h"
 
 namespace hipkkt {
 
 namespace {
 
-constexpr int kMaxN = 64;                          // HIPKKT_PSD_STEP_MAX_DIM
-constexpr int kMatDoubles = kMaxN * (kMaxN + 1);   // one n x n matrix with its padded leading dimension
+// the matrix layout, the cone record (Cone, cone_of) and load_svec: psd_cone.h, shared with scaling_psd.hip
+constexpr int kMaxN = kPsdMaxN;
+constexpr int kMatDoubles = kPsdMatDoubles;
 constexpr int kMaxSweeps = 30;
 constexpr double kEps = 2.220446049250313e-16;
-constexpr double kIsqrt2 = 0.7071067811865475;     // 1 / sqrt(2) as the caller rounds it
-
-struct Cone { int64_t row0; int n, ld; int64_t foff, loff; bool ok; };
-
-__device__ __forceinline__ Cone cone_of(const int64_t *__restrict__ tab, int c) {
-    Cone K;
-    K.row0 = tab[kPsdTab * c + kPsdRow0];
-    const int64_t n = tab[kPsdTab * c + kPsdN];
-    K.foff = tab[kPsdTab * c + kPsdFactor0];
-    K.loff = tab[kPsdTab * c + kPsdLambda0];
-    K.ok = n >= 1 && n <= kMaxN;
-    K.n = K.ok ? (int)n : 0;
-    K.ld = (K.n % 32 == 0) ? K.n + 1 : K.n;
-    return K;
-}
+constexpr double kIsqrt2 = kPsdIsqrt2;
 
 // F = the cone's n x n column-major factor
 __device__ __forceinline__ void load_factor(double *F, const double *__restrict__ src, const Cone &K) {
     const int n = K.n;
     for (int e = threadIdx.x; e < n * n; e += 256) { const int i = e % n, j = e / n; F[i + j * K.ld] = src[e]; }
-}
-// X = svec_to_mat(x)
-__device__ __forceinline__ void load_svec(double *X, const double *__restrict__ x, const Cone &K) {
-    const int n = K.n;
-    for (int e = threadIdx.x; e < n * n; e += 256) {
-        const int i = e % n, j = e / n;
-        const int r = i < j ? i : j, c = i < j ? j : i;
-        const double v = x[c * (c + 1) / 2 + r];
-        X[i + j * K.ld] = i == j ? v : v * kIsqrt2;
-    }
 }
 // out = mat_to_svec(Y); diag_add goes to the diagonal positions; addc != NULL: out = -(out + addc)
 __device__ __forceinline__ void store_svec(double *__restrict__ out, const double *Y, const Cone &K, double diag_add,

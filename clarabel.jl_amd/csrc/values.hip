@@ -75,9 +75,9 @@ __device__ __forceinline__ long long tri_root(long long e) {   // largest t with
 }
 __global__ void __launch_bounds__(256)
 k_psd_hs(double *__restrict__ kval, const int64_t *__restrict__ map_hs, int64_t hs_off, const double *__restrict__ W, int n,
-         int64_t nent) {
+         int64_t nent, const int *__restrict__ skip) {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= nent) return;
+    if (e >= nent || (skip && *skip != 0)) return;
     const long long b = tri_root(e), a = e - b * (b + 1) / 2;
     const long long j = tri_root(a), i = a - j * (j + 1) / 2;
     const long long l = tri_root(b), k = b - l * (l + 1) / 2;
@@ -99,9 +99,9 @@ k_psd_hs(double *__restrict__ kval, const int64_t *__restrict__ map_hs, int64_t 
     }
     kval[map_hs[hs_off + e]] = -v;
 }
-void launch_psd_hs(hipStream_t st, double *kval, const int64_t *map_hs, int64_t hs_off, const double *W, int n) {
+void launch_psd_hs(hipStream_t st, double *kval, const int64_t *map_hs, int64_t hs_off, const double *W, int n, const int *skip) {
     const int64_t numel = (int64_t)n * (n + 1) / 2, nent = numel * (numel + 1) / 2;
-    if (nent > 0) hipLaunchKernelGGL(k_psd_hs, dim3(nblk(nent)), dim3(256), 0, st, kval, map_hs, hs_off, W, n, nent);
+    if (nent > 0) hipLaunchKernelGGL(k_psd_hs, dim3(nblk(nent)), dim3(256), 0, st, kval, map_hs, hs_off, W, n, nent, skip);
 }
 void launch_zero_words(hipStream_t st, void *p, int nwords) {
     if (nwords > 0) hipLaunchKernelGGL(k_zero_words, dim3(nblk(nwords, 64)), dim3(64), 0, st, (int *)p, nwords);

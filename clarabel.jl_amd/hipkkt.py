@@ -46,6 +46,8 @@ SYMBOLS = [
     "hipkkt_step_enable_cone3", "hipkkt_cone_barrier", "hipkkt_step_barrier_dev", "hipkkt_step_enable_genpow",
     # ... and for the PSD triangle cones from the caller's factors (opt-in, added within ABI version 5)
     "hipkkt_step_enable_psd", "hipkkt_psd_set_factors", "hipkkt_psd_set_factors_dev",
+    # ... whose Cholesky / SVD the device does too (opt-in, added within ABI version 5)
+    "hipkkt_psd_scaling_enable", "hipkkt_psd_get_factors",
 ]
 
 PSD_STEP_MAX_DIM = 64      # include/hipkkt.h HIPKKT_PSD_STEP_MAX_DIM
@@ -160,6 +162,8 @@ def lib():
     L.hipkkt_step_enable_psd.argtypes = [vp, i32]
     L.hipkkt_psd_set_factors.argtypes = [vp, _f64p, _f64p]
     L.hipkkt_psd_set_factors_dev.argtypes = [vp, vp, vp]
+    L.hipkkt_psd_scaling_enable.argtypes = [vp, i32]
+    L.hipkkt_psd_get_factors.argtypes = [vp, vp, vp, vp]
     L.hipkkt_cone_barrier.argtypes = [vp, _f64p, _f64p, _f64p, i64, _f64p]
     L.hipkkt_step_barrier_dev.argtypes = [vp, vp, _f64p, i64, _f64p]
     L.hipkkt_debug_dump.argtypes = [vp, i32, vp, i64, C.POINTER(i64)]
@@ -715,6 +719,19 @@ class Handle:
             raise ValueError(f"psd_set_factors: Rinv holds {self._psd_r_len} doubles and lambda {nel}, got {rinv.size} and {lam.size}")
         self._chk_step(self.L.hipkkt_psd_set_factors(self.h, rinv, lam), "psd_set_factors")
         _count(rinv.size + lam.size, 0)
+
+    def psd_scaling_enable(self, enable):
+        """on a handle after step_enable_psd(True) (ValueError otherwise): update_scaling[_ex][_dev] without psd_R and without staged
+        factors computes the PSD cones' (R, Rinv, lambda) on the device from the (s, z) of the call"""
+        self._chk_step(self.L.hipkkt_psd_scaling_enable(self.h, int(bool(enable))), "psd_scaling_enable")
+
+    def psd_get_factors(self):
+        """-> (R, Rinv, lambda) resident since the last scaling: R, Rinv n x n column-major per PSD cone, concatenated like psd_R, lambda
+        n per cone; ValueError when no scaling has completed since the enable.  The entries of a cone whose scaling failed are NaN."""
+        R, rinv, lam = np.zeros(max(self._psd_r_len, 1)), np.zeros(max(self._psd_r_len, 1)), np.zeros(max(self._psd_lam_len, 1))
+        self._chk_step(self.L.hipkkt_psd_get_factors(self.h, R.ctypes.data, rinv.ctypes.data, lam.ctypes.data), "psd_get_factors")
+        _count(0, 2 * self._psd_r_len + self._psd_lam_len)
+        return R[: self._psd_r_len], rinv[: self._psd_r_len], lam[: self._psd_lam_len]
 
     @staticmethod
     def _alphas(alphas):

@@ -109,6 +109,12 @@ class HipKKTSolver:
             self._psd_span = (rows[0].start, rows[-1].stop)
             self._psd_nr = int(np.sum(self._psd_dim * self._psd_dim))
             self._psd_dev = None      # [R | Rinv | lambda] in device memory (kktsolver_update_scaling_dev)
+        # ... whose Cholesky / SVD the device does as well when Settings.device_scaling_psd is set (hipkkt_psd_scaling_enable): the
+        # scaling call then takes nothing but the resident (s, z)
+        self.scales_psd = False
+        if self.steps_psd and getattr(settings, "device_scaling_psd", False):
+            self.h.psd_scaling_enable(True)
+            self.scales_psd = True
         self.scaling_nonsym = None
         self.scaling_w = self.scaling_lambda = self.scaling_soc_eta = None
         self.diagonal_regularizer = 0.0
@@ -303,8 +309,9 @@ class HipKKTSolver:
 
     def kktsolver_update_scaling_dev(self, xzs) -> bool:
         """update_scaling! + get_Hs! from the resident (s, z); False = a cone's s or z is not interior.
-        steps_psd: the PSD cones' (R, Rinv, lambda) of the caller's update_scaling! go along in one upload"""
-        if self.steps_psd:
+        steps_psd: the PSD cones' (R, Rinv, lambda) of the caller's update_scaling! go along in one upload -- unless scales_psd, where
+        the device computes them from the resident (s, z) and nothing is uploaded"""
+        if self.steps_psd and not self.scales_psd:
             if self._psd_dev is None:
                 self._psd_dev = hipkkt.DeviceBuffer(2 * self._psd_nr + int(np.sum(self._psd_dim)))
             rinv, lam = self._psd_factors()

@@ -72,4 +72,8 @@ class Settings:
     # on the host: every iteration downloads the PSD rows of (s, z) and uploads (R, Rinv, lambda).  Needs device_step: the caller
     # raises ValueError otherwise.
     device_step_psd: bool = False
+    # device_step_psd with the Cholesky / SVD of the PSD cones' scaling on the device as well (hipkkt_psd_scaling_enable: one workgroup
+    # per cone, one-sided Jacobi sweeps in LDS): no download of (s, z) rows and no upload of factors, an iteration moves scalars only.
+    # Needs device_step_psd: the caller raises ValueError otherwise.
+    device_scaling_psd: bool = False
     extra: dict = field(default_factory=dict)

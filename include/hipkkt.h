@@ -74,7 +74,8 @@ int32_t hipkkt_is_available(void);
  * 5: hipkkt_set_cone_types_ex / hipkkt_get_nonsym_len / hipkkt_update_scaling_ex[_dev] (the bindings bind them when they load).
  *    Added within 5, no signature changed: the step entry points hipkkt_cone_* / hipkkt_set_equilibration / hipkkt_step_*;
  *    hipkkt_step_enable_cone3 / hipkkt_cone_barrier / hipkkt_step_barrier_dev; hipkkt_step_enable_genpow;
- *    HIPKKT_PSD_STEP_MAX_DIM / hipkkt_step_enable_psd / hipkkt_psd_set_factors / hipkkt_psd_set_factors_dev. */
+ *    HIPKKT_PSD_STEP_MAX_DIM / hipkkt_step_enable_psd / hipkkt_psd_set_factors / hipkkt_psd_set_factors_dev;
+ *    hipkkt_psd_scaling_enable / hipkkt_psd_get_factors. */
 #define HIPKKT_ABI_VERSION 5
 int32_t hipkkt_abi_version(void);
 /* releases the process-wide cache of device memory blocks the library keeps between handles (not in the reference: an embedding
@@ -412,6 +413,31 @@ int32_t hipkkt_step_enable_psd(hipkkt_handle h, int32_t enable);
  * next synchronising call on this handle has returned (the rule of hipkkt_set_hs_dev). */
 int32_t hipkkt_psd_set_factors(hipkkt_handle h, const double *Rinv_all, const double *lambda_all);
 int32_t hipkkt_psd_set_factors_dev(hipkkt_handle h, const double *Rinv_all, const double *lambda_all);
+/* Opt-in on top of hipkkt_step_enable_psd (HIPKKT_ERR_ARGUMENT before it): the Cholesky / SVD of update_scaling!(::PSDTriangleCone),
+ * coneops_psdtrianglecone.jl:78-143, on the device.  On an enabled handle a hipkkt_update_scaling[_ex][_dev] with psd_R == NULL and no
+ * factors staged computes, from the (s, z) of that call and per PSD cone (one workgroup each, everything in LDS, same stream, the call
+ * keeps its single host synchronisation):
+ *   S = L1 L1', Z = L2 L2' (:93-98, lower Cholesky, k-sums in ascending order; a pivot that is not > 0 or not finite fails the cone as
+ *     LAPACK's potrf does);
+ *   the singular values and vectors of L2' L1 (:107-110) by a one-sided Jacobi iteration on its columns: round-robin sets of disjoint
+ *     pairs, a pair rotates when |g_p . g_q| > eps |g_p| |g_q|, at most 40 sweeps, stop after a sweep without a rotation, then one
+ *     polishing sweep that rotates every pair;
+ *   lambda = the singular values in descending order (:112-113), R = L1 V Sigma^-1/2 (:115-123), Rinv = Sigma^-1/2 U' L2' (:125-131);
+ *   one refinement on the (s, z) of the call: lambda_j^2 = (r_j' Z r_j)(q_j' S q_j) / (q_j' r_j)^2 (q_j = row j of Rinv), the three
+ *     sums in twice the precision, and r_j, q_j rescaled to r_j' Z r_j = q_j' S q_j = lambda_j, q_j' r_j = 1: lambda is then the
+ *     singular value of the exact factors of the float64 (S, Z) to about one eps, whatever cond(S), cond(Z) at an early iterate;
+ * and then forms W = R R' and the Hs block as with a caller's psd_R.  R is unique up to column signs (and rotations among equal
+ * singular values): R R', lambda and every step operation are what the caller's factors give, to rounding.  The result is the same
+ * bits on every run.  A cone that fails (Cholesky, a non-finite entry of s / z, the sweep bound) sets *scaling_ok = 0 with
+ * HIPKKT_OK, gets NaN factors and none of its entries of K is written; the other cones are served.  With a non-NULL psd_R and staged
+ * factors the call does what it does without this enable.  Enabling or disabling invalidates the resident scaling; enable == 0
+ * switches it off, and so do hipkkt_step_enable_psd and every hipkkt_set_cone_types[_ex]. */
+int32_t hipkkt_psd_scaling_enable(hipkkt_handle h, int32_t enable);
+/* The resident factors of the last scaling of a handle in PSD step mode, whoever computed them (K.data.R, .Rinv, .lambda of
+ * coneops_psdtrianglecone.jl:112-131): R and Rinv n x n column-major per cone, concatenated like psd_R, lambda n per cone.  Host
+ * pointers, any may be NULL.  HIPKKT_ERR_ARGUMENT when no scaling call has completed since the enable; after a call that reported
+ * *scaling_ok = 0 the failed cones' entries are NaN. */
+int32_t hipkkt_psd_get_factors(hipkkt_handle h, double *R_out, double *Rinv_out, double *lambda_out);
 /* compute_barrier of the cone set (Zero 0, Nonnegative -sum log((s + a ds)(z + a dz)), coneops_socone.jl:288-305,
  * coneops_expcone.jl:189-248, coneops_powcone.jl:228-251) and dot_shifted (mathutils.jl:23-43) at nalpha <= 8 candidate step lengths:
  * out[2 j] = the barrier, out[2 j + 1] = <z + a_j dz, s + a_j ds>, both summed over fixed slices in a fixed order.  A point outside a

@@ -147,6 +147,18 @@ function hip_psd_set_factors_dev!(handle::Ptr{Cvoid}, Rinv_dev::Ptr{Float64}, λ
     rc = ccall((:hipkkt_psd_set_factors_dev, libhipkkt), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), handle, Rinv_dev, λ_dev)
     return hip_step_check(handle, rc, "hipkkt_psd_set_factors_dev")
 end
+# after hip_step_enable_psd!: a hip update_scaling without psd_R computes the PSD cones' (R, R⁻¹, λ) on the device
+# (update_scaling!(::PSDTriangleCone), coneops_psdtrianglecone.jl:78-143)
+function hip_psd_scaling_enable!(handle::Ptr{Cvoid}, enable::Bool)
+    rc = ccall((:hipkkt_psd_scaling_enable, libhipkkt), Int32, (Ptr{Cvoid}, Int32), handle, enable ? 1 : 0)
+    return hip_step_check(handle, rc, "hipkkt_psd_scaling_enable")
+end
+# the resident factors of the last scaling (K.data.R, .Rinv, .λ): n x n column-major per cone, concatenated like psd_R; λ n per cone
+function hip_psd_get_factors!(handle::Ptr{Cvoid}, R_all::Vector{Float64}, Rinv_all::Vector{Float64}, λ_all::Vector{Float64})
+    rc = ccall((:hipkkt_psd_get_factors, libhipkkt), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), handle, R_all,
+               Rinv_all, λ_all)
+    return hip_step_check(handle, rc, "hipkkt_psd_get_factors")
+end
 # -> out[2j-1] = the cones' barrier, out[2j] = <z + αⱼΔz, s + αⱼΔs> for at most 8 candidates αⱼ
 function hip_cone_barrier(handle::Ptr{Cvoid}, Δz::Vector{Float64}, Δs::Vector{Float64}, αs::Vector{Float64})
     out = zeros(Float64, 2 * length(αs))

@@ -400,6 +400,8 @@ class Solver:
             raise ValueError("Settings.device_step_genpower needs device_step_nonsymmetric")
         if getattr(st, "device_step_psd", False) and not getattr(st, "device_step", False):
             raise ValueError("Settings.device_step_psd needs device_step")
+        if getattr(st, "device_scaling_psd", False) and not getattr(st, "device_step_psd", False):
+            raise ValueError("Settings.device_scaling_psd needs device_step_psd")
         self._device_step = bool(getattr(st, "device_step", False)) and hasattr(ks, "kktsolver_step_affine") and \
             bool(getattr(ks, "steps_on_device", False))
         if self._device_step and not self.cones.is_symmetric():
@@ -412,6 +414,10 @@ class Solver:
         # a symmetric set with PSD members (Settings.device_step_psd, a plugin with steps_psd): the loop of _solve_device_step, with the
         # Cholesky / SVD of the PSD cones' scaling done here before every scaling call
         self._device_step_psd = self._device_step and bool(getattr(ks, "steps_psd", False))
+        # ... or done by the plugin from the resident (s, z) (Settings.device_scaling_psd, a plugin with scales_psd).  The host cones'
+        # R / Rinv / lam / _hs_valid then keep what set_identity_scaling left for the default start: nothing in _solve_device_step reads
+        # them after a scaling (hipkkt_psd_get_factors serves a caller who wants them)
+        self._device_scaling_psd = self._device_step_psd and bool(getattr(ks, "scales_psd", False))
         self.barrier_searches = self.barrier_backtracks = 0      # _backtrack_step_to_barrier calls / candidates it rejected (last solve)
         self._needs_qb = self._needs_qb or (self._device_step and hasattr(ks, "set_problem_vectors"))
         if self._needs_qb:               # q, b resident in the plugin (N4 residuals, N2 reduced-system algebra)
@@ -719,7 +725,7 @@ class Solver:
                 break
             t0 = time.perf_counter()
             ok_scaling = True
-            if self._device_step_psd:
+            if self._device_step_psd and not self._device_scaling_psd:
                 # the PSD rows of the resident (s, z) come to the host, the cones' own update_scaling! gives R, Rinv, lambda (skron!
                 # stays deferred: the plugin forms the Hs block), and the plugin takes the factors along with its scaling call
                 s_h, z_h = ks.psd_rows_download(xzs)

@@ -4,7 +4,7 @@ algebra between the device calls runs on the host, the iterate crosses PCIe seve
 added (the iterate stays in device memory, scalars cross).  Per path: one warm-up solve, then `--repeats` timed solves; the medians of
 wall time per iteration and of the stand-in's timers, the bytes the Python binding moved per iteration in each direction
 (clarabel.jl_amd/hipkkt.py TRAFFIC) and hipkkt_box_probe go into ONE JSON line on stdout.
-usage: step_path_compare.py [--cfgs 3,2a,exp_pow,genpow,psd] [--repeats 5] [--one-solve CFG]   (--one-solve: a single device_step solve, for a kernel trace)"""
+usage: step_path_compare.py [--cfgs 3,2a,exp_pow,genpow,psd] [--repeats 5] [--one-solve CFG [--third]]   (--one-solve: a single device_step solve, for a kernel trace)"""
 import argparse
 import json
 import os
@@ -24,13 +24,14 @@ CONFIGS = {"3": ("portfolio_socp", problems.portfolio_socp), "2a": ("random_spar
            # ... and Generalized Power cones: device_step_genpower on top (the Dual strategy and its barrier search in every iteration)
            "genpow": ("nonsymmetric_mix_genpow",
                       lambda: problems.nonsymmetric_mix(n=80, nexp=10, npow=10, ngenpow=20, nn=20, nzero=3, socdim=5, seed=5)),
-           # PSD triangle cones (benchmark configuration 5 at its size, 20 x PSD(50)): device_step_psd on top; the Cholesky / SVD of the
-           # scaling stay on the host
+           # PSD triangle cones (benchmark configuration 5 at its size, 20 x PSD(50)): device_step_psd on top, the Cholesky / SVD of the
+           # scaling on the host; and a third path with device_scaling_psd, where the device does them too
            "psd": ("sdp_blocks", problems.sdp_blocks)}
 PARENT = dict(device_scaling=True, device_reduced=True, device_residuals=True)
 STEP_EXTRA = {"exp_pow": dict(device_step_nonsymmetric=True),
               "genpow": dict(device_step_nonsymmetric=True, device_step_genpower=True),
               "psd": dict(device_step_psd=True)}      # what device_step needs on top, per configuration
+THIRD = {"psd": ("device_step_and_scaling", dict(device_scaling_psd=True))}      # a further path on top of device_step, where there is one
 
 
 def one_solve(prob, **flags):
@@ -63,9 +64,11 @@ def main():
     ap.add_argument("--cfgs", default="3,2a")
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--one-solve", default=None)
+    ap.add_argument("--third", action="store_true", help="--one-solve with the configuration's third path (psd: device_scaling_psd)")
     args = ap.parse_args()
     if args.one_solve:
-        rec = one_solve(CONFIGS[args.one_solve][1](), device_step=True, **PARENT, **STEP_EXTRA.get(args.one_solve, {}))
+        rec = one_solve(CONFIGS[args.one_solve][1](), device_step=True, **PARENT, **STEP_EXTRA.get(args.one_solve, {}),
+                        **(THIRD[args.one_solve][1] if args.third and args.one_solve in THIRD else {}))
         print(json.dumps({"cfg": args.one_solve, "device_step": rec}))
         return
     result = {"tool": "step_path_compare", "repeats": args.repeats, "configs": {}}
@@ -73,12 +76,19 @@ def main():
         name, make = CONFIGS[cfg]
         prob = make()
         paths = {}
-        for label, flags in (("host_cone_algebra", PARENT), ("device_step", dict(device_step=True, **PARENT, **STEP_EXTRA.get(cfg, {})))):
+        step = dict(device_step=True, **PARENT, **STEP_EXTRA.get(cfg, {}))
+        todo = [("host_cone_algebra", PARENT), ("device_step", step)]
+        if cfg in THIRD:
+            todo.append((THIRD[cfg][0], dict(step, **THIRD[cfg][1])))
+        for label, flags in todo:
             one_solve(prob, **flags)                                   # warm-up: plan cache, graphs, code objects
             paths[label] = median_of([one_solve(prob, **flags) for _ in range(args.repeats)])
         assert paths["device_step"]["device_step"] and not paths["host_cone_algebra"]["device_step"]
         result["configs"][cfg] = dict(problem=name, **paths,
                                       speedup=paths["host_cone_algebra"]["ms_per_iteration"] / paths["device_step"]["ms_per_iteration"])
+        if cfg in THIRD:
+            result["configs"][cfg]["speedup_third_over_device_step"] = \
+                paths["device_step"]["ms_per_iteration"] / paths[THIRD[cfg][0]]["ms_per_iteration"]
     result["box_probe"] = hipkkt.box_probe(0)
     print(json.dumps(result))
 
