@@ -49,6 +49,7 @@ static int32_t set_cone_types_impl(hipkkt_handle h, int64_t ncones, const int32_
     std::vector<signed char> kind((size_t)std::max<int64_t>(m, 1), 2);
     std::vector<int64_t> rowhs((size_t)std::max<int64_t>(m, 1), 0), socdesc;
     C.reg.psd_hs.clear(); C.reg.psd_n.clear(); C.reg.psd_row.clear(); C.reg.psd_total = C.reg.psd_lam_total = 0; C.reg.nsoc = 0;
+    C.reg.degree = 0;
     int64_t row = 0, hs = 0;
     int sparse_idx = 0;
     for (int64_t c = 0; c < ncones; c++) {
@@ -59,6 +60,7 @@ static int32_t set_cone_types_impl(hipkkt_handle h, int64_t ncones, const int32_
         if (kinds[c] == 0 || kinds[c] == 1) {
             if (dense || sk != 0) { S->err = "set_cone_types: a Zero / Nonnegative cone has a diagonal Hs block and no expansion"; return HIPKKT_ERR_ARGUMENT; }
             for (int64_t i = 0; i < numel; i++) { kind[row + i] = (signed char)kinds[c]; rowhs[row + i] = hs + i; }
+            if (kinds[c] == 1) C.reg.degree += numel;
         } else if (kinds[c] == 2) {
             int64_t uv0 = -1, ord = -1;
             if (sk == 1) {
@@ -72,6 +74,7 @@ static int32_t set_cone_types_impl(hipkkt_handle h, int64_t ncones, const int32_
             const int64_t d[kSocDesc] = {row, numel, hs, uv0, ord};      // kSocRow0, kSocDim, kSocHs0, kSocUv0, kSocOrd
             socdesc.insert(socdesc.end(), d, d + kSocDesc);
             C.reg.nsoc++;
+            C.reg.degree += 1;
         } else if (kinds[c] == 3) {
             int64_t n = (int64_t)((std::sqrt(8.0 * (double)numel + 1.0) - 1.0) * 0.5 + 0.5);
             if (!dense || sk != 0 || n * (n + 1) / 2 != numel) { S->err = "set_cone_types: a PSD triangle cone has a dense block of triangular size"; return HIPKKT_ERR_ARGUMENT; }
@@ -80,6 +83,7 @@ static int32_t set_cone_types_impl(hipkkt_handle h, int64_t ncones, const int32_
             C.reg.psd_row.push_back(row);
             C.reg.psd_total += n * n;
             C.reg.psd_lam_total += n;
+            C.reg.degree += n;
         } else if (ex && (kinds[c] == HIPKKT_CONE_EXP || kinds[c] == HIPKKT_CONE_POW)) {
             if (numel != 3 || !dense || sk != 0) { S->err = "set_cone_types_ex: an Exponential / Power cone has three rows, a dense Hs block and no expansion"; return HIPKKT_ERR_ARGUMENT; }
             double a = 0.0;

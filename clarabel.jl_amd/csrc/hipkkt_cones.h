@@ -29,6 +29,7 @@ struct ConeState {
         bool nonsym = false;                               // it named an Exponential / Power / GenPower cone
         int nexp = 0, npow = 0, ngenpow = 0;
         int64_t nonsym_len = 0;                            // doubles of their output vector (hipkkt_get_nonsym_len)
+        int64_t degree = 0;                                // Nonnegative rows + second-order cones + PSD sides (the default start's target)
     } reg;
     // device tables and results of the scaling: allocated on the first use, re-used by later calls while large enough (cap_*)
     struct Tables {
@@ -50,6 +51,7 @@ struct ConeState {
         int64_t *psdtab = nullptr;
         double *psd_rinv = nullptr, *psd_lam = nullptr, *psd_stage = nullptr;
         int *psd_bad = nullptr;                            // per PSD cone: its device-side scaling failed (scaling_psd.hip)
+        int64_t *psd_hs0 = nullptr;                        // per PSD cone: its first Hs entry (start.hip)
     } tab;
     // what the step entry points work on between the calls
     struct Step {
@@ -67,6 +69,7 @@ struct ConeState {
         double *part = nullptr, *out = nullptr;            // partial results of the step length / the norms; results (cone_layout.h kStOut*)
         double *eq = nullptr;                              // [d | e | dinv | einv] (hipkkt_set_equilibration)
         double *bar = nullptr;                             // work buffer of the barrier (step3_barrier_doubles)
+        double *start = nullptr;                           // partials and decision records of the default start (start_work_doubles)
     } step;
 };
 

@@ -5,10 +5,10 @@
 //   hipkkt_factor.cpp  the factorisation's launch sequence, its graph, hipkkt_refactor and the robust-order twin
 //   solve_schedule.cpp the solve schedule of a plan: level lists, segments, item order (host arithmetic only; solve_schedule.h)
 //   hipkkt_solve.cpp   LDL solves, device-side iterative refinement, the solve entry points
-//   hipkkt_step.cpp    the cone algebra of an interior-point step around the reduced solve (hipkkt_cone_* / hipkkt_step_*)
+//   hipkkt_step.cpp    the cone algebra of an interior-point step around the reduced solve (hipkkt_cone_* / hipkkt_step_*), the default start
 // hipkkt_parts.h holds the parts a handle is made of besides its cones (hipkkt_cones.h).
 // Host orchestration only; all numeric work is in the .hip files: values / kernels / front_block2 (front_block: testing build) /
-// solve_sweep / front_sweep / refine / assemble_dev / scaling / step, step_cone3, step_genpow, step_psd; kernels.h lists their launchers.
+// solve_sweep / front_sweep / refine / assemble_dev / scaling / step, step_cone3, step_genpow, step_psd / start; kernels.h lists their launchers.
 #pragma once
 #include "../../include/hipkkt.h"
 
@@ -131,6 +131,7 @@ struct RefineOpts {
 // section 8(f) row N2: the constant-rhs solve and the affine solve of an IPM iteration): the sweeps are bound by
 // dependency latency, not by throughput, so two of them overlap almost perfectly.
 constexpr int kNumCtx = 2;
+constexpr int kScalRedDoubles = 16;   // what h_scal_red may hold: the pinned chunk's second half (hipkkt_setup.cpp init_runtime)
 struct SolveCtx {
     hipStream_t stream = nullptr;
     bool own_stream = false;
@@ -192,7 +193,8 @@ struct hipkkt_solver {
     int64_t *d_stage_idx = nullptr;
     int64_t stage_cap = 0;
     double *h_scal = nullptr;    // pinned read-back area
-    double *h_scal_red = nullptr;   // ... its second half: the ten scalars of the reduced solve
+    double *h_scal_red = nullptr;   // ... its second half, kScalRedDoubles doubles: the ten scalars of the reduced solve and the step lengths behind
+                                    // them (hipkkt_step.cpp fused_solve), or the two decision records of the default start
     int *h_flags = nullptr;
 
     hipkkt_host::GraphSlot g_factor;
@@ -287,7 +289,8 @@ void init_runtime(hipkkt_solver *S);
 void setup_device(hipkkt_solver *S);
 int32_t finish_create(hipkkt_solver *S, const hipkkt_opts *opts, hipkkt_handle *out);
 // hipkkt_solve.cpp
-int32_t solve_many(hipkkt_solver *S, hipkkt_solver *T, int nrhs, const RefineOpts &ir, int64_t *ir_steps, double *const *out_dev, int nm);
+int32_t solve_many(hipkkt_solver *S, hipkkt_solver *T, int nrhs, const RefineOpts &ir, int64_t *ir_steps, double *const *out_dev, int nm,
+                   const std::function<void(hipStream_t)> *after = nullptr);
 hipkkt_solver *solve_target(hipkkt_solver *S);
 // kkt_solve! around the two solves (hipkkt_kkt_solve_reduced*, hipkkt_step_*_dev): input either on the host or [rhs.x | workz | variables.x]
 // on the device; outputs whichever of them are set

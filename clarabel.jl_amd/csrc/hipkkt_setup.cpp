@@ -78,8 +78,8 @@ void init_runtime(hipkkt_solver *S) {
     for (hipEvent_t *e : {&S->ev0, &S->ev1, &S->ev2, &S->ev3, &S->ev_fork, &S->ev_join}) *e = (hipEvent_t)need(rp.event_get(S->device));
     S->h_scal = (double *)need(rp.pinned_alloc(S->device));
     S->h_flags = (int *)need(rp.pinned_alloc(S->device));
-    S->h_scal_red = S->h_scal + 16;     // second half of the same pinned chunk (10 doubles; RuntimePool::kPinned = 256 bytes)
-    static_assert((16 + 10) * sizeof(double) <= RuntimePool::kPinned, "pinned chunk too small for the reduced-solve scalars");
+    S->h_scal_red = S->h_scal + 16;     // second half of the same pinned chunk (kScalRedDoubles; RuntimePool::kPinned = 256 bytes)
+    static_assert((16 + kScalRedDoubles) * sizeof(double) <= RuntimePool::kPinned, "pinned chunk too small for the reduced-solve scalars");
     memset(S->h_scal, 0, SC_COUNT * sizeof(double));
     memset(S->h_flags, 0, FL_COUNT * sizeof(int));
     if (debug_opts().no_graph) S->use_graph = false;

@@ -212,25 +212,43 @@ static int32_t solve_finish(hipkkt_solver *S, SolveCtx &C, int64_t *ir_steps, do
 hipkkt_solver *solve_target(hipkkt_solver *S) { return (S->twin.using_fallback && S->twin.fallback) ? S->twin.fallback : S; }
 
 // nrhs (<= kNumCtx) right-hand sides already in T->ctx[c].d_b (T = solve_target(S)): solved concurrently, results optionally
-// copied to out_dev[c]
-int32_t solve_many(hipkkt_solver *S, hipkkt_solver *T, int nrhs, const RefineOpts &ir, int64_t *ir_steps, double *const *out_dev, int nm) {
+// copied to out_dev[c].  after (hipkkt_step_default_start_dev): work on the copies, enqueued on context 0's stream behind all of them
+// before anything is waited for, and once more when a solve took refinement steps beyond the one in its graph (the copies changed);
+// the first synchronisation of context 0 then covers it.
+int32_t solve_many(hipkkt_solver *S, hipkkt_solver *T, int nrhs, const RefineOpts &ir, int64_t *ir_steps, double *const *out_dev, int nm,
+                   const std::function<void(hipStream_t)> *after) {
     int32_t rc = HIPKKT_OK;
     double ms = 0;
-    with_sweep_retry(T, [&] {
+    bool redo = false;
+    auto run_after = [&] {
+        for (int c = 1; c < nrhs; c++) {
+            HK_CHECK(hipEventRecord(S->ev2, T->ctx[c].stream));
+            HK_CHECK(hipStreamWaitEvent(T->ctx[0].stream, S->ev2, 0));
+        }
+        (*after)(T->ctx[0].stream);
+    };
+    const bool gave_up = with_sweep_retry(T, [&] {
         for (int c = 0; c < nrhs; c++) {
             solve_begin(T, T->ctx[c], ir);
             solve_copy_out_dev(T, T->ctx[c], out_dev ? out_dev[c] : nullptr, nm);
         }
+        if (after) run_after();
         rc = HIPKKT_OK;
         ms = 0;
+        redo = false;
         bool timed_out = false;
         for (int c = 0; c < nrhs; c++) {
             rc = merge_rc(rc, solve_finish(T, T->ctx[c], ir_steps ? ir_steps + c : nullptr, out_dev ? out_dev[c] : nullptr, nm));
             ms = std::max(ms, T->ctx[c].last_ms);
             timed_out = timed_out || sweep_failed(T->ctx[c]);
+            redo = redo || T->ctx[c].extra_steps;
         }
         return timed_out;
     });
+    if (after && !gave_up && rc == HIPKKT_OK) {
+        if (redo) run_after();
+        HK_CHECK(hipStreamSynchronize(T->ctx[0].stream));      // (returns at once unless `after` ran again or context 1 finished last)
+    }
     account_solve(S, T, ms, nrhs);
     return rc;
 }

@@ -5,6 +5,8 @@
 // [Hs | H_dual | grad] that hipkkt_update_scaling_ex[_dev] left resident; then hipkkt_cone_barrier / hipkkt_step_barrier_dev as well.
 // After hipkkt_step_enable_genpow the Generalized Power cones too (step_genpow.hip), on their slot [grad | d1 | d2 | p | q | r].
 // After hipkkt_step_enable_psd the PSD triangle cones of a symmetric registration (step_psd.hip), on the caller's (R, Rinv, lambda).
+// The default start of a symmetric cone set (start.hip): hipkkt_cone_set_identity_scaling / _margins / _shift_to_interior and the fused
+// hipkkt_step_default_start_dev, which need no scaling.
 #include "hipkkt_internal.h"
 
 #pragma clang fp contract(off)      // the scalars below repeat the caller's expressions (variables.jl:14-43, :124-162) rounding by rounding
@@ -35,6 +37,7 @@ static void ensure_step_buffers(hipkkt_solver *S) {
     C.step.part = S->dalloc<double>((size_t)std::max<int64_t>(2 * pairs, step_norm_part_doubles()));
     C.step.out = S->dalloc<double>(kStOutDoubles);      // step lengths, norms, barrier results, the parked symmetric pair (cone_layout.h)
     C.step.bar = S->dalloc<double>((size_t)step3_barrier_doubles((int64_t)S->cone_numel.size()));
+    C.step.start = S->dalloc<double>((size_t)start_work_doubles((int64_t)S->cone_numel.size()));
 }
 
 struct ConeTables {
@@ -168,6 +171,7 @@ static int32_t fused_solve(hipkkt_solver *S, const StepScalars &sc, const double
     ConeState &C = S->cones;
     const ConeTables T = tables(S);
     if (solve_target(S) != S) HK_CHECK(hipStreamSynchronize(S->stream));      // the robust-order twin solves on its own stream
+    static_assert(10 + 2 <= kScalRedDoubles, "the step lengths do not fit behind the ten scalars");
     double *h2 = S->h_scal_red + 10;
     const std::function<void(hipStream_t, const double *)> after = [&](hipStream_t st, const double *d_lhs) {
         double *dz = C.step.step + n, *ds = dz + m;
@@ -337,13 +341,15 @@ int32_t hipkkt_step_enable_psd(hipkkt_handle h, int32_t enable) {
         foff += n * n; loff += n;
     }
     if (npsd > C.tab.cap_psd_cones) {
-        C.tab.psdtab = S->dalloc<int64_t>(kPsdTab * npsd); C.tab.psd_bad = S->dalloc<int>(npsd); C.tab.cap_psd_cones = npsd;
+        C.tab.psdtab = S->dalloc<int64_t>(kPsdTab * npsd); C.tab.psd_bad = S->dalloc<int>(npsd); C.tab.psd_hs0 = S->dalloc<int64_t>(npsd);
+        C.tab.cap_psd_cones = npsd;
     }
     if (foff > C.tab.cap_psd_mat || loff > C.tab.cap_psd_lam) {
         C.tab.psd_rinv = S->dalloc<double>(foff); C.tab.psd_lam = S->dalloc<double>(loff); C.tab.psd_stage = S->dalloc<double>(foff + loff);
         C.tab.cap_psd_mat = foff; C.tab.cap_psd_lam = loff;
     }
     copy_sync(S->stream, C.tab.psdtab, tab.data(), tab.size() * sizeof(int64_t), hipMemcpyHostToDevice);
+    copy_sync(S->stream, C.tab.psd_hs0, C.reg.psd_hs.data(), (size_t)npsd * sizeof(int64_t), hipMemcpyHostToDevice);      // (the default start's identity scaling)
     C.step.mode = StepMode::Psd;
     C.step.psd_fresh = false;
     C.step.psd_scaling = C.step.psd_resident = false;
@@ -527,6 +533,130 @@ int32_t hipkkt_step_get(hipkkt_handle h, double *out) {
     ConeState &C = S->cones;
     if (!S->l1 || !C.step.have_step || !out) { S->err = "step_get: no step resident"; return HIPKKT_ERR_ARGUMENT; }
     copy_sync(S->stream, out, C.step.step, (size_t)(S->img.n + 2 * S->img.m) * sizeof(double), hipMemcpyDeviceToHost);
+    return HIPKKT_OK;
+    HK_LEAVE
+}
+
+// ---- the default start of a symmetric cone set (solver.jl:383-405; start.hip) ------------------------------------------------------
+// served: L1 handles in step mode Symmetric (kinds 0..2) or Psd (kinds 0..3 after hipkkt_step_enable_psd); needs no scaling
+static bool start_ready(hipkkt_solver *S, const char *who) {
+    const ConeState &C = S->cones;
+    if (!S->l1 || !C.reg.ready || (C.step.mode != StepMode::Symmetric && C.step.mode != StepMode::Psd)) {
+        S->err = std::string(who) + ": needs an L1 handle whose registered cones are Zero / Nonnegative / SecondOrder only, or one with PSD "
+                                    "triangle cones next to them after hipkkt_step_enable_psd";
+        return false;
+    }
+    return true;
+}
+
+// set_identity_scaling! + get_Hs! + the Hs / sparse-cone part of _kktsolver_update_inner! (kktsolver_directldl.jl:197-245), enqueued
+static void start_identity(hipkkt_solver *S) {
+    ConeState &C = S->cones;
+    const ConeTables T = tables(S);
+    int64_t max_numel = 0;
+    if (T.npsd) for (int64_t n : C.reg.psd_n) max_numel = std::max(max_numel, n * (n + 1) / 2);
+    launch_start_identity(S->stream, C.tab.kind, C.tab.rowhs, S->d_mapHs, T.nsoc, T.desc, S->soc.d_u, S->soc.d_v, S->soc.d_eta2, T.npsd,
+                          T.psdtab, C.tab.psd_hs0, max_numel, S->dp.kval, T.m);
+    if (S->soc.n > 0)      // u, v, D entries of the sparse cones (the same kernel hipkkt_set_soc_batch uses)
+        launch_soc_batch(S->stream, S->dp.kval, S->soc.d_uidx, S->soc.d_vidx, S->soc.d_cone, S->soc.d_u, S->soc.d_v, S->soc.d_eta2,
+                         S->soc.total, S->soc.d_didx, S->soc.n);
+    // the resident (w, lambda, eta, R, Rinv) belong to another scaling than K now: the step calls wait for the next hipkkt_update_scaling*
+    C.step.scaled = false;
+    C.step.psd_resident = false;
+    C.step.have_step = false;
+    S->red.have_const = false;
+}
+
+// margins (and the shift when `shift`) of one host vector: nout doubles of its decision record come back
+static int32_t start_host_op(hipkkt_solver *S, double *v, int32_t pd, bool shift, double *out, int nout) {
+    ConeState &C = S->cones;
+    const ConeTables T = tables(S);
+    const int64_t m = T.m, ncones = (int64_t)S->cone_numel.size();
+    ensure_step_buffers(S);
+    S->ensure_stage(m);
+    double *dv = S->d_stage, *dec = start_decision(C.step.start, ncones);
+    if (m) HK_CHECK(hipMemcpyAsync(dv, v, m * sizeof(double), hipMemcpyHostToDevice, S->stream));
+    launch_start_margins(S->stream, T.kind, T.nsoc, T.desc, T.npsd, T.psdtab, dv, nullptr, 1, (double)C.reg.degree, C.step.start, ncones, m);
+    if (shift) {
+        launch_start_shift(S->stream, T.kind, T.nsoc, T.desc, T.npsd, T.psdtab, dec, dv, pd, nullptr, 0, 1, m);
+        if (m) HK_CHECK(hipMemcpyAsync(v, dv, m * sizeof(double), hipMemcpyDeviceToHost, S->stream));
+    }
+    copy_sync(S->stream, out, dec, (size_t)nout * sizeof(double), hipMemcpyDeviceToHost);
+    return HIPKKT_OK;
+}
+
+int32_t hipkkt_cone_set_identity_scaling(hipkkt_handle h) {
+    HK_ENTER(h)
+    if (!start_ready(S, "cone_set_identity_scaling")) return HIPKKT_ERR_ARGUMENT;
+    start_identity(S);
+    HK_CHECK(hipStreamSynchronize(S->stream));
+    return HIPKKT_OK;
+    HK_LEAVE
+}
+
+int32_t hipkkt_cone_margins(hipkkt_handle h, const double *v, int32_t pd, double *out2) {
+    HK_ENTER(h)
+    if (!start_ready(S, "cone_margins")) return HIPKKT_ERR_ARGUMENT;
+    if ((pd != 0 && pd != 1) || !out2 || (S->img.m && !v)) { S->err = "cone_margins: pd is 0 (primal) or 1 (dual) / null argument"; return HIPKKT_ERR_ARGUMENT; }
+    return start_host_op(S, const_cast<double *>(v), pd, false, out2, 2);
+    HK_LEAVE
+}
+
+int32_t hipkkt_cone_shift_to_interior(hipkkt_handle h, double *v, int32_t pd, double *out4) {
+    HK_ENTER(h)
+    if (!start_ready(S, "cone_shift_to_interior")) return HIPKKT_ERR_ARGUMENT;
+    if ((pd != 0 && pd != 1) || !out4 || (S->img.m && !v)) { S->err = "cone_shift_to_interior: pd is 0 (primal) or 1 (dual) / null argument"; return HIPKKT_ERR_ARGUMENT; }
+    return start_host_op(S, v, pd, true, out4, 4);
+    HK_LEAVE
+}
+
+int32_t hipkkt_step_default_start_dev(hipkkt_handle h, double *xzs_dev, int32_t static_reg_enable, double eps_const, double eps_prop,
+                                      int32_t ir_enable, double reltol, double abstol, int64_t max_iter, double stop_ratio,
+                                      double *scal_out8, int64_t *ir_steps2) {
+    HK_ENTER(h)
+    ConeState &C = S->cones;
+    if (!start_ready(S, "step_default_start_dev")) return HIPKKT_ERR_ARGUMENT;
+    if (!S->res.d_qb || !xzs_dev || !scal_out8) { S->err = "step_default_start_dev: call hipkkt_set_qb first / bad arguments"; return HIPKKT_ERR_ARGUMENT; }
+    const int64_t n = S->img.n, m = S->img.m, ncones = (int64_t)S->cone_numel.size();
+    const int nm = (int)(n + m);
+    ensure_step_buffers(S);
+    for (int k = 0; k < 8; k++) scal_out8[k] = 0.0;
+    if (ir_steps2) ir_steps2[0] = ir_steps2[1] = 0;
+    // kkt_update! of the identity scaling (kktsystem.jl:62-78): hipkkt_refactor's code path, twin included; it synchronises
+    start_identity(S);
+    double eps = 0.0;
+    int64_t nreg = 0;
+    int32_t rc = hipkkt_refactor(h, static_reg_enable, eps_const, eps_prop, &eps, &nreg);
+    scal_out8[0] = eps; scal_out8[1] = (double)nreg;
+    if (rc != HIPKKT_OK) return rc;
+    // kkt_solve_initial_point! (kktsystem.jl:95-132): structural nnz(P) != 0 one solve of [-q; b] for (x, z), s = -z; otherwise
+    // [0; b] for (x, -s) and [-q; 0] for z on the two solve contexts
+    const ConeTables T = tables(S);
+    hipkkt_solver *F = solve_target(S);
+    const bool pair = S->img.nnzP == 0;
+    double *sa = C.step.step, *sb = C.step.in;      // (n + m doubles of each are used)
+    if (pair) {
+        launch_start_rhs(F->ctx[0].stream, F->ctx[0].d_b, S->res.d_qb, (int)n, nm, F->N, 1);
+        launch_start_rhs(F->ctx[1].stream, F->ctx[1].d_b, S->res.d_qb, (int)n, nm, F->N, 2);
+    } else {
+        launch_const_rhs(F->ctx[0].stream, F->ctx[0].d_b, S->res.d_qb, (int)n, nm, F->N);
+    }
+    // variables_symmetric_initialization! (variables.jl:167-208) behind the solves, read back with their synchronisation
+    double *dec = start_decision(C.step.start, ncones), *h16 = S->h_scal_red;
+    static_assert(2 * 8 <= kScalRedDoubles, "the two decision records do not fit the pinned read-back area");
+    double *s_dev = xzs_dev + n + m, *z_dev = xzs_dev + n;
+    const std::function<void(hipStream_t)> after = [&](hipStream_t st) {
+        launch_start_assemble(st, xzs_dev, sa, pair ? sb : nullptr, n, m);
+        launch_start_margins(st, T.kind, T.nsoc, T.desc, T.npsd, T.psdtab, s_dev, z_dev, 2, (double)C.reg.degree, C.step.start, ncones, m);
+        launch_start_shift(st, T.kind, T.nsoc, T.desc, T.npsd, T.psdtab, dec, s_dev, 0, z_dev, 1, 2, m);
+        HK_CHECK(hipMemcpyAsync(h16, dec, 2 * 8 * sizeof(double), hipMemcpyDeviceToHost, st));
+    };
+    double *outs[kNumCtx] = {sa, sb};
+    int64_t steps[kNumCtx] = {0, 0};
+    rc = solve_many(S, F, pair ? 2 : 1, RefineOpts{ir_enable, reltol, abstol, max_iter, stop_ratio}, steps, outs, nm, &after);
+    if (ir_steps2) { ir_steps2[0] = steps[0]; ir_steps2[1] = steps[1]; }
+    if (rc != HIPKKT_OK) return rc;
+    for (int k = 0; k < 3; k++) { scal_out8[2 + k] = h16[k]; scal_out8[5 + k] = h16[8 + k]; }
     return HIPKKT_OK;
     HK_LEAVE
 }

@@ -167,4 +167,23 @@ void launch_psd_step_check(hipStream_t st, const double *lam, int64_t len, int *
 // that fails sets *fail and bad[cone] (0 otherwise) and gets NaN factors.
 void launch_psd_nt_scaling(hipStream_t st, int npsd, const int64_t *tab, const double *s, const double *z, double *R, double *Rinv,
                            double *lam, int *bad, int *fail);
+// start.hip: the default start of a symmetric cone set (solver.jl:383-405) on the tables above.
+// launch_start_identity writes the identity scaling's Hs values and sparse second-order terms into kval (psd_hs0 = first Hs entry per
+// PSD cone, psd_max_numel = the largest numel among them).  launch_start_margins leaves, for each of nsides vectors (v1 is not read
+// when nsides == 1), the record {min_margin, pos_margin, target, branch, a, b, two_stage, 0} at start_decision(work, ncones) + 8 side;
+// work has start_work_doubles(ncones) doubles, degree = the cone set's degree.  launch_start_shift applies scaled_unit_shift! twice
+// (a, then b when two_stage) to v0 / v1 in place, pd 0 primal (Zero rows become 0) / 1 dual (Zero rows stay).
+// launch_start_rhs: mode 1 [0; b; 0], mode 2 [-q; 0; 0].  launch_start_assemble: xzs = [x | z | s] from the solutions sa, sb
+// (sb == NULL: z = sa.z, s = -z; otherwise s = -sa.z, z = sb.z).
+int64_t start_work_doubles(int64_t ncones);
+double *start_decision(double *work, int64_t ncones);
+void launch_start_identity(hipStream_t st, const signed char *row_kind, const int64_t *row_hs, const int64_t *map_hs, int nsoc,
+                           const int64_t *desc, double *soc_u, double *soc_v, double *soc_eta2, int npsd, const int64_t *psdtab,
+                           const int64_t *psd_hs0, int64_t psd_max_numel, double *kval, int64_t m);
+void launch_start_margins(hipStream_t st, const signed char *row_kind, int nsoc, const int64_t *desc, int npsd, const int64_t *psdtab,
+                          const double *v0, const double *v1, int nsides, double degree, double *work, int64_t ncones, int64_t m);
+void launch_start_shift(hipStream_t st, const signed char *row_kind, int nsoc, const int64_t *desc, int npsd, const int64_t *psdtab,
+                        const double *dec, double *v0, int pd0, double *v1, int pd1, int nsides, int64_t m);
+void launch_start_rhs(hipStream_t st, double *dst, const double *qb, int n, int nm, int N, int mode);
+void launch_start_assemble(hipStream_t st, double *xzs, const double *sa, const double *sb, int64_t n, int64_t m);
 }  // namespace hipkkt

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "cone_layout.h"
+#include "cone_reduce.h"
 
 namespace hipkkt {
 
@@ -36,6 +37,85 @@ __device__ __forceinline__ void load_svec(double *X, const double *__restrict__ 
         const double v = x[c * (c + 1) / 2 + r];
         X[i + j * K.ld] = i == j ? v : v * kPsdIsqrt2;
     }
+}
+
+constexpr int kPsdMaxSweeps = 30;
+constexpr double kPsdEps = 2.220446049250313e-16;
+
+// The cyclic two-sided Jacobi iteration of the step length (step_psd.hip k_psd_len) and of the default start's margins (start.hip) on
+// the symmetric n x n matrix M in LDS; tot2 = |M|_F^2, the same value in every thread.  red[4], rc / rs / rp / rq[kPsdMaxN / 2]: LDS
+// scratch (rs = the rotations' s, rc = their s / (1 + c), rp < rq their index pairs).  Returns whether M was finite; afterwards the
+// diagonal of M holds the eigenvalues (after a barrier: the last loop ends with one).  One definition: both kernels round alike.
+__device__ __forceinline__ bool psd_jacobi_sweeps(double *M, const Cone &K, double tot2, double *red, double *rc, double *rs, int *rp,
+                                                  int *rq) {
+    const int n = K.n, ld = K.ld, t = threadIdx.x;
+    // cyclic Jacobi: per sweep np - 1 sets of np / 2 disjoint rotations (round robin over np = n rounded up to even; the index n of an
+    // odd n is a dummy).  Stops when off(M) <= eps |M|_F; a non-finite |M|_F skips the sweeps (uniform: block_sum gives every thread
+    // the same value)
+    const int np = n + (n & 1), half = np / 2;
+    const bool finite = tot2 - tot2 == 0.0;
+    for (int sweep = 0; finite && sweep < kPsdMaxSweeps; sweep++) {
+        double off2 = 0.0;
+        for (int e = t; e < n * n; e += 256) {
+            const int i = e % n, j = e / n;
+            if (i != j) off2 += M[i + j * ld] * M[i + j * ld];
+        }
+        off2 = block_sum(off2, red);
+        if (!(off2 > kPsdEps * kPsdEps * tot2)) break;
+        for (int r = 0; r < np - 1; r++) {
+            // pair k of set r: (np - 1, r) for k = 0, ((r + k) mod (np - 1), (r - k) mod (np - 1)) otherwise; a pair with the dummy index
+            // or with a zero entry keeps s = 0 and is skipped below
+            if (t < half) {
+                const int a = t == 0 ? np - 1 : (r + t) % (np - 1), b = (r + np - 1 - t) % (np - 1);
+                const int p = a < b ? a : b, q = a < b ? b : a;
+                // the stable formula: t = sign(tau) / (|tau| + sqrt(1 + tau^2)), c = 1 / sqrt(1 + t^2), s = t c; the rotation is applied
+                // as x_p - s (x_q + r x_p), x_q + s (x_p - r x_q) with r = s / (1 + c), whose rounding error shrinks with the angle
+                double sn = 0.0, rr = 0.0;
+                if (q < n) {
+                    const double apq = M[p + q * ld];
+                    if (apq != 0.0) {
+                        const double tau = (M[q + q * ld] - M[p + p * ld]) / (2.0 * apq);
+                        const double tt = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
+                        const double cs = 1.0 / sqrt(1.0 + tt * tt);
+                        sn = tt * cs;
+                        rr = sn / (1.0 + cs);
+                    }
+                }
+                rs[t] = sn; rc[t] = rr; rp[t] = p; rq[t] = q;
+            }
+            __syncthreads();
+            // rows: M <- J' M.  Lane -> (pair k = t mod 32, column j = t / 32 + 8 i): half <= 32, no division in the loop
+            {
+                const int k = t & 31;
+                if (k < half && rs[k] != 0.0) {
+                    const int p = rp[k], q = rq[k];
+                    const double sn = rs[k], rr = rc[k];
+                    for (int j = t >> 5; j < n; j += 8) {
+                        const double mp = M[p + j * ld], mq = M[q + j * ld];
+                        M[p + j * ld] = mp - sn * (mq + rr * mp);
+                        M[q + j * ld] = mq + sn * (mp - rr * mq);
+                    }
+                }
+            }
+            __syncthreads();
+            // columns: M <- M J.  Lane -> (row i = t mod 64, pair k = t / 64 + 4 i); the rotated pair is zero by construction
+            {
+                const int i = t & 63;
+                if (i < n) {
+                    for (int k = t >> 6; k < half; k += 4) {
+                        const double sn = rs[k], rr = rc[k];
+                        if (sn == 0.0) continue;
+                        const int p = rp[k], q = rq[k];
+                        const double mp = M[i + p * ld], mq = M[i + q * ld];
+                        M[i + p * ld] = i == q ? 0.0 : mp - sn * (mq + rr * mp);
+                        M[i + q * ld] = i == p ? 0.0 : mq + sn * (mp - rr * mq);
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    return finite;
 }
 
 }  // namespace hipkkt

@@ -48,6 +48,8 @@ SYMBOLS = [
     "hipkkt_step_enable_psd", "hipkkt_psd_set_factors", "hipkkt_psd_set_factors_dev",
     # ... whose Cholesky / SVD the device does too (opt-in, added within ABI version 5)
     "hipkkt_psd_scaling_enable", "hipkkt_psd_get_factors",
+    # the default start of a symmetric cone set on the device (opt-in, added within ABI version 5)
+    "hipkkt_cone_set_identity_scaling", "hipkkt_cone_margins", "hipkkt_cone_shift_to_interior", "hipkkt_step_default_start_dev",
 ]
 
 PSD_STEP_MAX_DIM = 64      # include/hipkkt.h HIPKKT_PSD_STEP_MAX_DIM
@@ -165,6 +167,10 @@ def lib():
     L.hipkkt_psd_scaling_enable.argtypes = [vp, i32]
     L.hipkkt_psd_get_factors.argtypes = [vp, vp, vp, vp]
     L.hipkkt_cone_barrier.argtypes = [vp, _f64p, _f64p, _f64p, i64, _f64p]
+    L.hipkkt_cone_set_identity_scaling.argtypes = [vp]
+    L.hipkkt_cone_margins.argtypes = [vp, _f64p, i32, _f64p]
+    L.hipkkt_cone_shift_to_interior.argtypes = [vp, _f64p, i32, _f64p]
+    L.hipkkt_step_default_start_dev.argtypes = [vp, vp, i32, f64, f64, i32, f64, f64, i64, f64, _f64p, vp]
     L.hipkkt_step_barrier_dev.argtypes = [vp, vp, _f64p, i64, _f64p]
     L.hipkkt_debug_dump.argtypes = [vp, i32, vp, i64, C.POINTER(i64)]
     L.hipkkt_debug_extra_tiles.argtypes = [i32, i32, i32, C.POINTER(i32)]
@@ -688,6 +694,42 @@ class Handle:
         out = np.zeros(max(self.n + 2 * self.m, 1))
         self._chk_step(self.L.hipkkt_step_get(self.h, out), "step_get")
         return out[: self.n + 2 * self.m]
+
+    # ---- the default start of a symmetric cone set (solver.jl:383-405): Zero / Nonnegative / SecondOrder registrations, PSD triangle
+    # cones after step_enable_psd.  pd: "primal" / "dual" or 0 / 1.  ValueError = the handle cannot serve them.
+    @staticmethod
+    def _pd(pd):
+        return {"primal": 0, "dual": 1}.get(pd, pd)
+
+    def cone_set_identity_scaling(self):
+        """the identity scaling's Hs values and sparse second-order terms written into the resident K; nothing is uploaded"""
+        self._chk_step(self.L.hipkkt_cone_set_identity_scaling(self.h), "cone_set_identity_scaling")
+
+    def cone_margins(self, v, pd):
+        """-> (alpha, beta) of margins(::CompositeCone) for the host vector v"""
+        out = np.zeros(2)
+        self._chk_step(self.L.hipkkt_cone_margins(self.h, self._vec_m(v, "v"), int(self._pd(pd)), out), "cone_margins")
+        _count(self.m, 2)
+        return float(out[0]), float(out[1])
+
+    def cone_shift_to_interior(self, v, pd):
+        """_shift_to_cone_interior! of a copy of the host vector v -> (shifted, min_margin, pos_margin, target, branch 0 / 1 / 2)"""
+        w = self._vec_m(v, "v").copy()
+        out = np.zeros(4)
+        self._chk_step(self.L.hipkkt_cone_shift_to_interior(self.h, w, int(self._pd(pd)), out), "cone_shift_to_interior")
+        _count(self.m, self.m + 4)
+        return w[: self.m], float(out[0]), float(out[1]), float(out[2]), int(out[3])
+
+    def step_default_start_dev(self, xzs_ptr, static_enable=True, eps_const=1e-8, eps_prop=float(np.finfo(np.float64).eps) ** 2, **ir):
+        """identity scaling + refactor + kkt_solve_initial_point! + both shifts into xzs = [x | z | s] (device) -> (ok, scal[8] = eps_used,
+        regularised pivots, (min_margin, pos_margin, target) of s and of z, steps[2])"""
+        scal = np.zeros(8)
+        steps = np.zeros(2, dtype=np.int64)
+        rc = self._chk_step(self.L.hipkkt_step_default_start_dev(
+            self.h, xzs_ptr, int(static_enable), eps_const, eps_prop, int(ir.get("ir_enable", True)), ir.get("reltol", 1e-13),
+            ir.get("abstol", 1e-12), ir.get("max_iter", 10), ir.get("stop_ratio", 5.0), scal, steps.ctypes.data), "step_default_start_dev")
+        _count(0, 8)
+        return rc == 0, scal, steps
 
     # ---- the same entry points for the Exponential / Power cones (opt-in per registration) and the barrier of the line search
     def step_enable_cone3(self, enable, linesearch_backtrack_step, min_terminate_step_length):

@@ -50,6 +50,7 @@ class HipKKTSolver:
         self.settings = settings
         self.m, self.n = m, n
         numel, hs_dense, sparse_kind, dim1 = cones.kkt_descriptors()
+        self.p_nnz = int(P.nnz)
         self.h = hipkkt.Handle.from_parts(
             P, A, numel, hs_dense, sparse_kind, dim1, device=settings.device_id,
             dynamic_reg_eps=settings.dynamic_regularization_eps,
@@ -359,6 +360,28 @@ class HipKKTSolver:
         ok, scal, steps = self.h.step_combined_dev(xzs.ptr, res.ptr, tau, kappa, r_tau, dtau_aff, dkappa_aff, sigma, mu, m_corr,
                                                    self.settings.max_step_fraction, False, **self._ir())
         return self._step_done(ok, scal, steps, False)
+
+    @property
+    def default_start_on_device(self) -> bool:
+        """the default start of the cone set (solver.jl:383-405) can run on the resident iterate: kktsolver_default_start"""
+        return self._steps_on_device and not self.steps_nonsymmetric
+
+    def kktsolver_default_start(self, xzs):
+        """set_identity_scaling! + kkt_update! + kkt_solve_initial_point! + variables_symmetric_initialization! into the resident
+        [x | z | s] -> (ok, scal[8] = eps_used, regularised pivots, (min_margin, pos_margin, target) of s and of z); tau = kappa = 1
+        are the caller's.  Needs set_problem_vectors(q, b)."""
+        st = self.settings
+        ok, scal, steps = self.h.step_default_start_dev(xzs.ptr, st.static_regularization_enable, st.static_regularization_constant,
+                                                        st.static_regularization_proportional, **self._ir())
+        self.diagonal_regularizer = float(scal[0])
+        self.last_nreg = int(scal[1])
+        self.last_ir_steps = int(steps[0])
+        self.total_ir_steps += int(np.sum(steps))
+        self.nsolves += 1 if self.p_nnz else 2
+        self.last_start_scalars = scal
+        if _DEBUG:
+            print(f"[hipkkt] default_start ok={ok} eps={scal[0]:.3e} dynamic_regularisations={int(scal[1])} ir_steps={list(steps)}")
+        return ok, scal
 
     def kktsolver_step_apply(self, alpha, xzs):
         """[x | z | s] += alpha [dx | dz | ds] in place (not synchronised: the next call on the handle reads the result)"""

@@ -76,4 +76,9 @@ class Settings:
     # per cone, one-sided Jacobi sweeps in LDS): no download of (s, z) rows and no upload of factors, an iteration moves scalars only.
     # Needs device_step_psd: the caller raises ValueError otherwise.
     device_scaling_psd: bool = False
+    # device_step with the default start (solver.jl:383-405) on the device as well (hipkkt_step_default_start_dev: the identity scaling
+    # written into the resident K, the first factorisation, the initial-point solves and the shifts into the cones), for symmetric cone
+    # sets the device step serves: no Hs upload, no host eigenvalues, no upload of the start.  Non-symmetric sets keep their host unit
+    # initialisation.  Needs device_step: the caller raises ValueError otherwise.
+    device_default_start: bool = False
     extra: dict = field(default_factory=dict)

@@ -75,7 +75,8 @@ int32_t hipkkt_is_available(void);
  *    Added within 5, no signature changed: the step entry points hipkkt_cone_* / hipkkt_set_equilibration / hipkkt_step_*;
  *    hipkkt_step_enable_cone3 / hipkkt_cone_barrier / hipkkt_step_barrier_dev; hipkkt_step_enable_genpow;
  *    HIPKKT_PSD_STEP_MAX_DIM / hipkkt_step_enable_psd / hipkkt_psd_set_factors / hipkkt_psd_set_factors_dev;
- *    hipkkt_psd_scaling_enable / hipkkt_psd_get_factors. */
+ *    hipkkt_psd_scaling_enable / hipkkt_psd_get_factors;
+ *    hipkkt_cone_set_identity_scaling / hipkkt_cone_margins / hipkkt_cone_shift_to_interior / hipkkt_step_default_start_dev. */
 #define HIPKKT_ABI_VERSION 5
 int32_t hipkkt_abi_version(void);
 /* releases the process-wide cache of device memory blocks the library keeps between handles (not in the reference: an embedding
@@ -476,6 +477,40 @@ int32_t hipkkt_step_combined_dev(hipkkt_handle h, const double *xzs_dev, const d
 int32_t hipkkt_step_apply_dev(hipkkt_handle h, double alpha, double *xzs_dev);
 int32_t hipkkt_step_info_norms_dev(hipkkt_handle h, const double *xzs_dev, const double *res_dev, double *out8);
 int32_t hipkkt_step_get(hipkkt_handle h, double *out);
+/* The default start of a symmetric cone set (solver.jl:383-405) on the device.  Served: L1 handles whose registration is Zero /
+ * Nonnegative / SecondOrder only, or holds PSD triangle cones next to them after hipkkt_step_enable_psd (every side <=
+ * HIPKKT_PSD_STEP_MAX_DIM); anything else (a kind 4..6, PSD without the enable, an L0 handle) is HIPKKT_ERR_ARGUMENT.  No scaling is
+ * needed.  pd: 0 = primal cone, 1 = dual cone.
+ *   hipkkt_cone_set_identity_scaling  set_identity_scaling! (coneops_compositecone.jl:92-101) + get_Hs! (:123-131) + the Hs / sparse-cone
+ *     part of _kktsolver_update_inner! (kktsolver_directldl.jl:211-245) for that scaling, written into the resident K; nothing is
+ *     uploaded.  K holds the bits hipkkt_set_hs / hipkkt_set_soc_batch leave after the host cones' identity scaling: Zero rows -0,
+ *     Nonnegative rows -1, second-order cones their dense (dim <= 4) block or d = 0.5, u = [sqrt 0.5, 0 ...], v = 0, eta^2 = 1
+ *     (coneops_socone.jl:57-73, directldl_datamaps.jl:61-79), PSD cones the packed upper triangle of I (coneops_psdtrianglecone.jl:66-75).
+ *     The resident scaling and the resident constant-rhs solution are dropped: the step calls are refused until the next successful
+ *     hipkkt_update_scaling*.
+ *   hipkkt_cone_margins  out2 = (alpha, beta) of margins(::CompositeCone) (coneops_compositecone.jl:49-63) for the host vector v[m]:
+ *     Zero (floatmax, 0), Nonnegative (minimum, sum of the positive entries; coneops_nncone.jl:19-38), second-order (z0 - |z1|,
+ *     max(0, alpha); coneops_socone.jl:13-22), PSD (smallest eigenvalue, sum of the positive eigenvalues of svec_to_mat;
+ *     coneops_psdtrianglecone.jl:8-27; cyclic Jacobi sweeps).  beta is summed over fixed slices in a fixed order (Nonnegative rows,
+ *     second-order cones, PSD cones), not in cone order.  min and max propagate a NaN as the reference's do.
+ *   hipkkt_cone_shift_to_interior  _shift_to_cone_interior! (variables.jl:180-208) of v[m] in place; out4 = {min_margin, pos_margin,
+ *     target, branch}: target = max(1, 0.1 pos_margin / degree) (1 when the degree is 0), branch 0: min_margin <= 0, shift by
+ *     -min_margin and then by target (two additions); 1: min_margin < target, shift by target - min_margin; 2: shift by 0 (which
+ *     zeroes the Zero rows of a primal vector and turns -0 into +0).  A NaN min_margin takes branch 2.
+ *   hipkkt_step_default_start_dev  the fused call: the identity scaling, hipkkt_refactor's code path (robust-order twin included),
+ *     kkt_solve_initial_point! (kktsystem.jl:95-132) with the right-hand sides formed from the resident q, b (needs hipkkt_set_qb) --
+ *     structural nnz(P) != 0: one refined solve of [-q; b] for (x, z), s = -z; nnz(P) == 0: [0; b] for (x, -s) and [-q; 0] for z on the
+ *     two solve contexts -- then variables_symmetric_initialization! (variables.jl:167-208): the primal shift of s and the dual shift of
+ *     z.  xzs_dev = [x | z | s] (device, n + 2 m doubles) is written; vectors never cross PCIe.  scal_out8 = {eps_used, n_dynamic_reg,
+ *     min_margin_s, pos_margin_s, target_s, min_margin_z, pos_margin_z, target_z}; ir_steps2 (may be NULL) = the refinement steps of
+ *     the solve(s).  The cone algebra is enqueued behind the solves and read back with their synchronisation.  Return codes as
+ *     hipkkt_step_affine_dev; HIPKKT_NUMERICAL_FAILURE when the factorisation or a solve fails (xzs_dev is then unspecified). */
+int32_t hipkkt_cone_set_identity_scaling(hipkkt_handle h);
+int32_t hipkkt_cone_margins(hipkkt_handle h, const double *v, int32_t pd, double *out2);
+int32_t hipkkt_cone_shift_to_interior(hipkkt_handle h, double *v, int32_t pd, double *out4);
+int32_t hipkkt_step_default_start_dev(hipkkt_handle h, double *xzs_dev, int32_t static_reg_enable, double eps_const, double eps_prop,
+                                      int32_t ir_enable, double reltol, double abstol, int64_t max_iter, double stop_ratio,
+                                      double *scal_out8, int64_t *ir_steps2);
 
 /* ---- timing (device time on the handle's stream, HIP events) ------------------------------- */
 /* out[0] = ms of last refactor (value scatter + numeric LDL), out[1] = ms of last solve call

@@ -178,3 +178,32 @@ function hip_step_get!(handle::Ptr{Cvoid}, out::Vector{Float64})
     rc = ccall((:hipkkt_step_get, libhipkkt), Int32, (Ptr{Cvoid}, Ptr{Float64}), handle, out)
     return hip_step_check(handle, rc, "hipkkt_step_get")
 end
+
+# The default start of a symmetric cone set on the device (include/hipkkt.h "The default start ..."; solver.jl:383-405).  pd: 0 primal, 1 dual.
+function hip_cone_set_identity_scaling!(handle::Ptr{Cvoid})
+    rc = ccall((:hipkkt_cone_set_identity_scaling, libhipkkt), Int32, (Ptr{Cvoid},), handle)
+    return hip_step_check(handle, rc, "hipkkt_cone_set_identity_scaling")
+end
+# -> (α, β) of margins(::CompositeCone)
+function hip_cone_margins(handle::Ptr{Cvoid}, v::Vector{Float64}, pd::Integer)
+    out = zeros(Float64, 2)
+    rc = ccall((:hipkkt_cone_margins, libhipkkt), Int32, (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}), handle, v, pd, out)
+    hip_step_check(handle, rc, "hipkkt_cone_margins")
+    return (out[1], out[2])
+end
+# _shift_to_cone_interior!(v) in place -> (min_margin, pos_margin, target, branch 0 / 1 / 2)
+function hip_cone_shift_to_interior!(handle::Ptr{Cvoid}, v::Vector{Float64}, pd::Integer)
+    out = zeros(Float64, 4)
+    rc = ccall((:hipkkt_cone_shift_to_interior, libhipkkt), Int32, (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}), handle, v, pd, out)
+    hip_step_check(handle, rc, "hipkkt_cone_shift_to_interior")
+    return (out[1], out[2], out[3], Int(out[4]))
+end
+# -> (is_success, scal_out8 = eps_used, regularised pivots, (min_margin, pos_margin, target) of s and of z); sreg = (enable, constant, proportional)
+function hip_step_default_start_dev!(handle::Ptr{Cvoid}, xzs_dev::Ptr{Float64}, sreg::Tuple{Bool,Float64,Float64},
+                                     ir::Tuple{Bool,Float64,Float64,Int64,Float64})
+    scal_out = zeros(Float64, 8)
+    rc = ccall((:hipkkt_step_default_start_dev, libhipkkt), Int32,
+               (Ptr{Cvoid}, Ptr{Float64}, Int32, Float64, Float64, Int32, Float64, Float64, Int64, Float64, Ptr{Float64}, Ptr{Int64}),
+               handle, xzs_dev, sreg[1], sreg[2], sreg[3], ir[1], ir[2], ir[3], ir[4], ir[5], scal_out, C_NULL)
+    return (hip_step_check(handle, rc, "hipkkt_step_default_start_dev"), scal_out)
+end

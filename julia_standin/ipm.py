@@ -402,6 +402,8 @@ class Solver:
             raise ValueError("Settings.device_step_psd needs device_step")
         if getattr(st, "device_scaling_psd", False) and not getattr(st, "device_step_psd", False):
             raise ValueError("Settings.device_scaling_psd needs device_step_psd")
+        if getattr(st, "device_default_start", False) and not getattr(st, "device_step", False):
+            raise ValueError("Settings.device_default_start needs device_step")
         self._device_step = bool(getattr(st, "device_step", False)) and hasattr(ks, "kktsolver_step_affine") and \
             bool(getattr(ks, "steps_on_device", False))
         if self._device_step and not self.cones.is_symmetric():
@@ -418,6 +420,10 @@ class Solver:
         # R / Rinv / lam / _hs_valid then keep what set_identity_scaling left for the default start: nothing in _solve_device_step reads
         # them after a scaling (hipkkt_psd_get_factors serves a caller who wants them)
         self._device_scaling_psd = self._device_step_psd and bool(getattr(ks, "scales_psd", False))
+        # the default start on the resident iterate as well (Settings.device_default_start, a plugin that offers it): symmetric sets only,
+        # a non-symmetric set keeps its host unit initialisation
+        self._device_default_start = self._device_step and bool(getattr(st, "device_default_start", False)) and \
+            self.cones.is_symmetric() and hasattr(ks, "kktsolver_default_start") and bool(getattr(ks, "default_start_on_device", False))
         self.barrier_searches = self.barrier_backtracks = 0      # _backtrack_step_to_barrier calls / candidates it rejected (last solve)
         self._needs_qb = self._needs_qb or (self._device_step and hasattr(ks, "set_problem_vectors"))
         if self._needs_qb:               # q, b resident in the plugin (N4 residuals, N2 reduced-system algebra)
@@ -684,7 +690,8 @@ class Solver:
         """The loop of _solve for Settings.device_step: [x | z | s] and the residual buffer live in device memory for the whole solve and
         the plugin does residuals, norms, scaling, both steps and the update there; tau, kappa, the termination test, sigma and the
         strategy checkpoints stay here, fed by scalars.  Zero / Nonnegative / SecondOrder cone sets (symmetric: PrimalDual scaling, no
-        backtracking); with Settings.device_step_psd also PSD triangle members, whose Cholesky / SVD run here per scaling.  The default start runs on the host as in _solve and is uploaded once; the iterate comes back once, at the end."""
+        backtracking); with Settings.device_step_psd also PSD triangle members, whose Cholesky / SVD run here per scaling.  The default start runs on the host as in _solve and is uploaded once; the iterate comes back once, at the end.
+        With Settings.device_default_start the plugin runs the default start on the resident iterate too: nothing is uploaded."""
         st, info, data, cones = self.settings, self.info, self.data, self.cones
         v, r = self.variables, self.residuals
         ks = self.kktsystem.kktsolver
@@ -698,13 +705,25 @@ class Solver:
         info.iterations = 0
         t_start = time.perf_counter()
         t0 = time.perf_counter()
-        self._default_start()
-        xzs, res, prev = ks.device_buffer(n + 2 * m), ks.device_buffer(3 * n + 2 * m), ks.device_buffer(n + 2 * m)
-        xzs.upload(np.concatenate([v.x, v.z, v.s]))
+        start_ok = True
+        if self._device_default_start:
+            # solver.jl:383-405 by the plugin: identity scaling, kkt_update!, kkt_solve_initial_point! and both shifts on the resident
+            # iterate; a failure ends the solve as a failed kkt_update! of the first iteration would
+            xzs, res, prev = ks.device_buffer(n + 2 * m), ks.device_buffer(3 * n + 2 * m), ks.device_buffer(n + 2 * m)
+            start_ok, _ = ks.kktsolver_default_start(xzs)
+            v.tau = v.kappa = 1.0
+        else:
+            self._default_start()
+            xzs, res, prev = ks.device_buffer(n + 2 * m), ks.device_buffer(3 * n + 2 * m), ks.device_buffer(n + 2 * m)
+            xzs.upload(np.concatenate([v.x, v.z, v.s]))
         prev_tau, prev_kappa = v.tau, v.kappa
         tm["default start"] = time.perf_counter() - t0
         t_loop = time.perf_counter()
-        while True:
+        if not start_ok:      # no iterate and no iteration: nothing that info_post_process! could take for an almost-solved point
+            info.status = NUMERICAL_ERROR
+            info.gap_abs = info.gap_rel = info.res_primal = info.res_dual = float("inf")
+            xzs.upload(np.zeros(n + 2 * m))      # (a failed start leaves the resident iterate unspecified)
+        while start_ok:
             r.dot_qx, r.dot_bz, r.dot_sz, r.dot_xPx, r.rtau = ks.residuals_update_dev(xzs, res, v.tau, v.kappa)
             mu = (r.dot_sz + v.tau * v.kappa) / (cones.degree + 1)
             info.mu, info.step_length, info.sigma, info.iterations = mu, alpha, sigma, it

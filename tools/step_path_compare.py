@@ -4,7 +4,9 @@ algebra between the device calls runs on the host, the iterate crosses PCIe seve
 added (the iterate stays in device memory, scalars cross).  Per path: one warm-up solve, then `--repeats` timed solves; the medians of
 wall time per iteration and of the stand-in's timers, the bytes the Python binding moved per iteration in each direction
 (clarabel.jl_amd/hipkkt.py TRAFFIC) and hipkkt_box_probe go into ONE JSON line on stdout.
-usage: step_path_compare.py [--cfgs 3,2a,exp_pow,genpow,psd] [--repeats 5] [--one-solve CFG [--third]]   (--one-solve: a single device_step solve, for a kernel trace)"""
+Symmetric configurations (3, 2a, psd) get one more path: the last one with device_default_start added (the default start on the
+device as well), so that default_start_ms and the bytes of a whole solve stand next to the same path without it in the same run.
+usage: step_path_compare.py [--cfgs 3,2a,exp_pow,genpow,psd] [--repeats 5] [--one-solve CFG [--third] [--start]]   (--one-solve: a single device_step solve, for a kernel trace)"""
 import argparse
 import json
 import os
@@ -32,6 +34,7 @@ STEP_EXTRA = {"exp_pow": dict(device_step_nonsymmetric=True),
               "genpow": dict(device_step_nonsymmetric=True, device_step_genpower=True),
               "psd": dict(device_step_psd=True)}      # what device_step needs on top, per configuration
 THIRD = {"psd": ("device_step_and_scaling", dict(device_scaling_psd=True))}      # a further path on top of device_step, where there is one
+START = ("3", "2a", "psd")      # symmetric cone sets: the last path once more with device_default_start
 
 
 def one_solve(prob, **flags):
@@ -44,7 +47,8 @@ def one_solve(prob, **flags):
     rec = dict(status=sol.status, iterations=sol.iterations, obj_val=sol.obj_val, device_step=bool(solver._device_step),
                ms_per_iteration=1e3 * tm["IP iteration"] / it,
                timers_ms_per_iteration={k: 1e3 * tm[k] / it for k in ("kkt update", "kkt solve", "scale cones")},
-               default_start_ms=1e3 * tm["default start"],
+               default_start_ms=1e3 * tm["default start"], device_default_start=bool(getattr(solver, "_device_default_start", False)),
+               h2d_bytes=hipkkt.TRAFFIC["h2d_bytes"], d2h_bytes=hipkkt.TRAFFIC["d2h_bytes"],
                h2d_bytes_per_iteration=hipkkt.TRAFFIC["h2d_bytes"] / it, d2h_bytes_per_iteration=hipkkt.TRAFFIC["d2h_bytes"] / it)
     return rec
 
@@ -65,10 +69,12 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--one-solve", default=None)
     ap.add_argument("--third", action="store_true", help="--one-solve with the configuration's third path (psd: device_scaling_psd)")
+    ap.add_argument("--start", action="store_true", help="--one-solve with device_default_start (symmetric configurations)")
     args = ap.parse_args()
     if args.one_solve:
         rec = one_solve(CONFIGS[args.one_solve][1](), device_step=True, **PARENT, **STEP_EXTRA.get(args.one_solve, {}),
-                        **(THIRD[args.one_solve][1] if args.third and args.one_solve in THIRD else {}))
+                        **(THIRD[args.one_solve][1] if args.third and args.one_solve in THIRD else {}),
+                        **(dict(device_default_start=True) if args.start and args.one_solve in START else {}))
         print(json.dumps({"cfg": args.one_solve, "device_step": rec}))
         return
     result = {"tool": "step_path_compare", "repeats": args.repeats, "configs": {}}
@@ -80,10 +86,13 @@ def main():
         todo = [("host_cone_algebra", PARENT), ("device_step", step)]
         if cfg in THIRD:
             todo.append((THIRD[cfg][0], dict(step, **THIRD[cfg][1])))
+        if cfg in START:
+            todo.append((todo[-1][0] + "_and_default_start", dict(todo[-1][1], device_default_start=True)))
         for label, flags in todo:
             one_solve(prob, **flags)                                   # warm-up: plan cache, graphs, code objects
             paths[label] = median_of([one_solve(prob, **flags) for _ in range(args.repeats)])
         assert paths["device_step"]["device_step"] and not paths["host_cone_algebra"]["device_step"]
+        assert all(r["device_default_start"] == label.endswith("_and_default_start") for label, r in paths.items())
         result["configs"][cfg] = dict(problem=name, **paths,
                                       speedup=paths["host_cone_algebra"]["ms_per_iteration"] / paths["device_step"]["ms_per_iteration"])
         if cfg in THIRD:
