@@ -35,12 +35,14 @@ $HIPCC $FLAGS -ffp-contract=off -c step_cone3.hip -o $OBJ/step_cone3.o & pids+=(
 $HIPCC $FLAGS -ffp-contract=off -c step_genpow.hip -o $OBJ/step_genpow.o & pids+=($!)
 # step_psd.hip: the same for the PSD triangle cones, one workgroup per cone, the smallest eigenvalue by Jacobi sweeps in LDS
 $HIPCC $FLAGS -ffp-contract=off -c step_psd.hip -o $OBJ/step_psd.o & pids+=($!)
+# step_psd_large.hip: the same arithmetic for PSD sides 65 .. 128, matrices in global memory, products as batched tile launches
+$HIPCC $FLAGS -ffp-contract=off -c step_psd_large.hip -o $OBJ/step_psd_large.o & pids+=($!)
 # scaling_psd.hip: the Cholesky / SVD of the PSD cones' Nesterov-Todd scaling, one workgroup per cone, rounded product by product
 $HIPCC $FLAGS -ffp-contract=off -c scaling_psd.hip -o $OBJ/scaling_psd.o & pids+=($!)
 # start.hip: the default start (identity scaling, margins, shift into the cones); shares the Jacobi sweeps of psd_cone.h with step_psd.hip
 $HIPCC $FLAGS -ffp-contract=off -c start.hip -o $OBJ/start.o & pids+=($!)
 for p in "${pids[@]}"; do wait $p; done
-COMMON="$OBJ/hipkkt_solve.o $OBJ/hipkkt_cones.o $OBJ/hipkkt_step.o $OBJ/symbolic.o $OBJ/solve_schedule.o $OBJ/ordering.o $OBJ/assemble.o $OBJ/assemble_dev.o $OBJ/scaling.o $OBJ/step.o $OBJ/step_cone3.o $OBJ/step_genpow.o $OBJ/step_psd.o $OBJ/scaling_psd.o $OBJ/start.o $OBJ/front_block2.o $OBJ/front_sweep.o $OBJ/probe.o $OBJ/kernels.o $OBJ/values.o $OBJ/solve_sweep.o $OBJ/refine.o"
+COMMON="$OBJ/hipkkt_solve.o $OBJ/hipkkt_cones.o $OBJ/hipkkt_step.o $OBJ/symbolic.o $OBJ/solve_schedule.o $OBJ/ordering.o $OBJ/assemble.o $OBJ/assemble_dev.o $OBJ/scaling.o $OBJ/step.o $OBJ/step_cone3.o $OBJ/step_genpow.o $OBJ/step_psd.o $OBJ/step_psd_large.o $OBJ/scaling_psd.o $OBJ/start.o $OBJ/front_block2.o $OBJ/front_sweep.o $OBJ/probe.o $OBJ/kernels.o $OBJ/values.o $OBJ/solve_sweep.o $OBJ/refine.o"
 $HIPCC --offload-arch=gfx950 -shared -fPIC -o ../libclarabel_hipkkt.so $OBJ/hipkkt_abi.o $OBJ/hipkkt_setup.o $OBJ/hipkkt_factor.o $COMMON
 $HIPCC --offload-arch=gfx950 -shared -fPIC -o ../libclarabel_hipkkt_testing.so $OBJT/hipkkt_abi.o $OBJT/hipkkt_setup.o $OBJT/hipkkt_factor.o $OBJT/front_block.o $COMMON
 echo "built $(readlink -f ../libclarabel_hipkkt.so) and $(readlink -f ../libclarabel_hipkkt_testing.so)"

@@ -614,6 +614,18 @@ int32_t hipkkt_debug_dump(hipkkt_handle h, int32_t what, double *out, int64_t ca
             host(S->cones.reg.npow, [&](int64_t i) { return v[i]; });
             break;
         }
+        case 24: {   // the PSD cones step_psd_large.hip serves (hipkkt_step_enable_psd_large): indices into the PSD cones, from the device list
+            const int nl = S->cones.step.mode == StepMode::Psd ? S->cones.step.psd_nlarge : 0;
+            std::vector<int> v((size_t)std::max(nl, 1), 0);
+            if (nl) copy_sync(S->stream, v.data(), S->cones.tab.psd_lidx, (size_t)nl * sizeof(int), hipMemcpyDeviceToHost);
+            host(nl, [&](int64_t i) { return v[i]; });
+            break;
+        }
+        case 25: {   // the workspace of step_psd_large.hip as the last operation left it: kPsdLargeMats matrices per served cone (kernels.h)
+            const int nl = S->cones.step.mode == StepMode::Psd ? S->cones.step.psd_nlarge : 0;
+            if (nl) dev(S->cones.tab.psd_ws, psd_large_ws_doubles(nl)); else host(0, [](int64_t) { return 0.0; });
+            break;
+        }
         case 7: dev(S->soc.d_u, S->soc.total); break;
         case 8: dev(S->soc.d_v, S->soc.total); break;
         case 10: host(P.nsuper + 1, [&](int64_t i) { return P.sn_first[i]; }); break;
@@ -730,6 +742,11 @@ int32_t hipkkt_debug_set(const char *key, const char *value) {
         if (!value) o.accurate = def.accurate;
         else if (!num(&v)) return HIPKKT_ERR_ARGUMENT;
         else o.accurate = v == 0.0 ? 1e300 : v;
+    } else if (k == "PSD_LARGE_MIN") {
+        // the bit-identity test of step_psd_large.hip sends small cones through it; 0 = the default, as unset
+        if (!value) o.psd_large_min = def.psd_large_min;
+        else if (!num(&v) || v < 0 || v > 128 || v != (double)(int)v) return HIPKKT_ERR_ARGUMENT;
+        else o.psd_large_min = v == 0.0 ? def.psd_large_min : (int)v;
     } else if (k == "FB_EXTRA_PW") {
         o.fb_extra_pw = def.fb_extra_pw; o.fb_pen1 = def.fb_pen1; o.fb_pen2 = def.fb_pen2;
         if (value) {

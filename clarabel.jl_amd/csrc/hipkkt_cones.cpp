@@ -38,6 +38,7 @@ static int32_t set_cone_types_impl(hipkkt_handle h, int64_t ncones, const int32_
     C.step.psd_fresh = false;
     C.step.psd_scaling = false;
     C.step.psd_resident = false;
+    C.step.psd_nlarge = 0;
     C.reg.cls = cone_class(ncones, kinds, ex);      // what the enables of hipkkt_step.cpp may switch on: per registration
     C.step.mode = C.reg.cls == ConeClass::Symmetric ? StepMode::Symmetric : StepMode::Off;
     // the non-symmetric cones: three-row cones in two lists (joined [Exponential | Power] below), GenPower descriptors (cone_layout.h)

@@ -1,5 +1,5 @@
 // The cone state of a handle: what hipkkt_set_cone_types[_ex] registered, the device tables of the scaling kernels (scaling.hip) and
-// what the step entry points keep resident (hipkkt_step.cpp; step.hip, step_cone3.hip, step_genpow.hip, step_psd.hip).
+// what the step entry points keep resident (hipkkt_step.cpp; step.hip, step_cone3.hip, step_genpow.hip, step_psd.hip, step_psd_large.hip).
 // Written by hipkkt_cones.cpp (registration, scaling) and hipkkt_step.cpp (enables, step); record layouts: cone_layout.h.
 #pragma once
 #include <cstdint>
@@ -15,7 +15,7 @@ namespace hipkkt_host {
 enum class ConeClass { Other, Symmetric, Cone3, GenPow, Psd };
 
 // Which cones the step entry points serve.  A registration sets Symmetric for the class Symmetric and Off otherwise; the enables
-// hipkkt_step_enable_cone3 / _genpow / _psd move a handle of their class to Cone3 / GenPow / Psd and back to Off.
+// hipkkt_step_enable_cone3 / _genpow / _psd / _psd_large move a handle of their class to Cone3 / GenPow / Psd and back to Off.
 enum class StepMode { Off, Symmetric, Cone3, GenPow, Psd };
 
 struct ConeState {
@@ -52,6 +52,10 @@ struct ConeState {
         double *psd_rinv = nullptr, *psd_lam = nullptr, *psd_stage = nullptr;
         int *psd_bad = nullptr;                            // per PSD cone: its device-side scaling failed (scaling_psd.hip)
         int64_t *psd_hs0 = nullptr;                        // per PSD cone: its first Hs entry (start.hip)
+        // hipkkt_step_enable_psd_large: the indices into psdtab of the cones step_psd_large.hip serves, their matrix workspace
+        int64_t cap_psd_large = 0;
+        int *psd_lidx = nullptr;
+        double *psd_ws = nullptr;
     } tab;
     // what the step entry points work on between the calls
     struct Step {
@@ -61,6 +65,7 @@ struct ConeState {
         bool psd_fresh = false;                            // factors staged since the last scaling
         bool psd_scaling = false;                          // hipkkt_psd_scaling_enable: a scaling without psd_R computes the factors
         bool psd_resident = false;                         // a scaling since the enable left (R, Rinv, lambda) resident (hipkkt_psd_get_factors)
+        int psd_nlarge = 0, psd_lmin = 65, psd_lmax = 0;   // hipkkt_step_enable_psd_large: cones of side psd_lmin .. psd_lmax go to step_psd_large.hip
         double ls_step = 0.0, ls_amin = 0.0;               // linesearch_backtrack_step, min_terminate_step_length (Cone3 / GenPow)
         int ls_trips = 0;                                  // bound of the backtracking loop: ceil(log amin / log step) + 2
         double mu = 0.0;                                   // mu of the last hipkkt_update_scaling_ex[_dev] (mul_Hs of the GenPower cones)

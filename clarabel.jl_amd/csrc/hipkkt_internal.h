@@ -101,6 +101,7 @@ struct DebugOpts {
     double accurate = 64.0;        // ACCURATE=<tau>: 0 = never, negative = every wide block
     int fb_extra_pw = 1;           // FB_EXTRA_PW=<tiles per wavefront>,<penalty 1>,<penalty 2>
     double fb_pen1 = 10.0, fb_pen2 = 28.0;
+    int psd_large_min = 65;        // PSD_LARGE_MIN=<n>: the smallest PSD side hipkkt_step_enable_psd_large routes to step_psd_large.hip (0 = 65; read at the enable)
 };
 DebugOpts &debug_opts();
 bool verbose();                    // HIPKKT_VERBOSE in the environment: diagnostic lines on stderr (changes no result)

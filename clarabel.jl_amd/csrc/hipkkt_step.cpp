@@ -4,7 +4,8 @@
 // After hipkkt_step_enable_cone3 also the Exponential / Power cones of the registration (step_cone3.hip), on the (s, z) and the
 // [Hs | H_dual | grad] that hipkkt_update_scaling_ex[_dev] left resident; then hipkkt_cone_barrier / hipkkt_step_barrier_dev as well.
 // After hipkkt_step_enable_genpow the Generalized Power cones too (step_genpow.hip), on their slot [grad | d1 | d2 | p | q | r].
-// After hipkkt_step_enable_psd the PSD triangle cones of a symmetric registration (step_psd.hip), on the caller's (R, Rinv, lambda).
+// After hipkkt_step_enable_psd the PSD triangle cones of a symmetric registration (step_psd.hip), on the caller's (R, Rinv, lambda);
+// after hipkkt_step_enable_psd_large those of side 65 .. 128 as well (step_psd_large.hip).
 // The default start of a symmetric cone set (start.hip): hipkkt_cone_set_identity_scaling / _margins / _shift_to_interior and the fused
 // hipkkt_step_default_start_dev, which need no scaling.
 #include "hipkkt_internal.h"
@@ -19,7 +20,7 @@ static bool step_ready(hipkkt_solver *S, const char *who) {
     if (!S->l1 || !C.reg.ready || C.step.mode == StepMode::Off) {
         S->err = std::string(who) + ": needs an L1 handle whose registered cones are Zero / Nonnegative / SecondOrder only, or one with "
                                     "Exponential / Power cones next to them after hipkkt_step_enable_cone3, or with Generalized Power cones "
-                                    "after hipkkt_step_enable_genpow, or with PSD triangle cones after hipkkt_step_enable_psd";
+                                    "after hipkkt_step_enable_genpow, or with PSD triangle cones after hipkkt_step_enable_psd[_large]";
         return false;
     }
     if (!C.step.scaled) { S->err = std::string(who) + ": no successful hipkkt_update_scaling since the cones were registered"; return false; }
@@ -58,6 +59,7 @@ struct ConeTables {
     int npsd = 0;
     const int64_t *psdtab = nullptr;
     const double *psdR = nullptr, *psdRinv = nullptr, *psdlam = nullptr;
+    PsdLargeBatch large;      // ... and those of them step_psd_large.hip serves (hipkkt_step_enable_psd_large; none otherwise)
     // the backtracking line search of the non-symmetric cones decides the step length
     bool line_search() const { return mode == StepMode::Cone3 || mode == StepMode::GenPow; }
 };
@@ -81,36 +83,42 @@ static ConeTables tables(hipkkt_solver *S) {
             break;
         case StepMode::Psd:
             T.npsd = (int)C.reg.psd_n.size(); T.psdtab = C.tab.psdtab; T.psdR = C.tab.R; T.psdRinv = C.tab.psd_rinv; T.psdlam = C.tab.psd_lam;
+            if (C.step.psd_nlarge > 0) T.large = PsdLargeBatch{C.step.psd_nlarge, C.tab.psd_lidx, C.step.psd_lmin, C.step.psd_lmax, C.tab.psd_ws};
             break;
     }
     return T;
 }
 
 // every operation: the kernels of step.hip on the Zero / Nonnegative / SecondOrder rows (unchanged), then the Exponential / Power rows,
-// then the Generalized Power rows, then the PSD rows (a set has either non-symmetric or PSD members on this path)
+// then the Generalized Power rows, then the PSD rows (a set has either non-symmetric or PSD members on this path): step_psd.hip leaves a
+// cone of side > 64 alone, step_psd_large.hip computes it
 static void op_affine_ds(hipStream_t st, const ConeTables &T, double *out) {
     launch_step_affine_ds(st, T.kind, T.nsoc, T.desc, T.lam, out, T.m);
     launch_step3_copy(st, T.n3, T.row0, T.s, out);
     launch_genpow_copy(st, T.ngp, T.gpdesc, T.s, out);
     launch_psd_step_affine_ds(st, T.npsd, T.psdtab, T.psdlam, out);
+    launch_psd_large_affine_ds(st, T.large, T.psdtab, T.psdlam, out);
 }
 static void op_shift(hipStream_t st, const ConeTables &T, const double *dz, const double *ds, double sigma_mu, double *out) {
     launch_step_shift(st, T.kind, T.nsoc, T.desc, T.w, T.eta, dz, ds, sigma_mu, out, T.m);
     if (T.n3) launch_step3_shift(st, T.nexp, T.npow, T.row0, T.out0, T.alpha, T.nsout, T.z, dz, ds, sigma_mu, out);
     launch_genpow_shift(st, T.ngp, T.gpdesc, T.nsout, sigma_mu, out);
     launch_psd_step_shift(st, T.npsd, T.psdtab, T.psdR, T.psdRinv, dz, ds, sigma_mu, out);
+    launch_psd_large_shift(st, T.large, T.psdtab, T.psdR, T.psdRinv, T.psdlam, dz, ds, sigma_mu, out);
 }
 static void op_offset(hipStream_t st, const ConeTables &T, const double *ds, double *out) {
     launch_step_offset(st, T.kind, T.nsoc, T.desc, T.z, T.w, T.lam, T.eta, ds, out, T.m);
     launch_step3_copy(st, T.n3, T.row0, ds, out);
     launch_genpow_copy(st, T.ngp, T.gpdesc, ds, out);
     launch_psd_step_offset(st, T.npsd, T.psdtab, T.psdR, T.psdlam, ds, out);
+    launch_psd_large_offset(st, T.large, T.psdtab, T.psdR, T.psdlam, ds, out);
 }
 static void op_mulhs(hipStream_t st, const ConeTables &T, const double *x, const double *addc, double *y) {
     launch_step_mulhs(st, T.kind, T.nsoc, T.desc, T.w, T.eta, x, addc, y, T.m);
     launch_step3_mulhs(st, T.n3, T.row0, T.out0, T.nsout, x, addc, y);
     launch_genpow_mulhs(st, T.ngp, T.gpdesc, T.nsout, T.mu, x, addc, y);
     launch_psd_step_mulhs(st, T.npsd, T.psdtab, T.psdR, x, addc, y);
+    launch_psd_large_mulhs(st, T.large, T.psdtab, T.psdR, T.psdlam, x, addc, y);
 }
 // out2 = (alpha_z, alpha_s) of the symmetric cones; with Exponential / Power / Generalized Power cones the composite (alpha, alpha) of
 // coneops_compositecone.jl:216-252, started from min(alpha_tau, alpha_kappa, 1) when dtau (device) is given (variables.jl:14-43)
@@ -127,8 +135,11 @@ static void op_length(hipkkt_solver *S, hipStream_t st, const ConeTables &T, con
             // (2 (ceil(m / 256) + ncones) doubles: second-order and PSD cones together are at most ncones)
             double *sym2 = St.out + kStOutSymPsd;
             launch_step_length(st, T.kind, T.nsoc, T.desc, T.z, T.s, dz, ds, alpha_max, St.part, sym2, T.m);
-            launch_psd_step_length(st, T.npsd, T.psdtab, T.psdR, T.psdRinv, T.psdlam, dz, ds, alpha_max, sym2,
-                                   St.part + 2 * step_len_pairs(T.m, T.nsoc), out2);
+            // step_psd.hip parks alpha_max for a cone of side > 64; step_psd_large.hip overwrites it before the final minimum reads it
+            double *pairs = St.part + 2 * step_len_pairs(T.m, T.nsoc);
+            launch_psd_step_length_cones(st, T.npsd, T.psdtab, T.psdR, T.psdRinv, T.psdlam, dz, ds, alpha_max, pairs);
+            launch_psd_large_length(st, T.large, T.psdtab, T.psdR, T.psdRinv, T.psdlam, dz, ds, alpha_max, pairs);
+            launch_psd_step_length_final(st, T.npsd, sym2, pairs, out2);
             break;
         }
         case StepMode::Cone3:
@@ -316,18 +327,23 @@ int32_t hipkkt_step_enable_genpow(hipkkt_handle h, int32_t enable, double linese
     HK_LEAVE
 }
 
-int32_t hipkkt_step_enable_psd(hipkkt_handle h, int32_t enable) {
+// hipkkt_step_enable_psd (large = false: sides <= HIPKKT_PSD_STEP_MAX_DIM) and hipkkt_step_enable_psd_large (sides <=
+// HIPKKT_PSD_STEP_LARGE_MAX_DIM; cones of side >= lmin go to step_psd_large.hip, the others to step_psd.hip as after the first)
+static int32_t enable_psd_impl(hipkkt_handle h, int32_t enable, bool large) {
     HK_ENTER(h)
     ConeState &C = S->cones;
     if (!enable) {
-        if (C.step.mode == StepMode::Psd) { C.step.mode = StepMode::Off; C.step.psd_scaling = C.step.psd_resident = false; }
+        if (C.step.mode == StepMode::Psd) { C.step.mode = StepMode::Off; C.step.psd_scaling = C.step.psd_resident = false; C.step.psd_nlarge = 0; }
         return HIPKKT_OK;
     }
+    const int64_t max_side = large ? HIPKKT_PSD_STEP_LARGE_MAX_DIM : HIPKKT_PSD_STEP_MAX_DIM;
     bool ok = S->l1 && C.reg.ready && C.reg.cls == ConeClass::Psd;
-    for (size_t c = 0; ok && c < C.reg.psd_n.size(); c++) ok = C.reg.psd_n[c] <= HIPKKT_PSD_STEP_MAX_DIM;
+    for (size_t c = 0; ok && c < C.reg.psd_n.size(); c++) ok = C.reg.psd_n[c] <= max_side;
     if (!ok) {
-        S->err = "step_enable_psd: needs an L1 handle whose last hipkkt_set_cone_types[_ex] names Zero / Nonnegative / SecondOrder / PSD "
-                 "triangle cones only, at least one PSD cone, every PSD side <= HIPKKT_PSD_STEP_MAX_DIM";
+        S->err = std::string(large ? "step_enable_psd_large" : "step_enable_psd") +
+                 ": needs an L1 handle whose last hipkkt_set_cone_types[_ex] names Zero / Nonnegative / SecondOrder / PSD "
+                 "triangle cones only, at least one PSD cone, every PSD side <= " +
+                 (large ? "HIPKKT_PSD_STEP_LARGE_MAX_DIM" : "HIPKKT_PSD_STEP_MAX_DIM");
         return HIPKKT_ERR_ARGUMENT;
     }
     // the cone table and the factor buffers: allocated on the first call, re-used while large enough (as the d_sc_* buffers)
@@ -350,6 +366,19 @@ int32_t hipkkt_step_enable_psd(hipkkt_handle h, int32_t enable) {
     }
     copy_sync(S->stream, C.tab.psdtab, tab.data(), tab.size() * sizeof(int64_t), hipMemcpyHostToDevice);
     copy_sync(S->stream, C.tab.psd_hs0, C.reg.psd_hs.data(), (size_t)npsd * sizeof(int64_t), hipMemcpyHostToDevice);      // (the default start's identity scaling)
+    // the cones of step_psd_large.hip: their indices into the table and kPsdLargeMats n x n work matrices each
+    std::vector<int> lidx;
+    int lmax = 0;
+    const int lmin = debug_opts().psd_large_min;      // (65 for ever in the product: hipkkt_debug_set refuses there)
+    for (int64_t c = 0; large && c < npsd; c++)
+        if (C.reg.psd_n[c] >= lmin) { lidx.push_back((int)c); lmax = std::max(lmax, (int)C.reg.psd_n[c]); }
+    if ((int64_t)lidx.size() > C.tab.cap_psd_large) {
+        C.tab.psd_lidx = S->dalloc<int>(lidx.size());
+        C.tab.psd_ws = S->dalloc<double>((size_t)psd_large_ws_doubles((int)lidx.size()));
+        C.tab.cap_psd_large = (int64_t)lidx.size();
+    }
+    copy_sync(S->stream, C.tab.psd_lidx, lidx.data(), lidx.size() * sizeof(int), hipMemcpyHostToDevice);
+    C.step.psd_nlarge = (int)lidx.size(); C.step.psd_lmin = lmin; C.step.psd_lmax = lmax;
     C.step.mode = StepMode::Psd;
     C.step.psd_fresh = false;
     C.step.psd_scaling = C.step.psd_resident = false;
@@ -357,6 +386,16 @@ int32_t hipkkt_step_enable_psd(hipkkt_handle h, int32_t enable) {
     C.step.have_step = false;
     return HIPKKT_OK;
     HK_LEAVE
+}
+int32_t hipkkt_step_enable_psd(hipkkt_handle h, int32_t enable) { return enable_psd_impl(h, enable, false); }
+int32_t hipkkt_step_enable_psd_large(hipkkt_handle h, int32_t enable) { return enable_psd_impl(h, enable, true); }
+
+// a handle in PSD step mode whose registration holds a side above HIPKKT_PSD_STEP_MAX_DIM (hipkkt_step_enable_psd_large): the device
+// scaling (scaling_psd.hip) and the default start (start.hip) keep their matrices in LDS and would leave such a cone alone
+static bool psd_side_above_small(const ConeState &C) {
+    if (C.step.mode != StepMode::Psd) return false;
+    for (int64_t n : C.reg.psd_n) if (n > HIPKKT_PSD_STEP_MAX_DIM) return true;
+    return false;
 }
 
 static int32_t psd_set_factors_impl(hipkkt_handle h, const double *Rinv_all, const double *lambda_all, bool dev) {
@@ -387,6 +426,10 @@ int32_t hipkkt_psd_scaling_enable(hipkkt_handle h, int32_t enable) {
     ConeState &C = S->cones;
     if (C.step.mode != StepMode::Psd) {
         S->err = "psd_scaling_enable: needs hipkkt_step_enable_psd first";
+        return HIPKKT_ERR_ARGUMENT;
+    }
+    if (psd_side_above_small(C)) {
+        S->err = "psd_scaling_enable: a PSD side above HIPKKT_PSD_STEP_MAX_DIM keeps its Cholesky / SVD with the caller";
         return HIPKKT_ERR_ARGUMENT;
     }
     C.step.psd_scaling = enable != 0;
@@ -544,6 +587,10 @@ static bool start_ready(hipkkt_solver *S, const char *who) {
     if (!S->l1 || !C.reg.ready || (C.step.mode != StepMode::Symmetric && C.step.mode != StepMode::Psd)) {
         S->err = std::string(who) + ": needs an L1 handle whose registered cones are Zero / Nonnegative / SecondOrder only, or one with PSD "
                                     "triangle cones next to them after hipkkt_step_enable_psd";
+        return false;
+    }
+    if (psd_side_above_small(C)) {
+        S->err = std::string(who) + ": a PSD side above HIPKKT_PSD_STEP_MAX_DIM keeps the default start with the caller";
         return false;
     }
     return true;

@@ -162,6 +162,32 @@ void launch_psd_step_offset(hipStream_t st, int npsd, const int64_t *tab, const 
 void launch_psd_step_length(hipStream_t st, int npsd, const int64_t *tab, const double *R, const double *Rinv, const double *lam,
                             const double *dz, const double *ds, double alpha_max, const double *sym2, double *part, double *out2);
 void launch_psd_step_check(hipStream_t st, const double *lam, int64_t len, int *fail);
+// the two halves of launch_psd_step_length: the cones' pairs into `part` (a cone the kernels do not serve gets alpha_max), then out2
+// = the minimum.  step_psd_large.hip writes its cones' pairs between the two.
+void launch_psd_step_length_cones(hipStream_t st, int npsd, const int64_t *tab, const double *R, const double *Rinv, const double *lam,
+                                  const double *dz, const double *ds, double alpha_max, double *part);
+void launch_psd_step_length_final(hipStream_t st, int npsd, const double *sym2, const double *part, double *out2);
+// step_psd_large.hip: the same operations for the cones of that table with a side in lmin .. psd_step_large_max_dim() (after
+// hipkkt_step_enable_psd_large; lmin = 65 unless the testing switch PSD_LARGE_MIN says otherwise), matrices in global memory: products
+// as batched 16 x 16 tile launches, the Jacobi iteration of the step length with M alone in LDS.  Same arithmetic as step_psd.hip --
+// applied to a side <= 64 the same bits.  lidx = the nlarge cones' indices into tab, max_n = the largest of their sides, ws =
+// psd_large_ws_doubles(nlarge) doubles (kPsdLargeMats matrices of kPsdLargeMatDoubles per large cone).  launch_psd_large_length writes
+// its cones' pairs to part[2 c + (0 | 1)] and belongs between the two halves above.
+constexpr int kPsdLargeMaxN = 128;                                           // HIPKKT_PSD_STEP_LARGE_MAX_DIM
+constexpr int kPsdLargeMats = 4;
+constexpr int kPsdLargeMatDoubles = kPsdLargeMaxN * kPsdLargeMaxN;
+struct PsdLargeBatch { int nlarge = 0; const int *lidx = nullptr; int lmin = 65, max_n = 0; double *ws = nullptr; };
+int psd_step_large_max_dim();
+int64_t psd_large_ws_doubles(int nlarge);
+void launch_psd_large_affine_ds(hipStream_t st, const PsdLargeBatch &L, const int64_t *tab, const double *lam, double *out);
+void launch_psd_large_mulhs(hipStream_t st, const PsdLargeBatch &L, const int64_t *tab, const double *R, const double *lam, const double *x,
+                            const double *addc, double *y);
+void launch_psd_large_shift(hipStream_t st, const PsdLargeBatch &L, const int64_t *tab, const double *R, const double *Rinv,
+                            const double *lam, const double *dz, const double *ds, double sigma_mu, double *out);
+void launch_psd_large_offset(hipStream_t st, const PsdLargeBatch &L, const int64_t *tab, const double *R, const double *lam,
+                             const double *ds, double *out);
+void launch_psd_large_length(hipStream_t st, const PsdLargeBatch &L, const int64_t *tab, const double *R, const double *Rinv,
+                             const double *lam, const double *dz, const double *ds, double alpha_max, double *part);
 // scaling_psd.hip: update_scaling!(::PSDTriangleCone) for the cones of the same table, one workgroup per cone: Cholesky factors of
 // svec_to_mat of the cone's rows of (s, z), the SVD of L2' L1 by one-sided Jacobi sweeps, (R, Rinv, lam) in the layout above.  A cone
 // that fails sets *fail and bad[cone] (0 otherwise) and gets NaN factors.

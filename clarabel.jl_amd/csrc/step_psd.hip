@@ -249,9 +249,15 @@ void launch_psd_step_offset(hipStream_t st, int npsd, const int64_t *tab, const 
 }
 void launch_psd_step_length(hipStream_t st, int npsd, const int64_t *tab, const double *R, const double *Rinv, const double *lam,
                             const double *dz, const double *ds, double alpha_max, const double *sym2, double *part, double *out2) {
-    if (npsd <= 0) return;
-    hipLaunchKernelGGL(k_psd_len, dim3(npsd, 2), dim3(256), 0, st, tab, R, Rinv, lam, dz, ds, alpha_max, part);
-    hipLaunchKernelGGL(k_psd_len_final, dim3(1), dim3(256), 0, st, part, npsd, sym2, out2);
+    launch_psd_step_length_cones(st, npsd, tab, R, Rinv, lam, dz, ds, alpha_max, part);
+    launch_psd_step_length_final(st, npsd, sym2, part, out2);
+}
+void launch_psd_step_length_cones(hipStream_t st, int npsd, const int64_t *tab, const double *R, const double *Rinv, const double *lam,
+                                  const double *dz, const double *ds, double alpha_max, double *part) {
+    if (npsd > 0) hipLaunchKernelGGL(k_psd_len, dim3(npsd, 2), dim3(256), 0, st, tab, R, Rinv, lam, dz, ds, alpha_max, part);
+}
+void launch_psd_step_length_final(hipStream_t st, int npsd, const double *sym2, const double *part, double *out2) {
+    if (npsd > 0) hipLaunchKernelGGL(k_psd_len_final, dim3(1), dim3(256), 0, st, part, npsd, sym2, out2);
 }
 void launch_psd_step_check(hipStream_t st, const double *lam, int64_t len, int *fail) {
     if (len > 0) hipLaunchKernelGGL(k_psd_check_lambda, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, st, lam, len, fail);

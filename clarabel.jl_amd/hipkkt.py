@@ -20,7 +20,7 @@ LIB_PATH = os.environ.get("CLARABEL_HIPKKT_LIB", os.path.join(_HERE, "libclarabe
 # refuses to create a handle on the production library while one of them is set.
 DEBUG_KEYS = ["PLAN_CACHE", "FB_EXTRA", "FB_STREAM", "FB_V2", "FORCE_TWIN", "NO_GRAPH", "NO_PERSIST", "FULL_TILES", "FRONT_BLOCK", "SPLIT_K",
               "DENSE_TRI", "ORDERING", "NO_FRONT", "HOST_ASSEMBLY", "FRONT_BLOCK_MIN_ROWS", "SUPERHOP", "DEBUG_FLAGS", "SPIN_LIMIT",
-              "PERSIST_RETRY", "ACCURATE", "FB_EXTRA_PW", "GATHER_OVERLAP", "GATHER_SIDE_BLOCKS", "GATHER_SORT"]
+              "PERSIST_RETRY", "ACCURATE", "FB_EXTRA_PW", "GATHER_OVERLAP", "GATHER_SIDE_BLOCKS", "GATHER_SORT", "PSD_LARGE_MIN"]
 
 _i64p = np.ctypeslib.ndpointer(dtype=np.int64, flags="C_CONTIGUOUS")
 _i32p = np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")
@@ -50,9 +50,12 @@ SYMBOLS = [
     "hipkkt_psd_scaling_enable", "hipkkt_psd_get_factors",
     # the default start of a symmetric cone set on the device (opt-in, added within ABI version 5)
     "hipkkt_cone_set_identity_scaling", "hipkkt_cone_margins", "hipkkt_cone_shift_to_interior", "hipkkt_step_default_start_dev",
+    # the PSD step for sides 65 .. 128 (opt-in, added within ABI version 5)
+    "hipkkt_step_enable_psd_large",
 ]
 
 PSD_STEP_MAX_DIM = 64      # include/hipkkt.h HIPKKT_PSD_STEP_MAX_DIM
+PSD_STEP_LARGE_MAX_DIM = 128      # include/hipkkt.h HIPKKT_PSD_STEP_LARGE_MAX_DIM
 
 
 # doubles the calls below move across PCIe, counted from their argument sizes (tools/step_path_compare.py reads and resets them)
@@ -162,6 +165,7 @@ def lib():
     L.hipkkt_step_enable_cone3.argtypes = [vp, i32, f64, f64]
     L.hipkkt_step_enable_genpow.argtypes = [vp, i32, f64, f64]
     L.hipkkt_step_enable_psd.argtypes = [vp, i32]
+    L.hipkkt_step_enable_psd_large.argtypes = [vp, i32]
     L.hipkkt_psd_set_factors.argtypes = [vp, _f64p, _f64p]
     L.hipkkt_psd_set_factors_dev.argtypes = [vp, vp, vp]
     L.hipkkt_psd_scaling_enable.argtypes = [vp, i32]
@@ -747,6 +751,11 @@ class Handle:
         """the same for a symmetric registration with PSD triangle cones: ValueError unless it names kinds {0, 1, 2, 3} only with a 3
         and every PSD side is at most PSD_STEP_MAX_DIM.  The step then works on the factors of psd_set_factors + update_scaling(psd_R)"""
         self._chk_step(self.L.hipkkt_step_enable_psd(self.h, int(bool(enable))), "step_enable_psd")
+
+    def step_enable_psd_large(self, enable):
+        """step_enable_psd with the side limit PSD_STEP_LARGE_MAX_DIM: cones of side 65 .. 128 are served too, by kernels that keep their
+        matrices in device memory (same arithmetic).  ValueError when the registration does not qualify; the handle stays as it was"""
+        self._chk_step(self.L.hipkkt_step_enable_psd_large(self.h, int(bool(enable))), "step_enable_psd_large")
 
     def psd_set_factors(self, rinv, lam, dev=False):
         """stages the PSD cones' Rinv (n x n column-major each, concatenated like psd_R) and lambda (n each) for the next update_scaling;

@@ -18,14 +18,16 @@ from .settings import Settings
 _DEBUG = os.environ.get("HIPKKT_DEBUG", "0") == "1"
 
 
-def cone_set_steps_on_device(cones, nonsymmetric=False, genpower=False, psd=False) -> bool:
+def cone_set_steps_on_device(cones, nonsymmetric=False, genpower=False, psd=False, psd_large=False) -> bool:
     """the step entry points (hipkkt_cone_* / hipkkt_step_*) serve cone sets of ZeroCone, NonnegativeCone and SecondOrderCone only: a PSD
     cone's step length needs eigenvalue decompositions, the non-symmetric cones need backtracking and barriers.
     nonsymmetric=True: ExponentialCone and PowerCone members qualify as well (hipkkt_step_enable_cone3); Generalized Power and PSD
     members still do not.
     genpower=True (with nonsymmetric=True): Generalized Power members qualify too (hipkkt_step_enable_genpow); PSD members do not.
     psd=True: PSD triangle members qualify when every side is at most hipkkt.PSD_STEP_MAX_DIM and the set has no Exponential / Power /
-    Generalized Power member (hipkkt_step_enable_psd)"""
+    Generalized Power member (hipkkt_step_enable_psd).
+    psd_large=True (with psd=True): the side limit is hipkkt.PSD_STEP_LARGE_MAX_DIM (hipkkt_step_enable_psd_large); alone it widens
+    nothing"""
     if not hasattr(cones, "kkt_cone_kinds"):
         return False
     kinds = cones.kkt_cone_kinds_ex()[0] if hasattr(cones, "kkt_cone_kinds_ex") else cones.kkt_cone_kinds()
@@ -38,7 +40,7 @@ def cone_set_steps_on_device(cones, nonsymmetric=False, genpower=False, psd=Fals
     if psd and bool(np.any(kinds == 3)) and not bool(np.any(kinds >= 4)):
         numel = np.asarray(cones.kkt_descriptors()[0])[kinds == 3]
         sides = ((np.sqrt(8.0 * numel + 1.0) - 1.0) / 2.0 + 0.5).astype(np.int64)
-        if bool(np.all(sides <= hipkkt.PSD_STEP_MAX_DIM)):
+        if bool(np.all(sides <= (hipkkt.PSD_STEP_LARGE_MAX_DIM if psd_large else hipkkt.PSD_STEP_MAX_DIM))):
             ok = ok | (kinds == 3)
     return kinds.size > 0 and bool(np.all(ok))
 
@@ -100,11 +102,18 @@ class HipKKTSolver:
             self._steps_on_device = self.steps_nonsymmetric = True
         # ... and, opted in by Settings.device_step_psd, symmetric sets with PSD triangle members: the Cholesky / SVD of their scaling stay
         # with the caller, whose (R, Rinv, lambda) go to the device with every scaling (hipkkt_step_enable_psd)
-        self.steps_psd = False
-        if not self._steps_on_device and getattr(settings, "device_step_psd", False) and self._has_cone_kinds \
-                and not self.scales_nonsymmetric and cone_set_steps_on_device(cones, psd=True):
+        # With Settings.device_step_psd_large on top, a set with a side of 65 .. 128 qualifies too (hipkkt_step_enable_psd_large); its
+        # Cholesky / SVD and its default start stay with the caller whatever device_scaling_psd / device_default_start say
+        self.steps_psd = self.steps_psd_large = False
+        psd_ok = not self._steps_on_device and getattr(settings, "device_step_psd", False) and self._has_cone_kinds \
+            and not self.scales_nonsymmetric
+        if psd_ok and cone_set_steps_on_device(cones, psd=True):
             self.h.step_enable_psd(True)
             self._steps_on_device = self.steps_psd = True
+        elif psd_ok and getattr(settings, "device_step_psd_large", False) and cone_set_steps_on_device(cones, psd=True, psd_large=True):
+            self.h.step_enable_psd_large(True)
+            self._steps_on_device = self.steps_psd = self.steps_psd_large = True
+        if self.steps_psd:
             rows = [r for c, r in zip(cones.cones, cones.rng_cones) if hasattr(c, "RRt")]
             self._psd_rows = rows
             self._psd_span = (rows[0].start, rows[-1].stop)
@@ -113,7 +122,7 @@ class HipKKTSolver:
         # ... whose Cholesky / SVD the device does as well when Settings.device_scaling_psd is set (hipkkt_psd_scaling_enable): the
         # scaling call then takes nothing but the resident (s, z)
         self.scales_psd = False
-        if self.steps_psd and getattr(settings, "device_scaling_psd", False):
+        if self.steps_psd and not self.steps_psd_large and getattr(settings, "device_scaling_psd", False):
             self.h.psd_scaling_enable(True)
             self.scales_psd = True
         self.scaling_nonsym = None
@@ -364,7 +373,7 @@ class HipKKTSolver:
     @property
     def default_start_on_device(self) -> bool:
         """the default start of the cone set (solver.jl:383-405) can run on the resident iterate: kktsolver_default_start"""
-        return self._steps_on_device and not self.steps_nonsymmetric
+        return self._steps_on_device and not self.steps_nonsymmetric and not self.steps_psd_large
 
     def kktsolver_default_start(self, xzs):
         """set_identity_scaling! + kkt_update! + kkt_solve_initial_point! + variables_symmetric_initialization! into the resident

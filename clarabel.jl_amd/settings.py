@@ -81,4 +81,9 @@ class Settings:
     # sets the device step serves: no Hs upload, no host eigenvalues, no upload of the start.  Non-symmetric sets keep their host unit
     # initialisation.  Needs device_step: the caller raises ValueError otherwise.
     device_default_start: bool = False
+    # device_step_psd for PSD triangle cones of side 65 .. 128 as well (hipkkt_step_enable_psd_large: the same arithmetic with the
+    # matrices in device memory, products as batched tile launches).  For a set with such a side the Cholesky / SVD of the scaling and
+    # the default start stay on the host, whatever device_scaling_psd / device_default_start say; sides above 128 keep the host loop.
+    # Needs device_step_psd: the caller raises ValueError otherwise.
+    device_step_psd_large: bool = False
     extra: dict = field(default_factory=dict)

@@ -76,7 +76,8 @@ int32_t hipkkt_is_available(void);
  *    hipkkt_step_enable_cone3 / hipkkt_cone_barrier / hipkkt_step_barrier_dev; hipkkt_step_enable_genpow;
  *    HIPKKT_PSD_STEP_MAX_DIM / hipkkt_step_enable_psd / hipkkt_psd_set_factors / hipkkt_psd_set_factors_dev;
  *    hipkkt_psd_scaling_enable / hipkkt_psd_get_factors;
- *    hipkkt_cone_set_identity_scaling / hipkkt_cone_margins / hipkkt_cone_shift_to_interior / hipkkt_step_default_start_dev. */
+ *    hipkkt_cone_set_identity_scaling / hipkkt_cone_margins / hipkkt_cone_shift_to_interior / hipkkt_step_default_start_dev;
+ *    HIPKKT_PSD_STEP_LARGE_MAX_DIM / hipkkt_step_enable_psd_large. */
 #define HIPKKT_ABI_VERSION 5
 int32_t hipkkt_abi_version(void);
 /* releases the process-wide cache of device memory blocks the library keeps between handles (not in the reference: an embedding
@@ -379,6 +380,23 @@ int32_t hipkkt_residuals_dev(hipkkt_handle h, const double *xzs_dev, double tau,
  * the host's BLAS, so results agree to rounding, not bit for bit).  Rows of kinds 0..2 go through the same kernels as without the
  * enable, bit for bit.  Kinds 4..6 next to a PSD cone stay refused.
  *
+ * Opt-in for PSDTriangleCone of side 65 .. HIPKKT_PSD_STEP_LARGE_MAX_DIM: hipkkt_step_enable_psd_large accepts what hipkkt_step_enable_psd
+ * accepts with every PSD side <= HIPKKT_PSD_STEP_LARGE_MAX_DIM, and the same calls then serve all rows of the handle from the same
+ * (R, Rinv, lambda) protocol.  A cone of side <= HIPKKT_PSD_STEP_MAX_DIM is computed by the kernels of the paragraph above, bit for
+ * bit as after hipkkt_step_enable_psd.  A larger cone is computed with the same arithmetic in another placement: its matrices stay in
+ * device memory (a workspace of four n x n matrices per such cone, allocated at the enable), every product is a batch of 16 x 16
+ * output tiles over all such cones (and over z / s where an operation has both) whose operands -- a factor, its transpose,
+ * svec_to_mat of the rows, the mat_to_svec / svec_to_mat round trip of an intermediate result -- are read from device memory through
+ * LDS panels, and the Jacobi iteration runs with one workgroup per cone and side, M alone in LDS (128 x 129 doubles at side 128).
+ * Every entry of every product is still one fused multiply-add chain over k in ascending order, the elementwise expressions, the pair
+ * schedule, the rotation formulas, the sums of the stop rule and the bound of 30 sweeps are those of the smaller cones: the same
+ * input gives the same bits whichever kernels compute a cone.  An operation is a few launches on the handle's stream instead of one;
+ * the fused calls keep their single host synchronisation.  The Cholesky / SVD and the default start of such a handle stay with the
+ * caller: while the registration holds a side above HIPKKT_PSD_STEP_MAX_DIM, hipkkt_psd_scaling_enable, hipkkt_cone_set_identity_scaling,
+ * hipkkt_cone_margins, hipkkt_cone_shift_to_interior and hipkkt_step_default_start_dev return HIPKKT_ERR_ARGUMENT (their kernels
+ * keep whole matrices in LDS); with every side <= HIPKKT_PSD_STEP_MAX_DIM they behave as after hipkkt_step_enable_psd.  Sides above
+ * HIPKKT_PSD_STEP_LARGE_MAX_DIM keep the host loop.
+ *
  * One operation each, host vectors of length m in cone order (the unit-tested surface):
  *   hipkkt_cone_affine_ds            ds = lambda o lambda                  coneops_nncone.jl affine_ds!, coneops_socone.jl:219-228
  *   hipkkt_cone_combined_ds_shift    shift = W^-1 step_s o W step_z - sigma mu e   coneops_symmetric_common.jl:1-36, coneops_socone.jl:300-347
@@ -406,6 +424,14 @@ int32_t hipkkt_step_enable_genpow(hipkkt_handle h, int32_t enable, double linese
  * PSD side <= HIPKKT_PSD_STEP_MAX_DIM.  Enabling invalidates the resident scaling, as hipkkt_step_enable_cone3 does.  enable == 0
  * switches it off.  Every hipkkt_set_cone_types[_ex] clears it. */
 int32_t hipkkt_step_enable_psd(hipkkt_handle h, int32_t enable);
+/* The largest PSD side hipkkt_step_enable_psd_large serves: the matrix of the step length's Jacobi iteration (128 x 129 doubles, 129 KiB)
+ * is the one thing that must fit one workgroup's LDS. */
+#define HIPKKT_PSD_STEP_LARGE_MAX_DIM 128
+/* hipkkt_step_enable_psd with the side limit HIPKKT_PSD_STEP_LARGE_MAX_DIM: enable != 0 returns HIPKKT_ERR_ARGUMENT and leaves the handle
+ * as it was unless the last hipkkt_set_cone_types[_ex] names kinds {0, 1, 2, 3} only with at least one 3 and every PSD side <=
+ * HIPKKT_PSD_STEP_LARGE_MAX_DIM.  Enabling invalidates the resident scaling and allocates the larger cones' workspace.  enable == 0
+ * does what hipkkt_step_enable_psd(h, 0) does.  Every hipkkt_set_cone_types[_ex] clears it. */
+int32_t hipkkt_step_enable_psd_large(hipkkt_handle h, int32_t enable);
 /* The factors of the PSD cones' scaling for the step (HIPKKT_ERR_ARGUMENT before hipkkt_step_enable_psd): Rinv_all = the cones' Rinv, each
  * n x n column-major, concatenated like psd_R; lambda_all = the cones' lambda, n each, concatenated.  They are staged and consumed by
  * the next hipkkt_update_scaling[_ex][_dev]; on an enabled handle that call needs a non-NULL psd_R and factors staged since the last
@@ -478,7 +504,7 @@ int32_t hipkkt_step_apply_dev(hipkkt_handle h, double alpha, double *xzs_dev);
 int32_t hipkkt_step_info_norms_dev(hipkkt_handle h, const double *xzs_dev, const double *res_dev, double *out8);
 int32_t hipkkt_step_get(hipkkt_handle h, double *out);
 /* The default start of a symmetric cone set (solver.jl:383-405) on the device.  Served: L1 handles whose registration is Zero /
- * Nonnegative / SecondOrder only, or holds PSD triangle cones next to them after hipkkt_step_enable_psd (every side <=
+ * Nonnegative / SecondOrder only, or holds PSD triangle cones next to them after hipkkt_step_enable_psd[_large] (every side <=
  * HIPKKT_PSD_STEP_MAX_DIM); anything else (a kind 4..6, PSD without the enable, an L0 handle) is HIPKKT_ERR_ARGUMENT.  No scaling is
  * needed.  pd: 0 = primal cone, 1 = dual cone.
  *   hipkkt_cone_set_identity_scaling  set_identity_scaling! (coneops_compositecone.jl:92-101) + get_Hs! (:123-131) + the Hs / sparse-cone
@@ -560,7 +586,9 @@ int32_t hipkkt_get_counters(hipkkt_handle h, int64_t *out, int64_t cap);
  * slots -- tools/dense_stage_stats.py; 22 four values per front, written on the host: its first panel (supernode id), panels, rows,
  * and the panels per super-block of its solve sweeps, 0 = one hop per panel through that panel's inverse (k_front_fwd / k_front_bwd),
  * > 0 = products with the super-blocks' inverses (k_front_fwd_sb / k_front_bwd_sb), 23 the Newton steps of the last hipkkt_update_scaling_ex per
- * Power cone in cone order); *len receives the length, nothing is copied
+ * Power cone in cone order, 24 the PSD cones step_psd_large.hip serves on this handle, as indices into the registration's PSD cones,
+ * read back from the device list -- empty unless hipkkt_step_enable_psd_large is in place, 25 the work matrices of those cones as the
+ * last step operation left them, four of 128 x 128 doubles per served cone, each n x n column-major from its start); *len receives the length, nothing is copied
  * when cap is too small */
 int32_t hipkkt_debug_dump(hipkkt_handle h, int32_t what, double *out, int64_t cap, int64_t *len);
 /* developer diagnostic, host logic only (no device needed): how many of the `nd` dense tiles of a front batch's far stage -- the

@@ -137,6 +137,12 @@ function hip_step_enable_psd!(handle::Ptr{Cvoid}, enable::Bool)
     rc = ccall((:hipkkt_step_enable_psd, libhipkkt), Int32, (Ptr{Cvoid}, Int32), handle, enable ? 1 : 0)
     return hip_step_check(handle, rc, "hipkkt_step_enable_psd")
 end
+# the same with the side limit 128: cones of side 65 .. 128 keep their matrices in device memory (same arithmetic); the scaling's
+# Cholesky / SVD and the default start of such a set stay with the caller
+function hip_step_enable_psd_large!(handle::Ptr{Cvoid}, enable::Bool)
+    rc = ccall((:hipkkt_step_enable_psd_large, libhipkkt), Int32, (Ptr{Cvoid}, Int32), handle, enable ? 1 : 0)
+    return hip_step_check(handle, rc, "hipkkt_step_enable_psd_large")
+end
 # Rinv_all: the cones' Rinv (n x n column-major each, concatenated like psd_R), λ_all: their λ; consumed by the next hip update_scaling
 function hip_psd_set_factors!(handle::Ptr{Cvoid}, Rinv_all::Vector{Float64}, λ_all::Vector{Float64})
     rc = ccall((:hipkkt_psd_set_factors, libhipkkt), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), handle, Rinv_all, λ_all)

@@ -402,6 +402,8 @@ class Solver:
             raise ValueError("Settings.device_step_psd needs device_step")
         if getattr(st, "device_scaling_psd", False) and not getattr(st, "device_step_psd", False):
             raise ValueError("Settings.device_scaling_psd needs device_step_psd")
+        if getattr(st, "device_step_psd_large", False) and not getattr(st, "device_step_psd", False):
+            raise ValueError("Settings.device_step_psd_large needs device_step_psd")
         if getattr(st, "device_default_start", False) and not getattr(st, "device_step", False):
             raise ValueError("Settings.device_default_start needs device_step")
         self._device_step = bool(getattr(st, "device_step", False)) and hasattr(ks, "kktsolver_step_affine") and \

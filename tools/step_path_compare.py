@@ -6,7 +6,7 @@ wall time per iteration and of the stand-in's timers, the bytes the Python bindi
 (clarabel.jl_amd/hipkkt.py TRAFFIC) and hipkkt_box_probe go into ONE JSON line on stdout.
 Symmetric configurations (3, 2a, psd) get one more path: the last one with device_default_start added (the default start on the
 device as well), so that default_start_ms and the bytes of a whole solve stand next to the same path without it in the same run.
-usage: step_path_compare.py [--cfgs 3,2a,exp_pow,genpow,psd] [--repeats 5] [--one-solve CFG [--third] [--start]]   (--one-solve: a single device_step solve, for a kernel trace)"""
+usage: step_path_compare.py [--cfgs 3,2a,exp_pow,genpow,psd,psd_large] [--repeats 5] [--one-solve CFG [--third] [--start]]   (--one-solve: a single device_step solve, for a kernel trace)"""
 import argparse
 import json
 import os
@@ -28,11 +28,14 @@ CONFIGS = {"3": ("portfolio_socp", problems.portfolio_socp), "2a": ("random_spar
                       lambda: problems.nonsymmetric_mix(n=80, nexp=10, npow=10, ngenpow=20, nn=20, nzero=3, socdim=5, seed=5)),
            # PSD triangle cones (benchmark configuration 5 at its size, 20 x PSD(50)): device_step_psd on top, the Cholesky / SVD of the
            # scaling on the host; and a third path with device_scaling_psd, where the device does them too
-           "psd": ("sdp_blocks", problems.sdp_blocks)}
+           "psd": ("sdp_blocks", problems.sdp_blocks),
+           # two PSD triangle cones of side 96: without device_step_psd_large the whole set keeps the host loop
+           "psd_large": ("sdp_blocks_2x96", lambda: problems.sdp_blocks(n=200, ncones=2, dim=96, seed=5))}
 PARENT = dict(device_scaling=True, device_reduced=True, device_residuals=True)
 STEP_EXTRA = {"exp_pow": dict(device_step_nonsymmetric=True),
               "genpow": dict(device_step_nonsymmetric=True, device_step_genpower=True),
-              "psd": dict(device_step_psd=True)}      # what device_step needs on top, per configuration
+              "psd": dict(device_step_psd=True),
+              "psd_large": dict(device_step_psd=True, device_step_psd_large=True)}      # what device_step needs on top, per configuration
 THIRD = {"psd": ("device_step_and_scaling", dict(device_scaling_psd=True))}      # a further path on top of device_step, where there is one
 START = ("3", "2a", "psd")      # symmetric cone sets: the last path once more with device_default_start
 
