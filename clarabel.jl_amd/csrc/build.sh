@@ -41,8 +41,10 @@ $HIPCC $FLAGS -ffp-contract=off -c step_psd_large.hip -o $OBJ/step_psd_large.o &
 $HIPCC $FLAGS -ffp-contract=off -c scaling_psd.hip -o $OBJ/scaling_psd.o & pids+=($!)
 # start.hip: the default start (identity scaling, margins, shift into the cones); shares the Jacobi sweeps of psd_cone.h with step_psd.hip
 $HIPCC $FLAGS -ffp-contract=off -c start.hip -o $OBJ/start.o & pids+=($!)
+# barrier_psd.hip: the log-det barrier of the PSD cones of a set with non-symmetric members, one workgroup per (cone, candidate, side)
+$HIPCC $FLAGS -ffp-contract=off -c barrier_psd.hip -o $OBJ/barrier_psd.o & pids+=($!)
 for p in "${pids[@]}"; do wait $p; done
-COMMON="$OBJ/hipkkt_solve.o $OBJ/hipkkt_cones.o $OBJ/hipkkt_step.o $OBJ/symbolic.o $OBJ/solve_schedule.o $OBJ/ordering.o $OBJ/assemble.o $OBJ/assemble_dev.o $OBJ/scaling.o $OBJ/step.o $OBJ/step_cone3.o $OBJ/step_genpow.o $OBJ/step_psd.o $OBJ/step_psd_large.o $OBJ/scaling_psd.o $OBJ/start.o $OBJ/front_block2.o $OBJ/front_sweep.o $OBJ/probe.o $OBJ/kernels.o $OBJ/values.o $OBJ/solve_sweep.o $OBJ/refine.o"
+COMMON="$OBJ/hipkkt_solve.o $OBJ/hipkkt_cones.o $OBJ/hipkkt_step.o $OBJ/symbolic.o $OBJ/solve_schedule.o $OBJ/ordering.o $OBJ/assemble.o $OBJ/assemble_dev.o $OBJ/scaling.o $OBJ/step.o $OBJ/step_cone3.o $OBJ/step_genpow.o $OBJ/step_psd.o $OBJ/step_psd_large.o $OBJ/scaling_psd.o $OBJ/start.o $OBJ/barrier_psd.o $OBJ/front_block2.o $OBJ/front_sweep.o $OBJ/probe.o $OBJ/kernels.o $OBJ/values.o $OBJ/solve_sweep.o $OBJ/refine.o"
 $HIPCC --offload-arch=gfx950 -shared -fPIC -o ../libclarabel_hipkkt.so $OBJ/hipkkt_abi.o $OBJ/hipkkt_setup.o $OBJ/hipkkt_factor.o $COMMON
 $HIPCC --offload-arch=gfx950 -shared -fPIC -o ../libclarabel_hipkkt_testing.so $OBJT/hipkkt_abi.o $OBJT/hipkkt_setup.o $OBJT/hipkkt_factor.o $OBJT/front_block.o $COMMON
 echo "built $(readlink -f ../libclarabel_hipkkt.so) and $(readlink -f ../libclarabel_hipkkt_testing.so)"

@@ -15,7 +15,8 @@ static ConeClass cone_class(int64_t ncones, const int32_t *kinds, bool ex) {
         else return ConeClass::Other;
     }
     if (!any3 && !anygp) return anypsd ? ConeClass::Psd : ConeClass::Symmetric;
-    if (anypsd || !ex) return ConeClass::Other;
+    if (!ex) return ConeClass::Other;
+    if (anypsd) return ConeClass::Mixed;
     return anygp ? ConeClass::GenPow : ConeClass::Cone3;
 }
 
@@ -204,7 +205,7 @@ static int32_t update_scaling_impl(hipkkt_handle h, const double *s, const doubl
                                    double mu = 0.0, int32_t strategy = 0, double *nonsym_out = nullptr) {
     HK_ENTER(h)
     ConeState &C = S->cones;
-    const bool psd_step = C.step.mode == StepMode::Psd;
+    const bool psd_step = C.step.mode == StepMode::Psd || C.step.mode == StepMode::Mixed;
     if (!C.reg.ready) { S->err = "update_scaling: call hipkkt_set_cone_types first"; return HIPKKT_ERR_ARGUMENT; }
     if (!ex && C.reg.nonsym) { S->err = "update_scaling: the cone set has Exponential / Power / GenPower cones, which need mu: call hipkkt_update_scaling_ex"; return HIPKKT_ERR_ARGUMENT; }
     if (ex && strategy != 0 && strategy != 1) { S->err = "update_scaling_ex: strategy is 0 (PrimalDual) or 1 (Dual)"; return HIPKKT_ERR_ARGUMENT; }
@@ -215,7 +216,7 @@ static int32_t update_scaling_impl(hipkkt_handle h, const double *s, const doubl
     if (psd_step && !psd_nt && (!psd_R || !C.step.psd_fresh)) {
         C.step.scaled = false;
         C.step.psd_resident = false;
-        S->err = "update_scaling: after hipkkt_step_enable_psd the call needs psd_R and the factors of a hipkkt_psd_set_factors[_dev] since the last scaling";
+        S->err = "update_scaling: after hipkkt_step_enable_psd / _mixed the call needs psd_R and the factors of a hipkkt_psd_set_factors[_dev] since the last scaling";
         return HIPKKT_ERR_ARGUMENT;
     }
     const double *ds = s, *dz = z, *dR = psd_R;

@@ -1,5 +1,6 @@
 // The cone state of a handle: what hipkkt_set_cone_types[_ex] registered, the device tables of the scaling kernels (scaling.hip) and
-// what the step entry points keep resident (hipkkt_step.cpp; step.hip, step_cone3.hip, step_genpow.hip, step_psd.hip, step_psd_large.hip).
+// what the step entry points keep resident (hipkkt_step.cpp; step.hip, step_cone3.hip, step_genpow.hip, step_psd.hip, step_psd_large.hip,
+// barrier_psd.hip).
 // Written by hipkkt_cones.cpp (registration, scaling) and hipkkt_step.cpp (enables, step); record layouts: cone_layout.h.
 #pragma once
 #include <cstdint>
@@ -12,11 +13,14 @@ namespace hipkkt_host {
 //   Cone3      an _ex registration, kinds in {0, 1, 2, 4, 5}, at least one Exponential / Power cone
 //   GenPow     an _ex registration, kinds in {0, 1, 2, 4, 5, 6}, at least one Generalized Power cone
 //   Psd        kinds in 0..3, at least one PSD triangle cone (the sides are checked at the enable)
-enum class ConeClass { Other, Symmetric, Cone3, GenPow, Psd };
+//   Mixed      an _ex registration, kinds in 0..6, at least one PSD triangle cone and at least one Exponential / Power / Generalized
+//              Power cone (the sides are checked at the enable)
+enum class ConeClass { Other, Symmetric, Cone3, GenPow, Psd, Mixed };
 
 // Which cones the step entry points serve.  A registration sets Symmetric for the class Symmetric and Off otherwise; the enables
-// hipkkt_step_enable_cone3 / _genpow / _psd / _psd_large move a handle of their class to Cone3 / GenPow / Psd and back to Off.
-enum class StepMode { Off, Symmetric, Cone3, GenPow, Psd };
+// hipkkt_step_enable_cone3 / _genpow / _psd / _psd_large / _mixed move a handle of their class to Cone3 / GenPow / Psd / Mixed and back
+// to Off.
+enum class StepMode { Off, Symmetric, Cone3, GenPow, Psd, Mixed };
 
 struct ConeState {
     // what the last hipkkt_set_cone_types[_ex] established (host side)
@@ -46,7 +50,7 @@ struct ConeState {
         int *trips = nullptr;                              // Newton steps of the last update per table entry (debug_dump 23)
         int64_t *gpdesc = nullptr, *gpidx = nullptr;
         double *gpalpha = nullptr, *nsout = nullptr;
-        // hipkkt_step_enable_psd: the cone table, the resident factors of the last scaling, the staged [Rinv (psd_total) | lambda]
+        // hipkkt_step_enable_psd / _mixed: the cone table, the resident factors of the last scaling, the staged [Rinv (psd_total) | lambda]
         int64_t cap_psd_cones = 0, cap_psd_mat = 0, cap_psd_lam = 0;
         int64_t *psdtab = nullptr;
         double *psd_rinv = nullptr, *psd_lam = nullptr, *psd_stage = nullptr;
@@ -66,7 +70,7 @@ struct ConeState {
         bool psd_scaling = false;                          // hipkkt_psd_scaling_enable: a scaling without psd_R computes the factors
         bool psd_resident = false;                         // a scaling since the enable left (R, Rinv, lambda) resident (hipkkt_psd_get_factors)
         int psd_nlarge = 0, psd_lmin = 65, psd_lmax = 0;   // hipkkt_step_enable_psd_large: cones of side psd_lmin .. psd_lmax go to step_psd_large.hip
-        double ls_step = 0.0, ls_amin = 0.0;               // linesearch_backtrack_step, min_terminate_step_length (Cone3 / GenPow)
+        double ls_step = 0.0, ls_amin = 0.0;               // linesearch_backtrack_step, min_terminate_step_length (Cone3 / GenPow / Mixed)
         int ls_trips = 0;                                  // bound of the backtracking loop: ceil(log amin / log step) + 2
         double mu = 0.0;                                   // mu of the last hipkkt_update_scaling_ex[_dev] (mul_Hs of the GenPower cones)
         double *step = nullptr;                            // [dx | dz | ds] of the last fused step call

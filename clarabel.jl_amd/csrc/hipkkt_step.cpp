@@ -6,6 +6,8 @@
 // After hipkkt_step_enable_genpow the Generalized Power cones too (step_genpow.hip), on their slot [grad | d1 | d2 | p | q | r].
 // After hipkkt_step_enable_psd the PSD triangle cones of a symmetric registration (step_psd.hip), on the caller's (R, Rinv, lambda);
 // after hipkkt_step_enable_psd_large those of side 65 .. 128 as well (step_psd_large.hip).
+// After hipkkt_step_enable_mixed PSD triangle cones (sides <= 64) next to Exponential / Power / Generalized Power cones: the launches of
+// the families above composed, plus the PSD cones' barrier (barrier_psd.hip).
 // The default start of a symmetric cone set (start.hip): hipkkt_cone_set_identity_scaling / _margins / _shift_to_interior and the fused
 // hipkkt_step_default_start_dev, which need no scaling.
 #include "hipkkt_internal.h"
@@ -20,7 +22,8 @@ static bool step_ready(hipkkt_solver *S, const char *who) {
     if (!S->l1 || !C.reg.ready || C.step.mode == StepMode::Off) {
         S->err = std::string(who) + ": needs an L1 handle whose registered cones are Zero / Nonnegative / SecondOrder only, or one with "
                                     "Exponential / Power cones next to them after hipkkt_step_enable_cone3, or with Generalized Power cones "
-                                    "after hipkkt_step_enable_genpow, or with PSD triangle cones after hipkkt_step_enable_psd[_large]";
+                                    "after hipkkt_step_enable_genpow, or with PSD triangle cones after hipkkt_step_enable_psd[_large], or with PSD "
+                                    "triangle cones next to Exponential / Power / Generalized Power cones after hipkkt_step_enable_mixed";
         return false;
     }
     if (!C.step.scaled) { S->err = std::string(who) + ": no successful hipkkt_update_scaling since the cones were registered"; return false; }
@@ -55,13 +58,13 @@ struct ConeTables {
     const int64_t *gpdesc = nullptr;
     const double *gpalpha = nullptr;
     double mu = 0.0;
-    // Psd: the PSD triangle cones' table and factors
+    // Psd / Mixed: the PSD triangle cones' table and factors
     int npsd = 0;
     const int64_t *psdtab = nullptr;
     const double *psdR = nullptr, *psdRinv = nullptr, *psdlam = nullptr;
     PsdLargeBatch large;      // ... and those of them step_psd_large.hip serves (hipkkt_step_enable_psd_large; none otherwise)
     // the backtracking line search of the non-symmetric cones decides the step length
-    bool line_search() const { return mode == StepMode::Cone3 || mode == StepMode::GenPow; }
+    bool line_search() const { return mode == StepMode::Cone3 || mode == StepMode::GenPow || mode == StepMode::Mixed; }
 };
 static ConeTables tables(hipkkt_solver *S) {
     const ConeState &C = S->cones;
@@ -74,6 +77,9 @@ static ConeTables tables(hipkkt_solver *S) {
         case StepMode::Off:
         case StepMode::Symmetric:
             break;
+        case StepMode::Mixed:      // the PSD fields (no side above 64: no large batch), then every non-symmetric field
+            T.npsd = (int)C.reg.psd_n.size(); T.psdtab = C.tab.psdtab; T.psdR = C.tab.R; T.psdRinv = C.tab.psd_rinv; T.psdlam = C.tab.psd_lam;
+            [[fallthrough]];
         case StepMode::GenPow:
             T.ngp = C.reg.ngenpow; T.gpdesc = C.tab.gpdesc; T.gpalpha = C.tab.gpalpha; T.mu = C.step.mu;
             [[fallthrough]];      // and the three-row members of the set
@@ -90,8 +96,8 @@ static ConeTables tables(hipkkt_solver *S) {
 }
 
 // every operation: the kernels of step.hip on the Zero / Nonnegative / SecondOrder rows (unchanged), then the Exponential / Power rows,
-// then the Generalized Power rows, then the PSD rows (a set has either non-symmetric or PSD members on this path): step_psd.hip leaves a
-// cone of side > 64 alone, step_psd_large.hip computes it
+// then the Generalized Power rows, then the PSD rows (a launcher skips an empty family; only a Mixed set has both non-symmetric and PSD
+// members): step_psd.hip leaves a cone of side > 64 alone, step_psd_large.hip computes it
 static void op_affine_ds(hipStream_t st, const ConeTables &T, double *out) {
     launch_step_affine_ds(st, T.kind, T.nsoc, T.desc, T.lam, out, T.m);
     launch_step3_copy(st, T.n3, T.row0, T.s, out);
@@ -142,10 +148,20 @@ static void op_length(hipkkt_solver *S, hipStream_t st, const ConeTables &T, con
             launch_psd_step_length_final(st, T.npsd, sym2, pairs, out2);
             break;
         }
+        case StepMode::Mixed:
         case StepMode::Cone3:
         case StepMode::GenPow: {
             double *sym2 = St.out + kStOutSym;
-            launch_step_length(st, T.kind, T.nsoc, T.desc, T.z, T.s, dz, ds, alpha_max, St.part, sym2, T.m);
+            if (T.mode == StepMode::Mixed) {
+                // "symmetric cones first" (coneops_compositecone.jl:216-252) includes the PSD cones: the three launches of the Psd arm
+                // leave the pair of kinds 0..3 at kStOutSym; the partials in St.part are consumed before the line search reuses it
+                double *sympsd2 = St.out + kStOutSymPsd, *pairs = St.part + 2 * step_len_pairs(T.m, T.nsoc);
+                launch_step_length(st, T.kind, T.nsoc, T.desc, T.z, T.s, dz, ds, alpha_max, St.part, sympsd2, T.m);
+                launch_psd_step_length_cones(st, T.npsd, T.psdtab, T.psdR, T.psdRinv, T.psdlam, dz, ds, alpha_max, pairs);
+                launch_psd_step_length_final(st, T.npsd, sympsd2, pairs, sym2);
+            } else {
+                launch_step_length(st, T.kind, T.nsoc, T.desc, T.z, T.s, dz, ds, alpha_max, St.part, sym2, T.m);
+            }
             // (St.part holds 2 (ceil(m / 256) + ncones) doubles: room for the three-row workgroups' partials and one per Generalized Power cone)
             launch_genpow_length(st, T.ngp, T.gpdesc, T.gpalpha, T.z, T.s, dz, ds, sym2, dtau, tau, kappa, rhs_kappa, alpha_max,
                                  St.ls_step, St.ls_amin, St.ls_trips, St.part + step3_length_parts(T.nexp, T.npow));
@@ -269,14 +285,19 @@ int32_t hipkkt_cone_step_length(hipkkt_handle h, const double *dz, const double 
 }
 
 // the barrier of the cone set and the shifted <z, s> at nalpha candidates: (z, s, dz, ds) and dout are device pointers
-// (without the enable T names no Exponential / Power cone: the symmetric cones' barrier)
+// (without the enable T names no Exponential / Power cone: the symmetric cones' barrier).  A Mixed set: the PSD cones' slots before, their
+// sum onto out[2 j] behind the two launches every set runs; a set without PSD cones executes exactly those two
 static void barrier_impl(hipkkt_solver *S, const ConeTables &T, const double *z, const double *s, const double *dz, const double *ds,
                          const double *alphas, int64_t nalpha, double *dout) {
-    // (the work buffer has 8 doubles per registered cone for the per-cone partials: second-order, three-row and Generalized Power together)
+    // (the work buffer has 16 doubles per registered cone for the per-cone partials: 8 per second-order, three-row and Generalized Power
+    // cone, 16 per PSD cone)
     double *bar = S->cones.step.bar;
+    double *psd_slots = psd_barrier_slots(bar, T.nsoc, T.n3, T.ngp);
+    launch_psd_barrier(S->stream, T.npsd, T.psdtab, z, s, dz, ds, alphas, (int)nalpha, psd_slots);
     launch_genpow_barrier(S->stream, T.ngp, T.gpdesc, T.gpalpha, z, s, dz, ds, alphas, (int)nalpha, step3_barrier_gppart(bar, T.nsoc, T.n3));
     launch_step3_barrier(S->stream, T.kind, T.nsoc, T.desc, T.nexp, T.npow, T.row0, T.alpha, z, s, dz, ds, alphas, (int)nalpha, bar, dout,
                          T.m, T.ngp);
+    launch_psd_barrier_add(S->stream, T.npsd, psd_slots, (int)nalpha, dout);
 }
 
 // the parameter checks, the trip bound and the invalidation both enables share; the handle is in `mode` afterwards
@@ -296,7 +317,7 @@ static int32_t enable_line_search(hipkkt_solver *S, const char *who, StepMode mo
     return HIPKKT_OK;
 }
 
-// enable = 0 of either entry point: Cone3 and GenPow go off, the other modes stay
+// enable = 0 of hipkkt_step_enable_cone3 / _genpow: Cone3 and GenPow go off, the other modes stay
 static void disable_line_search(ConeState &C) {
     if (C.step.mode == StepMode::Cone3 || C.step.mode == StepMode::GenPow) C.step.mode = StepMode::Off;
 }
@@ -327,25 +348,18 @@ int32_t hipkkt_step_enable_genpow(hipkkt_handle h, int32_t enable, double linese
     HK_LEAVE
 }
 
-// hipkkt_step_enable_psd (large = false: sides <= HIPKKT_PSD_STEP_MAX_DIM) and hipkkt_step_enable_psd_large (sides <=
-// HIPKKT_PSD_STEP_LARGE_MAX_DIM; cones of side >= lmin go to step_psd_large.hip, the others to step_psd.hip as after the first)
-static int32_t enable_psd_impl(hipkkt_handle h, int32_t enable, bool large) {
-    HK_ENTER(h)
-    ConeState &C = S->cones;
-    if (!enable) {
-        if (C.step.mode == StepMode::Psd) { C.step.mode = StepMode::Off; C.step.psd_scaling = C.step.psd_resident = false; C.step.psd_nlarge = 0; }
-        return HIPKKT_OK;
-    }
-    const int64_t max_side = large ? HIPKKT_PSD_STEP_LARGE_MAX_DIM : HIPKKT_PSD_STEP_MAX_DIM;
-    bool ok = S->l1 && C.reg.ready && C.reg.cls == ConeClass::Psd;
+// an L1 handle whose registration is of class `cls` with every PSD side <= max_side
+static bool psd_class_fits(hipkkt_solver *S, ConeClass cls, int64_t max_side) {
+    const ConeState &C = S->cones;
+    bool ok = S->l1 && C.reg.ready && C.reg.cls == cls;
     for (size_t c = 0; ok && c < C.reg.psd_n.size(); c++) ok = C.reg.psd_n[c] <= max_side;
-    if (!ok) {
-        S->err = std::string(large ? "step_enable_psd_large" : "step_enable_psd") +
-                 ": needs an L1 handle whose last hipkkt_set_cone_types[_ex] names Zero / Nonnegative / SecondOrder / PSD "
-                 "triangle cones only, at least one PSD cone, every PSD side <= " +
-                 (large ? "HIPKKT_PSD_STEP_LARGE_MAX_DIM" : "HIPKKT_PSD_STEP_MAX_DIM");
-        return HIPKKT_ERR_ARGUMENT;
-    }
+    return ok;
+}
+
+// what hipkkt_step_enable_psd[_large] and hipkkt_step_enable_mixed share: the PSD cone table, the factor buffers, the list of the cones
+// step_psd_large.hip serves (`large`), the invalidation; the handle is in `mode` afterwards
+static void enable_psd_tables(hipkkt_solver *S, StepMode mode, bool large) {
+    ConeState &C = S->cones;
     // the cone table and the factor buffers: allocated on the first call, re-used while large enough (as the d_sc_* buffers)
     const int64_t npsd = (int64_t)C.reg.psd_n.size();
     std::vector<int64_t> tab((size_t)(kPsdTab * npsd));
@@ -379,16 +393,55 @@ static int32_t enable_psd_impl(hipkkt_handle h, int32_t enable, bool large) {
     }
     copy_sync(S->stream, C.tab.psd_lidx, lidx.data(), lidx.size() * sizeof(int), hipMemcpyHostToDevice);
     C.step.psd_nlarge = (int)lidx.size(); C.step.psd_lmin = lmin; C.step.psd_lmax = lmax;
-    C.step.mode = StepMode::Psd;
+    C.step.mode = mode;
     C.step.psd_fresh = false;
     C.step.psd_scaling = C.step.psd_resident = false;
     C.step.scaled = false;      // the step reads the factors of a scaling that ran with the enable in place
     C.step.have_step = false;
+}
+
+// enable = 0 of the entry points below: `mode` goes off, the other modes stay
+static void disable_psd_mode(ConeState &C, StepMode mode) {
+    if (C.step.mode == mode) { C.step.mode = StepMode::Off; C.step.psd_scaling = C.step.psd_resident = false; C.step.psd_nlarge = 0; }
+}
+
+// hipkkt_step_enable_psd (large = false: sides <= HIPKKT_PSD_STEP_MAX_DIM) and hipkkt_step_enable_psd_large (sides <=
+// HIPKKT_PSD_STEP_LARGE_MAX_DIM; cones of side >= lmin go to step_psd_large.hip, the others to step_psd.hip as after the first)
+static int32_t enable_psd_impl(hipkkt_handle h, int32_t enable, bool large) {
+    HK_ENTER(h)
+    if (!enable) { disable_psd_mode(S->cones, StepMode::Psd); return HIPKKT_OK; }
+    if (!psd_class_fits(S, ConeClass::Psd, large ? HIPKKT_PSD_STEP_LARGE_MAX_DIM : HIPKKT_PSD_STEP_MAX_DIM)) {
+        S->err = std::string(large ? "step_enable_psd_large" : "step_enable_psd") +
+                 ": needs an L1 handle whose last hipkkt_set_cone_types[_ex] names Zero / Nonnegative / SecondOrder / PSD "
+                 "triangle cones only, at least one PSD cone, every PSD side <= " +
+                 (large ? "HIPKKT_PSD_STEP_LARGE_MAX_DIM" : "HIPKKT_PSD_STEP_MAX_DIM");
+        return HIPKKT_ERR_ARGUMENT;
+    }
+    enable_psd_tables(S, StepMode::Psd, large);
     return HIPKKT_OK;
     HK_LEAVE
 }
 int32_t hipkkt_step_enable_psd(hipkkt_handle h, int32_t enable) { return enable_psd_impl(h, enable, false); }
 int32_t hipkkt_step_enable_psd_large(hipkkt_handle h, int32_t enable) { return enable_psd_impl(h, enable, true); }
+
+// PSD triangle cones (sides <= HIPKKT_PSD_STEP_MAX_DIM: the barrier keeps its matrix in LDS) next to Exponential / Power / Generalized
+// Power cones: the tables of hipkkt_step_enable_psd and the line search of hipkkt_step_enable_cone3 / _genpow
+int32_t hipkkt_step_enable_mixed(hipkkt_handle h, int32_t enable, double linesearch_backtrack_step, double min_terminate_step_length) {
+    HK_ENTER(h)
+    if (!enable) { disable_psd_mode(S->cones, StepMode::Mixed); return HIPKKT_OK; }
+    if (!psd_class_fits(S, ConeClass::Mixed, HIPKKT_PSD_STEP_MAX_DIM)) {
+        S->err = "step_enable_mixed: needs an L1 handle whose last hipkkt_set_cone_types_ex names Zero / Nonnegative / SecondOrder / PSD "
+                 "triangle / Exponential / Power / GenPower cones only, at least one PSD cone and at least one of the last three, every "
+                 "PSD side <= HIPKKT_PSD_STEP_MAX_DIM";
+        return HIPKKT_ERR_ARGUMENT;
+    }
+    // (the parameter checks come first: a refused call leaves the handle as it was)
+    const int32_t rc = enable_line_search(S, "step_enable_mixed", StepMode::Mixed, linesearch_backtrack_step, min_terminate_step_length);
+    if (rc != HIPKKT_OK) return rc;
+    enable_psd_tables(S, StepMode::Mixed, false);
+    return HIPKKT_OK;
+    HK_LEAVE
+}
 
 // a handle in PSD step mode whose registration holds a side above HIPKKT_PSD_STEP_MAX_DIM (hipkkt_step_enable_psd_large): the device
 // scaling (scaling_psd.hip) and the default start (start.hip) keep their matrices in LDS and would leave such a cone alone
@@ -398,11 +451,14 @@ static bool psd_side_above_small(const ConeState &C) {
     return false;
 }
 
+// the modes whose step reads resident PSD factors (R, Rinv, lambda)
+static bool psd_factors_mode(const ConeState &C) { return C.step.mode == StepMode::Psd || C.step.mode == StepMode::Mixed; }
+
 static int32_t psd_set_factors_impl(hipkkt_handle h, const double *Rinv_all, const double *lambda_all, bool dev) {
     HK_ENTER(h)
     ConeState &C = S->cones;
-    if (C.step.mode != StepMode::Psd || !Rinv_all || !lambda_all) {
-        S->err = "psd_set_factors: needs hipkkt_step_enable_psd first / null argument";
+    if (!psd_factors_mode(C) || !Rinv_all || !lambda_all) {
+        S->err = "psd_set_factors: needs hipkkt_step_enable_psd / _mixed first / null argument";
         return HIPKKT_ERR_ARGUMENT;
     }
     const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
@@ -424,8 +480,8 @@ int32_t hipkkt_psd_set_factors_dev(hipkkt_handle h, const double *Rinv_all, cons
 int32_t hipkkt_psd_scaling_enable(hipkkt_handle h, int32_t enable) {
     HK_ENTER(h)
     ConeState &C = S->cones;
-    if (C.step.mode != StepMode::Psd) {
-        S->err = "psd_scaling_enable: needs hipkkt_step_enable_psd first";
+    if (!psd_factors_mode(C)) {
+        S->err = "psd_scaling_enable: needs hipkkt_step_enable_psd / _mixed first";
         return HIPKKT_ERR_ARGUMENT;
     }
     if (psd_side_above_small(C)) {
@@ -443,8 +499,8 @@ int32_t hipkkt_psd_scaling_enable(hipkkt_handle h, int32_t enable) {
 int32_t hipkkt_psd_get_factors(hipkkt_handle h, double *R_out, double *Rinv_out, double *lambda_out) {
     HK_ENTER(h)
     ConeState &C = S->cones;
-    if (C.step.mode != StepMode::Psd || !C.step.psd_resident) {
-        S->err = "psd_get_factors: no PSD scaling is resident (hipkkt_step_enable_psd, then a hipkkt_update_scaling[_ex][_dev])";
+    if (!psd_factors_mode(C) || !C.step.psd_resident) {
+        S->err = "psd_get_factors: no PSD scaling is resident (hipkkt_step_enable_psd / _mixed, then a hipkkt_update_scaling[_ex][_dev])";
         return HIPKKT_ERR_ARGUMENT;
     }
     const size_t nr = (size_t)C.reg.psd_total * sizeof(double), nl = (size_t)C.reg.psd_lam_total * sizeof(double);

@@ -193,6 +193,16 @@ void launch_psd_large_length(hipStream_t st, const PsdLargeBatch &L, const int64
 // that fails sets *fail and bad[cone] (0 otherwise) and gets NaN factors.
 void launch_psd_nt_scaling(hipStream_t st, int npsd, const int64_t *tab, const double *s, const double *z, double *R, double *Rinv,
                            double *lam, int *bad, int *fail);
+// barrier_psd.hip: compute_barrier of the PSD triangle cones of the same table (sides <= psd_step_max_dim()) at nalpha <=
+// step3_max_candidates() step lengths (host array), for a cone set that holds PSD cones next to non-symmetric ones
+// (hipkkt_step_enable_mixed).  launch_psd_barrier leaves [(0 - logdet(Z + a dZ)) | logdet(S + a dS)] per (cone, candidate) in slots =
+// psd_barrier_slots(work, nsoc, n3, ngp), 16 doubles per PSD cone of the work buffer of launch_step3_barrier; launch_psd_barrier_add,
+// behind launch_step3_barrier on the same stream, adds the cones' (0 - logdet_z) - logdet_s in PSD-cone order to out[2 j].  A shifted
+// point outside the cone gives -Inf (the reference subtracts typemax).
+double *psd_barrier_slots(double *work, int nsoc, int n3, int ngp);
+void launch_psd_barrier(hipStream_t st, int npsd, const int64_t *tab, const double *z, const double *s, const double *dz, const double *ds,
+                        const double *alphas, int nalpha, double *slots);
+void launch_psd_barrier_add(hipStream_t st, int npsd, const double *slots, int nalpha, double *out);
 // start.hip: the default start of a symmetric cone set (solver.jl:383-405) on the tables above.
 // launch_start_identity writes the identity scaling's Hs values and sparse second-order terms into kval (psd_hs0 = first Hs entry per
 // PSD cone, psd_max_numel = the largest numel among them).  launch_start_margins leaves, for each of nsides vectors (v1 is not read

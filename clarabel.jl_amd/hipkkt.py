@@ -52,6 +52,8 @@ SYMBOLS = [
     "hipkkt_cone_set_identity_scaling", "hipkkt_cone_margins", "hipkkt_cone_shift_to_interior", "hipkkt_step_default_start_dev",
     # the PSD step for sides 65 .. 128 (opt-in, added within ABI version 5)
     "hipkkt_step_enable_psd_large",
+    # PSD triangle cones next to Exponential / Power / Generalized Power cones (opt-in, added within ABI version 5)
+    "hipkkt_step_enable_mixed",
 ]
 
 PSD_STEP_MAX_DIM = 64      # include/hipkkt.h HIPKKT_PSD_STEP_MAX_DIM
@@ -166,6 +168,7 @@ def lib():
     L.hipkkt_step_enable_genpow.argtypes = [vp, i32, f64, f64]
     L.hipkkt_step_enable_psd.argtypes = [vp, i32]
     L.hipkkt_step_enable_psd_large.argtypes = [vp, i32]
+    L.hipkkt_step_enable_mixed.argtypes = [vp, i32, f64, f64]
     L.hipkkt_psd_set_factors.argtypes = [vp, _f64p, _f64p]
     L.hipkkt_psd_set_factors_dev.argtypes = [vp, vp, vp]
     L.hipkkt_psd_scaling_enable.argtypes = [vp, i32]
@@ -756,6 +759,14 @@ class Handle:
         """step_enable_psd with the side limit PSD_STEP_LARGE_MAX_DIM: cones of side 65 .. 128 are served too, by kernels that keep their
         matrices in device memory (same arithmetic).  ValueError when the registration does not qualify; the handle stays as it was"""
         self._chk_step(self.L.hipkkt_step_enable_psd_large(self.h, int(bool(enable))), "step_enable_psd_large")
+
+    def step_enable_mixed(self, enable, linesearch_backtrack_step, min_terminate_step_length):
+        """for a registration (set_cone_types_ex) with PSD triangle cones next to Exponential / Power / Generalized Power cones: ValueError
+        unless it names kinds 0..6 only with a 3 and one of 4..6 and every PSD side is at most PSD_STEP_MAX_DIM.  The PSD members step as
+        after step_enable_psd (same factor protocol), the others as after step_enable_cone3 / _genpow with these parameters, and the
+        barrier calls add the PSD cones' log-det barrier"""
+        self._chk_step(self.L.hipkkt_step_enable_mixed(self.h, int(bool(enable)), float(linesearch_backtrack_step),
+                                                       float(min_terminate_step_length)), "step_enable_mixed")
 
     def psd_set_factors(self, rinv, lam, dev=False):
         """stages the PSD cones' Rinv (n x n column-major each, concatenated like psd_R) and lambda (n each) for the next update_scaling;

@@ -18,7 +18,7 @@ from .settings import Settings
 _DEBUG = os.environ.get("HIPKKT_DEBUG", "0") == "1"
 
 
-def cone_set_steps_on_device(cones, nonsymmetric=False, genpower=False, psd=False, psd_large=False) -> bool:
+def cone_set_steps_on_device(cones, nonsymmetric=False, genpower=False, psd=False, psd_large=False, mixed=False) -> bool:
     """the step entry points (hipkkt_cone_* / hipkkt_step_*) serve cone sets of ZeroCone, NonnegativeCone and SecondOrderCone only: a PSD
     cone's step length needs eigenvalue decompositions, the non-symmetric cones need backtracking and barriers.
     nonsymmetric=True: ExponentialCone and PowerCone members qualify as well (hipkkt_step_enable_cone3); Generalized Power and PSD
@@ -27,7 +27,10 @@ def cone_set_steps_on_device(cones, nonsymmetric=False, genpower=False, psd=Fals
     psd=True: PSD triangle members qualify when every side is at most hipkkt.PSD_STEP_MAX_DIM and the set has no Exponential / Power /
     Generalized Power member (hipkkt_step_enable_psd).
     psd_large=True (with psd=True): the side limit is hipkkt.PSD_STEP_LARGE_MAX_DIM (hipkkt_step_enable_psd_large); alone it widens
-    nothing"""
+    nothing.
+    mixed=True (with nonsymmetric=True and psd=True): PSD triangle members of side at most hipkkt.PSD_STEP_MAX_DIM qualify next to
+    Exponential / Power members, and next to Generalized Power members with genpower=True (hipkkt_step_enable_mixed); psd_large does not
+    widen that limit; alone it widens nothing"""
     if not hasattr(cones, "kkt_cone_kinds"):
         return False
     kinds = cones.kkt_cone_kinds_ex()[0] if hasattr(cones, "kkt_cone_kinds_ex") else cones.kkt_cone_kinds()
@@ -37,10 +40,12 @@ def cone_set_steps_on_device(cones, nonsymmetric=False, genpower=False, psd=Fals
         ok = ok | (kinds == 4) | (kinds == 5)
         if genpower:
             ok = ok | (kinds == 6)
-    if psd and bool(np.any(kinds == 3)) and not bool(np.any(kinds >= 4)):
+    has_nonsym = bool(np.any(kinds >= 4))
+    if psd and bool(np.any(kinds == 3)) and (not has_nonsym or (mixed and nonsymmetric)):
         numel = np.asarray(cones.kkt_descriptors()[0])[kinds == 3]
         sides = ((np.sqrt(8.0 * numel + 1.0) - 1.0) / 2.0 + 0.5).astype(np.int64)
-        if bool(np.all(sides <= (hipkkt.PSD_STEP_LARGE_MAX_DIM if psd_large else hipkkt.PSD_STEP_MAX_DIM))):
+        limit = hipkkt.PSD_STEP_LARGE_MAX_DIM if psd_large and not has_nonsym else hipkkt.PSD_STEP_MAX_DIM
+        if bool(np.all(sides <= limit)):
             ok = ok | (kinds == 3)
     return kinds.size > 0 and bool(np.all(ok))
 
@@ -113,6 +118,17 @@ class HipKKTSolver:
         elif psd_ok and getattr(settings, "device_step_psd_large", False) and cone_set_steps_on_device(cones, psd=True, psd_large=True):
             self.h.step_enable_psd_large(True)
             self._steps_on_device = self.steps_psd = self.steps_psd_large = True
+        # ... and, opted in by Settings.device_step_mixed on top of device_step_nonsymmetric and device_step_psd, sets that hold PSD
+        # triangle members (sides <= 64) next to Exponential / Power members, and next to Generalized Power members with
+        # device_step_genpower (hipkkt_step_enable_mixed).  The PSD factors follow the protocol of steps_psd / scales_psd
+        self.steps_mixed = False
+        if not self._steps_on_device and getattr(settings, "device_step_mixed", False) \
+                and getattr(settings, "device_step_nonsymmetric", False) and getattr(settings, "device_step_psd", False) \
+                and self.scales_nonsymmetric and self._psd_cones \
+                and cone_set_steps_on_device(cones, nonsymmetric=True, genpower=bool(getattr(settings, "device_step_genpower", False)),
+                                             psd=True, mixed=True):
+            self.h.step_enable_mixed(True, settings.linesearch_backtrack_step, settings.min_terminate_step_length)
+            self._steps_on_device = self.steps_nonsymmetric = self.steps_psd = self.steps_mixed = True
         if self.steps_psd:
             rows = [r for c, r in zip(cones.cones, cones.rng_cones) if hasattr(c, "RRt")]
             self._psd_rows = rows
@@ -182,6 +198,8 @@ class HipKKTSolver:
             if strategy is None:
                 strategy = 0 if cones.allows_primal_dual_scaling() else 1
             strategy = {"primal_dual": 0, "dual": 1}.get(strategy, strategy)
+            if self.steps_psd:      # (steps_mixed: the step reads the PSD factors, as below)
+                self.h.psd_set_factors(*self._psd_factors())
             ok, self.scaling_w, self.scaling_lambda, self.scaling_soc_eta, self.scaling_nonsym = \
                 self.h.update_scaling_ex(s, z, mu, strategy, R)
             if not ok:
@@ -308,6 +326,17 @@ class HipKKTSolver:
         """(Rinv, lambda) of the PSD cones' current scaling, concatenated like psd_R"""
         return (np.concatenate([c.Rinv.ravel(order="F") for c in self._psd_cones]), np.concatenate([c.lam for c in self._psd_cones]))
 
+    def _psd_factors_upload(self):
+        """[R | Rinv | lambda] of the PSD cones' current scaling in one upload, (Rinv, lambda) staged for the next scaling call -> the
+        device pointer of R"""
+        if self._psd_dev is None:
+            self._psd_dev = hipkkt.DeviceBuffer(2 * self._psd_nr + int(np.sum(self._psd_dim)))
+        rinv, lam = self._psd_factors()
+        self._psd_dev.upload(np.concatenate([np.concatenate([c.R.ravel(order="F") for c in self._psd_cones]), rinv, lam]))
+        p = self._psd_dev.ptr
+        self.h.psd_set_factors(p + 8 * self._psd_nr, p + 16 * self._psd_nr, dev=True)
+        return p
+
     def psd_rows_download(self, xzs):
         """-> (s, z) of length m with the rows first PSD row .. last PSD row filled from the resident iterate (steps_psd: what the
         caller's update_scaling! of the PSD cones needs), the rest zero"""
@@ -322,18 +351,17 @@ class HipKKTSolver:
         steps_psd: the PSD cones' (R, Rinv, lambda) of the caller's update_scaling! go along in one upload -- unless scales_psd, where
         the device computes them from the resident (s, z) and nothing is uploaded"""
         if self.steps_psd and not self.scales_psd:
-            if self._psd_dev is None:
-                self._psd_dev = hipkkt.DeviceBuffer(2 * self._psd_nr + int(np.sum(self._psd_dim)))
-            rinv, lam = self._psd_factors()
-            self._psd_dev.upload(np.concatenate([np.concatenate([c.R.ravel(order="F") for c in self._psd_cones]), rinv, lam]))
-            p = self._psd_dev.ptr
-            self.h.psd_set_factors(p + 8 * self._psd_nr, p + 16 * self._psd_nr, dev=True)
+            p = self._psd_factors_upload()
             return self.h.update_scaling_dev(xzs.ptr + 8 * (self.n + self.m), xzs.ptr + 8 * self.n, R_ptr=p)
         return self.h.update_scaling_dev(xzs.ptr + 8 * (self.n + self.m), xzs.ptr + 8 * self.n)
 
     def kktsolver_update_scaling_dev_ex(self, xzs, mu, strategy) -> bool:
-        """the same with Exponential / Power members: mu and the strategy ("primal_dual" / "dual" or 0 / 1) as kktsolver_update_scaled"""
+        """the same with Exponential / Power members: mu and the strategy ("primal_dual" / "dual" or 0 / 1) as kktsolver_update_scaled.
+        steps_psd (a mixed set): the PSD cones' (R, Rinv, lambda) go along as in kktsolver_update_scaling_dev, unless scales_psd"""
         strategy = {"primal_dual": 0, "dual": 1}.get(strategy, strategy)
+        if self.steps_psd and not self.scales_psd:
+            p = self._psd_factors_upload()
+            return self.h.update_scaling_ex_dev(xzs.ptr + 8 * (self.n + self.m), xzs.ptr + 8 * self.n, mu, strategy, R_ptr=p)
         return self.h.update_scaling_ex_dev(xzs.ptr + 8 * (self.n + self.m), xzs.ptr + 8 * self.n, mu, strategy)
 
     def cone_barrier(self, dz, ds, alphas):

@@ -155,3 +155,60 @@ def nonsymmetric_mix(n=300, nexp=60, npow=40, ngenpow=10, nn=100, nzero=10, socd
     b = A @ x0 + s0
     q = rng.standard_normal(n)
     return P, q, A, b, cones
+
+
+def _psd_s0(rng, dim):
+    """svec(M M' / dim + I) with M ~ N(0,1): the strictly feasible slack of one PSD triangle block, as in sdp_blocks"""
+    il = np.tril_indices(dim)
+    r, c = il[1], il[0]
+    M = rng.standard_normal((dim, dim))
+    S = M @ M.T / dim + np.eye(dim)
+    return np.where(r == c, S[r, c], S[r, c] * np.sqrt(2.0))
+
+
+def mixed_psd_nonsym(n=80, psd_sides=(20, 20, 20, 20), nexp=20, npow=10, ngenpow=0, nn=20, nzero=3, socdim=5, seed=5, kA=4):
+    """PSD triangle cones next to the non-symmetric cones (an LMI next to relative-entropy or geometric-mean constraints): the recipe of
+    nonsymmetric_mix with the cones in the order Zero(nzero), NN(nn), PSD(side) for psd_sides[:-1], nexp x Exp, npow x Pow, ngenpow x GenPow,
+    SOC(socdim), PSD(psd_sides[-1]) -- PSD rows before and behind the other families.  Each PSD block's s0 = svec(M M' / side + I) as in
+    sdp_blocks; every draw comes from the one generator in cone order, then A, P, x0, q."""
+    rng = np.random.default_rng(seed)
+    psd_sides = [int(d) for d in psd_sides]
+    cones, s0 = [], []
+    if nzero:
+        cones.append(ZeroConeT(nzero))
+        s0.append(np.zeros(nzero))
+    if nn:
+        cones.append(NonnegativeConeT(nn))
+        s0.append(rng.uniform(0.1, 1.0, nn))
+    for d in psd_sides[:-1]:
+        cones.append(PSDTriangleConeT(d))
+        s0.append(_psd_s0(rng, d))
+    for _ in range(nexp):
+        cones.append(ExponentialConeT())
+        s0.append(rng.uniform(0.5, 2.0) * np.array([-1.051383945322714, 0.556409619469370, 1.258967884768947]))
+    for _ in range(npow):
+        a = float(rng.uniform(0.1, 0.9))
+        cones.append(PowerConeT(a))
+        s0.append(rng.uniform(0.5, 2.0) * np.array([np.sqrt(1.0 + a), np.sqrt(2.0 - a), 0.0]))
+    for _ in range(ngenpow):
+        d1, d2 = int(rng.integers(2, 5)), int(rng.integers(1, 4))
+        a = rng.uniform(0.2, 1.0, d1)
+        a = a / a.sum()
+        a[-1] = 1.0 - a[:-1].sum()
+        cones.append(GenPowerConeT(tuple(float(v) for v in a), d2))
+        s0.append(rng.uniform(0.5, 2.0) * np.concatenate([np.sqrt(1.0 + a), np.zeros(d2)]))
+    if socdim:
+        cones.append(SecondOrderConeT(socdim))
+        v = rng.standard_normal(socdim - 1)
+        s0.append(np.concatenate([[1.0 + np.linalg.norm(v)], v]))
+    for d in psd_sides[-1:]:
+        cones.append(PSDTriangleConeT(d))
+        s0.append(_psd_s0(rng, d))
+    s0 = np.concatenate(s0)
+    m = s0.size
+    A = _sparse_rows(rng, m, n, kA)
+    P = _psd_P(rng, n, 2)
+    x0 = rng.standard_normal(n)
+    b = A @ x0 + s0
+    q = rng.standard_normal(n)
+    return P, q, A, b, cones

@@ -86,4 +86,10 @@ class Settings:
     # the default start stay on the host, whatever device_scaling_psd / device_default_start say; sides above 128 keep the host loop.
     # Needs device_step_psd: the caller raises ValueError otherwise.
     device_step_psd_large: bool = False
+    # device_step for cone sets that hold PSD triangle cones of side <= 64 next to Exponential / Power cones -- and next to Generalized
+    # Power cones when device_step_genpower is set -- (hipkkt_step_enable_mixed: each family's kernels composed, plus the log-det
+    # barrier of the PSD cones for the Dual strategy's search).  The PSD factors follow device_scaling_psd as in a symmetric set; the
+    # unit initialisation stays on the host.  A PSD side above 64 in such a set keeps the host loop.  Needs device_step_nonsymmetric
+    # and device_step_psd: the caller raises ValueError otherwise.
+    device_step_mixed: bool = False
     extra: dict = field(default_factory=dict)

@@ -77,7 +77,8 @@ int32_t hipkkt_is_available(void);
  *    HIPKKT_PSD_STEP_MAX_DIM / hipkkt_step_enable_psd / hipkkt_psd_set_factors / hipkkt_psd_set_factors_dev;
  *    hipkkt_psd_scaling_enable / hipkkt_psd_get_factors;
  *    hipkkt_cone_set_identity_scaling / hipkkt_cone_margins / hipkkt_cone_shift_to_interior / hipkkt_step_default_start_dev;
- *    HIPKKT_PSD_STEP_LARGE_MAX_DIM / hipkkt_step_enable_psd_large. */
+ *    HIPKKT_PSD_STEP_LARGE_MAX_DIM / hipkkt_step_enable_psd_large;
+ *    hipkkt_step_enable_mixed. */
 #define HIPKKT_ABI_VERSION 5
 int32_t hipkkt_abi_version(void);
 /* releases the process-wide cache of device memory blocks the library keeps between handles (not in the reference: an embedding
@@ -378,7 +379,7 @@ int32_t hipkkt_residuals_dev(hipkkt_handle h, const double *xzs_dev, double tau,
  *     off(M) <= eps |M|_F; an M with a non-finite entry gives a NaN gamma and therefore alpha_max, as the reference's comparison does.
  * One workgroup per cone, matrices in LDS, every k-sum of a product in ascending order (deterministic; the association differs from
  * the host's BLAS, so results agree to rounding, not bit for bit).  Rows of kinds 0..2 go through the same kernels as without the
- * enable, bit for bit.  Kinds 4..6 next to a PSD cone stay refused.
+ * enable, bit for bit.  Kinds 4..6 next to a PSD cone stay refused here; they have their own opt-in, last in this list.
  *
  * Opt-in for PSDTriangleCone of side 65 .. HIPKKT_PSD_STEP_LARGE_MAX_DIM: hipkkt_step_enable_psd_large accepts what hipkkt_step_enable_psd
  * accepts with every PSD side <= HIPKKT_PSD_STEP_LARGE_MAX_DIM, and the same calls then serve all rows of the handle from the same
@@ -396,6 +397,23 @@ int32_t hipkkt_residuals_dev(hipkkt_handle h, const double *xzs_dev, double tau,
  * hipkkt_cone_margins, hipkkt_cone_shift_to_interior and hipkkt_step_default_start_dev return HIPKKT_ERR_ARGUMENT (their kernels
  * keep whole matrices in LDS); with every side <= HIPKKT_PSD_STEP_MAX_DIM they behave as after hipkkt_step_enable_psd.  Sides above
  * HIPKKT_PSD_STEP_LARGE_MAX_DIM keep the host loop.
+ *
+ * Opt-in for PSDTriangleCone next to kinds 4..6: after hipkkt_step_enable_mixed on a registration (hipkkt_set_cone_types_ex) of kinds
+ * {0, .., 6} with at least one 3, at least one of 4 / 5 / 6 and every PSD side <= HIPKKT_PSD_STEP_MAX_DIM, every call of this section
+ * serves all rows of that handle.  Each family's rows go through the kernels of its own paragraph above: kinds 0..2 and 4..6 bit for
+ * bit as on a handle without the PSD cones, the PSD rows bit for bit as after hipkkt_step_enable_psd, from the same (R, Rinv, lambda)
+ * protocol (hipkkt_psd_set_factors[_dev] + psd_R per hipkkt_update_scaling_ex[_dev], or hipkkt_psd_scaling_enable).
+ *   step length = the composite rule: the pair of the kind 0..2 rows and of the PSD cones first (the minimum of the PSD paragraph),
+ *     then the kind 4 / 5 / 6 cones backtrack from alpha0 = min(that, 1 - sqrt(eps)) on the grid alpha0 step^k as above;
+ *   barrier: hipkkt_cone_barrier / hipkkt_step_barrier_dev add, per PSD cone, compute_barrier of coneops_psdtrianglecone.jl:256-290:
+ *     Q = svec_to_mat(x + alpha dx), a right-looking lower Cholesky (k-sums in ascending order; a pivot that is not > 0 or not finite
+ *     ends it), logdet = dd + dd with dd = sum_j log l_jj in ascending j, +Inf after a failed factorisation, and the cone's term
+ *     (0 - logdet_z) - logdet_s, the terms added in PSD-cone order behind the other cones' sum.  As in the reference a shifted point
+ *     outside a PSD cone therefore gives -Inf, not +Inf (`barrier -= typemax(T)`); in a solve the step length has bounded alpha inside.
+ *     One workgroup per (cone, candidate, z | s), the matrix in LDS: hence the side limit.
+ * A PSD side of 65 .. HIPKKT_PSD_STEP_LARGE_MAX_DIM next to a kind 4..6 cone keeps the host loop, and so does the default start of such
+ * a set (the hipkkt_cone_set_identity_scaling group returns HIPKKT_ERR_ARGUMENT): a non-symmetric set starts from the caller's unit
+ * initialisation.  Every other hipkkt_step_enable_* keeps refusing such a registration.
  *
  * One operation each, host vectors of length m in cone order (the unit-tested surface):
  *   hipkkt_cone_affine_ds            ds = lambda o lambda                  coneops_nncone.jl affine_ds!, coneops_socone.jl:219-228
@@ -432,7 +450,12 @@ int32_t hipkkt_step_enable_psd(hipkkt_handle h, int32_t enable);
  * HIPKKT_PSD_STEP_LARGE_MAX_DIM.  Enabling invalidates the resident scaling and allocates the larger cones' workspace.  enable == 0
  * does what hipkkt_step_enable_psd(h, 0) does.  Every hipkkt_set_cone_types[_ex] clears it. */
 int32_t hipkkt_step_enable_psd_large(hipkkt_handle h, int32_t enable);
-/* The factors of the PSD cones' scaling for the step (HIPKKT_ERR_ARGUMENT before hipkkt_step_enable_psd): Rinv_all = the cones' Rinv, each
+/* enable != 0: HIPKKT_ERR_ARGUMENT, and the handle as it was, unless the last hipkkt_set_cone_types_ex names kinds {0, .., 6} only with at
+ * least one 3, at least one of 4 / 5 / 6 and every PSD side <= HIPKKT_PSD_STEP_MAX_DIM; the parameter checks, the trip bound and the
+ * invalidation of the resident scaling are those of hipkkt_step_enable_cone3, the tables and factor buffers those of
+ * hipkkt_step_enable_psd.  enable == 0 switches it off.  Every hipkkt_set_cone_types[_ex] clears it. */
+int32_t hipkkt_step_enable_mixed(hipkkt_handle h, int32_t enable, double linesearch_backtrack_step, double min_terminate_step_length);
+/* The factors of the PSD cones' scaling for the step (HIPKKT_ERR_ARGUMENT before hipkkt_step_enable_psd / _mixed): Rinv_all = the cones' Rinv, each
  * n x n column-major, concatenated like psd_R; lambda_all = the cones' lambda, n each, concatenated.  They are staged and consumed by
  * the next hipkkt_update_scaling[_ex][_dev]; on an enabled handle that call needs a non-NULL psd_R and factors staged since the last
  * scaling, otherwise it returns HIPKKT_ERR_ARGUMENT and the step calls stay refused until a scaling succeeds.  A lambda entry that is
@@ -440,7 +463,7 @@ int32_t hipkkt_step_enable_psd_large(hipkkt_handle h, int32_t enable);
  * next synchronising call on this handle has returned (the rule of hipkkt_set_hs_dev). */
 int32_t hipkkt_psd_set_factors(hipkkt_handle h, const double *Rinv_all, const double *lambda_all);
 int32_t hipkkt_psd_set_factors_dev(hipkkt_handle h, const double *Rinv_all, const double *lambda_all);
-/* Opt-in on top of hipkkt_step_enable_psd (HIPKKT_ERR_ARGUMENT before it): the Cholesky / SVD of update_scaling!(::PSDTriangleCone),
+/* Opt-in on top of hipkkt_step_enable_psd / _mixed (HIPKKT_ERR_ARGUMENT before it): the Cholesky / SVD of update_scaling!(::PSDTriangleCone),
  * coneops_psdtrianglecone.jl:78-143, on the device.  On an enabled handle a hipkkt_update_scaling[_ex][_dev] with psd_R == NULL and no
  * factors staged computes, from the (s, z) of that call and per PSD cone (one workgroup each, everything in LDS, same stream, the call
  * keeps its single host synchronisation):
@@ -460,7 +483,7 @@ int32_t hipkkt_psd_set_factors_dev(hipkkt_handle h, const double *Rinv_all, cons
  * factors the call does what it does without this enable.  Enabling or disabling invalidates the resident scaling; enable == 0
  * switches it off, and so do hipkkt_step_enable_psd and every hipkkt_set_cone_types[_ex]. */
 int32_t hipkkt_psd_scaling_enable(hipkkt_handle h, int32_t enable);
-/* The resident factors of the last scaling of a handle in PSD step mode, whoever computed them (K.data.R, .Rinv, .lambda of
+/* The resident factors of the last scaling of a handle in PSD or mixed step mode, whoever computed them (K.data.R, .Rinv, .lambda of
  * coneops_psdtrianglecone.jl:112-131): R and Rinv n x n column-major per cone, concatenated like psd_R, lambda n per cone.  Host
  * pointers, any may be NULL.  HIPKKT_ERR_ARGUMENT when no scaling call has completed since the enable; after a call that reported
  * *scaling_ok = 0 the failed cones' entries are NaN. */
@@ -468,7 +491,8 @@ int32_t hipkkt_psd_get_factors(hipkkt_handle h, double *R_out, double *Rinv_out,
 /* compute_barrier of the cone set (Zero 0, Nonnegative -sum log((s + a ds)(z + a dz)), coneops_socone.jl:288-305,
  * coneops_expcone.jl:189-248, coneops_powcone.jl:228-251) and dot_shifted (mathutils.jl:23-43) at nalpha <= 8 candidate step lengths:
  * out[2 j] = the barrier, out[2 j + 1] = <z + a_j dz, s + a_j ds>, both summed over fixed slices in a fixed order.  A point outside a
- * cone gives +Inf or what logsafe gives.  dz, ds: host vectors of length m; (s, z) are the resident ones.
+ * cone gives +Inf or what logsafe gives; after hipkkt_step_enable_mixed the PSD cones' -logdet(Z + a dZ) - logdet(S + a dS) is added
+ * (coneops_psdtrianglecone.jl:256-290), -Inf for a point outside such a cone.  dz, ds: host vectors of length m; (s, z) are the resident ones.
  * hipkkt_step_barrier_dev: the same for the iterate xzs_dev = [x | z | s] and the resident step of the last fused call; one host
  * synchronisation per call. */
 int32_t hipkkt_cone_barrier(hipkkt_handle h, const double *dz, const double *ds, const double *alphas, int64_t nalpha, double *out);

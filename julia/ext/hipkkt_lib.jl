@@ -143,6 +143,13 @@ function hip_step_enable_psd_large!(handle::Ptr{Cvoid}, enable::Bool)
     rc = ccall((:hipkkt_step_enable_psd_large, libhipkkt), Int32, (Ptr{Cvoid}, Int32), handle, enable ? 1 : 0)
     return hip_step_check(handle, rc, "hipkkt_step_enable_psd_large")
 end
+# PSD triangle cones (side <= 64) next to Exponential / Power / Generalized Power cones: each family steps as after its own enable, the
+# barrier calls add the PSD cones' log-det barrier; sides above 64 in such a set and its unit initialisation stay with the caller
+function hip_step_enable_mixed!(handle::Ptr{Cvoid}, enable::Bool, backtrack_step::Float64, min_terminate_step_length::Float64)
+    rc = ccall((:hipkkt_step_enable_mixed, libhipkkt), Int32, (Ptr{Cvoid}, Int32, Float64, Float64), handle, enable ? 1 : 0,
+               backtrack_step, min_terminate_step_length)
+    return hip_step_check(handle, rc, "hipkkt_step_enable_mixed")
+end
 # Rinv_all: the cones' Rinv (n x n column-major each, concatenated like psd_R), λ_all: their λ; consumed by the next hip update_scaling
 function hip_psd_set_factors!(handle::Ptr{Cvoid}, Rinv_all::Vector{Float64}, λ_all::Vector{Float64})
     rc = ccall((:hipkkt_psd_set_factors, libhipkkt), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), handle, Rinv_all, λ_all)

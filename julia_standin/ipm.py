@@ -404,6 +404,10 @@ class Solver:
             raise ValueError("Settings.device_scaling_psd needs device_step_psd")
         if getattr(st, "device_step_psd_large", False) and not getattr(st, "device_step_psd", False):
             raise ValueError("Settings.device_step_psd_large needs device_step_psd")
+        if getattr(st, "device_step_mixed", False) and not getattr(st, "device_step_nonsymmetric", False):
+            raise ValueError("Settings.device_step_mixed needs device_step_nonsymmetric")
+        if getattr(st, "device_step_mixed", False) and not getattr(st, "device_step_psd", False):
+            raise ValueError("Settings.device_step_mixed needs device_step_psd")
         if getattr(st, "device_default_start", False) and not getattr(st, "device_step", False):
             raise ValueError("Settings.device_default_start needs device_step")
         self._device_step = bool(getattr(st, "device_step", False)) and hasattr(ks, "kktsolver_step_affine") and \
@@ -416,7 +420,8 @@ class Solver:
                 hasattr(ks, "kktsolver_update_scaling_dev_ex") and hasattr(ks, "kktsolver_step_barrier") and \
                 all(getattr(c, "is_symmetric", True) or getattr(c, "kind_code_ex", -1) in kinds_ok for c in self.cones)
         # a symmetric set with PSD members (Settings.device_step_psd, a plugin with steps_psd): the loop of _solve_device_step, with the
-        # Cholesky / SVD of the PSD cones' scaling done here before every scaling call
+        # Cholesky / SVD of the PSD cones' scaling done here before every scaling call; with Settings.device_step_mixed (a plugin with
+        # steps_mixed) the same holds for PSD members next to non-symmetric ones, in the loop of _solve_device_step_nonsymmetric
         self._device_step_psd = self._device_step and bool(getattr(ks, "steps_psd", False))
         # ... or done by the plugin from the resident (s, z) (Settings.device_scaling_psd, a plugin with scales_psd).  The host cones'
         # R / Rinv / lam / _hs_valid then keep what set_identity_scaling left for the default start: nothing in _solve_device_step reads
@@ -797,7 +802,9 @@ class Solver:
         """_solve_device_step for Settings.device_step_nonsymmetric: the loop of _solve with its three strategy checkpoints
         (solver.jl:453-506), fed by scalars.  mu and the strategy go to the scaling call; a re-run with the Dual strategy applies no
         step, so the resident iterate is reused; under Dual the combined step is backtracked to the barrier (solver.jl:427-445) with
-        eight candidates per call.  The unit initialisation runs on the host and is uploaded once."""
+        eight candidates per call.  The unit initialisation runs on the host and is uploaded once.
+        With Settings.device_step_mixed the set may hold PSD triangle members: their Cholesky / SVD run here before every scaling call,
+        as in _solve_device_step, unless Settings.device_scaling_psd leaves them to the plugin."""
         st, info, data, cones = self.settings, self.info, self.data, self.cones
         v, r = self.variables, self.residuals
         ks = self.kktsystem.kktsolver
@@ -842,6 +849,15 @@ class Solver:
                         continue
                 break
             t0 = time.perf_counter()
+            if self._device_step_psd and not self._device_scaling_psd:
+                # as in _solve_device_step: the PSD rows of the resident (s, z) come to the host, the cones' own update_scaling! gives
+                # R, Rinv, lambda, and the plugin takes them along with its scaling call.  A PSD member that fails is a symmetric member
+                # failing update_scaling!: NUMERICAL_ERROR before the iteration counts
+                s_h, z_h = ks.psd_rows_download(xzs)
+                if not all(c.update_scaling(s_h[rr], z_h[rr], mu) for c, rr in zip(cones.cones, cones.rng_cones) if hasattr(c, "RRt")):
+                    tm["scale cones"] += time.perf_counter() - t0
+                    info.status = NUMERICAL_ERROR
+                    break
             ok = ks.kktsolver_update_scaling_dev_ex(xzs, mu, scaling)
             if not ok:
                 # which cone is not interior decides, as on the host path with device_scaling: a symmetric member fails update_scaling!

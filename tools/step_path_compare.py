@@ -6,7 +6,8 @@ wall time per iteration and of the stand-in's timers, the bytes the Python bindi
 (clarabel.jl_amd/hipkkt.py TRAFFIC) and hipkkt_box_probe go into ONE JSON line on stdout.
 Symmetric configurations (3, 2a, psd) get one more path: the last one with device_default_start added (the default start on the
 device as well), so that default_start_ms and the bytes of a whole solve stand next to the same path without it in the same run.
-usage: step_path_compare.py [--cfgs 3,2a,exp_pow,genpow,psd,psd_large] [--repeats 5] [--one-solve CFG [--third] [--start]]   (--one-solve: a single device_step solve, for a kernel trace)"""
+usage: step_path_compare.py [--cfgs 3,2a,exp_pow,genpow,psd,psd_large,mixed] [--repeats 5] [--one-solve CFG [--third] [--start] [--dual]]   (--one-solve: a single device_step solve, for a kernel trace; --dual: min_switch_step_length = 1, so that a
+non-symmetric set runs the Dual strategy and its barrier search in every iteration)"""
 import argparse
 import json
 import os
@@ -30,18 +31,28 @@ CONFIGS = {"3": ("portfolio_socp", problems.portfolio_socp), "2a": ("random_spar
            # scaling on the host; and a third path with device_scaling_psd, where the device does them too
            "psd": ("sdp_blocks", problems.sdp_blocks),
            # two PSD triangle cones of side 96: without device_step_psd_large the whole set keeps the host loop
-           "psd_large": ("sdp_blocks_2x96", lambda: problems.sdp_blocks(n=200, ncones=2, dim=96, seed=5))}
+           "psd_large": ("sdp_blocks_2x96", lambda: problems.sdp_blocks(n=200, ncones=2, dim=96, seed=5)),
+           # four PSD triangle cones of side 20 next to Exponential / Power cones: without device_step_mixed the set keeps the host loop;
+           # a third path with device_scaling_psd
+           "mixed": ("mixed_psd_nonsym_4x20",
+                     lambda: problems.mixed_psd_nonsym(n=80, psd_sides=[20] * 4, nexp=20, npow=10, ngenpow=0, nn=20, nzero=3, socdim=5,
+                                                       seed=5))}
 PARENT = dict(device_scaling=True, device_reduced=True, device_residuals=True)
 STEP_EXTRA = {"exp_pow": dict(device_step_nonsymmetric=True),
               "genpow": dict(device_step_nonsymmetric=True, device_step_genpower=True),
               "psd": dict(device_step_psd=True),
-              "psd_large": dict(device_step_psd=True, device_step_psd_large=True)}      # what device_step needs on top, per configuration
-THIRD = {"psd": ("device_step_and_scaling", dict(device_scaling_psd=True))}      # a further path on top of device_step, where there is one
+              "psd_large": dict(device_step_psd=True, device_step_psd_large=True),
+              "mixed": dict(device_step_nonsymmetric=True, device_step_psd=True, device_step_mixed=True)}      # what device_step needs on top, per configuration
+THIRD = {"psd": ("device_step_and_scaling", dict(device_scaling_psd=True)),
+         "mixed": ("device_step_and_scaling", dict(device_scaling_psd=True))}      # a further path on top of device_step, where there is one
 START = ("3", "2a", "psd")      # symmetric cone sets: the last path once more with device_default_start
 
 
-def one_solve(prob, **flags):
-    solver = cl.Solver(*prob, cl.Settings(**flags))
+def one_solve(prob, dual=False, **flags):
+    st = cl.Settings(**flags)
+    if dual:
+        st.min_switch_step_length = 1.0
+    solver = cl.Solver(*prob, st)
     for k in hipkkt.TRAFFIC:
         hipkkt.TRAFFIC[k] = 0
     sol = solver.solve()
@@ -50,7 +61,7 @@ def one_solve(prob, **flags):
     rec = dict(status=sol.status, iterations=sol.iterations, obj_val=sol.obj_val, device_step=bool(solver._device_step),
                ms_per_iteration=1e3 * tm["IP iteration"] / it,
                timers_ms_per_iteration={k: 1e3 * tm[k] / it for k in ("kkt update", "kkt solve", "scale cones")},
-               default_start_ms=1e3 * tm["default start"], device_default_start=bool(getattr(solver, "_device_default_start", False)),
+               barrier_searches=int(getattr(solver, "barrier_searches", 0)), default_start_ms=1e3 * tm["default start"], device_default_start=bool(getattr(solver, "_device_default_start", False)),
                h2d_bytes=hipkkt.TRAFFIC["h2d_bytes"], d2h_bytes=hipkkt.TRAFFIC["d2h_bytes"],
                h2d_bytes_per_iteration=hipkkt.TRAFFIC["h2d_bytes"] / it, d2h_bytes_per_iteration=hipkkt.TRAFFIC["d2h_bytes"] / it)
     return rec
@@ -71,11 +82,12 @@ def main():
     ap.add_argument("--cfgs", default="3,2a")
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--one-solve", default=None)
-    ap.add_argument("--third", action="store_true", help="--one-solve with the configuration's third path (psd: device_scaling_psd)")
+    ap.add_argument("--third", action="store_true", help="--one-solve with the configuration's third path (psd, mixed: device_scaling_psd)")
+    ap.add_argument("--dual", action="store_true", help="--one-solve with min_switch_step_length = 1 (the Dual strategy throughout)")
     ap.add_argument("--start", action="store_true", help="--one-solve with device_default_start (symmetric configurations)")
     args = ap.parse_args()
     if args.one_solve:
-        rec = one_solve(CONFIGS[args.one_solve][1](), device_step=True, **PARENT, **STEP_EXTRA.get(args.one_solve, {}),
+        rec = one_solve(CONFIGS[args.one_solve][1](), dual=args.dual, device_step=True, **PARENT, **STEP_EXTRA.get(args.one_solve, {}),
                         **(THIRD[args.one_solve][1] if args.third and args.one_solve in THIRD else {}),
                         **(dict(device_default_start=True) if args.start and args.one_solve in START else {}))
         print(json.dumps({"cfg": args.one_solve, "device_step": rec}))
