@@ -27,9 +27,7 @@ namespace {
 constexpr int kBarPsdMax = 8;      // candidates per launch: step3_max_candidates()
 constexpr int kBarPsdSlots = 2 * kBarPsdMax;      // doubles per PSD cone: [(0 - logdet_z) | logdet_s] per candidate
 
-struct BarPsdAlphas { double a[kBarPsdMax]; };
-
-__device__ __forceinline__ bool pos_finite(double v) { return v > 0.0 && v - v == 0.0; }
+struct BarPsdAlphas { double a[kBarPsdMax]; };      // (pos_finite of the pivot test: psd_cone.h)
 
 }  // namespace
 
@@ -105,13 +103,13 @@ k_bar_psd_add(const double *__restrict__ slots, int npsd, int nalpha, double *__
 double *psd_barrier_slots(double *work, int nsoc, int n3, int ngp) {
     return step3_barrier_gppart(work, nsoc, n3) + (int64_t)kBarPsdMax * (ngp > 0 ? ngp : 0);
 }
-void launch_psd_barrier(hipStream_t st, int npsd, const int64_t *tab, const double *z, const double *s, const double *dz, const double *ds,
+void launch_psd_barrier(hipStream_t st, const PsdView &P, const double *z, const double *s, const double *dz, const double *ds,
                         const double *alphas, int nalpha, double *slots) {
-    if (npsd <= 0 || nalpha <= 0) return;
+    if (P.npsd <= 0 || nalpha <= 0) return;
     if (nalpha > kBarPsdMax) nalpha = kBarPsdMax;
     BarPsdAlphas A;
     for (int j = 0; j < kBarPsdMax; j++) A.a[j] = j < nalpha ? alphas[j] : 0.0;
-    hipLaunchKernelGGL(k_bar_psd, dim3(npsd, nalpha, 2), dim3(256), 0, st, tab, z, s, dz, ds, A, slots);
+    hipLaunchKernelGGL(k_bar_psd, dim3(P.npsd, nalpha, 2), dim3(256), 0, st, P.tab, z, s, dz, ds, A, slots);
 }
 void launch_psd_barrier_add(hipStream_t st, int npsd, const double *slots, int nalpha, double *out) {
     if (npsd <= 0 || nalpha <= 0) return;

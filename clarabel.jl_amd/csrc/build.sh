@@ -25,24 +25,15 @@ for f in $KSRC; do
   $HIPCC $FLAGS -c $f -o $OBJ/${f%.hip}.o & pids+=($!)
 done
 $HIPCC $FLAGS -c front_block.hip -o $OBJT/front_block.o & pids+=($!)
-# scaling.hip mirrors the reference's cone formulas operation by operation: no FMA contraction
-$HIPCC $FLAGS -ffp-contract=off -c scaling.hip -o $OBJ/scaling.o & pids+=($!)
-# step.hip does the same for the cone algebra of an interior-point step
-$HIPCC $FLAGS -ffp-contract=off -c step.hip -o $OBJ/step.o & pids+=($!)
-# step_cone3.hip: the same for the Exponential / Power cones (shares cone3_math.h with scaling.hip)
-$HIPCC $FLAGS -ffp-contract=off -c step_cone3.hip -o $OBJ/step_cone3.o & pids+=($!)
-# step_genpow.hip: the same for the Generalized Power cones, one wavefront per cone
-$HIPCC $FLAGS -ffp-contract=off -c step_genpow.hip -o $OBJ/step_genpow.o & pids+=($!)
-# step_psd.hip: the same for the PSD triangle cones, one workgroup per cone, the smallest eigenvalue by Jacobi sweeps in LDS
-$HIPCC $FLAGS -ffp-contract=off -c step_psd.hip -o $OBJ/step_psd.o & pids+=($!)
-# step_psd_large.hip: the same arithmetic for PSD sides 65 .. 128, matrices in global memory, products as batched tile launches
-$HIPCC $FLAGS -ffp-contract=off -c step_psd_large.hip -o $OBJ/step_psd_large.o & pids+=($!)
-# scaling_psd.hip: the Cholesky / SVD of the PSD cones' Nesterov-Todd scaling, one workgroup per cone, rounded product by product
-$HIPCC $FLAGS -ffp-contract=off -c scaling_psd.hip -o $OBJ/scaling_psd.o & pids+=($!)
-# start.hip: the default start (identity scaling, margins, shift into the cones); shares the Jacobi sweeps of psd_cone.h with step_psd.hip
-$HIPCC $FLAGS -ffp-contract=off -c start.hip -o $OBJ/start.o & pids+=($!)
-# barrier_psd.hip: the log-det barrier of the PSD cones of a set with non-symmetric members, one workgroup per (cone, candidate, side)
-$HIPCC $FLAGS -ffp-contract=off -c barrier_psd.hip -o $OBJ/barrier_psd.o & pids+=($!)
+# The cone kernels mirror the reference's formulas operation by operation, and the reference modules of tests/ emulate their rounding
+# order: no FMA contraction.  scaling.hip, step.hip: the scaling and the step's cone algebra of the symmetric cones; step_cone3.hip,
+# step_genpow.hip: the step of the Exponential / Power and the Generalized Power cones; step_psd.hip, step_psd_large.hip,
+# scaling_psd.hip, barrier_psd.hip: step, Nesterov-Todd scaling and barrier of the PSD triangle cones (psd_cone.h); start.hip: the
+# default start
+KSRC_NOCONTRACT="scaling.hip step.hip step_cone3.hip step_genpow.hip step_psd.hip step_psd_large.hip scaling_psd.hip start.hip barrier_psd.hip"
+for f in $KSRC_NOCONTRACT; do
+  $HIPCC $FLAGS -ffp-contract=off -c $f -o $OBJ/${f%.hip}.o & pids+=($!)
+done
 for p in "${pids[@]}"; do wait $p; done
 COMMON="$OBJ/hipkkt_solve.o $OBJ/hipkkt_cones.o $OBJ/hipkkt_step.o $OBJ/symbolic.o $OBJ/solve_schedule.o $OBJ/ordering.o $OBJ/assemble.o $OBJ/assemble_dev.o $OBJ/scaling.o $OBJ/step.o $OBJ/step_cone3.o $OBJ/step_genpow.o $OBJ/step_psd.o $OBJ/step_psd_large.o $OBJ/scaling_psd.o $OBJ/start.o $OBJ/barrier_psd.o $OBJ/front_block2.o $OBJ/front_sweep.o $OBJ/probe.o $OBJ/kernels.o $OBJ/values.o $OBJ/solve_sweep.o $OBJ/refine.o"
 $HIPCC --offload-arch=gfx950 -shared -fPIC -o ../libclarabel_hipkkt.so $OBJ/hipkkt_abi.o $OBJ/hipkkt_setup.o $OBJ/hipkkt_factor.o $COMMON

@@ -58,11 +58,9 @@ struct ConeTables {
     const int64_t *gpdesc = nullptr;
     const double *gpalpha = nullptr;
     double mu = 0.0;
-    // Psd / Mixed: the PSD triangle cones' table and factors
-    int npsd = 0;
-    const int64_t *psdtab = nullptr;
-    const double *psdR = nullptr, *psdRinv = nullptr, *psdlam = nullptr;
-    PsdLargeBatch large;      // ... and those of them step_psd_large.hip serves (hipkkt_step_enable_psd_large; none otherwise)
+    // Psd / Mixed: the PSD triangle cones' table and factors, and those of them step_psd_large.hip serves (hipkkt_step_enable_psd_large;
+    // none otherwise, and none in a Mixed set: no side above 64)
+    PsdView psd;
     // the backtracking line search of the non-symmetric cones decides the step length
     bool line_search() const { return mode == StepMode::Cone3 || mode == StepMode::GenPow || mode == StepMode::Mixed; }
 };
@@ -73,23 +71,22 @@ static ConeTables tables(hipkkt_solver *S) {
     T.m = S->img.m;
     T.kind = C.tab.kind; T.nsoc = C.reg.nsoc; T.desc = C.tab.socdesc;
     T.s = C.tab.sz; T.z = C.tab.sz + T.m; T.w = C.tab.wl; T.lam = C.tab.wl + T.m; T.eta = C.tab.eta;
+    if (T.mode == StepMode::Psd || T.mode == StepMode::Mixed) {
+        T.psd.npsd = (int)C.reg.psd_n.size(); T.psd.tab = C.tab.psdtab; T.psd.R = C.tab.R; T.psd.Rinv = C.tab.psd_rinv; T.psd.lam = C.tab.psd_lam;
+        if (C.step.psd_nlarge > 0) T.psd.large = PsdLargeBatch{C.step.psd_nlarge, C.tab.psd_lidx, C.step.psd_lmin, C.step.psd_lmax, C.tab.psd_ws};
+    }
     switch (T.mode) {
         case StepMode::Off:
         case StepMode::Symmetric:
+        case StepMode::Psd:
             break;
-        case StepMode::Mixed:      // the PSD fields (no side above 64: no large batch), then every non-symmetric field
-            T.npsd = (int)C.reg.psd_n.size(); T.psdtab = C.tab.psdtab; T.psdR = C.tab.R; T.psdRinv = C.tab.psd_rinv; T.psdlam = C.tab.psd_lam;
-            [[fallthrough]];
+        case StepMode::Mixed:      // every non-symmetric field
         case StepMode::GenPow:
             T.ngp = C.reg.ngenpow; T.gpdesc = C.tab.gpdesc; T.gpalpha = C.tab.gpalpha; T.mu = C.step.mu;
             [[fallthrough]];      // and the three-row members of the set
         case StepMode::Cone3:
             T.nexp = C.reg.nexp; T.npow = C.reg.npow; T.n3 = T.nexp + T.npow;
             T.row0 = C.tab.row0; T.out0 = C.tab.out0; T.alpha = C.tab.alpha; T.nsout = C.tab.nsout;
-            break;
-        case StepMode::Psd:
-            T.npsd = (int)C.reg.psd_n.size(); T.psdtab = C.tab.psdtab; T.psdR = C.tab.R; T.psdRinv = C.tab.psd_rinv; T.psdlam = C.tab.psd_lam;
-            if (C.step.psd_nlarge > 0) T.large = PsdLargeBatch{C.step.psd_nlarge, C.tab.psd_lidx, C.step.psd_lmin, C.step.psd_lmax, C.tab.psd_ws};
             break;
     }
     return T;
@@ -102,29 +99,41 @@ static void op_affine_ds(hipStream_t st, const ConeTables &T, double *out) {
     launch_step_affine_ds(st, T.kind, T.nsoc, T.desc, T.lam, out, T.m);
     launch_step3_copy(st, T.n3, T.row0, T.s, out);
     launch_genpow_copy(st, T.ngp, T.gpdesc, T.s, out);
-    launch_psd_step_affine_ds(st, T.npsd, T.psdtab, T.psdlam, out);
-    launch_psd_large_affine_ds(st, T.large, T.psdtab, T.psdlam, out);
+    launch_psd_step_affine_ds(st, T.psd, out);
+    launch_psd_large_affine_ds(st, T.psd, out);
 }
 static void op_shift(hipStream_t st, const ConeTables &T, const double *dz, const double *ds, double sigma_mu, double *out) {
     launch_step_shift(st, T.kind, T.nsoc, T.desc, T.w, T.eta, dz, ds, sigma_mu, out, T.m);
     if (T.n3) launch_step3_shift(st, T.nexp, T.npow, T.row0, T.out0, T.alpha, T.nsout, T.z, dz, ds, sigma_mu, out);
     launch_genpow_shift(st, T.ngp, T.gpdesc, T.nsout, sigma_mu, out);
-    launch_psd_step_shift(st, T.npsd, T.psdtab, T.psdR, T.psdRinv, dz, ds, sigma_mu, out);
-    launch_psd_large_shift(st, T.large, T.psdtab, T.psdR, T.psdRinv, T.psdlam, dz, ds, sigma_mu, out);
+    launch_psd_step_shift(st, T.psd, dz, ds, sigma_mu, out);
+    launch_psd_large_shift(st, T.psd, dz, ds, sigma_mu, out);
 }
 static void op_offset(hipStream_t st, const ConeTables &T, const double *ds, double *out) {
     launch_step_offset(st, T.kind, T.nsoc, T.desc, T.z, T.w, T.lam, T.eta, ds, out, T.m);
     launch_step3_copy(st, T.n3, T.row0, ds, out);
     launch_genpow_copy(st, T.ngp, T.gpdesc, ds, out);
-    launch_psd_step_offset(st, T.npsd, T.psdtab, T.psdR, T.psdlam, ds, out);
-    launch_psd_large_offset(st, T.large, T.psdtab, T.psdR, T.psdlam, ds, out);
+    launch_psd_step_offset(st, T.psd, ds, out);
+    launch_psd_large_offset(st, T.psd, ds, out);
 }
 static void op_mulhs(hipStream_t st, const ConeTables &T, const double *x, const double *addc, double *y) {
     launch_step_mulhs(st, T.kind, T.nsoc, T.desc, T.w, T.eta, x, addc, y, T.m);
     launch_step3_mulhs(st, T.n3, T.row0, T.out0, T.nsout, x, addc, y);
     launch_genpow_mulhs(st, T.ngp, T.gpdesc, T.nsout, T.mu, x, addc, y);
-    launch_psd_step_mulhs(st, T.npsd, T.psdtab, T.psdR, x, addc, y);
-    launch_psd_large_mulhs(st, T.large, T.psdtab, T.psdR, T.psdlam, x, addc, y);
+    launch_psd_step_mulhs(st, T.psd, x, addc, y);
+    launch_psd_large_mulhs(st, T.psd, x, addc, y);
+}
+// "symmetric cones first" of a set with PSD cones (Psd, Mixed): the symmetric rows' launch as it is, its pair parked at kStOutSymPsd;
+// the PSD cones' pairs follow its partials in `part` (2 (ceil(m / 256) + ncones) doubles: second-order and PSD cones together are at
+// most ncones); out2 = the minimum over kinds 0..3.  step_psd.hip parks alpha_max for a cone of side > 64, step_psd_large.hip
+// overwrites it before the final minimum reads it (a Mixed set has no such cone: that launcher returns without a launch)
+static void length_sym_psd(const ConeState::Step &St, hipStream_t st, const ConeTables &T, const double *dz, const double *ds,
+                           double alpha_max, double *out2) {
+    double *sym2 = St.out + kStOutSymPsd, *pairs = St.part + 2 * step_len_pairs(T.m, T.nsoc);
+    launch_step_length(st, T.kind, T.nsoc, T.desc, T.z, T.s, dz, ds, alpha_max, St.part, sym2, T.m);
+    launch_psd_step_length_cones(st, T.psd, dz, ds, alpha_max, pairs);
+    launch_psd_large_length(st, T.psd, dz, ds, alpha_max, pairs);
+    launch_psd_step_length_final(st, T.psd.npsd, sym2, pairs, out2);
 }
 // out2 = (alpha_z, alpha_s) of the symmetric cones; with Exponential / Power / Generalized Power cones the composite (alpha, alpha) of
 // coneops_compositecone.jl:216-252, started from min(alpha_tau, alpha_kappa, 1) when dtau (device) is given (variables.jl:14-43)
@@ -136,32 +145,17 @@ static void op_length(hipkkt_solver *S, hipStream_t st, const ConeTables &T, con
         case StepMode::Symmetric:
             launch_step_length(st, T.kind, T.nsoc, T.desc, T.z, T.s, dz, ds, alpha_max, St.part, out2, T.m);
             break;
-        case StepMode::Psd: {
-            // the symmetric rows' launch as it is, its pair parked at kStOutSymPsd; the PSD cones' pairs follow its partials in St.part
-            // (2 (ceil(m / 256) + ncones) doubles: second-order and PSD cones together are at most ncones)
-            double *sym2 = St.out + kStOutSymPsd;
-            launch_step_length(st, T.kind, T.nsoc, T.desc, T.z, T.s, dz, ds, alpha_max, St.part, sym2, T.m);
-            // step_psd.hip parks alpha_max for a cone of side > 64; step_psd_large.hip overwrites it before the final minimum reads it
-            double *pairs = St.part + 2 * step_len_pairs(T.m, T.nsoc);
-            launch_psd_step_length_cones(st, T.npsd, T.psdtab, T.psdR, T.psdRinv, T.psdlam, dz, ds, alpha_max, pairs);
-            launch_psd_large_length(st, T.large, T.psdtab, T.psdR, T.psdRinv, T.psdlam, dz, ds, alpha_max, pairs);
-            launch_psd_step_length_final(st, T.npsd, sym2, pairs, out2);
+        case StepMode::Psd:
+            length_sym_psd(St, st, T, dz, ds, alpha_max, out2);
             break;
-        }
         case StepMode::Mixed:
         case StepMode::Cone3:
         case StepMode::GenPow: {
             double *sym2 = St.out + kStOutSym;
-            if (T.mode == StepMode::Mixed) {
-                // "symmetric cones first" (coneops_compositecone.jl:216-252) includes the PSD cones: the three launches of the Psd arm
-                // leave the pair of kinds 0..3 at kStOutSym; the partials in St.part are consumed before the line search reuses it
-                double *sympsd2 = St.out + kStOutSymPsd, *pairs = St.part + 2 * step_len_pairs(T.m, T.nsoc);
-                launch_step_length(st, T.kind, T.nsoc, T.desc, T.z, T.s, dz, ds, alpha_max, St.part, sympsd2, T.m);
-                launch_psd_step_length_cones(st, T.npsd, T.psdtab, T.psdR, T.psdRinv, T.psdlam, dz, ds, alpha_max, pairs);
-                launch_psd_step_length_final(st, T.npsd, sympsd2, pairs, sym2);
-            } else {
-                launch_step_length(st, T.kind, T.nsoc, T.desc, T.z, T.s, dz, ds, alpha_max, St.part, sym2, T.m);
-            }
+            // "symmetric cones first" (coneops_compositecone.jl:216-252) includes the PSD cones of a Mixed set: the pair of kinds 0..3
+            // goes to kStOutSym; the partials in St.part are consumed before the line search reuses it
+            if (T.mode == StepMode::Mixed) length_sym_psd(St, st, T, dz, ds, alpha_max, sym2);
+            else launch_step_length(st, T.kind, T.nsoc, T.desc, T.z, T.s, dz, ds, alpha_max, St.part, sym2, T.m);
             // (St.part holds 2 (ceil(m / 256) + ncones) doubles: room for the three-row workgroups' partials and one per Generalized Power cone)
             launch_genpow_length(st, T.ngp, T.gpdesc, T.gpalpha, T.z, T.s, dz, ds, sym2, dtau, tau, kappa, rhs_kappa, alpha_max,
                                  St.ls_step, St.ls_amin, St.ls_trips, St.part + step3_length_parts(T.nexp, T.npow));
@@ -293,11 +287,11 @@ static void barrier_impl(hipkkt_solver *S, const ConeTables &T, const double *z,
     // cone, 16 per PSD cone)
     double *bar = S->cones.step.bar;
     double *psd_slots = psd_barrier_slots(bar, T.nsoc, T.n3, T.ngp);
-    launch_psd_barrier(S->stream, T.npsd, T.psdtab, z, s, dz, ds, alphas, (int)nalpha, psd_slots);
+    launch_psd_barrier(S->stream, T.psd, z, s, dz, ds, alphas, (int)nalpha, psd_slots);
     launch_genpow_barrier(S->stream, T.ngp, T.gpdesc, T.gpalpha, z, s, dz, ds, alphas, (int)nalpha, step3_barrier_gppart(bar, T.nsoc, T.n3));
     launch_step3_barrier(S->stream, T.kind, T.nsoc, T.desc, T.nexp, T.npow, T.row0, T.alpha, z, s, dz, ds, alphas, (int)nalpha, bar, dout,
                          T.m, T.ngp);
-    launch_psd_barrier_add(S->stream, T.npsd, psd_slots, (int)nalpha, dout);
+    launch_psd_barrier_add(S->stream, T.psd.npsd, psd_slots, (int)nalpha, dout);
 }
 
 // the parameter checks, the trip bound and the invalidation both enables share; the handle is in `mode` afterwards
@@ -657,9 +651,9 @@ static void start_identity(hipkkt_solver *S) {
     ConeState &C = S->cones;
     const ConeTables T = tables(S);
     int64_t max_numel = 0;
-    if (T.npsd) for (int64_t n : C.reg.psd_n) max_numel = std::max(max_numel, n * (n + 1) / 2);
-    launch_start_identity(S->stream, C.tab.kind, C.tab.rowhs, S->d_mapHs, T.nsoc, T.desc, S->soc.d_u, S->soc.d_v, S->soc.d_eta2, T.npsd,
-                          T.psdtab, C.tab.psd_hs0, max_numel, S->dp.kval, T.m);
+    if (T.psd.npsd) for (int64_t n : C.reg.psd_n) max_numel = std::max(max_numel, n * (n + 1) / 2);
+    launch_start_identity(S->stream, C.tab.kind, C.tab.rowhs, S->d_mapHs, T.nsoc, T.desc, S->soc.d_u, S->soc.d_v, S->soc.d_eta2, T.psd,
+                          C.tab.psd_hs0, max_numel, S->dp.kval, T.m);
     if (S->soc.n > 0)      // u, v, D entries of the sparse cones (the same kernel hipkkt_set_soc_batch uses)
         launch_soc_batch(S->stream, S->dp.kval, S->soc.d_uidx, S->soc.d_vidx, S->soc.d_cone, S->soc.d_u, S->soc.d_v, S->soc.d_eta2,
                          S->soc.total, S->soc.d_didx, S->soc.n);
@@ -679,9 +673,9 @@ static int32_t start_host_op(hipkkt_solver *S, double *v, int32_t pd, bool shift
     S->ensure_stage(m);
     double *dv = S->d_stage, *dec = start_decision(C.step.start, ncones);
     if (m) HK_CHECK(hipMemcpyAsync(dv, v, m * sizeof(double), hipMemcpyHostToDevice, S->stream));
-    launch_start_margins(S->stream, T.kind, T.nsoc, T.desc, T.npsd, T.psdtab, dv, nullptr, 1, (double)C.reg.degree, C.step.start, ncones, m);
+    launch_start_margins(S->stream, T.kind, T.nsoc, T.desc, T.psd, dv, nullptr, 1, (double)C.reg.degree, C.step.start, ncones, m);
     if (shift) {
-        launch_start_shift(S->stream, T.kind, T.nsoc, T.desc, T.npsd, T.psdtab, dec, dv, pd, nullptr, 0, 1, m);
+        launch_start_shift(S->stream, T.kind, T.nsoc, T.desc, T.psd, dec, dv, pd, nullptr, 0, 1, m);
         if (m) HK_CHECK(hipMemcpyAsync(v, dv, m * sizeof(double), hipMemcpyDeviceToHost, S->stream));
     }
     copy_sync(S->stream, out, dec, (size_t)nout * sizeof(double), hipMemcpyDeviceToHost);
@@ -750,8 +744,8 @@ int32_t hipkkt_step_default_start_dev(hipkkt_handle h, double *xzs_dev, int32_t 
     double *s_dev = xzs_dev + n + m, *z_dev = xzs_dev + n;
     const std::function<void(hipStream_t)> after = [&](hipStream_t st) {
         launch_start_assemble(st, xzs_dev, sa, pair ? sb : nullptr, n, m);
-        launch_start_margins(st, T.kind, T.nsoc, T.desc, T.npsd, T.psdtab, s_dev, z_dev, 2, (double)C.reg.degree, C.step.start, ncones, m);
-        launch_start_shift(st, T.kind, T.nsoc, T.desc, T.npsd, T.psdtab, dec, s_dev, 0, z_dev, 1, 2, m);
+        launch_start_margins(st, T.kind, T.nsoc, T.desc, T.psd, s_dev, z_dev, 2, (double)C.reg.degree, C.step.start, ncones, m);
+        launch_start_shift(st, T.kind, T.nsoc, T.desc, T.psd, dec, s_dev, 0, z_dev, 1, 2, m);
         HK_CHECK(hipMemcpyAsync(h16, dec, 2 * 8 * sizeof(double), hipMemcpyDeviceToHost, st));
     };
     double *outs[kNumCtx] = {sa, sb};

@@ -146,51 +146,50 @@ void launch_genpow_length(hipStream_t st, int ngp, const int64_t *desc, const do
                           double rhs_kappa, double alpha_max, double step, double alpha_min, int trips, double *part);
 void launch_genpow_barrier(hipStream_t st, int ngp, const int64_t *desc, const double *alpha, const double *z, const double *s,
                            const double *dz, const double *ds, const double *alphas, int nalpha, double *cpart);
-// step_psd.hip: the same operations on the rows of the PSD triangle cones after hipkkt_step_enable_psd, one workgroup per cone
-// (step length: per cone and per z / s).  tab = 4 int64 per cone [row0 | n | offset of the n x n factors | offset of lambda] with
-// n <= psd_step_max_dim(); R, Rinv = the cones' column-major factors concatenated, lam = their lambda concatenated.
-// launch_psd_step_length writes one (alpha_z, alpha_s) pair per cone to `part` and out2 = the minimum of those pairs and of sym2, the
-// pair launch_step_length left for the Zero / Nonnegative / SecondOrder rows.  launch_psd_step_check sets *fail when a lambda is not
-// finite or not positive.
-int psd_step_max_dim();
-void launch_psd_step_affine_ds(hipStream_t st, int npsd, const int64_t *tab, const double *lam, double *out);
-void launch_psd_step_mulhs(hipStream_t st, int npsd, const int64_t *tab, const double *R, const double *x, const double *addc, double *y);
-void launch_psd_step_shift(hipStream_t st, int npsd, const int64_t *tab, const double *R, const double *Rinv, const double *dz,
-                           const double *ds, double sigma_mu, double *out);
-void launch_psd_step_offset(hipStream_t st, int npsd, const int64_t *tab, const double *R, const double *lam, const double *ds,
-                            double *out);
-void launch_psd_step_length(hipStream_t st, int npsd, const int64_t *tab, const double *R, const double *Rinv, const double *lam,
-                            const double *dz, const double *ds, double alpha_max, const double *sym2, double *part, double *out2);
-void launch_psd_step_check(hipStream_t st, const double *lam, int64_t len, int *fail);
-// the two halves of launch_psd_step_length: the cones' pairs into `part` (a cone the kernels do not serve gets alpha_max), then out2
-// = the minimum.  step_psd_large.hip writes its cones' pairs between the two.
-void launch_psd_step_length_cones(hipStream_t st, int npsd, const int64_t *tab, const double *R, const double *Rinv, const double *lam,
-                                  const double *dz, const double *ds, double alpha_max, double *part);
-void launch_psd_step_length_final(hipStream_t st, int npsd, const double *sym2, const double *part, double *out2);
-// step_psd_large.hip: the same operations for the cones of that table with a side in lmin .. psd_step_large_max_dim() (after
-// hipkkt_step_enable_psd_large; lmin = 65 unless the testing switch PSD_LARGE_MIN says otherwise), matrices in global memory: products
-// as batched 16 x 16 tile launches, the Jacobi iteration of the step length with M alone in LDS.  Same arithmetic as step_psd.hip --
-// applied to a side <= 64 the same bits.  lidx = the nlarge cones' indices into tab, max_n = the largest of their sides, ws =
-// psd_large_ws_doubles(nlarge) doubles (kPsdLargeMats matrices of kPsdLargeMatDoubles per large cone).  launch_psd_large_length writes
-// its cones' pairs to part[2 c + (0 | 1)] and belongs between the two halves above.
+// The PSD triangle cones' tables as every launcher below takes them (hipkkt_step.cpp fills one per call): tab = 4 int64 per cone
+// [row0 | n | offset of the n x n factors | offset of lambda] (cone_layout.h kPsd*); R, Rinv = the cones' column-major factors
+// concatenated, lam = their lambda concatenated; large = the cones of that table step_psd_large.hip serves: lidx = the nlarge cones'
+// indices into tab, sides lmin .. psd_step_large_max_dim() (after hipkkt_step_enable_psd_large; lmin = 65 unless the testing switch
+// PSD_LARGE_MIN says otherwise), max_n = the largest of their sides, ws = psd_large_ws_doubles(nlarge) doubles (kPsdLargeMats matrices
+// of kPsdLargeMatDoubles per large cone).  A launcher reads the fields its operation needs; the default start needs npsd and tab only.
 constexpr int kPsdLargeMaxN = 128;                                           // HIPKKT_PSD_STEP_LARGE_MAX_DIM
 constexpr int kPsdLargeMats = 4;
 constexpr int kPsdLargeMatDoubles = kPsdLargeMaxN * kPsdLargeMaxN;
 struct PsdLargeBatch { int nlarge = 0; const int *lidx = nullptr; int lmin = 65, max_n = 0; double *ws = nullptr; };
+struct PsdView {
+    int npsd = 0;
+    const int64_t *tab = nullptr;
+    const double *R = nullptr, *Rinv = nullptr, *lam = nullptr;
+    PsdLargeBatch large;
+};
+// step_psd.hip: the same operations on the rows of the PSD triangle cones after hipkkt_step_enable_psd, one workgroup per cone
+// (step length: per cone and per z / s), sides <= psd_step_max_dim().  The step length has two halves:
+// launch_psd_step_length_cones writes one (alpha_z, alpha_s) pair per cone to `part` (a cone the kernels do not serve gets alpha_max),
+// launch_psd_step_length_final writes out2 = the minimum of those pairs and of sym2, the pair launch_step_length left for the Zero /
+// Nonnegative / SecondOrder rows; step_psd_large.hip writes its cones' pairs between the two.  launch_psd_step_check sets *fail when
+// a lambda is not finite or not positive.
+int psd_step_max_dim();
+void launch_psd_step_affine_ds(hipStream_t st, const PsdView &P, double *out);
+void launch_psd_step_mulhs(hipStream_t st, const PsdView &P, const double *x, const double *addc, double *y);
+void launch_psd_step_shift(hipStream_t st, const PsdView &P, const double *dz, const double *ds, double sigma_mu, double *out);
+void launch_psd_step_offset(hipStream_t st, const PsdView &P, const double *ds, double *out);
+void launch_psd_step_length_cones(hipStream_t st, const PsdView &P, const double *dz, const double *ds, double alpha_max, double *part);
+void launch_psd_step_length_final(hipStream_t st, int npsd, const double *sym2, const double *part, double *out2);
+void launch_psd_step_check(hipStream_t st, const double *lam, int64_t len, int *fail);
+// step_psd_large.hip: the same operations for the cones of P.large, matrices in global memory: products as batched 16 x 16 tile
+// launches, the Jacobi iteration of the step length with M alone in LDS.  Same arithmetic as step_psd.hip -- applied to a side <= 64
+// the same bits.  launch_psd_large_length writes its cones' pairs to part[2 c + (0 | 1)] and belongs between the two halves above.
+// With P.large.nlarge == 0 none of them launches anything.
 int psd_step_large_max_dim();
 int64_t psd_large_ws_doubles(int nlarge);
-void launch_psd_large_affine_ds(hipStream_t st, const PsdLargeBatch &L, const int64_t *tab, const double *lam, double *out);
-void launch_psd_large_mulhs(hipStream_t st, const PsdLargeBatch &L, const int64_t *tab, const double *R, const double *lam, const double *x,
-                            const double *addc, double *y);
-void launch_psd_large_shift(hipStream_t st, const PsdLargeBatch &L, const int64_t *tab, const double *R, const double *Rinv,
-                            const double *lam, const double *dz, const double *ds, double sigma_mu, double *out);
-void launch_psd_large_offset(hipStream_t st, const PsdLargeBatch &L, const int64_t *tab, const double *R, const double *lam,
-                             const double *ds, double *out);
-void launch_psd_large_length(hipStream_t st, const PsdLargeBatch &L, const int64_t *tab, const double *R, const double *Rinv,
-                             const double *lam, const double *dz, const double *ds, double alpha_max, double *part);
+void launch_psd_large_affine_ds(hipStream_t st, const PsdView &P, double *out);
+void launch_psd_large_mulhs(hipStream_t st, const PsdView &P, const double *x, const double *addc, double *y);
+void launch_psd_large_shift(hipStream_t st, const PsdView &P, const double *dz, const double *ds, double sigma_mu, double *out);
+void launch_psd_large_offset(hipStream_t st, const PsdView &P, const double *ds, double *out);
+void launch_psd_large_length(hipStream_t st, const PsdView &P, const double *dz, const double *ds, double alpha_max, double *part);
 // scaling_psd.hip: update_scaling!(::PSDTriangleCone) for the cones of the same table, one workgroup per cone: Cholesky factors of
-// svec_to_mat of the cone's rows of (s, z), the SVD of L2' L1 by one-sided Jacobi sweeps, (R, Rinv, lam) in the layout above.  A cone
-// that fails sets *fail and bad[cone] (0 otherwise) and gets NaN factors.
+// svec_to_mat of the cone's rows of (s, z), the SVD of L2' L1 by one-sided Jacobi sweeps, (R, Rinv, lam) written in the layout above.
+// A cone that fails sets *fail and bad[cone] (0 otherwise) and gets NaN factors.
 void launch_psd_nt_scaling(hipStream_t st, int npsd, const int64_t *tab, const double *s, const double *z, double *R, double *Rinv,
                            double *lam, int *bad, int *fail);
 // barrier_psd.hip: compute_barrier of the PSD triangle cones of the same table (sides <= psd_step_max_dim()) at nalpha <=
@@ -200,10 +199,10 @@ void launch_psd_nt_scaling(hipStream_t st, int npsd, const int64_t *tab, const d
 // behind launch_step3_barrier on the same stream, adds the cones' (0 - logdet_z) - logdet_s in PSD-cone order to out[2 j].  A shifted
 // point outside the cone gives -Inf (the reference subtracts typemax).
 double *psd_barrier_slots(double *work, int nsoc, int n3, int ngp);
-void launch_psd_barrier(hipStream_t st, int npsd, const int64_t *tab, const double *z, const double *s, const double *dz, const double *ds,
+void launch_psd_barrier(hipStream_t st, const PsdView &P, const double *z, const double *s, const double *dz, const double *ds,
                         const double *alphas, int nalpha, double *slots);
 void launch_psd_barrier_add(hipStream_t st, int npsd, const double *slots, int nalpha, double *out);
-// start.hip: the default start of a symmetric cone set (solver.jl:383-405) on the tables above.
+// start.hip: the default start of a symmetric cone set (solver.jl:383-405) on the tables above (P: its npsd and tab).
 // launch_start_identity writes the identity scaling's Hs values and sparse second-order terms into kval (psd_hs0 = first Hs entry per
 // PSD cone, psd_max_numel = the largest numel among them).  launch_start_margins leaves, for each of nsides vectors (v1 is not read
 // when nsides == 1), the record {min_margin, pos_margin, target, branch, a, b, two_stage, 0} at start_decision(work, ncones) + 8 side;
@@ -214,12 +213,12 @@ void launch_psd_barrier_add(hipStream_t st, int npsd, const double *slots, int n
 int64_t start_work_doubles(int64_t ncones);
 double *start_decision(double *work, int64_t ncones);
 void launch_start_identity(hipStream_t st, const signed char *row_kind, const int64_t *row_hs, const int64_t *map_hs, int nsoc,
-                           const int64_t *desc, double *soc_u, double *soc_v, double *soc_eta2, int npsd, const int64_t *psdtab,
+                           const int64_t *desc, double *soc_u, double *soc_v, double *soc_eta2, const PsdView &P,
                            const int64_t *psd_hs0, int64_t psd_max_numel, double *kval, int64_t m);
-void launch_start_margins(hipStream_t st, const signed char *row_kind, int nsoc, const int64_t *desc, int npsd, const int64_t *psdtab,
-                          const double *v0, const double *v1, int nsides, double degree, double *work, int64_t ncones, int64_t m);
-void launch_start_shift(hipStream_t st, const signed char *row_kind, int nsoc, const int64_t *desc, int npsd, const int64_t *psdtab,
-                        const double *dec, double *v0, int pd0, double *v1, int pd1, int nsides, int64_t m);
+void launch_start_margins(hipStream_t st, const signed char *row_kind, int nsoc, const int64_t *desc, const PsdView &P, const double *v0,
+                          const double *v1, int nsides, double degree, double *work, int64_t ncones, int64_t m);
+void launch_start_shift(hipStream_t st, const signed char *row_kind, int nsoc, const int64_t *desc, const PsdView &P, const double *dec,
+                        double *v0, int pd0, double *v1, int pd1, int nsides, int64_t m);
 void launch_start_rhs(hipStream_t st, double *dst, const double *qb, int n, int nm, int N, int mode);
 void launch_start_assemble(hipStream_t st, double *xzs, const double *sa, const double *sb, int64_t n, int64_t m);
 }  // namespace hipkkt

@@ -51,7 +51,7 @@ namespace {
 constexpr int kMaxSweeps = 40;
 constexpr double kEps = 2.220446049250313e-16;
 
-__device__ __forceinline__ bool pos_finite(double v) { return v > 0.0 && v - v == 0.0; }
+// (pos_finite: psd_cone.h)
 // the sum over the eight lanes of a pair (lanes 8 k .. 8 k + 7 of one wavefront); every lane gets the same bits
 __device__ __forceinline__ double sum8(double v) {
     v += __shfl_xor(v, 4);

@@ -234,32 +234,33 @@ static inline dim3 rows_grid(int64_t len) { return dim3((unsigned)((len + 255) /
 int64_t start_work_doubles(int64_t ncones) { return 2 * side_doubles((int)ncones, (int)ncones) + 16; }
 
 void launch_start_identity(hipStream_t st, const signed char *row_kind, const int64_t *row_hs, const int64_t *map_hs, int nsoc,
-                           const int64_t *desc, double *soc_u, double *soc_v, double *soc_eta2, int npsd, const int64_t *psdtab,
+                           const int64_t *desc, double *soc_u, double *soc_v, double *soc_eta2, const PsdView &P,
                            const int64_t *psd_hs0, int64_t psd_max_numel, double *kval, int64_t m) {
     if (m > 0) hipLaunchKernelGGL(k_start_identity_diag, rows_grid(m), dim3(256), 0, st, row_kind, row_hs, map_hs, kval, m);
     if (nsoc > 0) hipLaunchKernelGGL(k_start_identity_soc, dim3(nsoc), dim3(256), 0, st, desc, map_hs, soc_u, soc_v, soc_eta2, kval);
-    if (npsd > 0 && psd_max_numel > 0)
-        hipLaunchKernelGGL(k_start_identity_psd, dim3((unsigned)psd_max_numel, npsd), dim3(256), 0, st, psdtab, psd_hs0, map_hs, kval);
+    if (P.npsd > 0 && psd_max_numel > 0)
+        hipLaunchKernelGGL(k_start_identity_psd, dim3((unsigned)psd_max_numel, P.npsd), dim3(256), 0, st, P.tab, psd_hs0, map_hs, kval);
 }
 
 // work: start_work_doubles(ncones) doubles; the decision records of the nsides sides end up at start_decision(work, ncones)
 double *start_decision(double *work, int64_t ncones) { return work + 2 * side_doubles((int)ncones, (int)ncones); }
 
-void launch_start_margins(hipStream_t st, const signed char *row_kind, int nsoc, const int64_t *desc, int npsd, const int64_t *psdtab,
-                          const double *v0, const double *v1, int nsides, double degree, double *work, int64_t ncones, int64_t m) {
+void launch_start_margins(hipStream_t st, const signed char *row_kind, int nsoc, const int64_t *desc, const PsdView &P, const double *v0,
+                          const double *v1, int nsides, double degree, double *work, int64_t ncones, int64_t m) {
+    const int npsd = P.npsd;
     const int64_t stride = side_doubles(nsoc, npsd);
     hipLaunchKernelGGL(k_start_margin_nn, dim3(kSlices, nsides), dim3(256), 0, st, row_kind, v0, v1, work, stride, m);
     if (nsoc > 0) hipLaunchKernelGGL(k_start_margin_soc, dim3(nsoc, nsides), dim3(256), 0, st, desc, v0, v1, work, stride);
-    if (npsd > 0) hipLaunchKernelGGL(k_start_margin_psd, dim3(npsd, nsides), dim3(256), 0, st, psdtab, v0, v1, work, stride, nsoc);
+    if (npsd > 0) hipLaunchKernelGGL(k_start_margin_psd, dim3(npsd, nsides), dim3(256), 0, st, P.tab, v0, v1, work, stride, nsoc);
     hipLaunchKernelGGL(k_start_decide, dim3(nsides), dim3(256), 0, st, work, stride, nsoc, npsd, degree, start_decision(work, ncones));
 }
 
-void launch_start_shift(hipStream_t st, const signed char *row_kind, int nsoc, const int64_t *desc, int npsd, const int64_t *psdtab,
-                        const double *dec, double *v0, int pd0, double *v1, int pd1, int nsides, int64_t m) {
+void launch_start_shift(hipStream_t st, const signed char *row_kind, int nsoc, const int64_t *desc, const PsdView &P, const double *dec,
+                        double *v0, int pd0, double *v1, int pd1, int nsides, int64_t m) {
     const unsigned nrow = (unsigned)((m + 255) / 256), nsocb = (unsigned)((nsoc + 255) / 256);
-    const unsigned total = nrow + nsocb + (unsigned)npsd;
+    const unsigned total = nrow + nsocb + (unsigned)P.npsd;
     if (total > 0)
-        hipLaunchKernelGGL(k_start_shift, dim3(total, nsides), dim3(256), 0, st, row_kind, desc, psdtab, dec, v0, pd0, v1, pd1, m, nsoc,
+        hipLaunchKernelGGL(k_start_shift, dim3(total, nsides), dim3(256), 0, st, row_kind, desc, P.tab, dec, v0, pd0, v1, pd1, m, nsoc,
                            nrow, nsocb);
 }
 

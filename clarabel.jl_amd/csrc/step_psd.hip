@@ -12,10 +12,12 @@
 // One 256-thread workgroup per cone and operation (step length: per cone and per z / s), the factor, X and a work matrix in LDS
 // (column-major, leading dimension n + 1 when n is a multiple of 32: the column reads of A' would otherwise hit the same banks).
 // Products are plain FP64 FMA chains, every k-sum in ascending order: deterministic.  The smallest eigenvalue comes from a cyclic
-// two-sided Jacobi iteration in LDS (round-robin sets of disjoint rotations), at most kMaxSweeps sweeps; a non-finite M gives a NaN
-// gamma and therefore alpha_max, as the reference's `gamma < 0` does.  No assert, no trap, every loop has a fixed trip bound.
+// two-sided Jacobi iteration in LDS (psd_cone.h psd_jacobi_sweeps: round-robin sets of disjoint rotations, at most kPsdMaxSweeps
+// sweeps); a non-finite M gives a NaN gamma and therefore alpha_max, as the reference's `gamma < 0` does.  No assert, no trap, every
+// loop has a fixed trip bound.
 // The cone table: cone_layout.h kPsd* ([row0 | n | offset of the n x n factors | offset of lambda]); n <= kMaxN is the enable's condition
-// and is checked again here (a larger cone is left alone).
+// and is checked again here (a larger cone is left alone).  The entry expressions of svec_to_mat, mat_to_svec, their round trip and
+// affine_ds are psd_cone.h's, which step_psd_large.hip calls as well; the launchers take the tables as one PsdView (kernels.h).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -28,10 +30,9 @@ namespace hipkkt {
 
 namespace {
 
-// the matrix layout, the cone record (Cone, cone_of) and load_svec: psd_cone.h, shared with scaling_psd.hip
+// the matrix layout, the cone record (Cone, cone_of), load_svec and the entry expressions of the loops below: psd_cone.h
 constexpr int kMaxN = kPsdMaxN;
 constexpr int kMatDoubles = kPsdMatDoubles;
-constexpr double kIsqrt2 = kPsdIsqrt2;
 
 // F = the cone's n x n column-major factor
 __device__ __forceinline__ void load_factor(double *F, const double *__restrict__ src, const Cone &K) {
@@ -42,14 +43,7 @@ __device__ __forceinline__ void load_factor(double *F, const double *__restrict_
 __device__ __forceinline__ void store_svec(double *__restrict__ out, const double *Y, const Cone &K, double diag_add,
                                            const double *__restrict__ addc) {
     const int n = K.n;
-    for (int e = threadIdx.x; e < n * n; e += 256) {
-        const int i = e % n, j = e / n;
-        if (i > j) continue;
-        double v = i == j ? Y[i + i * K.ld] + diag_add : (Y[i + j * K.ld] + Y[j + i * K.ld]) * kIsqrt2;
-        const int k = j * (j + 1) / 2 + i;
-        if (addc) v = -(v + addc[k]);
-        out[k] = v;
-    }
+    for (int e = threadIdx.x; e < n * n; e += 256) store_svec_entry(out, Y, n, K.ld, e, diag_add, addc);
 }
 // Y <- svec_to_mat(mat_to_svec(Y)): what a result of mul_W goes through before the next operation reads it as a matrix
 __device__ __forceinline__ void svec_round_trip(double *Y, const Cone &K) {
@@ -57,7 +51,7 @@ __device__ __forceinline__ void svec_round_trip(double *Y, const Cone &K) {
     for (int e = threadIdx.x; e < n * n; e += 256) {
         const int i = e % n, j = e / n;
         if (i >= j) continue;
-        const double v = ((Y[i + j * K.ld] + Y[j + i * K.ld]) * kIsqrt2) * kIsqrt2;
+        const double v = round_trip_pair(Y[i + j * K.ld], Y[j + i * K.ld]);
         Y[i + j * K.ld] = v;
         Y[j + i * K.ld] = v;
     }
@@ -92,13 +86,7 @@ k_psd_affine_ds(const int64_t *__restrict__ tab, const double *__restrict__ lam_
     const Cone K = cone_of(tab, blockIdx.x);
     if (!K.ok) return;
     const int n = K.n;
-    double *out = out_all + K.row0;
-    for (int e = threadIdx.x; e < n * n; e += 256) {
-        const int i = e % n, j = e / n;
-        if (i > j) continue;
-        const double l = lam_all[K.loff + j];
-        out[j * (j + 1) / 2 + i] = i == j ? l * l : 0.0;
-    }
+    for (int e = threadIdx.x; e < n * n; e += 256) affine_ds_entry(out_all + K.row0, lam_all + K.loff, n, e);
 }
 
 // ---- mul_Hs; with addc != NULL: y = -(Hs x + addc) -----------------------------------------------------------------------------------
@@ -233,28 +221,20 @@ k_psd_check_lambda(const double *__restrict__ lam, int64_t len, int *__restrict_
 // ---- launchers ----------------------------------------------------------------------------------------------------------------------
 int psd_step_max_dim() { return kMaxN; }
 
-void launch_psd_step_affine_ds(hipStream_t st, int npsd, const int64_t *tab, const double *lam, double *out) {
-    if (npsd > 0) hipLaunchKernelGGL(k_psd_affine_ds, dim3(npsd), dim3(256), 0, st, tab, lam, out);
+void launch_psd_step_affine_ds(hipStream_t st, const PsdView &P, double *out) {
+    if (P.npsd > 0) hipLaunchKernelGGL(k_psd_affine_ds, dim3(P.npsd), dim3(256), 0, st, P.tab, P.lam, out);
 }
-void launch_psd_step_mulhs(hipStream_t st, int npsd, const int64_t *tab, const double *R, const double *x, const double *addc, double *y) {
-    if (npsd > 0) hipLaunchKernelGGL(k_psd_mulhs, dim3(npsd), dim3(256), 0, st, tab, R, x, addc, y);
+void launch_psd_step_mulhs(hipStream_t st, const PsdView &P, const double *x, const double *addc, double *y) {
+    if (P.npsd > 0) hipLaunchKernelGGL(k_psd_mulhs, dim3(P.npsd), dim3(256), 0, st, P.tab, P.R, x, addc, y);
 }
-void launch_psd_step_shift(hipStream_t st, int npsd, const int64_t *tab, const double *R, const double *Rinv, const double *dz,
-                           const double *ds, double sigma_mu, double *out) {
-    if (npsd > 0) hipLaunchKernelGGL(k_psd_shift, dim3(npsd), dim3(256), 0, st, tab, R, Rinv, dz, ds, sigma_mu, out);
+void launch_psd_step_shift(hipStream_t st, const PsdView &P, const double *dz, const double *ds, double sigma_mu, double *out) {
+    if (P.npsd > 0) hipLaunchKernelGGL(k_psd_shift, dim3(P.npsd), dim3(256), 0, st, P.tab, P.R, P.Rinv, dz, ds, sigma_mu, out);
 }
-void launch_psd_step_offset(hipStream_t st, int npsd, const int64_t *tab, const double *R, const double *lam, const double *ds,
-                            double *out) {
-    if (npsd > 0) hipLaunchKernelGGL(k_psd_offset, dim3(npsd), dim3(256), 0, st, tab, R, lam, ds, out);
+void launch_psd_step_offset(hipStream_t st, const PsdView &P, const double *ds, double *out) {
+    if (P.npsd > 0) hipLaunchKernelGGL(k_psd_offset, dim3(P.npsd), dim3(256), 0, st, P.tab, P.R, P.lam, ds, out);
 }
-void launch_psd_step_length(hipStream_t st, int npsd, const int64_t *tab, const double *R, const double *Rinv, const double *lam,
-                            const double *dz, const double *ds, double alpha_max, const double *sym2, double *part, double *out2) {
-    launch_psd_step_length_cones(st, npsd, tab, R, Rinv, lam, dz, ds, alpha_max, part);
-    launch_psd_step_length_final(st, npsd, sym2, part, out2);
-}
-void launch_psd_step_length_cones(hipStream_t st, int npsd, const int64_t *tab, const double *R, const double *Rinv, const double *lam,
-                                  const double *dz, const double *ds, double alpha_max, double *part) {
-    if (npsd > 0) hipLaunchKernelGGL(k_psd_len, dim3(npsd, 2), dim3(256), 0, st, tab, R, Rinv, lam, dz, ds, alpha_max, part);
+void launch_psd_step_length_cones(hipStream_t st, const PsdView &P, const double *dz, const double *ds, double alpha_max, double *part) {
+    if (P.npsd > 0) hipLaunchKernelGGL(k_psd_len, dim3(P.npsd, 2), dim3(256), 0, st, P.tab, P.R, P.Rinv, P.lam, dz, ds, alpha_max, part);
 }
 void launch_psd_step_length_final(hipStream_t st, int npsd, const double *sym2, const double *part, double *out2) {
     if (npsd > 0) hipLaunchKernelGGL(k_psd_len_final, dim3(1), dim3(256), 0, st, part, npsd, sym2, out2);

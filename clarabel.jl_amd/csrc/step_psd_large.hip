@@ -3,20 +3,20 @@
 // fit one workgroup's LDS, so the matrices stay in global memory (a per-handle workspace of kPsdLargeMats matrices per large cone) and
 // every product is a batched launch of 16 x 16 output tiles, grid (tile, large cone, z / s), whose operands are read through views:
 //   Plain / Trans    a column-major n x n factor or workspace matrix, or its transpose
-//   Svec             svec_to_mat of the cone's rows of a vector                                (psd_cone.h load_svec)
-//   RoundTrip        svec_to_mat(mat_to_svec(Y)) of a workspace matrix                         (step_psd.hip svec_round_trip)
+//   Svec             svec_to_mat of the cone's rows of a vector                                (psd_cone.h svec_entry)
+//   RoundTrip        svec_to_mat(mat_to_svec(Y)) of a workspace matrix                         (psd_cone.h round_trip_entry)
 //   Offset           the round trip of X~_ij = 2 DS_ij / (lambda_i + lambda_j)                 (step_psd.hip k_psd_offset)
 // Every entry of every product is ONE fma chain over k = 0 .. n - 1 in ascending order starting from 0.0, and the elementwise
-// expressions are those of step_psd.hip character for character; both files are compiled with -ffp-contract=off.  So these kernels
-// applied to a cone of side <= 64 give the bits of step_psd.hip (tests/test_gpu_psd_step_large.py holds them to that through the
-// testing switch PSD_LARGE_MIN).  A tile stages 16-wide panels of both operands in LDS; that changes where an operand is read from, not
-// the order of a sum.
+// expressions are the device functions of psd_cone.h that step_psd.hip calls too; both files are compiled with -ffp-contract=off.  So
+// these kernels applied to a cone of side <= 64 give the bits of step_psd.hip (tests/test_gpu_psd_step_large.py holds them to that
+// through the testing switch PSD_LARGE_MIN).  A tile stages 16-wide panels of both operands in LDS; that changes where an operand is
+// read from, not the order of a sum.
 // The smallest eigenvalue of the step length: one 256-thread workgroup per (cone, z / s) with M alone in LDS (128 x 129 doubles at side
-// 128, the layout rule of psd_cone.h) and the cyclic Jacobi iteration of psd_cone.h psd_jacobi_sweeps -- pair schedule, rotation
-// formulas, zeroing of the rotated pair, stop rule, kPsdMaxSweeps, the sums of tot2 / off2 -- with wider lane mappings of the two
-// rotation passes (half <= 64, rows <= 128).  The rotations of one set touch disjoint rows / columns: the mapping changes no bit.
+// 128, the layout rule of psd_cone.h) and psd_jacobi_sweeps<64, 128> of psd_cone.h: the iteration of k_psd_len with wider lane
+// mappings of the two rotation passes (half <= 64, rows <= 128).  The rotations of one set touch disjoint rows / columns: the mapping
+// changes no bit.
 // No assert, no trap, no waiting between workgroups; every loop has a fixed trip bound.  lidx = the large cones' indices into the table
-// of step_psd.hip (cone_layout.h kPsd*); an entry whose side is outside lmin .. kPsdLargeMaxN is left alone.
+// of step_psd.hip (cone_layout.h kPsd*); an entry whose side is outside lmin .. kPsdLargeMaxN is left alone (cone_of's lo / hi).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -31,21 +31,8 @@ namespace {
 
 constexpr int kMaxN = kPsdLargeMaxN;
 constexpr int kTile = 16;
-constexpr double kIsqrt2 = kPsdIsqrt2;
 constexpr int kLdsDoubles = kMaxN * (kMaxN + 1);      // M of the Jacobi kernel, leading dimension n + 1 when n % 32 == 0
-
-// the cone record of psd_cone.h for a side in lmin .. kMaxN; K.ld is the LDS layout of the Jacobi kernel (global matrices have ld = n)
-__device__ __forceinline__ Cone large_cone_of(const int64_t *__restrict__ tab, int c, int lmin) {
-    Cone K;
-    K.row0 = tab[kPsdTab * c + kPsdRow0];
-    const int64_t n = tab[kPsdTab * c + kPsdN];
-    K.foff = tab[kPsdTab * c + kPsdFactor0];
-    K.loff = tab[kPsdTab * c + kPsdLambda0];
-    K.ok = n >= 1 && n >= lmin && n <= kMaxN;
-    K.n = K.ok ? (int)n : 0;
-    K.ld = (K.n % 32 == 0) ? K.n + 1 : K.n;
-    return K;
-}
+// (the cone record is cone_of(tab, c, lmin, kMaxN) of psd_cone.h; its K.ld is that LDS layout, the global matrices have ld = n)
 
 enum View { kPlain = 0, kTrans = 1, kSvec = 2, kRoundTrip = 3, kOffset = 4 };
 enum Where { kRows = 0, kFactor = 1, kWs0 = 2 };      // kWs0 + w: matrix w of the cone's workspace slot
@@ -65,23 +52,14 @@ __device__ __forceinline__ double view_at(int view, const double *__restrict__ p
     switch (view) {
         case kPlain: return p[i + j * n];
         case kTrans: return p[j + i * n];
-        case kSvec: {
-            const int r = i < j ? i : j, c = i < j ? j : i;
-            const double v = p[c * (c + 1) / 2 + r];
-            return i == j ? v : v * kPsdIsqrt2;
-        }
-        case kRoundTrip: {
-            if (i == j) return p[i + i * n];
-            const int r = i < j ? i : j, c = i < j ? j : i;
-            return ((p[r + c * n] + p[c + r * n]) * kIsqrt2) * kIsqrt2;
-        }
+        case kSvec: return svec_entry(p, i, j);
+        case kRoundTrip: return round_trip_entry(p, n, i, j);
         default: {      // kOffset: X = svec_to_mat(ds), X_ij <- 2 X_ij / (lambda_i + lambda_j), then the round trip
+            const double x = svec_entry(p, i, j);
+            if (i == j) return 2.0 * x / (lam[i] + lam[j]);
             const int r = i < j ? i : j, c = i < j ? j : i;
-            const double v = p[c * (c + 1) / 2 + r];
-            if (i == j) return 2.0 * v / (lam[i] + lam[j]);
-            const double x = v * kPsdIsqrt2;
             const double up = 2.0 * x / (lam[r] + lam[c]), lo = 2.0 * x / (lam[c] + lam[r]);
-            return ((up + lo) * kIsqrt2) * kIsqrt2;
+            return round_trip_pair(up, lo);
         }
     }
 }
@@ -94,7 +72,7 @@ k_psdl_product(const int64_t *__restrict__ tab, const int *__restrict__ lidx, in
                const double *__restrict__ lam_all, double *__restrict__ ws) {
     __shared__ double As[kTile * kTile], Bs[kTile * kTile];      // As[k][i], Bs[j][k]
     const int slot = blockIdx.y;
-    const Cone K = large_cone_of(tab, lidx[slot], lmin);
+    const Cone K = cone_of(tab, lidx[slot], lmin, kMaxN);
     if (!K.ok) return;
     const int n = K.n, ti = threadIdx.x & (kTile - 1), tj = threadIdx.x >> 4;
     const int i0 = ((int)blockIdx.x % tiles) * kTile, j0 = ((int)blockIdx.x / tiles) * kTile;
@@ -122,7 +100,7 @@ k_psdl_circ(const int64_t *__restrict__ tab, const int *__restrict__ lidx, int l
             double *__restrict__ ws) {
     __shared__ double Ai[kTile * kTile], Bi[kTile * kTile], Aj[kTile * kTile], Bj[kTile * kTile];   // A(i, k), B(i, k) as [k][i]; A(k, j), B(k, j) as [j][k]
     const int slot = blockIdx.y;
-    const Cone K = large_cone_of(tab, lidx[slot], lmin);
+    const Cone K = cone_of(tab, lidx[slot], lmin, kMaxN);
     if (!K.ok) return;
     const int n = K.n, ti = threadIdx.x & (kTile - 1), tj = threadIdx.x >> 4;
     const int i0 = ((int)blockIdx.x % tiles) * kTile, j0 = ((int)blockIdx.x / tiles) * kTile;
@@ -155,35 +133,24 @@ __global__ void __launch_bounds__(256)
 k_psdl_store(const int64_t *__restrict__ tab, const int *__restrict__ lidx, int lmin, int iy, const double *__restrict__ ws,
              double diag_add, const double *__restrict__ addc_all, double *__restrict__ out_all) {
     const int slot = blockIdx.y;
-    const Cone K = large_cone_of(tab, lidx[slot], lmin);
+    const Cone K = cone_of(tab, lidx[slot], lmin, kMaxN);
     if (!K.ok) return;
     const int n = K.n;
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= n * n) return;
     const double *Y = ws + ((int64_t)slot * kPsdLargeMats + iy) * kPsdLargeMatDoubles;
-    const double *addc = addc_all ? addc_all + K.row0 : nullptr;
-    double *out = out_all + K.row0;
-    const int i = e % n, j = e / n;
-    if (i > j) return;
-    double v = i == j ? Y[i + i * n] + diag_add : (Y[i + j * n] + Y[j + i * n]) * kIsqrt2;
-    const int k = j * (j + 1) / 2 + i;
-    if (addc) v = -(v + addc[k]);
-    out[k] = v;
+    store_svec_entry(out_all + K.row0, Y, n, n, e, diag_add, addc_all ? addc_all + K.row0 : nullptr);
 }
 
 // ---- affine_ds: lambda_k^2 at the diagonal positions, 0 elsewhere -------------------------------------------------------------------------
 __global__ void __launch_bounds__(256)
 k_psdl_affine_ds(const int64_t *__restrict__ tab, const int *__restrict__ lidx, int lmin, const double *__restrict__ lam_all,
                  double *__restrict__ out_all) {
-    const Cone K = large_cone_of(tab, lidx[blockIdx.y], lmin);
+    const Cone K = cone_of(tab, lidx[blockIdx.y], lmin, kMaxN);
     if (!K.ok) return;
     const int n = K.n;
     const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= n * n) return;
-    const int i = e % n, j = e / n;
-    if (i > j) return;
-    const double l = lam_all[K.loff + j];
-    out_all[K.row0 + j * (j + 1) / 2 + i] = i == j ? l * l : 0.0;
+    if (e < n * n) affine_ds_entry(out_all + K.row0, lam_all + K.loff, n, e);
 }
 
 // ---- step length: M = Lambda^-1/2 D Lambda^-1/2 from the round trip of workspace matrix id0 + blockIdx.y, its smallest eigenvalue ----------
@@ -192,11 +159,16 @@ __global__ void __launch_bounds__(256)
 k_psdl_len(const int64_t *__restrict__ tab, const int *__restrict__ lidx, int lmin, int id0, const double *__restrict__ ws,
            const double *__restrict__ lam_all, double alpha_max, double *__restrict__ part) {
     __shared__ double M[kLdsDoubles];
-    __shared__ double red[4], rc[kMaxN / 2], rs[kMaxN / 2];      // rs = the rotations' s, rc = their s / (1 + c)
-    __shared__ int rp[kMaxN / 2], rq[kMaxN / 2];                  // and their index pairs p < q
+    __shared__ double red[4];
+    // the sweeps' scratch: rs = the rotations' s, rc = their s / (1 + c), rp < rq their index pairs.  One struct fixes the order in
+    // LDS: with rq below rp the compiler loads a pair's two indices with one ds_read2st64_b32 in both rotation passes (as separate
+    // arrays it did so in one pass only, and k_psdl_len measured 3 % slower with the shared loop than with its own copy)
+    __shared__ struct { double rc[kMaxN / 2], rs[kMaxN / 2]; int rq[kMaxN / 2], rp[kMaxN / 2]; } rot;
+    double *rc = rot.rc, *rs = rot.rs;
+    int *rp = rot.rp, *rq = rot.rq;
     const int slot = blockIdx.x, which = blockIdx.y, t = threadIdx.x;
     const int c = lidx[slot];
-    const Cone K = large_cone_of(tab, c, lmin);
+    const Cone K = cone_of(tab, c, lmin, kMaxN);
     if (!K.ok) return;
     const int n = K.n, ld = K.ld;
     const double *lam = lam_all + K.loff;
@@ -209,68 +181,8 @@ k_psdl_len(const int64_t *__restrict__ tab, const int *__restrict__ lidx, int lm
         tot2 += v * v;
     }
     tot2 = block_sum(tot2, red);                          // (its barriers order the writes above before the reads below)
-    // psd_jacobi_sweeps of psd_cone.h with the lane mappings of a side up to 128: per sweep np - 1 sets of np / 2 disjoint rotations
-    // (round robin over np = n rounded up to even; the index n of an odd n is a dummy), until off(M) <= eps |M|_F; a non-finite |M|_F
-    // skips the sweeps (uniform: block_sum gives every thread the same value)
-    const int np = n + (n & 1), half = np / 2;
-    const bool finite = tot2 - tot2 == 0.0;
-    for (int sweep = 0; finite && sweep < kPsdMaxSweeps; sweep++) {
-        double off2 = 0.0;
-        for (int e = t; e < n * n; e += 256) {
-            const int i = e % n, j = e / n;
-            if (i != j) off2 += M[i + j * ld] * M[i + j * ld];
-        }
-        off2 = block_sum(off2, red);
-        if (!(off2 > kPsdEps * kPsdEps * tot2)) break;
-        for (int r = 0; r < np - 1; r++) {
-            if (t < half) {
-                const int a = t == 0 ? np - 1 : (r + t) % (np - 1), b = (r + np - 1 - t) % (np - 1);
-                const int p = a < b ? a : b, q = a < b ? b : a;
-                double sn = 0.0, rr = 0.0;
-                if (q < n) {
-                    const double apq = M[p + q * ld];
-                    if (apq != 0.0) {
-                        const double tau = (M[q + q * ld] - M[p + p * ld]) / (2.0 * apq);
-                        const double tt = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
-                        const double cs = 1.0 / sqrt(1.0 + tt * tt);
-                        sn = tt * cs;
-                        rr = sn / (1.0 + cs);
-                    }
-                }
-                rs[t] = sn; rc[t] = rr; rp[t] = p; rq[t] = q;
-            }
-            __syncthreads();
-            // rows: M <- J' M.  Lane -> (pair k = t mod 64, column j = t / 64 + 4 i): half <= 64
-            {
-                const int k = t & 63;
-                if (k < half && rs[k] != 0.0) {
-                    const int p = rp[k], q = rq[k];
-                    const double sn = rs[k], rr = rc[k];
-                    for (int j = t >> 6; j < n; j += 4) {
-                        const double mp = M[p + j * ld], mq = M[q + j * ld];
-                        M[p + j * ld] = mp - sn * (mq + rr * mp);
-                        M[q + j * ld] = mq + sn * (mp - rr * mq);
-                    }
-                }
-            }
-            __syncthreads();
-            // columns: M <- M J.  Lane -> (row i = t mod 128, pair k = t / 128 + 2 i); the rotated pair is zero by construction
-            {
-                const int i = t & 127;
-                if (i < n) {
-                    for (int k = t >> 7; k < half; k += 2) {
-                        const double sn = rs[k], rr = rc[k];
-                        if (sn == 0.0) continue;
-                        const int p = rp[k], q = rq[k];
-                        const double mp = M[i + p * ld], mq = M[i + q * ld];
-                        M[i + p * ld] = i == q ? 0.0 : mp - sn * (mq + rr * mp);
-                        M[i + q * ld] = i == p ? 0.0 : mq + sn * (mp - rr * mq);
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    }
+    // the Jacobi sweeps of psd_cone.h with the lane widths of a side up to 128 (half <= 64, rows <= 128); a non-finite |M|_F skips them
+    const bool finite = psd_jacobi_sweeps<64, 128>(M, K, tot2, red, rc, rs, rp, rq);
     double g = finite ? 1.7976931348623157e308 : tot2 - tot2;      // (a non-finite M: gamma = NaN)
     if (finite) for (int i = t; i < n; i += 256) g = nan_min(M[i + i * ld], g);
     g = block_nan_min(g, red);
@@ -283,71 +195,68 @@ int64_t psd_large_ws_doubles(int nlarge) { return (int64_t)nlarge * kPsdLargeMat
 
 namespace {
 
-// what every launch of one operation shares
+// what every launch of one operation shares: the stream, the tables and the tile count of the largest side
 struct Batch {
-    hipStream_t st; int nlarge; const int64_t *tab; const int *lidx; int lmin, tiles; const double *lam; double *ws;
+    hipStream_t st; const PsdView &P; const PsdLargeBatch &L; int tiles;
+    Batch(hipStream_t st_, const PsdView &P_) : st(st_), P(P_), L(P_.large), tiles((P_.large.max_n + kTile - 1) / kTile) {}
     Operand rows(int view, const double *v) const { return {view, kRows, v}; }
     Operand factor(int view, const double *f) const { return {view, kFactor, f}; }
-    Operand mat(int view, int w) const { return {view, kWs0 + w, ws}; }
+    Operand mat(int view, int w) const { return {view, kWs0 + w, L.ws}; }
     void product(const Product &pz, const Product *ps) const {
-        hipLaunchKernelGGL(k_psdl_product, dim3(tiles * tiles, nlarge, ps ? 2 : 1), dim3(256), 0, st, tab, lidx, lmin, tiles, pz,
-                           ps ? *ps : pz, lam, ws);
+        hipLaunchKernelGGL(k_psdl_product, dim3(tiles * tiles, L.nlarge, ps ? 2 : 1), dim3(256), 0, st, P.tab, L.lidx, L.lmin, tiles, pz,
+                           ps ? *ps : pz, P.lam, L.ws);
     }
     void store(int iy, double diag_add, const double *addc, double *out) const {
         const int n = tiles * kTile;
-        hipLaunchKernelGGL(k_psdl_store, dim3((n * n + 255) / 256, nlarge), dim3(256), 0, st, tab, lidx, lmin, iy, ws, diag_add, addc, out);
+        hipLaunchKernelGGL(k_psdl_store, dim3((n * n + 255) / 256, L.nlarge), dim3(256), 0, st, P.tab, L.lidx, L.lmin, iy, L.ws, diag_add,
+                           addc, out);
     }
     // the first two products of both chains: matrix 2 = R' dZ R (z, through matrix 0), matrix 3 = Rinv dS Rinv' (s, through matrix 1)
-    void scaled_pair(const double *R, const double *Rinv, const double *dz, const double *ds) const {
-        const Product z1{rows(kSvec, dz), factor(kPlain, R), 0}, s1{rows(kSvec, ds), factor(kTrans, Rinv), 1};
+    void scaled_pair(const double *dz, const double *ds) const {
+        const Product z1{rows(kSvec, dz), factor(kPlain, P.R), 0}, s1{rows(kSvec, ds), factor(kTrans, P.Rinv), 1};
         product(z1, &s1);
-        const Product z2{factor(kTrans, R), mat(kPlain, 0), 2}, s2{factor(kPlain, Rinv), mat(kPlain, 1), 3};
+        const Product z2{factor(kTrans, P.R), mat(kPlain, 0), 2}, s2{factor(kPlain, P.Rinv), mat(kPlain, 1), 3};
         product(z2, &s2);
     }
 };
 
-Batch batch_of(hipStream_t st, const PsdLargeBatch &L, const int64_t *tab, const double *lam) {
-    return {st, L.nlarge, tab, L.lidx, L.lmin, (L.max_n + kTile - 1) / kTile, lam, L.ws};
-}
-
 }  // namespace
 
-void launch_psd_large_affine_ds(hipStream_t st, const PsdLargeBatch &L, const int64_t *tab, const double *lam, double *out) {
+void launch_psd_large_affine_ds(hipStream_t st, const PsdView &P, double *out) {
+    const PsdLargeBatch &L = P.large;
     if (L.nlarge <= 0) return;
-    hipLaunchKernelGGL(k_psdl_affine_ds, dim3((L.max_n * L.max_n + 255) / 256, L.nlarge), dim3(256), 0, st, tab, L.lidx, L.lmin, lam, out);
+    hipLaunchKernelGGL(k_psdl_affine_ds, dim3((L.max_n * L.max_n + 255) / 256, L.nlarge), dim3(256), 0, st, P.tab, L.lidx, L.lmin, P.lam, out);
 }
-void launch_psd_large_mulhs(hipStream_t st, const PsdLargeBatch &L, const int64_t *tab, const double *R, const double *lam, const double *x,
-                            const double *addc, double *y) {
-    if (L.nlarge <= 0) return;
-    const Batch B = batch_of(st, L, tab, lam);
-    B.product({B.rows(kSvec, x), B.factor(kPlain, R), 0}, nullptr);          // T = X R
-    B.product({B.factor(kTrans, R), B.mat(kPlain, 0), 1}, nullptr);          // Y = R' T       (W x)
-    B.product({B.mat(kRoundTrip, 1), B.factor(kTrans, R), 0}, nullptr);      // T = Y R'
-    B.product({B.factor(kPlain, R), B.mat(kPlain, 0), 1}, nullptr);          // Y = R T        (W' W x)
+void launch_psd_large_mulhs(hipStream_t st, const PsdView &P, const double *x, const double *addc, double *y) {
+    if (P.large.nlarge <= 0) return;
+    const Batch B(st, P);
+    B.product({B.rows(kSvec, x), B.factor(kPlain, P.R), 0}, nullptr);        // T = X R
+    B.product({B.factor(kTrans, P.R), B.mat(kPlain, 0), 1}, nullptr);        // Y = R' T       (W x)
+    B.product({B.mat(kRoundTrip, 1), B.factor(kTrans, P.R), 0}, nullptr);    // T = Y R'
+    B.product({B.factor(kPlain, P.R), B.mat(kPlain, 0), 1}, nullptr);        // Y = R T        (W' W x)
     B.store(1, 0.0, addc, y);
 }
-void launch_psd_large_shift(hipStream_t st, const PsdLargeBatch &L, const int64_t *tab, const double *R, const double *Rinv,
-                            const double *lam, const double *dz, const double *ds, double sigma_mu, double *out) {
+void launch_psd_large_shift(hipStream_t st, const PsdView &P, const double *dz, const double *ds, double sigma_mu, double *out) {
+    const PsdLargeBatch &L = P.large;
     if (L.nlarge <= 0) return;
-    const Batch B = batch_of(st, L, tab, lam);
-    B.scaled_pair(R, Rinv, dz, ds);                                          // A = W dz in matrix 2, B = W^-T ds in matrix 3
-    hipLaunchKernelGGL(k_psdl_circ, dim3(B.tiles * B.tiles, L.nlarge), dim3(256), 0, st, tab, L.lidx, L.lmin, B.tiles, 2, 3, 0, L.ws);
+    const Batch B(st, P);
+    B.scaled_pair(dz, ds);                                                   // A = W dz in matrix 2, B = W^-T ds in matrix 3
+    hipLaunchKernelGGL(k_psdl_circ, dim3(B.tiles * B.tiles, L.nlarge), dim3(256), 0, st, P.tab, L.lidx, L.lmin, B.tiles, 2, 3, 0, L.ws);
     B.store(0, -sigma_mu, nullptr, out);
 }
-void launch_psd_large_offset(hipStream_t st, const PsdLargeBatch &L, const int64_t *tab, const double *R, const double *lam,
-                             const double *ds, double *out) {
-    if (L.nlarge <= 0) return;
-    const Batch B = batch_of(st, L, tab, lam);
-    B.product({B.rows(kOffset, ds), B.factor(kTrans, R), 0}, nullptr);       // T = X~ R'
-    B.product({B.factor(kPlain, R), B.mat(kPlain, 0), 1}, nullptr);          // Y = R T
+void launch_psd_large_offset(hipStream_t st, const PsdView &P, const double *ds, double *out) {
+    if (P.large.nlarge <= 0) return;
+    const Batch B(st, P);
+    B.product({B.rows(kOffset, ds), B.factor(kTrans, P.R), 0}, nullptr);     // T = X~ R'
+    B.product({B.factor(kPlain, P.R), B.mat(kPlain, 0), 1}, nullptr);        // Y = R T
     B.store(1, 0.0, nullptr, out);
 }
-void launch_psd_large_length(hipStream_t st, const PsdLargeBatch &L, const int64_t *tab, const double *R, const double *Rinv,
-                             const double *lam, const double *dz, const double *ds, double alpha_max, double *part) {
+void launch_psd_large_length(hipStream_t st, const PsdView &P, const double *dz, const double *ds, double alpha_max, double *part) {
+    const PsdLargeBatch &L = P.large;
     if (L.nlarge <= 0) return;
-    const Batch B = batch_of(st, L, tab, lam);
-    B.scaled_pair(R, Rinv, dz, ds);
-    hipLaunchKernelGGL(k_psdl_len, dim3(L.nlarge, 2), dim3(256), 0, st, tab, L.lidx, L.lmin, 2, L.ws, lam, alpha_max, part);
+    const Batch B(st, P);
+    B.scaled_pair(dz, ds);
+    hipLaunchKernelGGL(k_psdl_len, dim3(L.nlarge, 2), dim3(256), 0, st, P.tab, L.lidx, L.lmin, 2, L.ws, P.lam, alpha_max, part);
 }
 
 }  // namespace hipkkt
