@@ -1,35 +1,15 @@
 // The dense Schur-update tile (k_update_dense, kernels.hip): one wavefront keeps NT x NR blocks of 16 x 16 of a target tile in FP64
 // matrix-core accumulators while it sweeps all contributing source panels.  In a header because two translation units run it: the
-// update kernels (kernels.hip) and the extra workgroups of a k_front_block launch (front_block.hip), which apply tiles of the previous
-// update stage on compute units the panel kernel leaves idle.
+// update kernels (kernels.hip) and the extra workgroups of a front-batch launch (front_block2.hip, front_block.hip: dense_extra_tiles
+// below), which apply tiles of the previous update stage on compute units the panel kernel leaves idle.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "device_plan.h"
+#include "kernel_util.h"
 
 namespace hipkkt {
-
-#ifndef HIPKKT_V4F64_DEFINED
-#define HIPKKT_V4F64_DEFINED
-typedef double v4f64 __attribute__((ext_vector_type(4)));
-#endif
-__device__ __forceinline__ int rfl(int v) { return __builtin_amdgcn_readfirstlane(v); }
-
-template <class T>
-__device__ __forceinline__ T *rfl_ptr(T *p) {
-    const unsigned long long u = (unsigned long long)p;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-    return (T *)(((unsigned long long)hi << 32) | lo);
-}
-#define HK_GLOBAL __attribute__((address_space(1)))
-__device__ __forceinline__ double ld_off(const double *base, unsigned byte_off) {
-    // uniform base + 32-bit lane offset, explicitly in the global address space (global_load ... saddr)
-    return *(const HK_GLOBAL double *)((const HK_GLOBAL char *)base + byte_off);
-}
-__device__ __forceinline__ void st_off(double *base, unsigned byte_off, double v) {
-    *(HK_GLOBAL double *)((HK_GLOBAL char *)base + byte_off) = v;
-}
 
 // NT 16-column strips x NR 16-row blocks of a tile per wavefront
 template <int NT, int NR>
@@ -341,6 +321,16 @@ __device__ __forceinline__ void dense_tile(const DevPlan &P, const DenseGroup *G
         return;
     }
     dense_tile_core<NT, NR, DEEP>(P, tp, rt, nrt, wt, task_begin, task_end, lane, tj0, ti0);
+}
+
+// Rider workgroup xb of a front-batch launch (k_front_block, k_front_block2: the workgroups behind the batch's own): wavefront v takes
+// the tiles [(4 xb + v) per_wave, ... + per_wave) of the `count` tiles from group `begin`.  Each wavefront is alone on its SIMD (100 KB
+// of LDS per panel workgroup): tiles with four k-steps of operands in flight (DEEP), per_wave of them one after the other -- the launch
+// lasts as long as its panel chain anyway.
+__device__ __forceinline__ void dense_extra_tiles(const DevPlan &P, int begin, int count, int xb, int per_wave) {
+    const int lane = threadIdx.x & 63;
+    int idx = rfl((xb * 4 + (int)(threadIdx.x >> 6)) * per_wave);
+    for (int q = 0; q < per_wave && idx < count; q++, idx++) dense_tile<4, 4, true>(P, P.dgroups + begin + idx, lane, 0, 0);
 }
 
 }  // namespace hipkkt

@@ -32,29 +32,6 @@ namespace hipkkt {
 
 constexpr int FLD = 65;   // LDS row stride of a 64 x 64 tile
 
-__device__ __forceinline__ int fb_ldi(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ double fb_ld(const double *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void fb_st(double *p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ double fb_readlane(double x, int l) {   // l wave-uniform
-    const unsigned long long u = (unsigned long long)__double_as_longlong(x);
-    const unsigned lo = __builtin_amdgcn_readlane((unsigned)u, l), hi = __builtin_amdgcn_readlane((unsigned)(u >> 32), l);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-// 1 / d on the pivot chain: the hardware reciprocal r (2^-27 or better), then r (1 + e + e^2) with e = 1 - d r -- three dependent
-// operations instead of the four of two Newton steps, error ~ e^3 + one rounding
-__device__ __forceinline__ double fb_rcp3(double d) {
-    const double r = __builtin_amdgcn_rcp(d);
-    const double e = fma(-d, r, 1.0);
-    const double e2 = fma(e, e, e);
-    return fma(r, e2, r);
-}
-__device__ __forceinline__ double fb_rcp(double d) {   // kernels.hip pivot_rcp
-    double r = __builtin_amdgcn_rcp(d);
-    r = fma(fma(-d, r, 1.0), r, r);
-    r = fma(fma(-d, r, 1.0), r, r);
-    return r;
-}
-
 typedef unsigned v4u __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ double2 fb_unpack(v4u r) {
     double2 d;
@@ -78,21 +55,7 @@ __device__ __forceinline__ void fb_st16(double *p, double a, double b) {
     v4u r = {(unsigned)ua, (unsigned)(ua >> 32), (unsigned)ub, (unsigned)(ub >> 32)};
     asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 2" : : "v"(p), "v"(r) : "memory");
 }
-// LDS-only workgroup barrier: __syncthreads() also waits for this wave's outstanding global stores (vmcnt), which would put the
-// write-through latency of every streamed record on the pivot chain.  Nothing in the loops that use it communicates through global
-// memory inside the workgroup.
-__device__ __forceinline__ void fb_bar() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-// An exec-masked block (s_cbranch_execz) between a matrix-core instruction and the first read of its accumulators (v_accvgpr_read)
-// is a trap: the waves that skip the block arrive at the read with fewer wait states than the compiler's hazard recogniser counted
-// along the fall-through path, and read accumulators that are still being written (measured in round 4: deterministic 1e-4 errors
-// of the factorisation with a store block of two of the four waves behind the rank-8 update).  The loops below keep such blocks
-// away from that path (they sit behind a barrier, next to wave 0's eliminations); where one cannot be avoided, this pins 24 wait
-// states (enough for the 16-pass FP64 MFMA) between the matrix-core instructions before it and whatever follows.
-__device__ __forceinline__ void fb_mfma_settle() {
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
+// (kernel_util.h: lds_barrier, the workgroup barrier of the loops below, and mfma_settle, the wait states behind matrix-core code)
 // "not written yet" in a stream record: a NaN no arithmetic produces (both halves equal, so a 32-bit fill pattern would do too)
 constexpr unsigned kFbSentHalf = 0xFFFFFFFFu;               // (all ones: front_block2.hip tests a whole record with unsigned maxima of the high words)
 constexpr unsigned long long kFbSentinel = 0xFFFFFFFFFFFFFFFFull;
@@ -114,7 +77,7 @@ __device__ __forceinline__ bool fb_poll2(const double *p0, const double *p1, dou
                 atomicOr(failflag, 1);
                 return false;
             }
-            if (fb_ldi(err) != 0) return false;
+            if (ld_relaxed_i(err) != 0) return false;
         }
         __builtin_amdgcn_s_sleep(1);
     }
@@ -146,7 +109,7 @@ __device__ __forceinline__ void fb_tile_store(double *tl, const double *S, int t
 __device__ __forceinline__ bool fb_wait(const int *flag, int *err, int *failflag, unsigned lim, int *sres) {
     if (threadIdx.x == 0) {
         int ok = 1;
-        for (unsigned spins = 0; fb_ldi(flag) == 0; spins++) {
+        for (unsigned spins = 0; ld_relaxed_i(flag) == 0; spins++) {
             if ((spins & 63u) == 63u || lim < 64u) {
                 if (spins > lim) {
                     __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -154,7 +117,7 @@ __device__ __forceinline__ bool fb_wait(const int *flag, int *err, int *failflag
                     ok = 0;
                     break;
                 }
-                if (fb_ldi(err) != 0) { ok = 0; break; }
+                if (ld_relaxed_i(err) != 0) { ok = 0; break; }
             }
             __builtin_amdgcn_s_sleep(1);
         }
@@ -192,15 +155,6 @@ __device__ __forceinline__ void fb_store_panel(const DevPlan &P, const FrontPane
     }
 }
 
-// kept out of line: the register allocation of the panel path must not depend on it
-// Each wavefront is alone on its SIMD (100 KB of LDS per workgroup): tiles with four k-steps of operands in flight, kFbExtraPerWave
-// of them one after the other -- the launch lasts as long as its panel chain anyway.
-__device__ __forceinline__ void fb_extra_tiles(const DevPlan &P, int begin, int count, int xb, int per_wave) {
-    const int lane = threadIdx.x & 63;
-    int idx = rfl((xb * 4 + (int)(threadIdx.x >> 6)) * per_wave);
-    for (int q = 0; q < per_wave && idx < count; q++, idx++) dense_tile<4, 4, true>(P, P.dgroups + begin + idx, lane, 0, 0);
-}
-
 #define FB_T(slot) do { if (trace && tid == 0 && i < 5) trace[(B.sync_off / 128 * 8 + i) * 16 + (slot)] = (long long)wall_clock64(); } while (0)
 // shader-clock stamps of workgroup 0's pivot loop, 4 per block of 8 pivots (trace words 80 ..): after the first barrier, after wave 0's
 // eliminations, after the second barrier, after the rank-8 update
@@ -221,7 +175,7 @@ k_front_block(DevPlan P, FrontBatch B, int *sync_all, double *scratch_all, doubl
     double *stream = stream_all + B.stream_off;            // STREAM: record (panel j, block Bk) at ((8 j + Bk) * kFbRec)
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l15 = lane & 15, lk = lane >> 4;
     if ((int)blockIdx.x >= B.i_end - B.i_base) {          // extra workgroup: four tiles of the previous update stage (no hand-off, no LDS)
-        fb_extra_tiles(P, B.x_begin, B.x_count, (int)blockIdx.x - (B.i_end - B.i_base), B.pad > 0 ? B.pad : 1);
+        dense_extra_tiles(P, B.x_begin, B.x_count, (int)blockIdx.x - (B.i_end - B.i_base), B.pad > 0 ? B.pad : 1);
         return;
     }
     if (tid == 0) sblk = atomicAdd(sync + B.tick, 1);
@@ -279,7 +233,7 @@ k_front_block(DevPlan P, FrontBatch B, int *sync_all, double *scratch_all, doubl
             if (j == nsteps - 1) FB_T(2);
             const double *mv = scratch + (int64_t)j * 4160;
             fb_tile_load(mv, Sb, tid);                                                                        // Minv[k][c]
-            if (tid < 64) Sd[tid] = fb_ld(mv + 4096 + tid);
+            if (tid < 64) Sd[tid] = ld_relaxed(mv + 4096 + tid);
 #pragma unroll
             for (int sub = 0; sub < 4; sub++)
 #pragma unroll
@@ -348,7 +302,7 @@ k_front_block(DevPlan P, FrontBatch B, int *sync_all, double *scratch_all, doubl
     double (*colL)[64] = (double (*)[64])(Sa + 64 * 9);              // [8][64]   l_ik
     double (*colC)[64] = (double (*)[64])(Sa + 64 * 9 + 512);        // [8][64]   raw a_ik = d_k l_ik
     double *dsave = Sa + 64 * 9 + 1024;                              // [64]
-    double *dinvs = Sa + 64 * 9 + 1024 + 64;                         // [64]      1/d_k as used on the chain (fb_rcp)
+    double *dinvs = Sa + 64 * 9 + 1024 + 64;                         // [64]      1/d_k as used on the chain (pivot_rcp)
     double (*colC2)[64] = (double (*)[64])(Sa + 64 * 9 + 1024 + 128);   // [8][64] second buffer of colC for the pivot loop (STREAM)
     double lrow[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};       // STREAM, wave 3: the block of L(i, i-1) whose store is pending
     if (STREAM && diag && i > 0) {
@@ -371,8 +325,8 @@ k_front_block(DevPlan P, FrontBatch B, int *sync_all, double *scratch_all, doubl
         const int pc = wv < 2 ? 2 * tid : 0, pe = (tid >= 64 && tid < 72) ? 512 + 2 * (tid - 64) : 0;
         double n0 = 0.0, n1 = 0.0, n2 = 0.0, n3 = 0.0, n4 = 0.0, n5 = 0.0;
         auto request = [&](const double *rec) {
-            n0 = fb_ld(rec + pc); n1 = fb_ld(rec + pc + 1); n2 = fb_ld(rec + pc + 256); n3 = fb_ld(rec + pc + 257);
-            n4 = fb_ld(rec + pe); n5 = fb_ld(rec + pe + 1);
+            n0 = ld_relaxed(rec + pc); n1 = ld_relaxed(rec + pc + 1); n2 = ld_relaxed(rec + pc + 256); n3 = ld_relaxed(rec + pc + 257);
+            n4 = ld_relaxed(rec + pe); n5 = ld_relaxed(rec + pe + 1);
         };
         auto fresh = [&](double v) { return (unsigned long long)__double_as_longlong(v) != kFbSentinel; };
         if (wv < 2) request(rec0);
@@ -399,7 +353,7 @@ k_front_block(DevPlan P, FrontBatch B, int *sync_all, double *scratch_all, doubl
                 if (pe) { CR[pe] = n4; CR[pe + 1] = n5; }
                 if (!ok) sres = 0;
             }
-            fb_bar();
+            lds_barrier();
             if (sres == 0) return;                         // (uniform: nobody writes sres after this point)
             if (Bk == 0) FB_T(12);
             if (wv < 2 && Bk < 7) request(rec0 + (int64_t)(Bk + 1) * kFbRec);
@@ -423,7 +377,7 @@ k_front_block(DevPlan P, FrontBatch B, int *sync_all, double *scratch_all, doubl
 #pragma unroll
                 for (int q = 0; q < 4; q++) fb_st16(ltile + lane * 64 + 8 * (Bk - 1) + 2 * q, lrow[2 * q], lrow[2 * q + 1]);
             }
-            fb_bar();
+            lds_barrier();
             if (wv == 3) {                                 // this block's l values, stored during the next block's elimination
 #pragma unroll
                 for (int q = 0; q < 8; q++) lrow[q] = colL[q][lane];
@@ -439,11 +393,11 @@ k_front_block(DevPlan P, FrontBatch B, int *sync_all, double *scratch_all, doubl
                 for (int sub = 0; sub < 4; sub++)
                     tacc[sub] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, colC[4 * ks + lk][16 * sub + l15], tacc[sub], 0, 0, 0);
             }
-            // straight from the matrix-core instructions to the next iteration's accumulator reads (fb_mfma_settle's comment); Pc is
+            // straight from the matrix-core instructions to the next iteration's accumulator reads (mfma_settle's comment); Pc is
             // rewritten at once (only wave 0 read it, before the barrier above); colL / colC by wave 0 after the next iteration's
             // first barrier; the record buffer alternates
         }
-        fb_mfma_settle();                                  // the trace stamps / the ballot below are exec-masked blocks in front of the pivots' reads of tacc
+        mfma_settle();                                  // the trace stamps / the ballot below are exec-masked blocks in front of the pivots' reads of tacc
         FB_T(13);
     }
     FB_T(6);
@@ -468,7 +422,7 @@ k_front_block(DevPlan P, FrontBatch B, int *sync_all, double *scratch_all, doubl
         if (c >= 64 && c < 68) fb_st16(rec + 512 + 2 * (c - 64), dsave[8 * Bp + 2 * (c - 64)], dsave[8 * Bp + 2 * (c - 64) + 1]);
         if (c >= 68 && c < 72) fb_st16(rec + 520 + 2 * (c - 68), dinvs[8 * Bp + 2 * (c - 68)], dinvs[8 * Bp + 2 * (c - 68) + 1]);
     };
-    if (STREAM) fb_bar(); else __syncthreads();           // Sa (X_j) and Sb (the last operand tile / record) are free
+    if (STREAM) lds_barrier(); else __syncthreads();           // Sa (X_j) and Sb (the last operand tile / record) are free
 #pragma unroll
     for (int Bk = 0; Bk < 8; Bk++) {
         double (*cC)[64] = (STREAM && (Bk & 1)) ? colC2 : colC;
@@ -480,7 +434,7 @@ k_front_block(DevPlan P, FrontBatch B, int *sync_all, double *scratch_all, doubl
             }
         }
         if (STREAM) {
-            fb_bar();
+            lds_barrier();
         } else {
             if (Bk == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the L tile stores issued before the pivots have drained ...
             __syncthreads();
@@ -491,7 +445,7 @@ k_front_block(DevPlan P, FrontBatch B, int *sync_all, double *scratch_all, doubl
         if (wv == 0) {
             // Wave 0 is ISSUE-bound here (one FP64 instruction per 8 cycles, one 32-bit one per 4; measured with pieces compiled out:
             // DESIGN.md), so the loop is written for few instructions AND a short pivot-to-pivot chain:
-            //   d_k = a_kk - c_{k,k-1}^2 / d_{k-1}  ->  1 / d_k   is one fma, the hardware reciprocal and three more fma (fb_rcp3);
+            //   d_k = a_kk - c_{k,k-1}^2 / d_{k-1}  ->  1 / d_k   is one fma, the hardware reciprocal and three more fma (pivot_rcp3);
             //   a_kk and c_{k,k-1} are fetched from the lanes that hold them one pivot EARLIER (with the updates of the pivots before
             //   k-1 applied; what pivot k-1 contributes is the fma on the chain);
             //   the pivot rule is evaluated next to the reciprocal and applied by register selects -- written so that the compiler
@@ -501,14 +455,14 @@ k_front_block(DevPlan P, FrontBatch B, int *sync_all, double *scratch_all, doubl
             double pcol[8], dk[8], dik[8];
 #pragma unroll
             for (int q = 0; q < 8; q++) pcol[q] = Pc[lane * 9 + q];
-            double akk = fb_readlane(pcol[0], 8 * Bk), csq = 0.0, dinv_prev = 0.0;
+            double akk = readlane_f64(pcol[0], 8 * Bk), csq = 0.0, dinv_prev = 0.0;
 #pragma unroll
             for (int kk = 0; kk < 8; kk++) {
                 const int k = 8 * Bk + kk;
                 double d = fma(-csq, dinv_prev, akk);
                 const int sm = ((spos >> k) & 1ull) ? 0 : (int)0x80000000;               // expected sign negative: test -d, substitute -delta
                 const bool bad = __hiloint2double(__double2hiint(d) ^ sm, __double2loint(d)) < dyn_eps;
-                double dinv = fb_rcp3(d);
+                double dinv = pivot_rcp3(d);
                 double dsub = __hiloint2double(__double2hiint(dyn_delta) ^ sm, __double2loint(dyn_delta));
                 double isub = __hiloint2double(__double2hiint(dyn_delta_inv) ^ sm, __double2loint(dyn_delta_inv));
                 asm volatile("" : "+v"(dinv), "+v"(dsub), "+v"(isub));                   // all three in vector registers, unconditionally
@@ -519,8 +473,8 @@ k_front_block(DevPlan P, FrontBatch B, int *sync_all, double *scratch_all, doubl
                 dik[kk] = dinv;
                 const double reg = pcol[kk];
                 if (kk < 7) {
-                    akk = fb_readlane(pcol[kk + 1], k + 1);
-                    const double cn = fb_readlane(reg, k + 1);
+                    akk = readlane_f64(pcol[kk + 1], k + 1);
+                    const double cn = readlane_f64(reg, k + 1);
                     csq = cn * cn;
                 }
                 dinv_prev = dinv;
@@ -530,7 +484,7 @@ k_front_block(DevPlan P, FrontBatch B, int *sync_all, double *scratch_all, doubl
                 Sb[lane * FLD + k] = li;
 #pragma unroll
                 for (int jj = kk + 1; jj < 8; jj++) {
-                    const double cj = fb_readlane(reg, 8 * Bk + jj);
+                    const double cj = readlane_f64(reg, 8 * Bk + jj);
                     pcol[jj] = fma(-li, cj, pcol[jj]);
                 }
             }
@@ -552,7 +506,7 @@ k_front_block(DevPlan P, FrontBatch B, int *sync_all, double *scratch_all, doubl
             }
         }
         if (wv == 0) FB_TB(1);
-        if (STREAM) fb_bar(); else __syncthreads();
+        if (STREAM) lds_barrier(); else __syncthreads();
         FB_TB(2);
         if (Bk < 7) {
             // a_ij -= sum_k l_ik a_jk over the block's 8 pivots, for the 16-column strips that still hold live columns
@@ -565,7 +519,7 @@ k_front_block(DevPlan P, FrontBatch B, int *sync_all, double *scratch_all, doubl
                         tacc[sub] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, cC[4 * ks + lk][16 * sub + l15], tacc[sub], 0, 0, 0);
             }
         }
-        fb_mfma_settle();                                 // the stamp below is an exec-masked block between the matrix-core instructions above and the
+        mfma_settle();                                 // the stamp below is an exec-masked block between the matrix-core instructions above and the
         FB_TB(3);                                         // next iteration's reads of their accumulators (this form is not the default any more)
         // Pc / colL are rewritten after the next iteration's first barrier / by wave 0 after it: every wave is past its reads
     }
@@ -629,7 +583,7 @@ k_front_block(DevPlan P, FrontBatch B, int *sync_all, double *scratch_all, doubl
             const int idx = tid + 256 * q, k = idx >> 5, c = 2 * (idx & 31);
             fb_st16(mv + 2 * idx, c >= k ? Sa[c * FLD + k] * Sd[c] : 0.0, c + 1 >= k ? Sa[(c + 1) * FLD + k] * Sd[c + 1] : 0.0);
         }
-        if (tid < 64) fb_st(mv + 4096 + tid, dkeep);
+        if (tid < 64) st_relaxed(mv + 4096 + tid, dkeep);
         fb_publish(fl_minv + i);
     }
     FB_T(10);

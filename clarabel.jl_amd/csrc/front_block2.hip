@@ -42,33 +42,13 @@ namespace {
 constexpr int LDT = 65;   // LDS row stride of the 64 x 64 tiles of the inverse
 constexpr int CS = 68;    // row stride of the pivot loop's column buffers (the four k-rows a lane quad reads sit in different banks)
 
-__device__ __forceinline__ int f2_ldi(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ double f2_ld(const double *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void f2_st(double *p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ double f2_readlane(double x, int l) {   // l wave-uniform
-    const unsigned long long u = (unsigned long long)__double_as_longlong(x);
-    const unsigned lo = __builtin_amdgcn_readlane((unsigned)u, l), hi = __builtin_amdgcn_readlane((unsigned)(u >> 32), l);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-__device__ __forceinline__ double f2_rcp3(double d) {   // front_block.hip fb_rcp3
-    const double r = __builtin_amdgcn_rcp(d);
-    const double e = fma(-d, r, 1.0);
-    const double e2 = fma(e, e, e);
-    return fma(r, e2, r);
-}
-// LDS-only workgroup barrier (front_block.hip fb_bar: __syncthreads() would also wait for the write-through stores in flight)
-__device__ __forceinline__ void f2_bar() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-// front_block.hip fb_mfma_settle: wait states between matrix-core instructions and an exec-masked block / a loop back-edge
-__device__ __forceinline__ void f2_settle() {
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
-// "not written yet" in a stream record = all ones (k_fb_reset, front_block.hip): a NaN no arithmetic produces.  A record is complete
+// (kernel_util.h: the relaxed accesses, readlane_f64, pivot_rcp3, lds_barrier and mfma_settle, shared with k_factor_panel and front_block.hip)
+// "not written yet" in a stream record = all ones (k_fb_reset below): a NaN no arithmetic produces.  A record is complete
 // when the unsigned maximum of the high words of its values is below 0xFFFFFFFF (two v_max3_u32 per six values).
 __device__ __forceinline__ unsigned f2_hi(double v) { return (unsigned)__double2hiint(v); }
 __device__ __forceinline__ unsigned f2_max3(unsigned a, unsigned b, unsigned c) { return max(max(a, b), c); }
-// uniform base + 32-bit lane offset (+ immediate): one instruction per access, no 64-bit address arithmetic on the vector side
+// uniform base + 32-bit lane offset (+ immediate): one instruction per access, no 64-bit address arithmetic on the vector side.
+// The relaxed agent-scope form of kernel_util.h's ld_off / st_off (hand-off data: not the same instructions)
 __device__ __forceinline__ double f2_ldo(const double *base, unsigned byte_off) {
     return __hip_atomic_load((const HK_GLOBAL double *)((const HK_GLOBAL char *)base + byte_off), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -80,14 +60,14 @@ __device__ __forceinline__ void f2_sto(double *base, unsigned byte_off, double v
 // loop is a scalar branch (no exec-masked block next to matrix-core code).  false = timed out / somebody else failed.
 __device__ __forceinline__ bool f2_wait(const int *flag, int want, int *err, int *failflag, unsigned lim) {
     for (unsigned spins = 0;; spins++) {
-        if (__builtin_amdgcn_readfirstlane(f2_ldi(flag)) >= want) return true;
+        if (__builtin_amdgcn_readfirstlane(ld_relaxed_i(flag)) >= want) return true;
         if ((spins & 63u) == 63u || lim < 64u) {
             if (spins > lim) {
                 __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 if ((threadIdx.x & 63) == 0) atomicOr(failflag, 1);
                 return false;
             }
-            if (__builtin_amdgcn_readfirstlane(f2_ldi(err)) != 0) return false;
+            if (__builtin_amdgcn_readfirstlane(ld_relaxed_i(err)) != 0) return false;
         }
         __builtin_amdgcn_s_sleep(1);
     }
@@ -96,12 +76,6 @@ __device__ __forceinline__ bool f2_wait(const int *flag, int want, int *err, int
 __device__ __forceinline__ void f2_wave_done(int *flag) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_add(flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ void f2_extra_tiles(const DevPlan &P, int begin, int count, int xb, int per_wave) {   // front_block.hip fb_extra_tiles
-    const int lane = threadIdx.x & 63;
-    int idx = rfl((xb * 4 + (int)(threadIdx.x >> 6)) * per_wave);
-    for (int q = 0; q < per_wave && idx < count; q++, idx++) dense_tile<4, 4, true>(P, P.dgroups + begin + idx, lane, 0, 0);
 }
 
 #define F2_T(slot) do { if (TRACE) { if (trace && tid == 0 && i < 5) trace[(B.sync_off / 128 * 8 + i) * 16 + (slot)] = (long long)wall_clock64(); } } while (0)
@@ -128,7 +102,7 @@ k_front_block2(DevPlan P, FrontBatch B, int *sync_all, double *scratch_all, doub
     const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15, lk = lane >> 4;
     const int wv = rfl(tid >> 6);
     if ((int)blockIdx.x >= B.i_end - B.i_base) {          // extra workgroup: tiles of the previous update stage (no hand-off, no LDS)
-        f2_extra_tiles(P, B.x_begin, B.x_count, (int)blockIdx.x - (B.i_end - B.i_base), B.pad > 0 ? B.pad : 1);
+        dense_extra_tiles(P, B.x_begin, B.x_count, (int)blockIdx.x - (B.i_end - B.i_base), B.pad > 0 ? B.pad : 1);
         return;
     }
     if (tid == 0) sblk = atomicAdd(sync + B.tick, 1);
@@ -249,7 +223,7 @@ k_front_block2(DevPlan P, FrontBatch B, int *sync_all, double *scratch_all, doub
                             if (lane == 0) atomicOr(failflag, 1);
                             return false;
                         }
-                        if (__builtin_amdgcn_readfirstlane(f2_ldi(err)) != 0) return false;
+                        if (__builtin_amdgcn_readfirstlane(ld_relaxed_i(err)) != 0) return false;
                     }
                     __builtin_amdgcn_s_sleep(1);
                     F2_REQUEST(sl, Bk);
@@ -271,7 +245,7 @@ k_front_block2(DevPlan P, FrontBatch B, int *sync_all, double *scratch_all, doub
                 // (its l d of all 64 rows went to LDS in the previous iteration; the barrier closes that exchange).  The strips right
                 // of a wave's own rows are the upper triangle, but the slowest wave -- the last, all four strips -- sets the pace at
                 // the barrier: no per-wave branches here.
-                f2_bar();
+                lds_barrier();
                 const double *lp = ldx + ((Bk - 1) & 1) * 512;
                 double la[4][2];
 #pragma unroll
@@ -308,7 +282,7 @@ k_front_block2(DevPlan P, FrontBatch B, int *sync_all, double *scratch_all, doub
             }
         }
         if (WITH_TR) {                                    // the diagonal tile's update by the last record
-            f2_bar();
+            lds_barrier();
             const double *lp = ldx + 512;
             double la[4][2];
 #pragma unroll
@@ -330,10 +304,10 @@ k_front_block2(DevPlan P, FrontBatch B, int *sync_all, double *scratch_all, doub
         double v[16];
 #pragma unroll
         for (int q = 0; q < 16; q++) v[q] = f2_ldo(tile + (q >> 1) * 512, tid8 + (q & 1) * 2048);
-        f2_bar();                                         // everybody is done with the tile before
+        lds_barrier();                                    // everybody is done with the tile before
 #pragma unroll
         for (int q = 0; q < 16; q++) STG[tid + 256 * q] = v[q];
-        f2_bar();
+        lds_barrier();
     };
 #pragma unroll
     for (int j = 0; j < (diag ? 0 : kFbMax); j++) {
@@ -347,7 +321,7 @@ k_front_block2(DevPlan P, FrontBatch B, int *sync_all, double *scratch_all, doub
 #pragma unroll
                 for (int sub = 0; sub < 4; sub++)
 #pragma unroll
-                    for (int reg = 0; reg < 4; reg++) dj[sub][reg] = f2_ld(mv + 4096 + 16 * sub + lk + 4 * reg);
+                    for (int reg = 0; reg < 4; reg++) dj[sub][reg] = ld_relaxed(mv + 4096 + 16 * sub + lk + 4 * reg);
             }
             // The A operand -- the same for all four waves -- comes through LDS: every thread fetches 16 values of the tile (all in
             // flight at once, one memory round trip), the tile is laid down in operand order, each wave reads its k-steps back
@@ -383,7 +357,7 @@ k_front_block2(DevPlan P, FrontBatch B, int *sync_all, double *scratch_all, doub
             if (diag) {
                 // the diagonal tile  T_ii -= (X D) X^T
                 const double *xd = S0 + (j & 1) * 4096;
-                f2_bar();
+                lds_barrier();
 #pragma unroll
                 for (int so = 0; so < 4; so++) {
                     double xa[16];
@@ -393,12 +367,12 @@ k_front_block2(DevPlan P, FrontBatch B, int *sync_all, double *scratch_all, doub
                     for (int kk = 0; kk < 16; kk++)
                         tr[so] = __builtin_amdgcn_mfma_f64_16x16x4f64(xa[kk], x[kk >> 2][kk & 3], tr[so], 0, 0, 0);
                 }
-                f2_settle();
+                mfma_settle();
                 f2_wave_done(fl_L + 8 * i + j);
             }
             // the panel (column-major) and its row-major copy for the backward solves -- after the hand-off: the flag waits for this
             // wave's outstanding stores, and these 32 strided ones are slow to drain (x holds -X by now)
-            f2_settle();
+            mfma_settle();
             if (rowok) {
                 double *dst = P.Lx + pj.panel_off + 64 * (i - j) + n;
                 double *lt2 = P.LT + pj.lt_off + (int64_t)(64 * (i - j) - 64 + n) * 64;
@@ -445,7 +419,7 @@ k_front_block2(DevPlan P, FrontBatch B, int *sync_all, double *scratch_all, doub
         double dj[4][4];
         request_head(nb - 1);
         if (!consume(std::false_type{}, nb - 1, x, dj)) return;
-        f2_settle();
+        mfma_settle();
         if (rowok) {
             const FrontPanel pj = fp[nb - 1];
             double *dst = P.Lx + pj.panel_off + 64 * (i - (nb - 1)) + n;
@@ -525,7 +499,7 @@ k_front_block2(DevPlan P, FrontBatch B, int *sync_all, double *scratch_all, doub
                 }
 #pragma unroll
             for (int so = 0; so < 4; so++) x[so] = -x[so];
-            f2_bar();
+            lds_barrier();
 #pragma unroll
             for (int so = 0; so < 4; so++) {
                 double xa[16];
@@ -535,7 +509,7 @@ k_front_block2(DevPlan P, FrontBatch B, int *sync_all, double *scratch_all, doub
                 for (int kk = 0; kk < 16; kk++)
                     tr[so] = __builtin_amdgcn_mfma_f64_16x16x4f64(xa[kk], x[kk >> 2][kk & 3], tr[so], 0, 0, 0);
             }
-            f2_settle();
+            mfma_settle();
             if (j2 == i - 2) F2_T(11);
             f2_wave_done(fl_L + 8 * i + j2);
             pe = pn;
@@ -589,7 +563,7 @@ k_front_block2(DevPlan P, FrontBatch B, int *sync_all, double *scratch_all, doub
     // ---- streamed step: this workgroup's rows of panel i - 1, record by record behind the workgroup that eliminates tile i - 1.
     if (i > 0) {
         double dl[4][4];
-        f2_bar();                                         // the X D buffers of the steps before are free
+        lds_barrier();                                    // the X D buffers of the steps before are free
         head(i - 1, i > 1);
         if (!consume(std::true_type{}, i - 1, xr, dl)) return;
         // L(i, i-1) D for the workgroups below (operand order); the flag follows during the first pivot block
@@ -598,7 +572,7 @@ k_front_block2(DevPlan P, FrontBatch B, int *sync_all, double *scratch_all, doub
         for (int sub = 0; sub < 4; sub++)
 #pragma unroll
             for (int reg = 0; reg < 4; reg++) f2_sto(lt + (4 * sub + (reg & 2)) * 64, lane8 + (reg & 1) * 512, xr[sub][reg] * dl[sub][reg]);
-        f2_settle();
+        mfma_settle();
         F2_T(4);
     }
 
@@ -663,13 +637,13 @@ k_front_block2(DevPlan P, FrontBatch B, int *sync_all, double *scratch_all, doub
         double pcol[8], dk[8], dik[8];
 #pragma unroll
         for (int q = 0; q < 8; q++) pcol[q] = Pc[lane * 9 + q];
-        double akk = f2_readlane(pcol[0], 8 * Bk), csq = 0.0, dinv_prev = 0.0;
+        double akk = readlane_f64(pcol[0], 8 * Bk), csq = 0.0, dinv_prev = 0.0;
         int nr_ = 0;
 #pragma unroll
         for (int kk = 0; kk < 8; kk++) {
             const int k = 8 * Bk + kk;
             double d = fma(-csq, dinv_prev, akk);
-            double dinv = f2_rcp3(d);
+            double dinv = pivot_rcp3(d);
             if (RULE) {
                 const int sm = ((spos >> k) & 1ull) ? 0 : (int)0x80000000;               // expected sign negative: test -d, substitute -delta
                 const bool bad = __hiloint2double(__double2hiint(d) ^ sm, __double2loint(d)) < dyn_eps;
@@ -684,8 +658,8 @@ k_front_block2(DevPlan P, FrontBatch B, int *sync_all, double *scratch_all, doub
             dik[kk] = dinv;
             const double reg = pcol[kk];
             if (kk < 7) {
-                akk = f2_readlane(pcol[kk + 1], k + 1);
-                const double cn = f2_readlane(reg, k + 1);
+                akk = readlane_f64(pcol[kk + 1], k + 1);
+                const double cn = readlane_f64(reg, k + 1);
                 csq = cn * cn;
             }
             dinv_prev = dinv;
@@ -695,7 +669,7 @@ k_front_block2(DevPlan P, FrontBatch B, int *sync_all, double *scratch_all, doub
             L11[lane * LDT + k] = li;
 #pragma unroll
             for (int jj = kk + 1; jj < 8; jj++) {
-                const double cj = f2_readlane(reg, 8 * Bk + jj);
+                const double cj = readlane_f64(reg, 8 * Bk + jj);
                 pcol[jj] = fma(-li, cj, pcol[jj]);
             }
         }
@@ -747,7 +721,7 @@ k_front_block2(DevPlan P, FrontBatch B, int *sync_all, double *scratch_all, doub
             }
         }
     };
-    f2_bar();                                             // the l d buffers of the streamed step are free
+    lds_barrier();                                        // the l d buffers of the streamed step are free
     F2_T(5);
 #pragma unroll
     for (int Bk = 0; Bk < 8; Bk++) {
@@ -756,7 +730,7 @@ k_front_block2(DevPlan P, FrontBatch B, int *sync_all, double *scratch_all, doub
             Pc[n * 9 + lk] = tr[sb][2 * par];
             Pc[n * 9 + 4 + lk] = tr[sb][2 * par + 1];
         }
-        f2_bar();
+        lds_barrier();
         F2_TB(0);
         if (wv == 0) {
             double *cL = par ? colLb : colLa, *cC = par ? cCb : cCa;
@@ -772,7 +746,7 @@ k_front_block2(DevPlan P, FrontBatch B, int *sync_all, double *scratch_all, doub
             }
         }
         F2_TB(1);
-        f2_bar();
+        lds_barrier();
         F2_TB(2);
         if (wv == 0 && Bk == 0 && i > 0) f2_wave_done(fl_L + 8 * i + (i - 1));   // (wave 0: after its first elimination -- its stores are a block time old)
         if (Bk < 7) {
@@ -780,7 +754,7 @@ k_front_block2(DevPlan P, FrontBatch B, int *sync_all, double *scratch_all, doub
             const int u = (Bk + 1) >> 1;
             if (u <= wv) update_strip(Bk, u);
         }
-        f2_settle();
+        mfma_settle();
         F2_TB(3);
     }
     if (pub && wv > 0) publish(7);
@@ -853,9 +827,9 @@ k_front_block2(DevPlan P, FrontBatch B, int *sync_all, double *scratch_all, doub
         for (int q = 0; q < 16; q++) {
             const int g = wv + 4 * q;                     // group = 16 (c / 16) + k / 4; this wave's lanes are the group's 64 slots
             const int c = 16 * (g >> 4) + l15, k = 4 * (g & 15) + lk;
-            f2_st(mv + g * 64 + lane, c >= k ? Sa[c * LDT + k] * Sd[c] : 0.0);
+            st_relaxed(mv + g * 64 + lane, c >= k ? Sa[c * LDT + k] * Sd[c] : 0.0);
         }
-        if (tid < 64) f2_st(mv + 4096 + tid, dkeep);
+        if (tid < 64) st_relaxed(mv + 4096 + tid, dkeep);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (tid == 0) __hip_atomic_store(fl_minv + i, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

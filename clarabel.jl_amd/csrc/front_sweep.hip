@@ -22,6 +22,7 @@
 
 #include <type_traits>
 
+#include "kernel_util.h"
 #include "kernels.h"
 #include "sweep_common.h"
 
@@ -34,7 +35,6 @@ extern "C" int hipkkt_debug_sweep_trace(long long *out) { return (int)hipMemcpyF
 #endif
 namespace hipkkt {
 
-typedef double v4f64 __attribute__((ext_vector_type(4)));
 constexpr int SLD = 65;            // LDS row stride of a 64 x 64 tile
 constexpr int kSbThreads = 1024;   // 16 wavefronts: 4 values per tile and thread (two groups of 5 tiles = 80 VGPRs of the 128 available)
 constexpr int NW = kSbThreads / 64;  // wavefronts per workgroup
@@ -44,12 +44,7 @@ static_assert(kSbMaxPanels * 16 <= 24 * 1024, "panel table of the sweeps must fi
 __device__ __forceinline__ int64_t sb_tile(const FrontDesc &F, int B, int bl, int cl) {   // symbolic.h FrontDesc::sbinv_off
     return F.sbinv_off + ((int64_t)B * (kSbG * (kSbG - 1) / 2) + bl * (bl - 1) / 2 + cl) * 8192;
 }
-#define SB_GLOBAL __attribute__((address_space(1)))
-__device__ __forceinline__ double sb_ld(const double *base, unsigned byte_off) {   // uniform base + 32-bit lane offset (saddr form)
-    return *(const SB_GLOBAL double *)((const SB_GLOBAL char *)base + byte_off);
-}
-// wave-uniform values are forced into SGPRs (a FrontPanel record read through a plain pointer lands in VGPRs otherwise)
-__device__ __forceinline__ int sb_rfl(int v) { return __builtin_amdgcn_readfirstlane(v); }
+// (kernel_util.h: rfl forces the wave-uniform fields of a FrontPanel record into SGPRs; ld_off = uniform base + 32-bit lane offset)
 __device__ __forceinline__ int64_t sb_rfl64(int64_t v) {
     const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)(uint64_t)v), hi = __builtin_amdgcn_readfirstlane((unsigned)((uint64_t)v >> 32));
     return (int64_t)(((uint64_t)hi << 32) | lo);
@@ -89,7 +84,6 @@ __host__ __device__ constexpr int sb_op_row(int m) {
     return m < 2 ? 1 : m < 5 ? 2 : m < 9 ? 3 : m < 14 ? 4 : m < 20 ? 5 : m < 27 ? 6 : m < 35 ? 7 : 8;
 }
 static_assert(kSbG == 8 && sb_op_row(1) == 1 && sb_op_row(2) == 2 && sb_op_row(34) == 7 && sb_op_row(35) == 8, "operand list of k_invert_super");
-__device__ __forceinline__ void sb_bar() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 template <bool CW64>                     // the front's panels are 64 wide (all but its last one): FrontDesc::cw == 64
 __global__ void __launch_bounds__(kInvThreads)
@@ -104,7 +98,7 @@ k_invert_super(DevPlan P, FrontDesc F) {
     const int cl = blockIdx.x / per_cl, B = (blockIdx.x % per_cl) / kInvSlices, sl = blockIdx.x % kInvSlices;
     const int nbB = min(kSbG, F.np - kSbG * B);
     if (cl + 1 >= nbB) return;
-    const int tid = threadIdx.x, lane = tid & 63, wv = sb_rfl(tid >> 6), l15 = lane & 15, lk = lane >> 4;
+    const int tid = threadIdx.x, lane = tid & 63, wv = rfl(tid >> 6), l15 = lane & 15, lk = lane >> 4;
     const FrontPanel *fps = P.front_panels + F.fp_off;
     if (tid < nbB) {
         const FrontPanel q = fps[kSbG * B + tid];
@@ -135,12 +129,12 @@ k_invert_super(DevPlan P, FrontDesc F) {
             if (fjk < fjb) {
                 // rows past the block's width and columns past the source panel's width need no zeroing here: they meet zero rows of
                 // the B operand / zero columns of Linv_bl; the addresses only have to stay inside the panel
-                const int kl = min(cl + fjk, bl - 1), wk = sb_rfl(s_w[kl]), rk = sb_rfl(s_r[kl]);
+                const int kl = min(cl + fjk, bl - 1), wk = rfl(s_w[kl]), rk = rfl(s_r[kl]);
                 const double *base = P.Lx + sb_rfl64(s_off[kl]) + F.cw * (bl - kl);
                 if (CW64) {               // uniform base per k-step + one lane offset, no vector arithmetic (kl is never the front's last panel)
                     const unsigned lo = (unsigned)(ic + lk * rk) * 8u;
 #pragma unroll
-                    for (int kk = 0; kk < 16; kk++) ring[m % kInvRing][kk] = sb_ld(base + (int64_t)(4 * kk) * rk, lo);
+                    for (int kk = 0; kk < 16; kk++) ring[m % kInvRing][kk] = ld_off(base + (int64_t)(4 * kk) * rk, lo);
                 } else {
 #pragma unroll
                     for (int kk = 0; kk < 16; kk++) ring[m % kInvRing][kk] = base[ic + (int64_t)min(4 * kk + lk, wk - 1) * rk];
@@ -160,7 +154,7 @@ k_invert_super(DevPlan P, FrontDesc F) {
     };
 #pragma unroll
     for (int u = 0; u < kInvRing - 1; u++) fetch_op(u);
-    sb_bar();                             // Bs[0] is complete
+    lds_barrier();                        // Bs[0] is complete
     // the rows are nested (row jb + 1 inside the branch of row jb), not a sequence of seven branches: see fetch_op
     auto row = [&](auto &&self, auto jb_c) -> void {
         constexpr int jb = decltype(jb_c)::value;
@@ -196,7 +190,7 @@ k_invert_super(DevPlan P, FrontDesc F) {
             fetch_op(n + kInvRing - 1);
 #pragma unroll
             for (int reg = 0; reg < 4; reg++) Ss[(16 * wv + lk + 4 * reg) * 16 + l15] = acc[reg];
-            sb_bar();
+            lds_barrier();
             v4f64 po[4];
 #pragma unroll
             for (int c = 0; c < 4; c++) po[c] = v4f64{0.0, 0.0, 0.0, 0.0};
@@ -212,7 +206,7 @@ k_invert_super(DevPlan P, FrontDesc F) {
                 t[i + 64 * col] = v;                                             // column-major half [i + 64 k]
                 t[4096 + 64 * i + col] = v;                                      // row-major half [64 i + k]
             }
-            sb_bar();                     // the new tile is visible to every wavefront; Ss may be written again
+            lds_barrier();                // the new tile is visible to every wavefront; Ss may be written again
             if constexpr (jb + 1 < kSbG) self(self, std::integral_constant<int, jb + 1>{});
         }
     };
@@ -258,14 +252,14 @@ k_front_fwd_sb(DevPlan P, FrontDesc F, double *__restrict__ y, double *__restric
     }
     if (threadIdx.x == 0) { sb = atomicAdd(sync, 1); okflag = 1; }
     __syncthreads();
-    const int tk = sb_rfl(sb);                  // wave-uniform for the compiler too: scalar branches, SGPR tile bases
+    const int tk = rfl(sb);                  // wave-uniform for the compiler too: scalar branches, SGPR tile bases
     const int b = tk >> 1, h = tk & 1;
     if (b >= F.nb) return;
     SWT(0);
     // re-arm the backward sweep's block (idle during this launch), every workgroup a share
     for (int q = tk * kSbThreads + threadIdx.x; q < F.sync_blk; q += 2 * F.nb * kSbThreads) sync[F.sync_blk + q] = 0;
     FrontSlot *yslots = front_slots(sync, F.np), *rslots = yslots + (int64_t)F.np * 64;
-    const int tid = threadIdx.x, lane = tid & 63, wv = sb_rfl(tid >> 6);
+    const int tid = threadIdx.x, lane = tid & 63, wv = rfl(tid >> 6);
     const int lr = lane & 31, ph = lane >> 5, ir = 32 * h + lr, k0 = 2 * wv + ph;      // row inside the block, first column
     const FrontPanel *fps = P.front_panels + F.fp_off;
     const int g = kSbG;
@@ -273,7 +267,7 @@ k_front_fwd_sb(DevPlan P, FrontDesc F, double *__restrict__ y, double *__restric
     struct { int w, f; int64_t diag_off; } me;
     {
         const FrontPanel *mp = fps + (own ? b : 0);
-        me.w = sb_rfl(mp->w); me.f = sb_rfl(mp->f); me.diag_off = sb_rfl64(mp->diag_off);
+        me.w = rfl(mp->w); me.f = rfl(mp->f); me.diag_off = sb_rfl64(mp->diag_off);
     }
     const int B = own ? b / g : F.nsb, bl = own ? b - g * B : 0;
     const int i0 = own ? F.cw * b : F.W + 64 * (b - F.np);
@@ -298,13 +292,13 @@ k_front_fwd_sb(DevPlan P, FrontDesc F, double *__restrict__ y, double *__restric
         for (int p = 0; p < kSbG; p++) {
             const int q = g * G + p;
             const int qc = q < F.np ? q : F.np - 1;
-            const int fq_r = sb_rfl(pn_r[qc]), fq_w = sb_rfl(pn_w[qc]);
+            const int fq_r = rfl(pn_r[qc]), fq_w = rfl(pn_w[qc]);
             const double *pb = P.Lx + sb_rfl64(pn_off[qc]);
             const unsigned o0 = (unsigned)(i - F.cw * q + k0 * fq_r) * 8u, os = (unsigned)fq_r * (8u * 32u);
 #pragma unroll
             for (int t = 0; t < NT; t++) {
                 const int k = k0 + 32 * t;
-                dst[p][t] = (q < F.np && valid && k < fq_w && !(P.dbg & 1)) ? sb_ld(pb, o0 + (unsigned)t * os) : 0.0;
+                dst[p][t] = (q < F.np && valid && k < fq_w && !(P.dbg & 1)) ? ld_off(pb, o0 + (unsigned)t * os) : 0.0;
             }
         }
     };
@@ -318,12 +312,12 @@ k_front_fwd_sb(DevPlan P, FrontDesc F, double *__restrict__ y, double *__restric
         if (own && p < bl) {                     // (uniform) a full tile of the super-block inverse, column-major (rows past the panel's width are zero)
             const double *tl = P.SbInv + sb_tile(F, B, bl, p);
 #pragma unroll
-            for (int t = 0; t < NT; t++) inv[p][t] = sb_ld(tl, (unsigned)(ir + 64 * (k0 + 32 * t)) * 8u);
+            for (int t = 0; t < NT; t++) inv[p][t] = ld_off(tl, (unsigned)(ir + 64 * (k0 + 32 * t)) * 8u);
         } else if (own && p == bl) {             // the panel's own inverse (lower triangular, w x w column-major)
             const double *li = P.Linv + me.diag_off;
             const int irc = min(ir, me.w - 1);
 #pragma unroll
-            for (int t = 0; t < NT; t++) inv[p][t] = sb_ld(li, (unsigned)(irc + min(k0 + 32 * t, irc) * me.w) * 8u);
+            for (int t = 0; t < NT; t++) inv[p][t] = ld_off(li, (unsigned)(irc + min(k0 + 32 * t, irc) * me.w) * 8u);
         } else {
 #pragma unroll
             for (int t = 0; t < NT; t++) inv[p][t] = 0.0;
@@ -432,17 +426,17 @@ k_front_bwd_sb(DevPlan P, FrontDesc F, const double *__restrict__ z, double *__r
     for (int q = threadIdx.x; q < F.np; q += kSbThreads) pn_w[q] = P.front_panels[F.fp_off + q].w;
     if (threadIdx.x == 0) { sb = atomicAdd(sync, 1); okflag = 1; }
     __syncthreads();
-    const int tk = sb_rfl(sb);                  // wave-uniform for the compiler too
+    const int tk = rfl(sb);                  // wave-uniform for the compiler too
     if (tk >= 2 * F.np) return;
     // re-arm the forward sweep's block for the next solve (idle during this launch), every workgroup a share
     for (int q = tk * kSbThreads + threadIdx.x; q < F.sync_blk; q += 2 * F.np * kSbThreads) sync[q - F.sync_blk] = 0;
     FrontSlot *xslots = front_slots(sync, F.np), *sslots = xslots + (int64_t)F.np * 64;
     const int p = F.np - 1 - (tk >> 1), h = 1 - (tk & 1);
-    const int tid = threadIdx.x, lane = tid & 63, wv = sb_rfl(tid >> 6);
+    const int tid = threadIdx.x, lane = tid & 63, wv = rfl(tid >> 6);
     const int kc = 32 * h + (lane & 31), ph = lane >> 5, j0 = 2 * wv + ph;       // column of the panel, first tile row
     const FrontPanel *fps = P.front_panels + F.fp_off;
     struct { int w, f; int64_t diag_off, lt_off; } me;
-    me.w = sb_rfl(fps[p].w); me.f = sb_rfl(fps[p].f); me.diag_off = sb_rfl64(fps[p].diag_off); me.lt_off = sb_rfl64(fps[p].lt_off);
+    me.w = rfl(fps[p].w); me.f = rfl(fps[p].f); me.diag_off = sb_rfl64(fps[p].diag_off); me.lt_off = sb_rfl64(fps[p].lt_off);
     const int w = me.w;
     const bool cvalid = kc < w;
     const bool lead = wv == 0 && ph == 0;
@@ -476,12 +470,12 @@ k_front_bwd_sb(DevPlan P, FrontDesc F, const double *__restrict__ z, double *__r
 #pragma unroll
         for (int pp = 0; pp < kSbG; pp++) {
             const int q = g * Q + pp;
-            const int fq_w = sb_rfl(pn_w[q < F.np ? q : F.np - 1]);
+            const int fq_w = rfl(pn_w[q < F.np ? q : F.np - 1]);
             const unsigned o0 = (unsigned)((F.cw * (q - p) + j0 - w) * w + kc) * 8u, os = (unsigned)w * (8u * 32u);
 #pragma unroll
             for (int t = 0; t < NT; t++) {
                 const int jr = j0 + 32 * t;
-                dst[pp][t] = (q < F.np && cvalid && jr < fq_w && !(P.dbg & 1)) ? sb_ld(lt, o0 + (unsigned)t * os) : 0.0;
+                dst[pp][t] = (q < F.np && cvalid && jr < fq_w && !(P.dbg & 1)) ? ld_off(lt, o0 + (unsigned)t * os) : 0.0;
             }
         }
     };
@@ -493,12 +487,12 @@ k_front_bwd_sb(DevPlan P, FrontDesc F, const double *__restrict__ z, double *__r
         if (cl > pl && cl < nbB) {               // (uniform) a full tile of the super-block inverse, row-major half (columns past the width are zero)
             const double *tl = P.SbInv + sb_tile(F, B, cl, pl) + 4096;
 #pragma unroll
-            for (int t = 0; t < NT; t++) inv[cl][t] = sb_ld(tl, (unsigned)((j0 + 32 * t) * 64 + kc) * 8u);
+            for (int t = 0; t < NT; t++) inv[cl][t] = ld_off(tl, (unsigned)((j0 + 32 * t) * 64 + kc) * 8u);
         } else if (cl == pl) {                   // the panel's own inverse, transposed copy: Linv[i][k] at [k + i w]
             const double *lit = P.LinvT + me.diag_off;
             const int kcc = min(kc, w - 1);
 #pragma unroll
-            for (int t = 0; t < NT; t++) inv[cl][t] = sb_ld(lit, (unsigned)(kcc + min(max(j0 + 32 * t, kcc), w - 1) * w) * 8u);
+            for (int t = 0; t < NT; t++) inv[cl][t] = ld_off(lit, (unsigned)(kcc + min(max(j0 + 32 * t, kcc), w - 1) * w) * 8u);
         } else {
 #pragma unroll
             for (int t = 0; t < NT; t++) inv[cl][t] = 0.0;

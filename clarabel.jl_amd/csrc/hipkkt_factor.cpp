@@ -22,7 +22,7 @@ static void read_scalars(hipkkt_solver *S) {
 // ---- enqueue helpers (no synchronisation inside; capturable) ---------------------------------
 
 // narrow levels (w <= 8): LDS-resident kernel; wide panels: the register-resident 8-wave kernel
-void enqueue_factor_level(hipkkt_solver *S, int l) {
+static void enqueue_factor_level(hipkkt_solver *S, int l) {
     const HostPlan &P = S->plan;
     const int n = P.fac_lvl_ptr[l + 1] - P.fac_lvl_ptr[l];
     if (P.fac_lvl_maxw[l] <= 8)
@@ -46,14 +46,14 @@ static void enqueue_front_batch(hipkkt_solver *S, const FrontBatch &B) {
 }
 
 // split-K part of a stage's dense updates (hipkkt_setup.cpp plan_split_k): the chunk tiles, then their fixed-order reduction
-void enqueue_split_k(hipkkt_solver *S, int l) {
+static void enqueue_split_k(hipkkt_solver *S, int l) {
     if (S->split.group_count[l] <= 0) return;
     launch_update_dense(S->stream, S->dp, S->split.group_begin[l], S->split.group_count[l], false);
     launch_split_reduce(S->stream, S->dp, S->split.d_recs + S->split.rec_ptr[l], S->split.rec_ptr[l + 1] - S->split.rec_ptr[l]);
 }
 
 // The stage's per-entry gather lists; a split stage (hipkkt_setup.cpp split_gather_stages) runs its deferred part on the side stream
-void enqueue_gather(hipkkt_solver *S, int l) {
+static void enqueue_gather(hipkkt_solver *S, int l) {
     const HostPlan &P = S->plan;
     const int64_t e0 = P.gath_stage_ptr[l], n = P.gath_stage_ptr[l + 1] - e0, h0 = S->split.heavy_ptr[l], nh = S->split.heavy_ptr[l + 1] - h0;
     const int64_t head = S->split.gath[l];
@@ -67,28 +67,106 @@ void enqueue_gather(hipkkt_solver *S, int l) {
     S->side_join_level = l + P.update_batch_used;
 }
 // ... which everything from the far stage of the next batch on must wait for
-void join_side(hipkkt_solver *S, int l) {
+static void join_side(hipkkt_solver *S, int l) {
     if (S->side_join_level < 0 || l < S->side_join_level) return;
     HK_CHECK(hipStreamWaitEvent(S->stream, S->ev_join, 0));
     S->side_join_level = -1;
 }
 
+// The dense tiles of a stage that ride in the next front-batch launch instead of the stage's own (riders_of_stage): the last `count`
+// of its dense list, from group `begin`, `per_wave` of them per wavefront there
+struct Riders { int count = 0, begin = 0, per_wave = 1; };
+
+// What a profiled factorisation (hipkkt_set_profiling) hangs on enqueue_factor: events around every front-batch launch, every update
+// stage with at least one group and every dense launch of the one-wavefront-per-tile kernel, and the tile / flop counts that go with
+// them (SolverStats::prof_*, t_last_update).  The walk gets none under graph capture: no event call enters the captured sequence.
+struct FactorProbe {
+    struct Span { hipEvent_t a = nullptr, b = nullptr; };
+    struct DenseLaunch { Span t; double flops; int tiles; };   // t.a = the stage's start, t.b = behind its split-K part
+    hipkkt_solver *S;
+    std::vector<Span> batches, stages;
+    std::vector<DenseLaunch> dense;
+    std::vector<hipEvent_t> events;
+    int fb_panels = 0;
+    double fb_flops = 0;                  // update flops of the stages inside the batches (executed by the batch kernel)
+    double extra_tiles = 0, extra_flops = 0, stage_extra_flops = 0;
+
+    explicit FactorProbe(hipkkt_solver *S_) : S(S_) {}
+    ~FactorProbe() { for (hipEvent_t e : events) (void)hipEventDestroy(e); }
+    hipEvent_t create() { hipEvent_t e; HK_CHECK(hipEventCreate(&e)); events.push_back(e); return e; }
+    Span open() { Span s{create(), create()}; HK_CHECK(hipEventRecord(s.a, S->stream)); return s; }
+    void close(Span &s) { HK_CHECK(hipEventRecord(s.b, S->stream)); }
+    static double ms(const Span &s) { float t = 0; (void)hipEventElapsedTime(&t, s.a, s.b); return t; }
+    double dense_flops(int gb, int n) const {
+        const HostPlan &P = S->plan;
+        double f = 0;
+        for (int g = gb; g < gb + n; g++)
+            for (int q = P.upd_groups[g].task_begin; q < P.upd_groups[g].task_end; q++) {
+                const UpdTask &T = P.upd_tasks[q];
+                f += 2.0 * T.nrows * T.ncols * (P.sn_first[T.src + 1] - P.sn_first[T.src]);
+            }
+        return f;
+    }
+
+    void batch_begin() { batches.push_back(open()); }
+    void batch_end(int panels, int level_first, int level_last) {
+        close(batches.back());
+        fb_panels += panels;
+        for (int l = level_first; l < level_last; l++) fb_flops += S->plan.upd_stage_flops_dense[l];
+    }
+    void stage_begin(const Riders &x) {
+        stage_extra_flops = x.count > 0 ? dense_flops(x.begin, x.count) : 0.0;
+        extra_tiles += x.count; extra_flops += stage_extra_flops;
+        stages.push_back(open());
+    }
+    void dense_end(int l, int tiles) {    // behind the stage's dense launch of `tiles` tiles and its split-K part
+        if (tiles <= kDenseStripTiles) return;
+        Span t{stages.back().a, create()};
+        close(t);
+        dense.push_back({t, S->plan.upd_stage_flops_dense[l] - stage_extra_flops, tiles});
+    }
+    void stage_end() { close(stages.back()); }
+    void finish() {
+        HK_CHECK(hipStreamSynchronize(S->stream));
+        SolverStats &T = S->stats;
+        T.t_last_update = 0;
+        for (const Span &s : stages) T.t_last_update += ms(s);
+        T.prof_dense4_ms = 0; T.prof_dense4_flops = 0; T.prof_dense4_launches = (int)dense.size();
+        T.prof_launch_ms.clear(); T.prof_launch_flops.clear(); T.prof_launch_tiles.clear();
+        for (const DenseLaunch &d : dense) {
+            const double t = ms(d.t);
+            T.prof_dense4_ms += t;
+            T.prof_dense4_flops += d.flops;
+            T.prof_launch_ms.push_back(t);
+            T.prof_launch_flops.push_back(d.flops);
+            T.prof_launch_tiles.push_back(d.tiles);
+        }
+        T.prof_fb_ms = 0; T.prof_fb_launches = (int)batches.size(); T.prof_fb_panels = fb_panels; T.prof_fb_flops = fb_flops;
+        for (const Span &s : batches) T.prof_fb_ms += ms(s);
+        T.prof_extra_tiles = extra_tiles; T.prof_extra_flops = extra_flops;
+    }
+};
+
 // Schur-complement updates applied after level l is factored: dense register tiles (matrix cores),
 // per-entry gather lists (tiny scattered contributions), relative-index scatter (whatever is left).
 // The three kinds own disjoint target tiles, so their order inside a stage is immaterial.
-// dense_skip_tail: the last tiles of the stage's dense list ride in the next k_front_block launch instead.
-void enqueue_updates(hipkkt_solver *S, int l, int dense_skip_tail = 0) {
+// x: the last tiles of the stage's dense list ride in the next front-batch launch instead (riders_of_stage).
+static void enqueue_updates(hipkkt_solver *S, int l, const Riders &x, FactorProbe *probe) {
     const HostPlan &P = S->plan;
     hipStream_t st = S->stream;
     const int g0 = P.upd_stage_ptr[l], nd = P.upd_stage_ndense[l], ng = P.upd_stage_ngather[l];
+    if (P.upd_stage_ptr[l + 1] == g0) probe = nullptr;    // (the stage events bracket stages with at least one group)
+    if (probe) probe->stage_begin(x);
     join_side(S, l);
-    launch_update_dense(st, S->dp, g0, nd - dense_skip_tail, nd > 0 && P.upd_stage_flops_dense[l] >= 1.5e6 * nd);
+    launch_update_dense(st, S->dp, g0, nd - x.count, dense_full_k(nd, P.upd_stage_flops_dense[l]));
     enqueue_split_k(S, l);
+    if (probe) probe->dense_end(l, nd - x.count);
     enqueue_gather(S, l);
     launch_update_stage(st, S->dp, g0 + nd + ng, P.upd_stage_ptr[l + 1] - g0 - nd - ng);
+    if (probe) probe->stage_end();
 }
 
-// How many of a front batch's far tiles ride in the next k_front_block launch (enqueue_factor; HIPKKT_FB_EXTRA=0: none).  That launch
+// How many of a front batch's far tiles ride in the next k_front_block launch (riders_of_stage; HIPKKT_FB_EXTRA=0: none).  That launch
 // has `next_blk` workgroups of its own, one per compute unit (100 KB of LDS), and lasts ~86 us (five panels, cfg 2a; 112 us when the
 // tile counts below were measured, in round 4): every other compute unit can take one
 // extra workgroup = four wavefronts, each alone on its SIMD, with one tile (launch +10 us) or two tiles one after the other (+28 us)
@@ -99,7 +177,7 @@ void enqueue_updates(hipkkt_solver *S, int l, int dense_skip_tail = 0) {
 // groups of the stage).
 static double dense_stage_cost_us(int m) {
     if (m <= 0) return 0.0;
-    if (m <= 384) return 20.0 + 0.065 * m;
+    if (m <= kDenseStripTiles) return 20.0 + 0.065 * m;
     if (m <= 768) return 66.0;
     const int k = m / 1024, rem = m % 1024;
     const double base = k == 0 ? 0.0 : k == 1 ? 77.0 : 65.0 * k;
@@ -108,7 +186,7 @@ static double dense_stage_cost_us(int m) {
     if (rem <= 512) return base + 20.0;
     return k == 0 ? 77.0 : 65.0 * (k + 1);
 }
-int fb_extra_tiles_of_stage(int nd, int ncrit, int next_blk, int *per_wave_out) {
+static int fb_extra_tiles_of_stage(int nd, int ncrit, int next_blk, int *per_wave_out) {
     constexpr int cus = 254, rmin = 64;
     // what the panel launch gains in duration (us) with one / two tiles per wavefront (round 5: one tile per wavefront since the
     // panel chain got shorter than two tile times); experiments: debug switch FB_EXTRA_PW=<max tiles per wavefront>,<penalty 1>,<penalty 2>
@@ -122,7 +200,7 @@ int fb_extra_tiles_of_stage(int nd, int ncrit, int next_blk, int *per_wave_out) 
         if (rmax < rmin) continue;
         const int mmin = nd - rmax;
         int m;
-        if (mmin <= 384) m = mmin;
+        if (mmin <= kDenseStripTiles) m = mmin;
         else if (mmin <= 768) m = 768;
         else {
             const int k = mmin / 1024, rem = mmin % 1024;
@@ -138,7 +216,25 @@ int fb_extra_tiles_of_stage(int nd, int ncrit, int next_blk, int *per_wave_out) 
     return best_r;
 }
 
-static void enqueue_factor(hipkkt_solver *S, int static_enable, double eps_const, double eps_prop) {
+// The riders of stage l, the far stage of front batch cur_bi (-1: no batch so far).  That stage runs in rounds of 1024 tiles (one per
+// SIMD; 2048 with two co-resident wavefronts); what is left after the whole rounds keeps a fraction of the device busy for a full
+// tile time.  Those tiles -- taken from the END of the [columns of the next batch | rest] order, so the next panel kernel does not
+// need them -- ride in the next front-batch launch as extra workgroups on the compute units it leaves idle.  Only full-K stages
+// (kernels.h dense_full_k); hipkkt_set_profiling(h, 2) keeps every tile in its stage's own launch.
+static Riders riders_of_stage(const hipkkt_solver *S, int l, int cur_bi) {
+    const HostPlan &P = S->plan;
+    const int nd = P.upd_stage_ndense[l];
+    if (cur_bi < 0 || !S->fb.sw.extra || S->profiling_no_extra || S->fb.lvl[l] == -1 || !S->fb.next[(size_t)cur_bi].has_next ||
+        !dense_full_k(nd, P.upd_stage_flops_dense[l]))
+        return Riders();
+    const NextBatch &A = S->fb.next[(size_t)cur_bi];
+    int per_wave = 1;
+    const int r = fb_extra_tiles_of_stage(nd, A.ncrit, A.next_blk, &per_wave);
+    return r > 0 ? Riders{r, P.upd_stage_ptr[l] + nd - r, per_wave} : Riders();
+}
+
+// The whole factorisation, in launch order.  probe: null under graph capture (run_graphed), the profiled path's otherwise.
+static void enqueue_factor(hipkkt_solver *S, int static_enable, double eps_const, double eps_prop, FactorProbe *probe = nullptr) {
     const HostPlan &P = S->plan;
     hipStream_t st = S->stream;
     S->side_join_level = -1;
@@ -150,38 +246,27 @@ static void enqueue_factor(hipkkt_solver *S, int static_enable, double eps_const
     const bool fb = S->fb.sw.use && !S->fb.batches.empty();
     if (fb) launch_fb_reset(st, S->fb.d_sync, 128 * (int)S->fb.batches.size(), S->fb.d_stream, S->fb.stream_doubles);
     int cur_bi = -1;
-    int extra_begin = 0, extra_count = 0, extra_pw = 1;   // dense tiles handed to the next k_front_block launch, tiles per wavefront there
+    Riders ride;                                          // dense tiles handed to the next front-batch launch
     for (int l = 0; l < P.nlevels; l++) {
         if (fb && S->fb.lvl[l] != -1) {
             // a front's update batch: one launch for its panels and their just-in-time updates, then the batch's far stage
             if (S->fb.lvl[l] >= 0) {
                 cur_bi = S->fb.lvl[l];
+                if (probe) probe->batch_begin();
                 join_side(S, S->fb.last_level[(size_t)cur_bi]);       // (a batch that reaches beyond the join level touches deferred targets)
                 FrontBatch B = S->fb.batches[(size_t)cur_bi];
-                B.x_begin = extra_begin; B.x_count = extra_count; B.pad = extra_pw;     // far tiles of the stage before (fb_extra_tiles_of_stage)
-                extra_begin = extra_count = 0;
+                B.x_begin = ride.begin; B.x_count = ride.count; B.pad = ride.per_wave;   // far tiles of the stage before
+                ride = Riders();
                 enqueue_front_batch(S, B);
+                if (probe) probe->batch_end(B.nb, l, S->fb.last_level[(size_t)cur_bi]);
             }
-            const bool last = l + 1 >= P.nlevels || S->fb.lvl[l + 1] != -2;
-            if (!last) continue;                          // the stages inside the batch are applied by the kernel itself
+            if (!S->fb.ends_batch(l)) continue;           // the stages inside the batch are applied by the kernel itself
         } else {
             enqueue_factor_level(S, l);
         }
-        int skip = 0;
-        if (fb && S->fb.sw.extra && cur_bi >= 0 && S->fb.lvl[l] != -1 && S->fb.next[(size_t)cur_bi].has_next) {
-            // The far stage of a front batch runs in rounds of 1024 tiles (one per SIMD; 2048 with two co-resident wavefronts); what is
-            // left after the whole rounds keeps a fraction of the device busy for a full tile time.  Those tiles -- taken from the END
-            // of the [columns of the next batch | rest] order, so the next panel kernel does not need them -- ride in the next
-            // k_front_block launch as extra workgroups on the compute units it leaves idle.
-            const NextBatch &A = S->fb.next[(size_t)cur_bi];
-            const int r = fb_extra_tiles_of_stage(P.upd_stage_ndense[l], A.ncrit, A.next_blk, &extra_pw);
-            if (r > 0 && P.upd_stage_flops_dense[l] >= 1.5e6 * P.upd_stage_ndense[l]) {
-                skip = r;
-                extra_begin = P.upd_stage_ptr[l] + P.upd_stage_ndense[l] - r;
-                extra_count = r;
-            }
-        }
-        enqueue_updates(S, l, skip);
+        const Riders x = riders_of_stage(S, l, cur_bi);
+        if (x.count > 0) ride = x;                        // (they wait for the next front-batch launch)
+        enqueue_updates(S, l, x, probe);
     }
     join_side(S, P.nlevels);
     launch_invert_diag(st, S->dp, S->inv_nsmall, S->inv_wsmall, S->inv_nwide);
@@ -215,7 +300,7 @@ int32_t hipkkt_refactor(hipkkt_handle h, int32_t static_reg_enable, double eps_c
     // tests: HIPKKT_FORCE_TWIN=1 treats every successful factorisation in the cheap order as broken down, so that the robust-order
     // twin can be checked in ITS permutation on problems a scalar CPU factorisation finishes in seconds
     // (read once per handle in init_runtime: no getenv on the refactor path)
-    if (h && h->twin.force && rc == HIPKKT_OK && h && h->plan.ordering_used == 1) rc = HIPKKT_NUMERICAL_FAILURE;
+    if (h && h->twin.force && rc == HIPKKT_OK && h->plan.ordering_used == 1) rc = HIPKKT_NUMERICAL_FAILURE;
     if (rc != HIPKKT_NUMERICAL_FAILURE || !h || h->plan.ordering_used != 1) return rc;
     hipkkt_solver *S = h;
     try {
@@ -282,122 +367,9 @@ static int32_t refactor_once(hipkkt_handle h, int32_t static_reg_enable, double 
     S->red.have_const = false;   // the resident constant-rhs solution (N2) belongs to the previous factorisation
     HK_CHECK(hipEventRecord(S->ev0, S->stream));
     if (S->profiling) {
-        // eager, with the dense-update launches timed separately (adds event overhead)
-        const HostPlan &P = S->plan;
-        hipStream_t st = S->stream;
-        S->side_join_level = -1;
-        launch_zero_words(st, S->dp.scal, 2);
-        launch_zero_words(st, S->dp.flags, FL_COUNT);
-        launch_maxabs_gather(st, S->dp.kval, S->d_diag_full, S->N, (unsigned long long *)S->dp.scal + SC_MAXDIAG);
-        HK_CHECK(hipMemsetAsync(S->dp.Lx, 0, (size_t)(P.panel_doubles + S->split.scratch_doubles) * sizeof(double), st));   // (incl. the split-K partial tiles: a factorisation that aborted between a chunk launch and its reduce must not leave sums behind)
-        launch_init_panels(st, S->dp, S->nnzK, static_reg_enable, eps_const, eps_prop);
-        std::vector<hipEvent_t> evs, evd;   // evs: all update kernels of a stage; evd: its k_update_dense<4,4> launch alone
-        std::vector<int> evd_level;
-        const bool fb = S->fb.sw.use && !S->fb.batches.empty();
-        if (fb) launch_fb_reset(st, S->fb.d_sync, 128 * (int)S->fb.batches.size(), S->fb.d_stream, S->fb.stream_doubles);
-        std::vector<hipEvent_t> evf;        // around every k_front_block launch
-        int fb_panels = 0;
-        double fb_flops = 0;                // update flops of the stages inside the batches (executed by k_front_block)
-        int cur_bi = -1, extra_begin = 0, extra_count = 0, extra_pw = 1;
-        std::vector<double> evd_flops;      // flops / tiles of the timed dense launches (a launch may have handed tiles to the next k_front_block)
-        std::vector<int> evd_tiles;
-        S->stats.prof_extra_tiles = 0; S->stats.prof_extra_flops = 0;
-        auto dense_flops = [&](int gb, int n) {
-            double f = 0;
-            for (int g = gb; g < gb + n; g++)
-                for (int q = P.upd_groups[g].task_begin; q < P.upd_groups[g].task_end; q++) {
-                    const UpdTask &T = P.upd_tasks[q];
-                    f += 2.0 * T.nrows * T.ncols * (P.sn_first[T.src + 1] - P.sn_first[T.src]);
-                }
-            return f;
-        };
-        for (int l = 0; l < P.nlevels; l++) {
-            if (fb && S->fb.lvl[l] != -1) {
-                if (S->fb.lvl[l] >= 0) {
-                    hipEvent_t a, b;
-                    HK_CHECK(hipEventCreate(&a));
-                    HK_CHECK(hipEventCreate(&b));
-                    HK_CHECK(hipEventRecord(a, st));
-                    cur_bi = S->fb.lvl[l];
-                    join_side(S, S->fb.last_level[(size_t)cur_bi]);
-                    FrontBatch B = S->fb.batches[(size_t)cur_bi];
-                    B.x_begin = extra_begin; B.x_count = extra_count; B.pad = extra_pw;
-                    extra_begin = extra_count = 0;
-                    enqueue_front_batch(S, B);
-                    HK_CHECK(hipEventRecord(b, st));
-                    evf.push_back(a);
-                    evf.push_back(b);
-                    fb_panels += S->fb.batches[S->fb.lvl[l]].nb;
-                }
-                if (l + 1 < P.nlevels && S->fb.lvl[l + 1] == -2) { fb_flops += P.upd_stage_flops_dense[l]; continue; }   // applied by the kernel
-            } else {
-                enqueue_factor_level(S, l);
-            }
-            if (P.upd_stage_ptr[l + 1] > P.upd_stage_ptr[l]) {
-                hipEvent_t a, b, c2;
-                HK_CHECK(hipEventCreate(&a));
-                HK_CHECK(hipEventCreate(&b));
-                HK_CHECK(hipEventRecord(a, st));
-                const int g0 = P.upd_stage_ptr[l], nd = P.upd_stage_ndense[l], ng = P.upd_stage_ngather[l];
-                join_side(S, l);
-                int skip = 0;                                              // (the same rule as enqueue_factor)
-                if (fb && S->fb.sw.extra && !S->profiling_no_extra && cur_bi >= 0 && S->fb.lvl[l] != -1 && S->fb.next[(size_t)cur_bi].has_next &&
-                    P.upd_stage_flops_dense[l] >= 1.5e6 * nd) {
-                    skip = fb_extra_tiles_of_stage(nd, S->fb.next[(size_t)cur_bi].ncrit, S->fb.next[(size_t)cur_bi].next_blk, &extra_pw);
-                    if (skip > 0) { extra_begin = g0 + nd - skip; extra_count = skip; }
-                }
-                const double xf = skip > 0 ? dense_flops(g0 + nd - skip, skip) : 0.0;
-                S->stats.prof_extra_tiles += skip; S->stats.prof_extra_flops += xf;
-                launch_update_dense(st, S->dp, g0, nd - skip, nd > 0 && P.upd_stage_flops_dense[l] >= 1.5e6 * nd);
-                enqueue_split_k(S, l);
-                if (nd - skip > 384) {   // the one-wavefront-per-tile variant (see launch_update_dense)
-                    HK_CHECK(hipEventCreate(&c2));
-                    HK_CHECK(hipEventRecord(c2, st));
-                    evd.push_back(a);
-                    evd.push_back(c2);
-                    evd_level.push_back(l);
-                    evd_flops.push_back(P.upd_stage_flops_dense[l] - xf);
-                    evd_tiles.push_back(nd - skip);
-                }
-                enqueue_gather(S, l);
-                launch_update_stage(st, S->dp, g0 + nd + ng, P.upd_stage_ptr[l + 1] - g0 - nd - ng);
-                HK_CHECK(hipEventRecord(b, st));
-                evs.push_back(a);
-                evs.push_back(b);
-            }
-        }
-        join_side(S, P.nlevels);
-        launch_invert_diag(st, S->dp, S->inv_nsmall, S->inv_wsmall, S->inv_nwide);
-        for (const FrontDesc &F : P.fronts) launch_invert_super(st, S->dp, F);   // super-block inverses for the front sweeps
-        HK_CHECK(hipStreamSynchronize(st));
-        double tot = 0;
-        for (size_t i = 0; i + 1 < evs.size(); i += 2) {
-            float ms = 0;
-            (void)hipEventElapsedTime(&ms, evs[i], evs[i + 1]);
-            tot += ms;
-        }
-        S->stats.prof_dense4_ms = 0; S->stats.prof_dense4_flops = 0; S->stats.prof_dense4_launches = 0;
-        S->stats.prof_launch_ms.clear(); S->stats.prof_launch_flops.clear(); S->stats.prof_launch_tiles.clear();
-        for (size_t i = 0; i + 1 < evd.size(); i += 2) {
-            float ms = 0;
-            (void)hipEventElapsedTime(&ms, evd[i], evd[i + 1]);
-            S->stats.prof_dense4_ms += ms;
-            S->stats.prof_dense4_flops += evd_flops[i / 2];
-            S->stats.prof_dense4_launches++;
-            S->stats.prof_launch_ms.push_back(ms);
-            S->stats.prof_launch_flops.push_back(evd_flops[i / 2]);
-            S->stats.prof_launch_tiles.push_back(evd_tiles[i / 2]);
-        }
-        for (size_t i = 1; i < evd.size(); i += 2) (void)hipEventDestroy(evd[i]);
-        for (hipEvent_t e : evs) (void)hipEventDestroy(e);
-        S->stats.prof_fb_ms = 0; S->stats.prof_fb_launches = (int)(evf.size() / 2); S->stats.prof_fb_panels = fb_panels; S->stats.prof_fb_flops = fb_flops;
-        for (size_t i = 0; i + 1 < evf.size(); i += 2) {
-            float ms = 0;
-            (void)hipEventElapsedTime(&ms, evf[i], evf[i + 1]);
-            S->stats.prof_fb_ms += ms;
-        }
-        for (hipEvent_t e : evf) (void)hipEventDestroy(e);
-        S->stats.t_last_update = tot;
+        FactorProbe probe(S);    // eager: the launches of the graph, with the probe's events between them (adds event overhead)
+        enqueue_factor(S, static_reg_enable, eps_const, eps_prop, &probe);
+        probe.finish();
     } else {
         GraphSlot &g = S->g_factor;
         const bool same = g.static_enable == static_reg_enable && g.eps_const == eps_const && g.eps_prop == eps_prop;
@@ -405,7 +377,6 @@ static int32_t refactor_once(hipkkt_handle h, int32_t static_reg_enable, double 
         g.static_enable = static_reg_enable; g.eps_const = eps_const; g.eps_prop = eps_prop;
     }
     HK_CHECK(hipEventRecord(S->ev1, S->stream));
-    HK_CHECK(hipMemcpyAsync(S->h_flags, S->dp.flags, FL_COUNT * sizeof(int), hipMemcpyDeviceToHost, S->stream));
     read_scalars(S);
     S->kval_event_pending = false;       // (the main stream has been synchronised: every value update before it is complete)
     float ms = 0;

@@ -2,7 +2,8 @@
 //   hipkkt_abi.cpp     C entry points: creation / getters / value updates / residuals / diagnostics
 //   hipkkt_cones.cpp   cone registration and scaling (hipkkt_set_cone_types[_ex], hipkkt_update_scaling[_ex][_dev])
 //   hipkkt_setup.cpp   runtime objects, device residency of a plan, handle creation (finish_create)
-//   hipkkt_factor.cpp  the factorisation's launch sequence, its graph, hipkkt_refactor and the robust-order twin
+//   hipkkt_factor.cpp  the factorisation's launch sequence (enqueue_factor: one walk for the graph and, with a FactorProbe, the profiled
+//                      path), hipkkt_refactor and the robust-order twin
 //   solve_schedule.cpp the solve schedule of a plan: level lists, segments, item order (host arithmetic only; solve_schedule.h)
 //   hipkkt_solve.cpp   LDL solves, device-side iterative refinement, the solve entry points
 //   hipkkt_step.cpp    the cone algebra of an interior-point step around the reduced solve (hipkkt_cone_* / hipkkt_step_*), the default start

@@ -39,6 +39,7 @@ struct FrontBatchState {
     } sw;
     std::vector<hipkkt::FrontBatch> batches;
     std::vector<int> lvl;         // [nlevels] index of the batch that starts at this level, -2 inside a batch, -1 otherwise
+    bool ends_batch(int l) const { return l + 1 >= (int)lvl.size() || lvl[(size_t)l + 1] != -2; }   // l (lvl[l] != -1) is the last level of its batch
     std::vector<int> last_level;  // per batch
     std::vector<NextBatch> next;
     int *d_sync = nullptr;

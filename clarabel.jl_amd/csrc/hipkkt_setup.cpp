@@ -231,7 +231,7 @@ static int64_t plan_split_k(hipkkt_solver *S, std::vector<DenseGroup> &dg) {
         const int chunk = std::max(4, (int)((ntasks + nd - 1) / nd));
         int max_nt = 0;
         for (int g = g0; g < g0 + nd; g++) max_nt = std::max(max_nt, dg[g].task_end - dg[g].task_begin);
-        if (nd <= 384 || max_nt < 2 * chunk + 6) continue;
+        if (nd <= kDenseStripTiles || max_nt < 2 * chunk + 6) continue;
         int64_t scratch = 0;
         S->split.group_begin[l] = (int)dg.size();
         for (int g = g0; g < g0 + nd; g++) {

@@ -19,7 +19,12 @@ void launch_init_panels(hipStream_t st, const DevPlan &P, int64_t nnz, int stati
 void launch_factor_level(hipStream_t st, const DevPlan &P, int item_begin, int nitems, int wmax, double dyn_eps, double dyn_delta);
 void launch_factor_panel(hipStream_t st, const DevPlan &P, int item_begin, int nitems, double dyn_eps, double dyn_delta);
 void launch_update_stage(hipStream_t st, const DevPlan &P, int group_begin, int ngroups);
-// full_k: the tiles of this launch carry whole panels of sources (>= 1.5 MFLOP per tile): a partial last round is cut into pieces
+// Up to kDenseStripTiles tiles a dense launch runs the strip kernel (k_update_dense<1,2>, the just-in-time updates), above it one
+// wavefront per tile (k_update_dense<4,4>).  full_k: the tiles of this launch carry whole panels of sources (>= 1.5 MFLOP per tile,
+// dense_full_k over the stage's nd tiles and their flops): a partial last round is cut into pieces
+constexpr int kDenseStripTiles = 384;
+constexpr double kFullKFlopsPerTile = 1.5e6;
+inline bool dense_full_k(int nd, double flops) { return nd > 0 && flops >= kFullKFlopsPerTile * nd; }
 void launch_update_dense(hipStream_t st, const DevPlan &P, int group_begin, int ngroups, bool full_k = false);
 // split-K: adds the partial tiles of `n` split target tiles to their targets (fixed order) and clears them (k_split_reduce)
 void launch_split_reduce(hipStream_t st, const DevPlan &P, const SplitRec *recs, int n);

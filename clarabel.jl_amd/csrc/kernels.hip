@@ -164,25 +164,7 @@ k_factor_level(DevPlan P, int item_begin, int wmax, double dyn_eps, double dyn_d
 // Pivot rule = QDLDL's.  Every chunk repeats the diagonal block (bit-identical).
 // ------------------------------------------------------------------------------------------
 
-// 1/d on the pivot-to-pivot critical path: hardware reciprocal + two Newton steps (~50 clocks) instead of the IEEE
-// division sequence (~112 clocks, tools/ubench.hip).  |relative error| <= 1 ulp; the D and 1/D that are stored for
-// the solves are formed with the exact division after the loop.  d is never zero or subnormal here (the pivot rule
-// has replaced such values by +-delta); an infinite or NaN d propagates and is caught by the non-finite check.
-__device__ __forceinline__ double pivot_rcp(double d) {
-    double r = __builtin_amdgcn_rcp(d);
-    r = fma(fma(-d, r, 1.0), r, r);
-    r = fma(fma(-d, r, 1.0), r, r);
-    return r;
-}
-
-// r (1 + e + e^2), e = 1 - d r: three dependent operations after the hardware reciprocal instead of the four of two Newton steps
-// (error ~ e^3 + one rounding: 1.9 units of 2^-53 measured over 6.7e7 values, tools/ubench_pivot.hip)
-__device__ __forceinline__ double pivot_rcp3(double d) {
-    const double r = __builtin_amdgcn_rcp(d);
-    const double e = fma(-d, r, 1.0);
-    const double e2 = fma(e, e, e);
-    return fma(r, e2, r);
-}
+// 1/d on the pivot-to-pivot critical path: pivot_rcp / pivot_rcp3 (kernel_util.h) instead of the IEEE division sequence.
 
 // Blocked by 8 pivots: wave v of a group owns the column blocks {v, v+4} (8 columns each).  The owner of block B
 // eliminates its 8 columns WITHOUT leaving the wavefront (pivot and the entries a_jk come from the lanes that hold
@@ -195,8 +177,7 @@ __device__ __forceinline__ double pivot_rcp3(double d) {
 // chains of an SDP: 400 items per level on cfg 5 -- ran in two rounds of one workgroup per compute unit, 31 us per level against the
 // 15 us one round takes.  What went: the staging tile of the factored diagonal block (its columns now go from the published L columns
 // in LDS straight to Ldiag, by a wavefront that is not on the pivot chain, inside the loop -- whose barrier therefore no longer waits
-// for global memory).
-__device__ __forceinline__ void fp_bar() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }   // LDS-only workgroup barrier
+// for global memory: lds_barrier, kernel_util.h).
 
 __global__ void __launch_bounds__(512, 4)                 // (HIP: the second figure is wavefronts per SIMD: 4 = two of these workgroups per compute unit)
 k_factor_panel(DevPlan P, int item_begin, double dyn_eps, double dyn_delta) {
@@ -316,7 +297,7 @@ k_factor_panel(DevPlan P, int item_begin, double dyn_eps, double dyn_delta) {
                     for (int jj = kk + 1; jj < 8; jj++) a[rb + jj] = fma(-li, colC[p3][kk][8 * Bo + jj], a[rb + jj]);
                 }
             }
-            fp_bar();
+            lds_barrier();
             // the factored diagonal block goes to Ldiag from the published columns, by the diagonal-row wavefront that eliminated two
             // blocks ago (not the one that eliminates next); colL[B & 1] stays valid until block B + 2 is published
             if (grp == 0 && it.blk == 0 && B < nB && B < 8 && v == ((B + 2) & 3) && lane < w) {
@@ -780,7 +761,7 @@ void launch_update_stage(hipStream_t st, const DevPlan &P, int group_begin, int 
 // tile; full_k launches (whole panels of sources, >= 1.5 MFLOP per tile) cut the tiles of a partial last round into strips / halves.
 void launch_update_dense(hipStream_t st, const DevPlan &P, int group_begin, int ngroups, bool full_k) {
     if (ngroups <= 0) return;
-    if (ngroups > 384) {
+    if (ngroups > kDenseStripTiles) {
         const int round = 1024, r = ngroups % round, nfull = ngroups - r;   // nfull: multiple of 1024, hence of 4
         if (full_k && r > 0 && (r <= 256 || (nfull == 0 && r <= 768)))      // (a lone partial round: three strip sub-rounds still beat it)
             hipLaunchKernelGGL(k_update_dense_tail<4>, dim3(nfull / 4 + r), dim3(256), 0, st, P, group_begin, nfull, ngroups);
