@@ -28,14 +28,14 @@ $HIPCC $FLAGS -c front_block.hip -o $OBJT/front_block.o & pids+=($!)
 # The cone kernels mirror the reference's formulas operation by operation, and the reference modules of tests/ emulate their rounding
 # order: no FMA contraction.  scaling.hip, step.hip: the scaling and the step's cone algebra of the symmetric cones; step_cone3.hip,
 # step_genpow.hip: the step of the Exponential / Power and the Generalized Power cones; step_psd.hip, step_psd_large.hip,
-# scaling_psd.hip, barrier_psd.hip: step, Nesterov-Todd scaling and barrier of the PSD triangle cones (psd_cone.h); start.hip: the
+# scaling_psd.hip, scaling_psd_large.hip, barrier_psd.hip: step, Nesterov-Todd scaling and barrier of the PSD triangle cones (psd_cone.h); start.hip: the
 # default start
-KSRC_NOCONTRACT="scaling.hip step.hip step_cone3.hip step_genpow.hip step_psd.hip step_psd_large.hip scaling_psd.hip start.hip barrier_psd.hip"
+KSRC_NOCONTRACT="scaling.hip step.hip step_cone3.hip step_genpow.hip step_psd.hip step_psd_large.hip scaling_psd.hip scaling_psd_large.hip start.hip barrier_psd.hip"
 for f in $KSRC_NOCONTRACT; do
   $HIPCC $FLAGS -ffp-contract=off -c $f -o $OBJ/${f%.hip}.o & pids+=($!)
 done
 for p in "${pids[@]}"; do wait $p; done
-COMMON="$OBJ/hipkkt_solve.o $OBJ/hipkkt_cones.o $OBJ/hipkkt_step.o $OBJ/symbolic.o $OBJ/solve_schedule.o $OBJ/ordering.o $OBJ/assemble.o $OBJ/assemble_dev.o $OBJ/scaling.o $OBJ/step.o $OBJ/step_cone3.o $OBJ/step_genpow.o $OBJ/step_psd.o $OBJ/step_psd_large.o $OBJ/scaling_psd.o $OBJ/start.o $OBJ/barrier_psd.o $OBJ/front_block2.o $OBJ/front_sweep.o $OBJ/probe.o $OBJ/kernels.o $OBJ/values.o $OBJ/solve_sweep.o $OBJ/refine.o"
+COMMON="$OBJ/hipkkt_solve.o $OBJ/hipkkt_cones.o $OBJ/hipkkt_step.o $OBJ/symbolic.o $OBJ/solve_schedule.o $OBJ/ordering.o $OBJ/assemble.o $OBJ/assemble_dev.o $OBJ/scaling.o $OBJ/step.o $OBJ/step_cone3.o $OBJ/step_genpow.o $OBJ/step_psd.o $OBJ/step_psd_large.o $OBJ/scaling_psd.o $OBJ/scaling_psd_large.o $OBJ/start.o $OBJ/barrier_psd.o $OBJ/front_block2.o $OBJ/front_sweep.o $OBJ/probe.o $OBJ/kernels.o $OBJ/values.o $OBJ/solve_sweep.o $OBJ/refine.o"
 $HIPCC --offload-arch=gfx950 -shared -fPIC -o ../libclarabel_hipkkt.so $OBJ/hipkkt_abi.o $OBJ/hipkkt_setup.o $OBJ/hipkkt_factor.o $COMMON
 $HIPCC --offload-arch=gfx950 -shared -fPIC -o ../libclarabel_hipkkt_testing.so $OBJT/hipkkt_abi.o $OBJT/hipkkt_setup.o $OBJT/hipkkt_factor.o $OBJT/front_block.o $COMMON
 echo "built $(readlink -f ../libclarabel_hipkkt.so) and $(readlink -f ../libclarabel_hipkkt_testing.so)"

@@ -40,6 +40,7 @@ static int32_t set_cone_types_impl(hipkkt_handle h, int64_t ncones, const int32_
     C.step.psd_scaling = false;
     C.step.psd_resident = false;
     C.step.psd_nlarge = 0;
+    C.step.psd_large_enabled = C.step.psd_scaling_large = C.step.start_psd_large = false;
     C.reg.cls = cone_class(ncones, kinds, ex);      // what the enables of hipkkt_step.cpp may switch on: per registration
     C.step.mode = C.reg.cls == ConeClass::Symmetric ? StepMode::Symmetric : StepMode::Off;
     // the non-symmetric cones: three-row cones in two lists (joined [Exponential | Power] below), GenPower descriptors (cone_layout.h)
@@ -211,8 +212,10 @@ static int32_t update_scaling_impl(hipkkt_handle h, const double *s, const doubl
     if (ex && strategy != 0 && strategy != 1) { S->err = "update_scaling_ex: strategy is 0 (PrimalDual) or 1 (Dual)"; return HIPKKT_ERR_ARGUMENT; }
     const int64_t m = S->img.m;
     if (m && (!s || !z)) { S->err = "update_scaling: null s / z"; return HIPKKT_ERR_ARGUMENT; }
-    // hipkkt_psd_scaling_enable: without psd_R and without staged factors the PSD cones' (R, Rinv, lambda) come from scaling_psd.hip
-    const bool psd_nt = psd_step && C.step.psd_scaling && !psd_R && !C.step.psd_fresh;
+    // hipkkt_psd_scaling_enable[_large]: without psd_R and without staged factors the PSD cones' (R, Rinv, lambda) come from
+    // scaling_psd.hip and, for the cones of step_psd_large.hip after the second enable, from scaling_psd_large.hip
+    const bool psd_nt_large = C.step.mode == StepMode::Psd && C.step.psd_scaling_large;
+    const bool psd_nt = psd_step && (C.step.psd_scaling || psd_nt_large) && !psd_R && !C.step.psd_fresh;
     if (psd_step && !psd_nt && (!psd_R || !C.step.psd_fresh)) {
         C.step.scaled = false;
         C.step.psd_resident = false;
@@ -247,8 +250,15 @@ static int32_t update_scaling_impl(hipkkt_handle h, const double *s, const doubl
     double *dw = C.tab.wl, *dl = C.tab.wl + m;
     launch_zero_words(S->stream, C.tab.fail, 1);
     if (psd_nt) {
+        // (each cone is computed by one of the two launches: the first is given the bound below which the second serves none)
         launch_psd_nt_scaling(S->stream, (int)C.reg.psd_n.size(), C.tab.psdtab, ds, dz, C.tab.R, C.tab.psd_rinv, C.tab.psd_lam,
-                              C.tab.psd_bad, C.tab.fail);
+                              C.tab.psd_bad, C.tab.fail, psd_nt_large ? C.step.psd_lmin - 1 : psd_step_max_dim());
+        if (psd_nt_large && C.step.psd_nlarge > 0) {
+            PsdView P;
+            P.npsd = (int)C.reg.psd_n.size(); P.tab = C.tab.psdtab;
+            P.large = PsdLargeBatch{C.step.psd_nlarge, C.tab.psd_lidx, C.step.psd_lmin, C.step.psd_lmax, C.tab.psd_ws};
+            launch_psd_large_nt_scaling(S->stream, P, ds, dz, C.tab.R, C.tab.psd_rinv, C.tab.psd_lam, C.tab.psd_bad, C.tab.fail);
+        }
         dR = C.tab.R;
     }
     if (psd_step) launch_psd_step_check(S->stream, C.tab.psd_lam, C.reg.psd_lam_total, C.tab.fail);

@@ -390,13 +390,18 @@ static void enable_psd_tables(hipkkt_solver *S, StepMode mode, bool large) {
     C.step.mode = mode;
     C.step.psd_fresh = false;
     C.step.psd_scaling = C.step.psd_resident = false;
+    C.step.psd_large_enabled = large && mode == StepMode::Psd;
+    C.step.psd_scaling_large = C.step.start_psd_large = false;      // (they sit on top of this enable: every call of it clears them)
     C.step.scaled = false;      // the step reads the factors of a scaling that ran with the enable in place
     C.step.have_step = false;
 }
 
 // enable = 0 of the entry points below: `mode` goes off, the other modes stay
 static void disable_psd_mode(ConeState &C, StepMode mode) {
-    if (C.step.mode == mode) { C.step.mode = StepMode::Off; C.step.psd_scaling = C.step.psd_resident = false; C.step.psd_nlarge = 0; }
+    if (C.step.mode == mode) {
+        C.step.mode = StepMode::Off; C.step.psd_scaling = C.step.psd_resident = false; C.step.psd_nlarge = 0;
+        C.step.psd_large_enabled = C.step.psd_scaling_large = C.step.start_psd_large = false;
+    }
 }
 
 // hipkkt_step_enable_psd (large = false: sides <= HIPKKT_PSD_STEP_MAX_DIM) and hipkkt_step_enable_psd_large (sides <=
@@ -438,7 +443,8 @@ int32_t hipkkt_step_enable_mixed(hipkkt_handle h, int32_t enable, double linesea
 }
 
 // a handle in PSD step mode whose registration holds a side above HIPKKT_PSD_STEP_MAX_DIM (hipkkt_step_enable_psd_large): the device
-// scaling (scaling_psd.hip) and the default start (start.hip) keep their matrices in LDS and would leave such a cone alone
+// scaling of hipkkt_psd_scaling_enable (scaling_psd.hip) and the default start without its own enable (start.hip) keep their matrices
+// in LDS and would leave such a cone alone
 static bool psd_side_above_small(const ConeState &C) {
     if (C.step.mode != StepMode::Psd) return false;
     for (int64_t n : C.reg.psd_n) if (n > HIPKKT_PSD_STEP_MAX_DIM) return true;
@@ -486,6 +492,38 @@ int32_t hipkkt_psd_scaling_enable(hipkkt_handle h, int32_t enable) {
     C.step.scaled = false;      // as the other enables: the step reads the factors of a scaling that ran with this setting in place
     C.step.have_step = false;
     C.step.psd_resident = false;
+    return HIPKKT_OK;
+    HK_LEAVE
+}
+
+// what hipkkt_psd_scaling_enable_large and hipkkt_step_default_start_enable_psd_large require: PSD step mode through
+// hipkkt_step_enable_psd_large (so the list of the large cones and their workspace exist, and no side exceeds 128)
+static bool psd_large_handle(hipkkt_solver *S, const char *who) {
+    const ConeState &C = S->cones;
+    if (C.step.mode == StepMode::Psd && C.step.psd_large_enabled) return true;
+    S->err = std::string(who) + ": needs a handle in PSD step mode through hipkkt_step_enable_psd_large first";
+    return false;
+}
+
+// hipkkt_psd_scaling_enable for a handle of hipkkt_step_enable_psd_large: the cones of step_psd_large.hip through scaling_psd_large.hip,
+// the others through scaling_psd.hip
+int32_t hipkkt_psd_scaling_enable_large(hipkkt_handle h, int32_t enable) {
+    HK_ENTER(h)
+    ConeState &C = S->cones;
+    if (!psd_large_handle(S, "psd_scaling_enable_large")) return HIPKKT_ERR_ARGUMENT;
+    C.step.psd_scaling_large = enable != 0;
+    C.step.scaled = false;      // as hipkkt_psd_scaling_enable
+    C.step.have_step = false;
+    C.step.psd_resident = false;
+    return HIPKKT_OK;
+    HK_LEAVE
+}
+
+// the default start (start.hip) of a handle of hipkkt_step_enable_psd_large with a side above HIPKKT_PSD_STEP_MAX_DIM
+int32_t hipkkt_step_default_start_enable_psd_large(hipkkt_handle h, int32_t enable) {
+    HK_ENTER(h)
+    if (!psd_large_handle(S, "step_default_start_enable_psd_large")) return HIPKKT_ERR_ARGUMENT;
+    S->cones.step.start_psd_large = enable != 0;
     return HIPKKT_OK;
     HK_LEAVE
 }
@@ -631,7 +669,8 @@ int32_t hipkkt_step_get(hipkkt_handle h, double *out) {
 }
 
 // ---- the default start of a symmetric cone set (solver.jl:383-405; start.hip) ------------------------------------------------------
-// served: L1 handles in step mode Symmetric (kinds 0..2) or Psd (kinds 0..3 after hipkkt_step_enable_psd); needs no scaling
+// served: L1 handles in step mode Symmetric (kinds 0..2) or Psd (kinds 0..3 after hipkkt_step_enable_psd; a side above 64 after
+// hipkkt_step_default_start_enable_psd_large); needs no scaling
 static bool start_ready(hipkkt_solver *S, const char *who) {
     const ConeState &C = S->cones;
     if (!S->l1 || !C.reg.ready || (C.step.mode != StepMode::Symmetric && C.step.mode != StepMode::Psd)) {
@@ -639,8 +678,9 @@ static bool start_ready(hipkkt_solver *S, const char *who) {
                                     "triangle cones next to them after hipkkt_step_enable_psd";
         return false;
     }
-    if (psd_side_above_small(C)) {
-        S->err = std::string(who) + ": a PSD side above HIPKKT_PSD_STEP_MAX_DIM keeps the default start with the caller";
+    if (psd_side_above_small(C) && !C.step.start_psd_large) {
+        S->err = std::string(who) + ": a PSD side above HIPKKT_PSD_STEP_MAX_DIM keeps the default start with the caller "
+                                    "(hipkkt_step_default_start_enable_psd_large lifts that up to HIPKKT_PSD_STEP_LARGE_MAX_DIM)";
         return false;
     }
     return true;
@@ -673,9 +713,10 @@ static int32_t start_host_op(hipkkt_solver *S, double *v, int32_t pd, bool shift
     S->ensure_stage(m);
     double *dv = S->d_stage, *dec = start_decision(C.step.start, ncones);
     if (m) HK_CHECK(hipMemcpyAsync(dv, v, m * sizeof(double), hipMemcpyHostToDevice, S->stream));
-    launch_start_margins(S->stream, T.kind, T.nsoc, T.desc, T.psd, dv, nullptr, 1, (double)C.reg.degree, C.step.start, ncones, m);
+    const bool large = C.step.start_psd_large;
+    launch_start_margins(S->stream, T.kind, T.nsoc, T.desc, T.psd, dv, nullptr, 1, (double)C.reg.degree, C.step.start, ncones, m, large);
     if (shift) {
-        launch_start_shift(S->stream, T.kind, T.nsoc, T.desc, T.psd, dec, dv, pd, nullptr, 0, 1, m);
+        launch_start_shift(S->stream, T.kind, T.nsoc, T.desc, T.psd, dec, dv, pd, nullptr, 0, 1, m, large);
         if (m) HK_CHECK(hipMemcpyAsync(v, dv, m * sizeof(double), hipMemcpyDeviceToHost, S->stream));
     }
     copy_sync(S->stream, out, dec, (size_t)nout * sizeof(double), hipMemcpyDeviceToHost);
@@ -730,7 +771,7 @@ int32_t hipkkt_step_default_start_dev(hipkkt_handle h, double *xzs_dev, int32_t 
     // [0; b] for (x, -s) and [-q; 0] for z on the two solve contexts
     const ConeTables T = tables(S);
     hipkkt_solver *F = solve_target(S);
-    const bool pair = S->img.nnzP == 0;
+    const bool pair = S->img.nnzP == 0, large = C.step.start_psd_large;
     double *sa = C.step.step, *sb = C.step.in;      // (n + m doubles of each are used)
     if (pair) {
         launch_start_rhs(F->ctx[0].stream, F->ctx[0].d_b, S->res.d_qb, (int)n, nm, F->N, 1);
@@ -744,8 +785,8 @@ int32_t hipkkt_step_default_start_dev(hipkkt_handle h, double *xzs_dev, int32_t 
     double *s_dev = xzs_dev + n + m, *z_dev = xzs_dev + n;
     const std::function<void(hipStream_t)> after = [&](hipStream_t st) {
         launch_start_assemble(st, xzs_dev, sa, pair ? sb : nullptr, n, m);
-        launch_start_margins(st, T.kind, T.nsoc, T.desc, T.psd, s_dev, z_dev, 2, (double)C.reg.degree, C.step.start, ncones, m);
-        launch_start_shift(st, T.kind, T.nsoc, T.desc, T.psd, dec, s_dev, 0, z_dev, 1, 2, m);
+        launch_start_margins(st, T.kind, T.nsoc, T.desc, T.psd, s_dev, z_dev, 2, (double)C.reg.degree, C.step.start, ncones, m, large);
+        launch_start_shift(st, T.kind, T.nsoc, T.desc, T.psd, dec, s_dev, 0, z_dev, 1, 2, m, large);
         HK_CHECK(hipMemcpyAsync(h16, dec, 2 * 8 * sizeof(double), hipMemcpyDeviceToHost, st));
     };
     double *outs[kNumCtx] = {sa, sb};

@@ -194,9 +194,15 @@ void launch_psd_large_offset(hipStream_t st, const PsdView &P, const double *ds,
 void launch_psd_large_length(hipStream_t st, const PsdView &P, const double *dz, const double *ds, double alpha_max, double *part);
 // scaling_psd.hip: update_scaling!(::PSDTriangleCone) for the cones of the same table, one workgroup per cone: Cholesky factors of
 // svec_to_mat of the cone's rows of (s, z), the SVD of L2' L1 by one-sided Jacobi sweeps, (R, Rinv, lam) written in the layout above.
-// A cone that fails sets *fail and bad[cone] (0 otherwise) and gets NaN factors.
+// A cone that fails sets *fail and bad[cone] (0 otherwise) and gets NaN factors.  A cone of side above min(max_side,
+// psd_step_max_dim()) is left alone.
 void launch_psd_nt_scaling(hipStream_t st, int npsd, const int64_t *tab, const double *s, const double *z, double *R, double *Rinv,
-                           double *lam, int *bad, int *fail);
+                           double *lam, int *bad, int *fail, int max_side);
+// scaling_psd_large.hip: the same for the cones of P.large (hipkkt_psd_scaling_enable_large), one workgroup of 512 threads per cone,
+// one matrix in LDS and the cone's four workspace matrices of P.large.ws; the same arithmetic -- applied to a side <= 64 the same
+// bits.  launch_psd_nt_scaling gets max_side = P.large.lmin - 1 in the same call, so each cone is computed by one of the two.
+void launch_psd_large_nt_scaling(hipStream_t st, const PsdView &P, const double *s, const double *z, double *R, double *Rinv,
+                                 double *lam, int *bad, int *fail);
 // barrier_psd.hip: compute_barrier of the PSD triangle cones of the same table (sides <= psd_step_max_dim()) at nalpha <=
 // step3_max_candidates() step lengths (host array), for a cone set that holds PSD cones next to non-symmetric ones
 // (hipkkt_step_enable_mixed).  launch_psd_barrier leaves [(0 - logdet(Z + a dZ)) | logdet(S + a dS)] per (cone, candidate) in slots =
@@ -215,15 +221,18 @@ void launch_psd_barrier_add(hipStream_t st, int npsd, const double *slots, int n
 // (a, then b when two_stage) to v0 / v1 in place, pd 0 primal (Zero rows become 0) / 1 dual (Zero rows stay).
 // launch_start_rhs: mode 1 [0; b; 0], mode 2 [-q; 0; 0].  launch_start_assemble: xzs = [x | z | s] from the solutions sa, sb
 // (sb == NULL: z = sa.z, s = -z; otherwise s = -sa.z, z = sb.z).
+// psd_large (hipkkt_step_default_start_enable_psd_large): the margins of the cones of P.large come from a second launch with one
+// 128 x 129 matrix in LDS behind the first, and the shift serves PSD sides up to psd_step_large_max_dim(); without it both are the
+// launches of a handle whose sides are all <= psd_step_max_dim().
 int64_t start_work_doubles(int64_t ncones);
 double *start_decision(double *work, int64_t ncones);
 void launch_start_identity(hipStream_t st, const signed char *row_kind, const int64_t *row_hs, const int64_t *map_hs, int nsoc,
                            const int64_t *desc, double *soc_u, double *soc_v, double *soc_eta2, const PsdView &P,
                            const int64_t *psd_hs0, int64_t psd_max_numel, double *kval, int64_t m);
 void launch_start_margins(hipStream_t st, const signed char *row_kind, int nsoc, const int64_t *desc, const PsdView &P, const double *v0,
-                          const double *v1, int nsides, double degree, double *work, int64_t ncones, int64_t m);
+                          const double *v1, int nsides, double degree, double *work, int64_t ncones, int64_t m, bool psd_large);
 void launch_start_shift(hipStream_t st, const signed char *row_kind, int nsoc, const int64_t *desc, const PsdView &P, const double *dec,
-                        double *v0, int pd0, double *v1, int pd1, int nsides, int64_t m);
+                        double *v0, int pd0, double *v1, int pd1, int nsides, int64_t m, bool psd_large);
 void launch_start_rhs(hipStream_t st, double *dst, const double *qb, int n, int nm, int N, int mode);
 void launch_start_assemble(hipStream_t st, double *xzs, const double *sa, const double *sb, int64_t n, int64_t m);
 }  // namespace hipkkt

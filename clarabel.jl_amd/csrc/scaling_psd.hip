@@ -43,6 +43,7 @@
 #include "cone_reduce.h"
 #include "kernels.h"
 #include "psd_cone.h"
+#include "psd_nt.h"
 
 namespace hipkkt {
 
@@ -51,54 +52,19 @@ namespace {
 constexpr int kMaxSweeps = 40;
 constexpr double kEps = 2.220446049250313e-16;
 
-// (pos_finite: psd_cone.h)
-// the sum over the eight lanes of a pair (lanes 8 k .. 8 k + 7 of one wavefront); every lane gets the same bits
-__device__ __forceinline__ double sum8(double v) {
-    v += __shfl_xor(v, 4);
-    v += __shfl_xor(v, 2);
-    v += __shfl_xor(v, 1);
-    return v;
-}
-
-// dot2 (Ogita, Rump, Oishi): (h, l) += a b with the product's and the sum's rounding errors kept in l; h + l is the sum as if
-// accumulated in twice the precision.  fma is explicit, so -ffp-contract=off leaves it alone.
-__device__ __forceinline__ void dot2_step(double a, double b, double &h, double &l) {
-    const double p = a * b, e = fma(a, b, -p);
-    const double s = h + p, bb = s - h;
-    l = l + (((h - (s - bb)) + (p - bb)) + e);
-    h = s;
-}
-// the same for a (b + bl)
-__device__ __forceinline__ void dot2_step_pair(double a, double b, double bl, double &h, double &l) {
-    const double p = a * b, e = fma(a, b, -p);
-    const double s = h + p, bb = s - h;
-    l = l + ((((h - (s - bb)) + (p - bb)) + e) + a * bl);
-    h = s;
-}
-// the sum of the pairs of four neighbouring lanes, normalised (h = the rounded sum); every lane gets the same bits
-__device__ __forceinline__ void sum4_pair(double &h, double &l) {
-    for (int o = 2; o > 0; o >>= 1) {
-        const double h2 = __shfl_xor(h, o), l2 = __shfl_xor(l, o);
-        const double s = h + h2, bb = s - h;
-        l = (l + l2) + ((h - (s - bb)) + (h2 - bb));
-        h = s;
-    }
-    const double hn = h + l;
-    l = l - (hn - h);
-    h = hn;
-}
+// (pos_finite: psd_cone.h; sum8, dot2_step, dot2_step_pair, sum4_pair: psd_nt.h)
 
 }  // namespace
 
 __global__ void __launch_bounds__(256)
 k_psd_nt_scaling(const int64_t *__restrict__ tab, const double *__restrict__ s_all, const double *__restrict__ z_all,
                  double *__restrict__ R_all, double *__restrict__ Rinv_all, double *__restrict__ lam_all, int *__restrict__ bad,
-                 int *__restrict__ fail) {
+                 int *__restrict__ fail, int hi) {
     __shared__ double A[kPsdMatDoubles], B[kPsdMatDoubles], G[kPsdMatDoubles], V[kPsdMatDoubles];      // L1, L2, G -> U Sigma, V
     __shared__ double red[4], sig[kPsdMaxN], lis[kPsdMaxN], red2[kPsdMaxN];
     __shared__ int rank[kPsdMaxN], flag, sigbad;      // flag: Cholesky / sweep bound; sigbad: a sigma that is not finite and positive
     const int c = blockIdx.x, t = threadIdx.x;
-    const Cone K = cone_of(tab, c);
+    const Cone K = cone_of(tab, c, 1, hi);      // (hi < kPsdMaxN: scaling_psd_large.hip computes the cones above it)
     if (!K.ok) return;
     const int n = K.n, ld = K.ld;
     double *Rg = R_all + K.foff, *Rig = Rinv_all + K.foff, *lamg = lam_all + K.loff;
@@ -292,8 +258,9 @@ k_psd_nt_scaling(const int64_t *__restrict__ tab, const double *__restrict__ s_a
 }
 
 void launch_psd_nt_scaling(hipStream_t st, int npsd, const int64_t *tab, const double *s, const double *z, double *R, double *Rinv,
-                           double *lam, int *bad, int *fail) {
-    if (npsd > 0) hipLaunchKernelGGL(k_psd_nt_scaling, dim3(npsd), dim3(256), 0, st, tab, s, z, R, Rinv, lam, bad, fail);
+                           double *lam, int *bad, int *fail, int max_side) {
+    const int hi = max_side < kPsdMaxN ? max_side : kPsdMaxN;
+    if (npsd > 0) hipLaunchKernelGGL(k_psd_nt_scaling, dim3(npsd), dim3(256), 0, st, tab, s, z, R, Rinv, lam, bad, fail, hi);
 }
 
 }  // namespace hipkkt

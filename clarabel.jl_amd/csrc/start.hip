@@ -14,6 +14,9 @@
 // reference's rules: min and max propagate it, `x > 0 ? x : 0` drops it, both comparisons of the shift are false and the last arm
 // (shift by 0) is taken.  Sums run over fixed slices in a fixed order: deterministic.  Compiled with -ffp-contract=off: the shift is
 // two separately rounded additions.  No assert, no trap, no spin; every loop is bounded by a cone's size or kPsdMaxSweeps.
+// PSD sides of 65 .. 128 (hipkkt_step_default_start_enable_psd_large): the identity scaling is indexed by column of the packed triangle
+// and does not depend on the side, the margins of such a cone come from k_start_margin_psd_large (one 128 x 129 matrix in LDS, the
+// sweeps with the lane widths of k_psdl_len), the shift takes the side bound as an argument.
 // Everything is HBM / latency bound: the identity scaling writes nHs doubles through map_hs (8 + 8 bytes per entry), the rest moves a
 // few m doubles.
 #include <hip/hip_runtime.h>
@@ -117,6 +120,26 @@ k_start_margin_soc(const int64_t *__restrict__ desc, const double *__restrict__ 
     const double z1 = sqrt(block_sum(acc, red));
     if (threadIdx.x == 0) part[blockIdx.y * stride + 2 * kSlices + c] = z[0] - z1;
 }
+// (alpha, beta) of one PSD cone from the rows v of its vector: M = svec_to_mat, the Jacobi sweeps of psd_cone.h with the lane widths
+// of the caller's largest side, the minimum and the sum of the positive eigenvalues in ascending index order by thread 0
+template <int kPairLanes, int kRowLanes>
+__device__ __forceinline__ void margin_psd_cone(double *M, const Cone &K, const double *__restrict__ v, double *red, double *rc,
+                                                double *rs, int *rp, int *rq, double *out) {
+    const int n = K.n, ld = K.ld, t = threadIdx.x;
+    load_svec(M, v, K);
+    __syncthreads();
+    double tot2 = 0.0;
+    for (int e = t; e < n * n; e += 256) { const double x = M[e % n + (e / n) * ld]; tot2 += x * x; }
+    tot2 = block_sum(tot2, red);
+    const bool finite = psd_jacobi_sweeps<kPairLanes, kRowLanes>(M, K, tot2, red, rc, rs, rp, rq);
+    if (t != 0) return;
+    double a = tot2 - tot2, b = tot2 - tot2;      // (a non-finite matrix: NaN margins)
+    if (finite) {
+        a = kFloatMax; b = 0.0;
+        for (int i = 0; i < n; i++) { const double e = M[i + i * ld]; a = nan_min(e, a); b = e > 0.0 ? b + e : b; }
+    }
+    out[0] = a; out[1] = b;
+}
 // one workgroup per (cone, side), ONE matrix in LDS so that several workgroups share a compute unit
 __global__ void __launch_bounds__(256)
 k_start_margin_psd(const int64_t *__restrict__ tab, const double *__restrict__ v0, const double *__restrict__ v1,
@@ -128,20 +151,22 @@ k_start_margin_psd(const int64_t *__restrict__ tab, const double *__restrict__ v
     double *out = part + blockIdx.y * stride + 2 * kSlices + nsoc + 2 * (int64_t)c;
     const Cone K = cone_of(tab, c);
     if (!K.ok) { if (t == 0) { out[0] = kFloatMax; out[1] = 0.0; } return; }
-    const int n = K.n, ld = K.ld;
-    load_svec(M, (blockIdx.y ? v1 : v0) + K.row0, K);
-    __syncthreads();
-    double tot2 = 0.0;
-    for (int e = t; e < n * n; e += 256) { const double x = M[e % n + (e / n) * ld]; tot2 += x * x; }
-    tot2 = block_sum(tot2, red);
-    const bool finite = psd_jacobi_sweeps(M, K, tot2, red, rc, rs, rp, rq);
-    if (t != 0) return;
-    double a = tot2 - tot2, b = tot2 - tot2;      // (a non-finite matrix: NaN margins)
-    if (finite) {
-        a = kFloatMax; b = 0.0;
-        for (int i = 0; i < n; i++) { const double e = M[i + i * ld]; a = nan_min(e, a); b = e > 0.0 ? b + e : b; }
-    }
-    out[0] = a; out[1] = b;
+    margin_psd_cone<32, 64>(M, K, (blockIdx.y ? v1 : v0) + K.row0, red, rc, rs, rp, rq, out);
+}
+// the cones of side lmin .. 128 (hipkkt_step_default_start_enable_psd_large; lidx: their indices into tab), one workgroup per (cone,
+// side) with the LDS budget of k_psdl_len: launched behind k_start_margin_psd on the same stream, it overwrites the {floatmax, 0} that
+// kernel left for a side above 64 (and the same bits for a smaller side the testing switch routes here)
+__global__ void __launch_bounds__(256)
+k_start_margin_psd_large(const int64_t *__restrict__ tab, const int *__restrict__ lidx, int lmin, const double *__restrict__ v0,
+                         const double *__restrict__ v1, double *__restrict__ part, int64_t stride, int nsoc) {
+    __shared__ double M[kPsdLargeMaxN * (kPsdLargeMaxN + 1)];
+    __shared__ double red[4], rc[kPsdLargeMaxN / 2], rs[kPsdLargeMaxN / 2];
+    __shared__ int rp[kPsdLargeMaxN / 2], rq[kPsdLargeMaxN / 2];
+    const int c = lidx[blockIdx.x];
+    double *out = part + blockIdx.y * stride + 2 * kSlices + nsoc + 2 * (int64_t)c;
+    const Cone K = cone_of(tab, c, lmin, kPsdLargeMaxN);
+    if (!K.ok) return;
+    margin_psd_cone<64, 128>(M, K, (blockIdx.y ? v1 : v0) + K.row0, red, rc, rs, rp, rq, out);
 }
 
 // ---- the branch of _shift_to_cone_interior! ---------------------------------------------------------------------------------------
@@ -177,7 +202,7 @@ k_start_decide(const double *__restrict__ part, int64_t stride, int nsoc, int np
 __global__ void __launch_bounds__(256)
 k_start_shift(const signed char *__restrict__ row_kind, const int64_t *__restrict__ desc, const int64_t *__restrict__ tab,
               const double *__restrict__ dec, double *__restrict__ v0, int pd0, double *__restrict__ v1, int pd1, int64_t m, int nsoc,
-              unsigned nrow, unsigned nsocb) {
+              unsigned nrow, unsigned nsocb, int psd_max_side) {
     const int side = blockIdx.y;
     double *v = side ? v1 : v0;
     const int pd = side ? pd1 : pd0;
@@ -196,7 +221,7 @@ k_start_shift(const signed char *__restrict__ row_kind, const int64_t *__restric
     } else {
         const int c = blockIdx.x - nrow - nsocb;
         const int64_t n = tab[kPsdTab * c + kPsdN], k = threadIdx.x;
-        if (k < n && n <= kPsdMaxN) row = tab[kPsdTab * c + kPsdRow0] + (k + 1) * (k + 2) / 2 - 1;
+        if (k < n && n <= psd_max_side) row = tab[kPsdTab * c + kPsdRow0] + (k + 1) * (k + 2) / 2 - 1;
     }
     if (row < 0) return;
     double x = v[row];
@@ -246,22 +271,25 @@ void launch_start_identity(hipStream_t st, const signed char *row_kind, const in
 double *start_decision(double *work, int64_t ncones) { return work + 2 * side_doubles((int)ncones, (int)ncones); }
 
 void launch_start_margins(hipStream_t st, const signed char *row_kind, int nsoc, const int64_t *desc, const PsdView &P, const double *v0,
-                          const double *v1, int nsides, double degree, double *work, int64_t ncones, int64_t m) {
+                          const double *v1, int nsides, double degree, double *work, int64_t ncones, int64_t m, bool psd_large) {
     const int npsd = P.npsd;
     const int64_t stride = side_doubles(nsoc, npsd);
     hipLaunchKernelGGL(k_start_margin_nn, dim3(kSlices, nsides), dim3(256), 0, st, row_kind, v0, v1, work, stride, m);
     if (nsoc > 0) hipLaunchKernelGGL(k_start_margin_soc, dim3(nsoc, nsides), dim3(256), 0, st, desc, v0, v1, work, stride);
     if (npsd > 0) hipLaunchKernelGGL(k_start_margin_psd, dim3(npsd, nsides), dim3(256), 0, st, P.tab, v0, v1, work, stride, nsoc);
+    if (psd_large && P.large.nlarge > 0)
+        hipLaunchKernelGGL(k_start_margin_psd_large, dim3(P.large.nlarge, nsides), dim3(256), 0, st, P.tab, P.large.lidx, P.large.lmin, v0,
+                           v1, work, stride, nsoc);
     hipLaunchKernelGGL(k_start_decide, dim3(nsides), dim3(256), 0, st, work, stride, nsoc, npsd, degree, start_decision(work, ncones));
 }
 
 void launch_start_shift(hipStream_t st, const signed char *row_kind, int nsoc, const int64_t *desc, const PsdView &P, const double *dec,
-                        double *v0, int pd0, double *v1, int pd1, int nsides, int64_t m) {
+                        double *v0, int pd0, double *v1, int pd1, int nsides, int64_t m, bool psd_large) {
     const unsigned nrow = (unsigned)((m + 255) / 256), nsocb = (unsigned)((nsoc + 255) / 256);
     const unsigned total = nrow + nsocb + (unsigned)P.npsd;
     if (total > 0)
         hipLaunchKernelGGL(k_start_shift, dim3(total, nsides), dim3(256), 0, st, row_kind, desc, P.tab, dec, v0, pd0, v1, pd1, m, nsoc,
-                           nrow, nsocb);
+                           nrow, nsocb, psd_large ? kPsdLargeMaxN : kPsdMaxN);
 }
 
 void launch_start_rhs(hipStream_t st, double *dst, const double *qb, int n, int nm, int N, int mode) {

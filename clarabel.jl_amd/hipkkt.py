@@ -54,6 +54,8 @@ SYMBOLS = [
     "hipkkt_step_enable_psd_large",
     # PSD triangle cones next to Exponential / Power / Generalized Power cones (opt-in, added within ABI version 5)
     "hipkkt_step_enable_mixed",
+    # the Cholesky / SVD and the default start for PSD sides 65 .. 128 (opt-in, added within ABI version 5)
+    "hipkkt_psd_scaling_enable_large", "hipkkt_step_default_start_enable_psd_large",
 ]
 
 PSD_STEP_MAX_DIM = 64      # include/hipkkt.h HIPKKT_PSD_STEP_MAX_DIM
@@ -172,6 +174,8 @@ def lib():
     L.hipkkt_psd_set_factors.argtypes = [vp, _f64p, _f64p]
     L.hipkkt_psd_set_factors_dev.argtypes = [vp, vp, vp]
     L.hipkkt_psd_scaling_enable.argtypes = [vp, i32]
+    L.hipkkt_psd_scaling_enable_large.argtypes = [vp, i32]
+    L.hipkkt_step_default_start_enable_psd_large.argtypes = [vp, i32]
     L.hipkkt_psd_get_factors.argtypes = [vp, vp, vp, vp]
     L.hipkkt_cone_barrier.argtypes = [vp, _f64p, _f64p, _f64p, i64, _f64p]
     L.hipkkt_cone_set_identity_scaling.argtypes = [vp]
@@ -786,6 +790,17 @@ class Handle:
         """on a handle after step_enable_psd(True) (ValueError otherwise): update_scaling[_ex][_dev] without psd_R and without staged
         factors computes the PSD cones' (R, Rinv, lambda) on the device from the (s, z) of the call"""
         self._chk_step(self.L.hipkkt_psd_scaling_enable(self.h, int(bool(enable))), "psd_scaling_enable")
+
+    def psd_scaling_enable_large(self, enable):
+        """psd_scaling_enable for a handle after step_enable_psd_large(True) (ValueError otherwise): the cones of side 65 .. 128 get their
+        (R, Rinv, lambda) from kernels with one matrix in LDS and the others in device memory (same arithmetic), the smaller ones from
+        the kernel of psd_scaling_enable"""
+        self._chk_step(self.L.hipkkt_psd_scaling_enable_large(self.h, int(bool(enable))), "psd_scaling_enable_large")
+
+    def step_default_start_enable_psd_large(self, enable):
+        """on a handle after step_enable_psd_large(True) (ValueError otherwise): cone_set_identity_scaling, cone_margins,
+        cone_shift_to_interior and step_default_start_dev serve PSD sides up to PSD_STEP_LARGE_MAX_DIM"""
+        self._chk_step(self.L.hipkkt_step_default_start_enable_psd_large(self.h, int(bool(enable))), "step_default_start_enable_psd_large")
 
     def psd_get_factors(self):
         """-> (R, Rinv, lambda) resident since the last scaling: R, Rinv n x n column-major per PSD cone, concatenated like psd_R, lambda

@@ -108,7 +108,8 @@ class HipKKTSolver:
         # ... and, opted in by Settings.device_step_psd, symmetric sets with PSD triangle members: the Cholesky / SVD of their scaling stay
         # with the caller, whose (R, Rinv, lambda) go to the device with every scaling (hipkkt_step_enable_psd)
         # With Settings.device_step_psd_large on top, a set with a side of 65 .. 128 qualifies too (hipkkt_step_enable_psd_large); its
-        # Cholesky / SVD and its default start stay with the caller whatever device_scaling_psd / device_default_start say
+        # Cholesky / SVD and its default start stay with the caller whatever device_scaling_psd / device_default_start say, unless
+        # Settings.device_scaling_psd_large / device_default_start_psd_large are set on top of those (below)
         self.steps_psd = self.steps_psd_large = False
         psd_ok = not self._steps_on_device and getattr(settings, "device_step_psd", False) and self._has_cone_kinds \
             and not self.scales_nonsymmetric
@@ -141,6 +142,18 @@ class HipKKTSolver:
         if self.steps_psd and not self.steps_psd_large and getattr(settings, "device_scaling_psd", False):
             self.h.psd_scaling_enable(True)
             self.scales_psd = True
+        # ... for a set with a side of 65 .. 128 when Settings.device_scaling_psd_large is set on top (hipkkt_psd_scaling_enable_large)
+        elif self.steps_psd_large and getattr(settings, "device_scaling_psd", False) \
+                and getattr(settings, "device_scaling_psd_large", False):
+            self.h.psd_scaling_enable_large(True)
+            self.scales_psd = True
+        # ... and whose default start the device serves when Settings.device_default_start_psd_large is set on top of
+        # device_default_start (hipkkt_step_default_start_enable_psd_large)
+        self.starts_psd_large = False
+        if self.steps_psd_large and getattr(settings, "device_default_start", False) \
+                and getattr(settings, "device_default_start_psd_large", False):
+            self.h.step_default_start_enable_psd_large(True)
+            self.starts_psd_large = True
         self.scaling_nonsym = None
         self.scaling_w = self.scaling_lambda = self.scaling_soc_eta = None
         self.diagonal_regularizer = 0.0
@@ -401,7 +414,7 @@ class HipKKTSolver:
     @property
     def default_start_on_device(self) -> bool:
         """the default start of the cone set (solver.jl:383-405) can run on the resident iterate: kktsolver_default_start"""
-        return self._steps_on_device and not self.steps_nonsymmetric and not self.steps_psd_large
+        return self._steps_on_device and not self.steps_nonsymmetric and (not self.steps_psd_large or self.starts_psd_large)
 
     def kktsolver_default_start(self, xzs):
         """set_identity_scaling! + kkt_update! + kkt_solve_initial_point! + variables_symmetric_initialization! into the resident

@@ -83,9 +83,17 @@ class Settings:
     device_default_start: bool = False
     # device_step_psd for PSD triangle cones of side 65 .. 128 as well (hipkkt_step_enable_psd_large: the same arithmetic with the
     # matrices in device memory, products as batched tile launches).  For a set with such a side the Cholesky / SVD of the scaling and
-    # the default start stay on the host, whatever device_scaling_psd / device_default_start say; sides above 128 keep the host loop.
-    # Needs device_step_psd: the caller raises ValueError otherwise.
+    # the default start stay on the host, whatever device_scaling_psd / device_default_start say, unless the two flags below are set;
+    # sides above 128 keep the host loop.  Needs device_step_psd: the caller raises ValueError otherwise.
     device_step_psd_large: bool = False
+    # device_scaling_psd for a set with a PSD side of 65 .. 128 (hipkkt_psd_scaling_enable_large: the same Cholesky / one-sided Jacobi
+    # iteration with one matrix in LDS and the others in device memory): no download of (s, z) rows and no upload of factors for
+    # such a set either.  Needs device_scaling_psd and device_step_psd_large: the caller raises ValueError otherwise.
+    device_scaling_psd_large: bool = False
+    # device_default_start for a set with a PSD side of 65 .. 128 (hipkkt_step_default_start_enable_psd_large): no Hs upload and no
+    # host eigenvalues for such a set either.  Needs device_default_start and device_step_psd_large: the caller raises ValueError
+    # otherwise.
+    device_default_start_psd_large: bool = False
     # device_step for cone sets that hold PSD triangle cones of side <= 64 next to Exponential / Power cones -- and next to Generalized
     # Power cones when device_step_genpower is set -- (hipkkt_step_enable_mixed: each family's kernels composed, plus the log-det
     # barrier of the PSD cones for the Dual strategy's search).  The PSD factors follow device_scaling_psd as in a symmetric set; the

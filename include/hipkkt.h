@@ -78,7 +78,8 @@ int32_t hipkkt_is_available(void);
  *    hipkkt_psd_scaling_enable / hipkkt_psd_get_factors;
  *    hipkkt_cone_set_identity_scaling / hipkkt_cone_margins / hipkkt_cone_shift_to_interior / hipkkt_step_default_start_dev;
  *    HIPKKT_PSD_STEP_LARGE_MAX_DIM / hipkkt_step_enable_psd_large;
- *    hipkkt_step_enable_mixed. */
+ *    hipkkt_step_enable_mixed;
+ *    hipkkt_psd_scaling_enable_large / hipkkt_step_default_start_enable_psd_large. */
 #define HIPKKT_ABI_VERSION 5
 int32_t hipkkt_abi_version(void);
 /* releases the process-wide cache of device memory blocks the library keeps between handles (not in the reference: an embedding
@@ -393,10 +394,11 @@ int32_t hipkkt_residuals_dev(hipkkt_handle h, const double *xzs_dev, double tau,
  * schedule, the rotation formulas, the sums of the stop rule and the bound of 30 sweeps are those of the smaller cones: the same
  * input gives the same bits whichever kernels compute a cone.  An operation is a few launches on the handle's stream instead of one;
  * the fused calls keep their single host synchronisation.  The Cholesky / SVD and the default start of such a handle stay with the
- * caller: while the registration holds a side above HIPKKT_PSD_STEP_MAX_DIM, hipkkt_psd_scaling_enable, hipkkt_cone_set_identity_scaling,
- * hipkkt_cone_margins, hipkkt_cone_shift_to_interior and hipkkt_step_default_start_dev return HIPKKT_ERR_ARGUMENT (their kernels
- * keep whole matrices in LDS); with every side <= HIPKKT_PSD_STEP_MAX_DIM they behave as after hipkkt_step_enable_psd.  Sides above
- * HIPKKT_PSD_STEP_LARGE_MAX_DIM keep the host loop.
+ * caller unless their own opt-ins follow: while the registration holds a side above HIPKKT_PSD_STEP_MAX_DIM, hipkkt_psd_scaling_enable
+ * returns HIPKKT_ERR_ARGUMENT (its kernel keeps four matrices in LDS; hipkkt_psd_scaling_enable_large is the call for such a handle),
+ * and hipkkt_cone_set_identity_scaling, hipkkt_cone_margins, hipkkt_cone_shift_to_interior and hipkkt_step_default_start_dev return
+ * HIPKKT_ERR_ARGUMENT until hipkkt_step_default_start_enable_psd_large; with every side <= HIPKKT_PSD_STEP_MAX_DIM they behave as
+ * after hipkkt_step_enable_psd.  Sides above HIPKKT_PSD_STEP_LARGE_MAX_DIM keep the host loop.
  *
  * Opt-in for PSDTriangleCone next to kinds 4..6: after hipkkt_step_enable_mixed on a registration (hipkkt_set_cone_types_ex) of kinds
  * {0, .., 6} with at least one 3, at least one of 4 / 5 / 6 and every PSD side <= HIPKKT_PSD_STEP_MAX_DIM, every call of this section
@@ -483,6 +485,20 @@ int32_t hipkkt_psd_set_factors_dev(hipkkt_handle h, const double *Rinv_all, cons
  * factors the call does what it does without this enable.  Enabling or disabling invalidates the resident scaling; enable == 0
  * switches it off, and so do hipkkt_step_enable_psd and every hipkkt_set_cone_types[_ex]. */
 int32_t hipkkt_psd_scaling_enable(hipkkt_handle h, int32_t enable);
+/* hipkkt_psd_scaling_enable for a handle of hipkkt_step_enable_psd_large.  HIPKKT_ERR_ARGUMENT, and the handle as it was, unless the
+ * handle is in PSD step mode through hipkkt_step_enable_psd_large (not after hipkkt_step_enable_psd or _mixed; a side above
+ * HIPKKT_PSD_STEP_LARGE_MAX_DIM never gets that far).  Afterwards a hipkkt_update_scaling[_dev] with psd_R == NULL and no factors
+ * staged computes (R, Rinv, lambda) of every PSD cone of the set on the call's stream, with the call's single host synchronisation:
+ * the cones hipkkt_step_enable_psd_large routes to its own kernels (side > HIPKKT_PSD_STEP_MAX_DIM) by the algorithm of
+ * hipkkt_psd_scaling_enable operation for operation in another placement -- one workgroup of 512 threads per cone, one n x n matrix
+ * in LDS, the others in the cone's four matrices of the enable's workspace, the rotations of V applied in device memory -- and the
+ * other cones by the kernel of hipkkt_psd_scaling_enable, unchanged; each cone is computed by exactly one of the two.  Every sum runs
+ * in the order of the smaller cones' kernel: the same (s, z) give the same bits whichever kernel computes a cone, and on every run.
+ * Failures are those of hipkkt_psd_scaling_enable (*scaling_ok = 0 with HIPKKT_OK, NaN factors for that cone, none of its entries of
+ * K written, the other cones served); hipkkt_psd_get_factors reads the result back.  With a non-NULL psd_R and staged factors the
+ * call does what it does without this enable.  Enabling or disabling invalidates the resident scaling; enable == 0 switches it off,
+ * and so do hipkkt_step_enable_psd[_large] and every hipkkt_set_cone_types[_ex]. */
+int32_t hipkkt_psd_scaling_enable_large(hipkkt_handle h, int32_t enable);
 /* The resident factors of the last scaling of a handle in PSD or mixed step mode, whoever computed them (K.data.R, .Rinv, .lambda of
  * coneops_psdtrianglecone.jl:112-131): R and Rinv n x n column-major per cone, concatenated like psd_R, lambda n per cone.  Host
  * pointers, any may be NULL.  HIPKKT_ERR_ARGUMENT when no scaling call has completed since the enable; after a call that reported
@@ -529,7 +545,7 @@ int32_t hipkkt_step_info_norms_dev(hipkkt_handle h, const double *xzs_dev, const
 int32_t hipkkt_step_get(hipkkt_handle h, double *out);
 /* The default start of a symmetric cone set (solver.jl:383-405) on the device.  Served: L1 handles whose registration is Zero /
  * Nonnegative / SecondOrder only, or holds PSD triangle cones next to them after hipkkt_step_enable_psd[_large] (every side <=
- * HIPKKT_PSD_STEP_MAX_DIM); anything else (a kind 4..6, PSD without the enable, an L0 handle) is HIPKKT_ERR_ARGUMENT.  No scaling is
+ * HIPKKT_PSD_STEP_MAX_DIM, or <= HIPKKT_PSD_STEP_LARGE_MAX_DIM after hipkkt_step_default_start_enable_psd_large); anything else (a kind 4..6, PSD without the enable, an L0 handle) is HIPKKT_ERR_ARGUMENT.  No scaling is
  * needed.  pd: 0 = primal cone, 1 = dual cone.
  *   hipkkt_cone_set_identity_scaling  set_identity_scaling! (coneops_compositecone.jl:92-101) + get_Hs! (:123-131) + the Hs / sparse-cone
  *     part of _kktsolver_update_inner! (kktsolver_directldl.jl:211-245) for that scaling, written into the resident K; nothing is
@@ -561,6 +577,13 @@ int32_t hipkkt_cone_shift_to_interior(hipkkt_handle h, double *v, int32_t pd, do
 int32_t hipkkt_step_default_start_dev(hipkkt_handle h, double *xzs_dev, int32_t static_reg_enable, double eps_const, double eps_prop,
                                       int32_t ir_enable, double reltol, double abstol, int64_t max_iter, double stop_ratio,
                                       double *scal_out8, int64_t *ir_steps2);
+/* The default start for a handle of hipkkt_step_enable_psd_large with a side above HIPKKT_PSD_STEP_MAX_DIM.  HIPKKT_ERR_ARGUMENT, and
+ * the handle as it was, unless the handle is in PSD step mode through hipkkt_step_enable_psd_large.  Afterwards the four calls above
+ * serve the handle: the identity scaling does not depend on the side, the margins of a cone of side > HIPKKT_PSD_STEP_MAX_DIM come
+ * from a second launch with one 128 x 129 matrix in LDS (the same sweeps: the same bits as the smaller cones' kernel on the same
+ * matrix), the shift takes the larger side bound.  Without it they keep refusing such a handle.  enable == 0 switches it off, and so
+ * do hipkkt_step_enable_psd[_large] and every hipkkt_set_cone_types[_ex]. */
+int32_t hipkkt_step_default_start_enable_psd_large(hipkkt_handle h, int32_t enable);
 
 /* ---- timing (device time on the handle's stream, HIP events) ------------------------------- */
 /* out[0] = ms of last refactor (value scatter + numeric LDL), out[1] = ms of last solve call

@@ -166,6 +166,17 @@ function hip_psd_scaling_enable!(handle::Ptr{Cvoid}, enable::Bool)
     rc = ccall((:hipkkt_psd_scaling_enable, libhipkkt), Int32, (Ptr{Cvoid}, Int32), handle, enable ? 1 : 0)
     return hip_step_check(handle, rc, "hipkkt_psd_scaling_enable")
 end
+# after hip_step_enable_psd_large!: the same for a set with a side of 65 .. 128 (those cones with one matrix in LDS and the others in
+# device memory, same arithmetic), and the default start of such a set (hip_cone_set_identity_scaling! and its group); not wired
+# into the core like the others
+function hip_psd_scaling_enable_large!(handle::Ptr{Cvoid}, enable::Bool)
+    rc = ccall((:hipkkt_psd_scaling_enable_large, libhipkkt), Int32, (Ptr{Cvoid}, Int32), handle, enable ? 1 : 0)
+    return hip_step_check(handle, rc, "hipkkt_psd_scaling_enable_large")
+end
+function hip_step_default_start_enable_psd_large!(handle::Ptr{Cvoid}, enable::Bool)
+    rc = ccall((:hipkkt_step_default_start_enable_psd_large, libhipkkt), Int32, (Ptr{Cvoid}, Int32), handle, enable ? 1 : 0)
+    return hip_step_check(handle, rc, "hipkkt_step_default_start_enable_psd_large")
+end
 # the resident factors of the last scaling (K.data.R, .Rinv, .λ): n x n column-major per cone, concatenated like psd_R; λ n per cone
 function hip_psd_get_factors!(handle::Ptr{Cvoid}, R_all::Vector{Float64}, Rinv_all::Vector{Float64}, λ_all::Vector{Float64})
     rc = ccall((:hipkkt_psd_get_factors, libhipkkt), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), handle, R_all,

@@ -404,6 +404,12 @@ class Solver:
             raise ValueError("Settings.device_scaling_psd needs device_step_psd")
         if getattr(st, "device_step_psd_large", False) and not getattr(st, "device_step_psd", False):
             raise ValueError("Settings.device_step_psd_large needs device_step_psd")
+        if getattr(st, "device_scaling_psd_large", False) and not (getattr(st, "device_scaling_psd", False)
+                                                                   and getattr(st, "device_step_psd_large", False)):
+            raise ValueError("Settings.device_scaling_psd_large needs device_scaling_psd and device_step_psd_large")
+        if getattr(st, "device_default_start_psd_large", False) and not (getattr(st, "device_default_start", False)
+                                                                         and getattr(st, "device_step_psd_large", False)):
+            raise ValueError("Settings.device_default_start_psd_large needs device_default_start and device_step_psd_large")
         if getattr(st, "device_step_mixed", False) and not getattr(st, "device_step_nonsymmetric", False):
             raise ValueError("Settings.device_step_mixed needs device_step_nonsymmetric")
         if getattr(st, "device_step_mixed", False) and not getattr(st, "device_step_psd", False):

@@ -46,6 +46,9 @@ STEP_EXTRA = {"exp_pow": dict(device_step_nonsymmetric=True),
 THIRD = {"psd": ("device_step_and_scaling", dict(device_scaling_psd=True)),
          "mixed": ("device_step_and_scaling", dict(device_scaling_psd=True))}      # a further path on top of device_step, where there is one
 START = ("3", "2a", "psd")      # symmetric cone sets: the last path once more with device_default_start
+# further paths of a configuration, each on top of the one before it: the Cholesky / SVD and the default start of PSD sides 65 .. 128
+MORE = {"psd_large": [("device_step_and_scaling_large", dict(device_scaling_psd=True, device_scaling_psd_large=True)),
+                      ("device_step_and_scaling_large_and_default_start", dict(device_default_start=True, device_default_start_psd_large=True))]}
 
 
 def one_solve(prob, dual=False, **flags):
@@ -82,13 +85,15 @@ def main():
     ap.add_argument("--cfgs", default="3,2a")
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--one-solve", default=None)
-    ap.add_argument("--third", action="store_true", help="--one-solve with the configuration's third path (psd, mixed: device_scaling_psd)")
+    ap.add_argument("--third", action="store_true", help="--one-solve with the configuration's third path (psd, mixed: device_scaling_psd; psd_large: device_scaling_psd_large)")
     ap.add_argument("--dual", action="store_true", help="--one-solve with min_switch_step_length = 1 (the Dual strategy throughout)")
-    ap.add_argument("--start", action="store_true", help="--one-solve with device_default_start (symmetric configurations)")
+    ap.add_argument("--start", action="store_true", help="--one-solve with device_default_start (symmetric configurations; psd_large: device_default_start_psd_large)")
     args = ap.parse_args()
     if args.one_solve:
         rec = one_solve(CONFIGS[args.one_solve][1](), dual=args.dual, device_step=True, **PARENT, **STEP_EXTRA.get(args.one_solve, {}),
                         **(THIRD[args.one_solve][1] if args.third and args.one_solve in THIRD else {}),
+                        **(MORE[args.one_solve][0][1] if args.third and args.one_solve in MORE else {}),
+                        **(MORE[args.one_solve][1][1] if args.start and args.one_solve in MORE else {}),
                         **(dict(device_default_start=True) if args.start and args.one_solve in START else {}))
         print(json.dumps({"cfg": args.one_solve, "device_step": rec}))
         return
@@ -103,6 +108,8 @@ def main():
             todo.append((THIRD[cfg][0], dict(step, **THIRD[cfg][1])))
         if cfg in START:
             todo.append((todo[-1][0] + "_and_default_start", dict(todo[-1][1], device_default_start=True)))
+        for label, extra in MORE.get(cfg, []):
+            todo.append((label, dict(todo[-1][1], **extra)))
         for label, flags in todo:
             one_solve(prob, **flags)                                   # warm-up: plan cache, graphs, code objects
             paths[label] = median_of([one_solve(prob, **flags) for _ in range(args.repeats)])
