@@ -526,7 +526,8 @@ int32_t hipkkt_get_counters(hipkkt_handle h, int64_t *out, int64_t cap) {
 // developer diagnostic (not part of the plugin contract): internal vectors of the last LDL solve / plan tables as doubles.
 // what: 0 = the permuted right-hand side, 1 = z (forward result / D), 2 = x (permuted), 3 = ubuf, 4 = the unregularised KKT values,
 // 5 = D and 6 = 1/D of the last factorisation (permuted order), 7 / 8 = u / v of the sparse second-order cones (concatenated), 10 = sn_first, 11 = sn_level,
-// 12 = rows per supernode, 13 = sn_parent, 14 = persistent-sweep membership (1 = item of a segment launch), 22 = the fronts (4 values each)
+// 12 = rows per supernode, 13 = sn_parent, 14 = persistent-sweep membership (1 = item of a segment launch), 22 = the fronts (4 values each), 26 = the accepted iterate of the
+// last solve on context 0 (all N entries)
 int32_t hipkkt_debug_dump(hipkkt_handle h, int32_t what, double *out, int64_t cap, int64_t *len) {
     HK_ENTER(h)
     const HostPlan &P = S->plan;
@@ -558,6 +559,7 @@ int32_t hipkkt_debug_dump(hipkkt_handle h, int32_t what, double *out, int64_t ca
         }
         case 18: dev(S->ctx[0].d_e, S->N); break;       // residual b - K x of the last SpMV on context 0 (original ordering)
         case 19: host(1, [&](int64_t) { return (double)P.dtri.size(); }); break;   // dense triangles of K outside the symmetric view
+        case 26: dev(S->ctx[0].result(), S->N); break;  // the accepted iterate of the last solve on context 0, expansion variables included (original ordering)
         case 15: dev(S->fb.d_stream, std::max<int64_t>(S->fb.stream_doubles, 1)); break;   // stream records of the front batches (raw)
         case 16: dev(S->fb.d_scratch, (int64_t)kFbScratch * (int64_t)std::max<size_t>(S->fb.batches.size(), 1)); break;
         case 20: {   // the dense tiles of the plan, 6 values each: stage, tasks, sum of source widths, tasks through a tile map, full-tile

@@ -101,8 +101,14 @@ def test_step_length_matches_the_host_cones(seed, late):
 def test_fused_steps_match_the_stand_in_on_the_same_plugin(seed, late):
     """hipkkt_step_affine_dev (constant-rhs solve pending) and hipkkt_step_combined_dev (resident constant solution, m_corr != 1)
     against ipm.KKTSystem.kkt_solve driven through the same plugin; apply, step_get and the info norms on the way"""
+    _fused_steps_case(seed, late)
+
+
+def _fused_steps_case(seed, late, settings=None, expect_steps=None):
+    """settings: further Settings fields for both sides (tests/test_gpu_refinement_branches.py: forced refinement steps);
+    expect_steps: the refinement steps every solve of the fused calls and of the host loop must report"""
     prob = _mixed_problem(seed)
-    S = cl.Solver(*prob, cl.Settings(device_step=True, **STEP_FLAGS))
+    S = cl.Solver(*prob, cl.Settings(device_step=True, **STEP_FLAGS, **(settings or {})))
     assert S._device_step
     ks, data, cones, v = S.kktsystem.kktsolver, S.data, S.cones, S.variables
     n, m = data.n, data.m
@@ -154,8 +160,11 @@ def test_fused_steps_match_the_stand_in_on_the_same_plugin(seed, late):
         assert abs(alpha - a_ref) <= PARITY * a_ref, (what, alpha, a_ref)
 
     # ---- affine step, the constant-rhs solve pending
+    total = ks.total_ir_steps
     ok, alpha_aff, dtau_aff, dkappa_aff = ks.kktsolver_step_affine(xzs, res, v.tau, v.kappa, r.rtau, True)
     assert ok and np.array_equal(ks.h.debug_dump(4), K0)
+    if expect_steps is not None:       # both solves (this step's and the constant right-hand side's; neither can exceed max_iter)
+        assert ks.last_ir_steps == expect_steps and ks.total_ir_steps - total == 2 * expect_steps
     step_aff = ks.h.step_get()
     lhs, rhs = S.step_lhs, S.step_rhs
     rhs.x[:], rhs.z[:] = r.rx, r.rz
@@ -163,11 +172,13 @@ def test_fused_steps_match_the_stand_in_on_the_same_plugin(seed, late):
     rhs.tau, rhs.kappa = r.rtau, v.tau * v.kappa
     S.kktsystem._const_pending, S.kktsystem._have_const_dev = False, True      # (x2, z2) of this factorisation is resident now
     assert S.kktsystem.kkt_solve(lhs, rhs, data, v, cones, "affine")
+    assert expect_steps is None or ks.last_ir_steps == expect_steps
     check_step(step_aff, v.s, rhs.kappa, alpha_aff, dtau_aff, dkappa_aff, 1.0, lhs, "affine")
     # ---- combined step on the resident constant solution, m_corr != 1
     sigma, mcorr = (1.0 - alpha_aff) ** 3, 0.5 + 0.4 * alpha_aff
     ok, alpha, dtau, dkappa = ks.kktsolver_step_combined(xzs, res, v.tau, v.kappa, r.rtau, dtau_aff, dkappa_aff, sigma, mu, mcorr)
     assert ok and np.array_equal(ks.h.debug_dump(4), K0)
+    assert expect_steps is None or ks.last_ir_steps == expect_steps
     step = ks.h.step_get()
     # the host's right-hand side from the DEVICE's affine step (variables.jl:124-162)
     lhs.x[:], lhs.z[:], lhs.s[:] = step_aff[:n], step_aff[n:n + m], step_aff[n + m:]
@@ -181,6 +192,7 @@ def test_fused_steps_match_the_stand_in_on_the_same_plugin(seed, late):
     rhs.s += rhs.z
     rhs.z[:] = (1.0 - sigma) * r.rz
     assert S.kktsystem.kkt_solve(lhs, rhs, data, v, cones, "combined")
+    assert expect_steps is None or ks.last_ir_steps == expect_steps
     # ds = -(Hs dz + ds_const) is checked with the ds_const that the granular operations (each held against the host cones above)
     # give for the device's own affine step: the fused call must compose exactly those
     dz_m = step_aff[n:n + m] * mcorr

@@ -585,6 +585,7 @@ def test_refinement_steps_match_oracle_on_a_hard_system(oracle_factory):
         scale = max(1.0, np.max(np.abs(lx_c)), np.max(np.abs(lz_c)))
         assert np.max(np.abs(lx_g - lx_c)) <= 1e-9 * scale and np.max(np.abs(lz_g - lz_c)) <= 1e-9 * scale
     print("refinement steps seen on the oracle:", sorted(seen))
+    assert max(seen) >= 2          # (the oracle takes 1, 1, 2, 1, 2, 1 steps on these six: the loop beyond the first step runs)
 
 
 @pytest.mark.parametrize("name", ["qp_fixture", "cfg1", "portfolio_small", "sdp_small"])
