@@ -13,6 +13,11 @@
 // No assert, no trap, no spin, every loop bounded by n.  Every thread reads the same pivot from LDS, so the exit is uniform; a NaN in
 // the input reaches a pivot and takes the failure arm.  Compiled with -ffp-contract=off: tests/psd_barrier_reference.py emulates the
 // order of the subtractions and of the log sum.
+// A cone of side 65 .. 128 (hipkkt_step_enable_mixed_large, the cones of P.large) takes the failure arm of k_bar_psd; k_bar_psd_large
+// behind it on the same stream overwrites those two slots: the same expressions in the same order with one 128 x 129 matrix in LDS
+// (132 096 B, one workgroup per CU, the budget of start.hip's k_start_margin_psd_large) and 512 threads as 128 row lanes x 4 column
+// groups.  The rows of one column are disjoint across lanes and each entry's subtractions stay in ascending j, so applied to a side
+// <= 64 it gives the bits of k_bar_psd (tests/test_gpu_mixed_step_large.py holds it to that through the testing switch PSD_LARGE_MIN).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -83,6 +88,56 @@ k_bar_psd(const int64_t *__restrict__ tab, const double *__restrict__ z_all, con
     }
 }
 
+// grid (nlarge, nalpha, 2): the cones lidx[0 .. nlarge) of the table, sides lmin .. kPsdLargeMaxN; k_bar_psd statement by statement but
+// for the lane map of the update: row i = j + 1 + (t mod 128), columns k = j + 1 + t / 128 + 4 q.  Consecutive lanes read consecutive
+// rows of a column (no bank conflict with the padded leading dimension) and the same Q[k + j ld] (a broadcast)
+__global__ void __launch_bounds__(512)
+k_bar_psd_large(const int64_t *__restrict__ tab, const int *__restrict__ lidx, int lmin, const double *__restrict__ z_all,
+                const double *__restrict__ s_all, const double *__restrict__ dz_all, const double *__restrict__ ds_all, BarPsdAlphas A,
+                double *__restrict__ slots) {
+    __shared__ double Q[kPsdLargeMaxN * (kPsdLargeMaxN + 1)];
+    const int c = lidx[blockIdx.x], cand = blockIdx.y, side = blockIdx.z, t = threadIdx.x;
+    const Cone K = cone_of(tab, c, lmin, kPsdLargeMaxN);
+    if (!K.ok) return;      // (the list holds no such cone) the slot keeps what k_bar_psd left
+    double *slot = slots + (int64_t)c * kBarPsdSlots + 2 * cand + side;
+    const int n = K.n, ld = K.ld;
+    const double *x = (side ? s_all : z_all) + K.row0, *dx = (side ? ds_all : dz_all) + K.row0;
+    const double a = A.a[cand];
+    for (int e = t; e < n * n; e += 512) {
+        const int i = e % n, j = e / n;
+        if (i < j) continue;
+        const int idx = i * (i + 1) / 2 + j;
+        const double v = x[idx] + a * dx[idx];
+        Q[i + j * ld] = i == j ? v : v * kPsdIsqrt2;
+    }
+    __syncthreads();
+    bool ok = true;
+    for (int j = 0; j < n; j++) {
+        const double d = Q[j + j * ld];      // the same value in every thread
+        if (!pos_finite(d)) { ok = false; break; }
+        const double piv = sqrt(d);
+        for (int i = j + 1 + t; i < n; i += 512) Q[i + j * ld] = Q[i + j * ld] / piv;
+        __syncthreads();
+        {
+            const int i = j + 1 + (t & 127);
+            if (i < n) {
+                const double li = Q[i + j * ld];
+                for (int k = j + 1 + (t >> 7); k <= i; k += 4) Q[i + k * ld] = Q[i + k * ld] - li * Q[k + j * ld];
+            }
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        double logdet = __builtin_huge_val();
+        if (ok) {
+            double dd = 0.0;
+            for (int j = 0; j < n; j++) dd += log(sqrt(Q[j + j * ld]));
+            logdet = dd + dd;
+        }
+        *slot = side ? logdet : 0.0 - logdet;
+    }
+}
+
 // out[2 j] += sum over the PSD cones, in their order, of (0 - logdet_z) - logdet_s; thread j owns candidate j
 __global__ void __launch_bounds__(64)
 k_bar_psd_add(const double *__restrict__ slots, int npsd, int nalpha, double *__restrict__ out) {
@@ -110,6 +165,15 @@ void launch_psd_barrier(hipStream_t st, const PsdView &P, const double *z, const
     BarPsdAlphas A;
     for (int j = 0; j < kBarPsdMax; j++) A.a[j] = j < nalpha ? alphas[j] : 0.0;
     hipLaunchKernelGGL(k_bar_psd, dim3(P.npsd, nalpha, 2), dim3(256), 0, st, P.tab, z, s, dz, ds, A, slots);
+}
+void launch_psd_barrier_large(hipStream_t st, const PsdView &P, const double *z, const double *s, const double *dz, const double *ds,
+                              const double *alphas, int nalpha, double *slots) {
+    if (P.large.nlarge <= 0 || nalpha <= 0) return;
+    if (nalpha > kBarPsdMax) nalpha = kBarPsdMax;
+    BarPsdAlphas A;
+    for (int j = 0; j < kBarPsdMax; j++) A.a[j] = j < nalpha ? alphas[j] : 0.0;
+    hipLaunchKernelGGL(k_bar_psd_large, dim3(P.large.nlarge, nalpha, 2), dim3(512), 0, st, P.tab, P.large.lidx, P.large.lmin, z, s, dz, ds,
+                       A, slots);
 }
 void launch_psd_barrier_add(hipStream_t st, int npsd, const double *slots, int nalpha, double *out) {
     if (npsd <= 0 || nalpha <= 0) return;

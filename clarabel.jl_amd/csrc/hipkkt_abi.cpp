@@ -616,15 +616,15 @@ int32_t hipkkt_debug_dump(hipkkt_handle h, int32_t what, double *out, int64_t ca
             host(S->cones.reg.npow, [&](int64_t i) { return v[i]; });
             break;
         }
-        case 24: {   // the PSD cones step_psd_large.hip serves (hipkkt_step_enable_psd_large): indices into the PSD cones, from the device list
-            const int nl = S->cones.step.mode == StepMode::Psd ? S->cones.step.psd_nlarge : 0;
+        case 24: {   // the PSD cones step_psd_large.hip serves (hipkkt_step_enable_psd_large / _mixed_large): indices into the PSD cones, from the device list
+            const int nl = (S->cones.step.mode == StepMode::Psd || S->cones.step.mode == StepMode::Mixed) ? S->cones.step.psd_nlarge : 0;
             std::vector<int> v((size_t)std::max(nl, 1), 0);
             if (nl) copy_sync(S->stream, v.data(), S->cones.tab.psd_lidx, (size_t)nl * sizeof(int), hipMemcpyDeviceToHost);
             host(nl, [&](int64_t i) { return v[i]; });
             break;
         }
         case 25: {   // the workspace of step_psd_large.hip as the last operation left it: kPsdLargeMats matrices per served cone (kernels.h)
-            const int nl = S->cones.step.mode == StepMode::Psd ? S->cones.step.psd_nlarge : 0;
+            const int nl = (S->cones.step.mode == StepMode::Psd || S->cones.step.mode == StepMode::Mixed) ? S->cones.step.psd_nlarge : 0;
             if (nl) dev(S->cones.tab.psd_ws, psd_large_ws_doubles(nl)); else host(0, [](int64_t) { return 0.0; });
             break;
         }

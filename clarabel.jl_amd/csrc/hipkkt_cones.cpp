@@ -40,7 +40,7 @@ static int32_t set_cone_types_impl(hipkkt_handle h, int64_t ncones, const int32_
     C.step.psd_scaling = false;
     C.step.psd_resident = false;
     C.step.psd_nlarge = 0;
-    C.step.psd_large_enabled = C.step.psd_scaling_large = C.step.start_psd_large = false;
+    C.step.psd_large_enabled = C.step.mixed_large_enabled = C.step.psd_scaling_large = C.step.start_psd_large = false;
     C.reg.cls = cone_class(ncones, kinds, ex);      // what the enables of hipkkt_step.cpp may switch on: per registration
     C.step.mode = C.reg.cls == ConeClass::Symmetric ? StepMode::Symmetric : StepMode::Off;
     // the non-symmetric cones: three-row cones in two lists (joined [Exponential | Power] below), GenPower descriptors (cone_layout.h)
@@ -214,7 +214,7 @@ static int32_t update_scaling_impl(hipkkt_handle h, const double *s, const doubl
     if (m && (!s || !z)) { S->err = "update_scaling: null s / z"; return HIPKKT_ERR_ARGUMENT; }
     // hipkkt_psd_scaling_enable[_large]: without psd_R and without staged factors the PSD cones' (R, Rinv, lambda) come from
     // scaling_psd.hip and, for the cones of step_psd_large.hip after the second enable, from scaling_psd_large.hip
-    const bool psd_nt_large = C.step.mode == StepMode::Psd && C.step.psd_scaling_large;
+    const bool psd_nt_large = psd_step && C.step.psd_scaling_large;
     const bool psd_nt = psd_step && (C.step.psd_scaling || psd_nt_large) && !psd_R && !C.step.psd_fresh;
     if (psd_step && !psd_nt && (!psd_R || !C.step.psd_fresh)) {
         C.step.scaled = false;

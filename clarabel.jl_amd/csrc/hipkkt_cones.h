@@ -69,8 +69,9 @@ struct ConeState {
         bool psd_fresh = false;                            // factors staged since the last scaling
         bool psd_scaling = false;                          // hipkkt_psd_scaling_enable: a scaling without psd_R computes the factors
         bool psd_resident = false;                         // a scaling since the enable left (R, Rinv, lambda) resident (hipkkt_psd_get_factors)
-        int psd_nlarge = 0, psd_lmin = 65, psd_lmax = 0;   // hipkkt_step_enable_psd_large: cones of side psd_lmin .. psd_lmax go to step_psd_large.hip
+        int psd_nlarge = 0, psd_lmin = 65, psd_lmax = 0;   // hipkkt_step_enable_psd_large / _mixed_large: cones of side psd_lmin .. psd_lmax go to step_psd_large.hip
         bool psd_large_enabled = false;                    // the handle is in PSD step mode through hipkkt_step_enable_psd_large
+        bool mixed_large_enabled = false;                  // the handle is in Mixed step mode through hipkkt_step_enable_mixed_large
         bool psd_scaling_large = false;                    // hipkkt_psd_scaling_enable_large: psd_scaling for every side, those cones through scaling_psd_large.hip
         bool start_psd_large = false;                      // hipkkt_step_default_start_enable_psd_large: the default start serves sides above 64
         double ls_step = 0.0, ls_amin = 0.0;               // linesearch_backtrack_step, min_terminate_step_length (Cone3 / GenPow / Mixed)

@@ -7,7 +7,7 @@
 // After hipkkt_step_enable_psd the PSD triangle cones of a symmetric registration (step_psd.hip), on the caller's (R, Rinv, lambda);
 // after hipkkt_step_enable_psd_large those of side 65 .. 128 as well (step_psd_large.hip).
 // After hipkkt_step_enable_mixed PSD triangle cones (sides <= 64) next to Exponential / Power / Generalized Power cones: the launches of
-// the families above composed, plus the PSD cones' barrier (barrier_psd.hip).
+// the families above composed, plus the PSD cones' barrier (barrier_psd.hip); after hipkkt_step_enable_mixed_large sides 65 .. 128 too.
 // The default start of a symmetric cone set (start.hip): hipkkt_cone_set_identity_scaling / _margins / _shift_to_interior and the fused
 // hipkkt_step_default_start_dev, which need no scaling.
 #include "hipkkt_internal.h"
@@ -23,7 +23,7 @@ static bool step_ready(hipkkt_solver *S, const char *who) {
         S->err = std::string(who) + ": needs an L1 handle whose registered cones are Zero / Nonnegative / SecondOrder only, or one with "
                                     "Exponential / Power cones next to them after hipkkt_step_enable_cone3, or with Generalized Power cones "
                                     "after hipkkt_step_enable_genpow, or with PSD triangle cones after hipkkt_step_enable_psd[_large], or with PSD "
-                                    "triangle cones next to Exponential / Power / Generalized Power cones after hipkkt_step_enable_mixed";
+                                    "triangle cones next to Exponential / Power / Generalized Power cones after hipkkt_step_enable_mixed[_large]";
         return false;
     }
     if (!C.step.scaled) { S->err = std::string(who) + ": no successful hipkkt_update_scaling since the cones were registered"; return false; }
@@ -58,8 +58,8 @@ struct ConeTables {
     const int64_t *gpdesc = nullptr;
     const double *gpalpha = nullptr;
     double mu = 0.0;
-    // Psd / Mixed: the PSD triangle cones' table and factors, and those of them step_psd_large.hip serves (hipkkt_step_enable_psd_large;
-    // none otherwise, and none in a Mixed set: no side above 64)
+    // Psd / Mixed: the PSD triangle cones' table and factors, and those of them step_psd_large.hip serves (hipkkt_step_enable_psd_large,
+    // hipkkt_step_enable_mixed_large; none otherwise: no side above 64)
     PsdView psd;
     // the backtracking line search of the non-symmetric cones decides the step length
     bool line_search() const { return mode == StepMode::Cone3 || mode == StepMode::GenPow || mode == StepMode::Mixed; }
@@ -126,7 +126,7 @@ static void op_mulhs(hipStream_t st, const ConeTables &T, const double *x, const
 // "symmetric cones first" of a set with PSD cones (Psd, Mixed): the symmetric rows' launch as it is, its pair parked at kStOutSymPsd;
 // the PSD cones' pairs follow its partials in `part` (2 (ceil(m / 256) + ncones) doubles: second-order and PSD cones together are at
 // most ncones); out2 = the minimum over kinds 0..3.  step_psd.hip parks alpha_max for a cone of side > 64, step_psd_large.hip
-// overwrites it before the final minimum reads it (a Mixed set has no such cone: that launcher returns without a launch)
+// overwrites it before the final minimum reads it (without a list of large cones that launcher returns without a launch)
 static void length_sym_psd(const ConeState::Step &St, hipStream_t st, const ConeTables &T, const double *dz, const double *ds,
                            double alpha_max, double *out2) {
     double *sym2 = St.out + kStOutSymPsd, *pairs = St.part + 2 * step_len_pairs(T.m, T.nsoc);
@@ -280,7 +280,8 @@ int32_t hipkkt_cone_step_length(hipkkt_handle h, const double *dz, const double 
 
 // the barrier of the cone set and the shifted <z, s> at nalpha candidates: (z, s, dz, ds) and dout are device pointers
 // (without the enable T names no Exponential / Power cone: the symmetric cones' barrier).  A Mixed set: the PSD cones' slots before, their
-// sum onto out[2 j] behind the two launches every set runs; a set without PSD cones executes exactly those two
+// sum onto out[2 j] behind the two launches every set runs; a set without PSD cones executes exactly those two.  The cones of side
+// 65 .. 128 (hipkkt_step_enable_mixed_large) overwrite the failure arm barrier_psd.hip's first kernel left in their slots
 static void barrier_impl(hipkkt_solver *S, const ConeTables &T, const double *z, const double *s, const double *dz, const double *ds,
                          const double *alphas, int64_t nalpha, double *dout) {
     // (the work buffer has 16 doubles per registered cone for the per-cone partials: 8 per second-order, three-row and Generalized Power
@@ -288,6 +289,7 @@ static void barrier_impl(hipkkt_solver *S, const ConeTables &T, const double *z,
     double *bar = S->cones.step.bar;
     double *psd_slots = psd_barrier_slots(bar, T.nsoc, T.n3, T.ngp);
     launch_psd_barrier(S->stream, T.psd, z, s, dz, ds, alphas, (int)nalpha, psd_slots);
+    launch_psd_barrier_large(S->stream, T.psd, z, s, dz, ds, alphas, (int)nalpha, psd_slots);
     launch_genpow_barrier(S->stream, T.ngp, T.gpdesc, T.gpalpha, z, s, dz, ds, alphas, (int)nalpha, step3_barrier_gppart(bar, T.nsoc, T.n3));
     launch_step3_barrier(S->stream, T.kind, T.nsoc, T.desc, T.nexp, T.npow, T.row0, T.alpha, z, s, dz, ds, alphas, (int)nalpha, bar, dout,
                          T.m, T.ngp);
@@ -350,7 +352,7 @@ static bool psd_class_fits(hipkkt_solver *S, ConeClass cls, int64_t max_side) {
     return ok;
 }
 
-// what hipkkt_step_enable_psd[_large] and hipkkt_step_enable_mixed share: the PSD cone table, the factor buffers, the list of the cones
+// what hipkkt_step_enable_psd[_large] and hipkkt_step_enable_mixed[_large] share: the PSD cone table, the factor buffers, the list of the cones
 // step_psd_large.hip serves (`large`), the invalidation; the handle is in `mode` afterwards
 static void enable_psd_tables(hipkkt_solver *S, StepMode mode, bool large) {
     ConeState &C = S->cones;
@@ -391,6 +393,7 @@ static void enable_psd_tables(hipkkt_solver *S, StepMode mode, bool large) {
     C.step.psd_fresh = false;
     C.step.psd_scaling = C.step.psd_resident = false;
     C.step.psd_large_enabled = large && mode == StepMode::Psd;
+    C.step.mixed_large_enabled = large && mode == StepMode::Mixed;
     C.step.psd_scaling_large = C.step.start_psd_large = false;      // (they sit on top of this enable: every call of it clears them)
     C.step.scaled = false;      // the step reads the factors of a scaling that ran with the enable in place
     C.step.have_step = false;
@@ -400,7 +403,7 @@ static void enable_psd_tables(hipkkt_solver *S, StepMode mode, bool large) {
 static void disable_psd_mode(ConeState &C, StepMode mode) {
     if (C.step.mode == mode) {
         C.step.mode = StepMode::Off; C.step.psd_scaling = C.step.psd_resident = false; C.step.psd_nlarge = 0;
-        C.step.psd_large_enabled = C.step.psd_scaling_large = C.step.start_psd_large = false;
+        C.step.psd_large_enabled = C.step.mixed_large_enabled = C.step.psd_scaling_large = C.step.start_psd_large = false;
     }
 }
 
@@ -423,36 +426,47 @@ static int32_t enable_psd_impl(hipkkt_handle h, int32_t enable, bool large) {
 int32_t hipkkt_step_enable_psd(hipkkt_handle h, int32_t enable) { return enable_psd_impl(h, enable, false); }
 int32_t hipkkt_step_enable_psd_large(hipkkt_handle h, int32_t enable) { return enable_psd_impl(h, enable, true); }
 
-// PSD triangle cones (sides <= HIPKKT_PSD_STEP_MAX_DIM: the barrier keeps its matrix in LDS) next to Exponential / Power / Generalized
-// Power cones: the tables of hipkkt_step_enable_psd and the line search of hipkkt_step_enable_cone3 / _genpow
-int32_t hipkkt_step_enable_mixed(hipkkt_handle h, int32_t enable, double linesearch_backtrack_step, double min_terminate_step_length) {
+// PSD triangle cones next to Exponential / Power / Generalized Power cones: the tables of hipkkt_step_enable_psd[_large] and the line
+// search of hipkkt_step_enable_cone3 / _genpow.  hipkkt_step_enable_mixed (large = false: sides <= HIPKKT_PSD_STEP_MAX_DIM, the barrier's
+// first kernel keeps its matrix in 64 x 65 doubles of LDS) and hipkkt_step_enable_mixed_large (sides <= HIPKKT_PSD_STEP_LARGE_MAX_DIM;
+// cones of side >= lmin go to step_psd_large.hip and to the barrier's second kernel)
+static int32_t enable_mixed_impl(hipkkt_handle h, int32_t enable, bool large, double step, double amin) {
     HK_ENTER(h)
     if (!enable) { disable_psd_mode(S->cones, StepMode::Mixed); return HIPKKT_OK; }
-    if (!psd_class_fits(S, ConeClass::Mixed, HIPKKT_PSD_STEP_MAX_DIM)) {
-        S->err = "step_enable_mixed: needs an L1 handle whose last hipkkt_set_cone_types_ex names Zero / Nonnegative / SecondOrder / PSD "
+    const char *who = large ? "step_enable_mixed_large" : "step_enable_mixed";
+    if (!psd_class_fits(S, ConeClass::Mixed, large ? HIPKKT_PSD_STEP_LARGE_MAX_DIM : HIPKKT_PSD_STEP_MAX_DIM)) {
+        S->err = std::string(who) +
+                 ": needs an L1 handle whose last hipkkt_set_cone_types_ex names Zero / Nonnegative / SecondOrder / PSD "
                  "triangle / Exponential / Power / GenPower cones only, at least one PSD cone and at least one of the last three, every "
-                 "PSD side <= HIPKKT_PSD_STEP_MAX_DIM";
+                 "PSD side <= " + (large ? "HIPKKT_PSD_STEP_LARGE_MAX_DIM" : "HIPKKT_PSD_STEP_MAX_DIM");
         return HIPKKT_ERR_ARGUMENT;
     }
     // (the parameter checks come first: a refused call leaves the handle as it was)
-    const int32_t rc = enable_line_search(S, "step_enable_mixed", StepMode::Mixed, linesearch_backtrack_step, min_terminate_step_length);
+    const int32_t rc = enable_line_search(S, who, StepMode::Mixed, step, amin);
     if (rc != HIPKKT_OK) return rc;
-    enable_psd_tables(S, StepMode::Mixed, false);
+    enable_psd_tables(S, StepMode::Mixed, large);
     return HIPKKT_OK;
     HK_LEAVE
 }
-
-// a handle in PSD step mode whose registration holds a side above HIPKKT_PSD_STEP_MAX_DIM (hipkkt_step_enable_psd_large): the device
-// scaling of hipkkt_psd_scaling_enable (scaling_psd.hip) and the default start without its own enable (start.hip) keep their matrices
-// in LDS and would leave such a cone alone
-static bool psd_side_above_small(const ConeState &C) {
-    if (C.step.mode != StepMode::Psd) return false;
-    for (int64_t n : C.reg.psd_n) if (n > HIPKKT_PSD_STEP_MAX_DIM) return true;
-    return false;
+int32_t hipkkt_step_enable_mixed(hipkkt_handle h, int32_t enable, double linesearch_backtrack_step, double min_terminate_step_length) {
+    return enable_mixed_impl(h, enable, false, linesearch_backtrack_step, min_terminate_step_length);
+}
+int32_t hipkkt_step_enable_mixed_large(hipkkt_handle h, int32_t enable, double linesearch_backtrack_step, double min_terminate_step_length) {
+    return enable_mixed_impl(h, enable, true, linesearch_backtrack_step, min_terminate_step_length);
 }
 
 // the modes whose step reads resident PSD factors (R, Rinv, lambda)
 static bool psd_factors_mode(const ConeState &C) { return C.step.mode == StepMode::Psd || C.step.mode == StepMode::Mixed; }
+
+// a handle in PSD or Mixed step mode whose registration holds a side above HIPKKT_PSD_STEP_MAX_DIM (hipkkt_step_enable_psd_large,
+// hipkkt_step_enable_mixed_large): the device
+// scaling of hipkkt_psd_scaling_enable (scaling_psd.hip) and the default start without its own enable (start.hip) keep their matrices
+// in LDS and would leave such a cone alone
+static bool psd_side_above_small(const ConeState &C) {
+    if (!psd_factors_mode(C)) return false;
+    for (int64_t n : C.reg.psd_n) if (n > HIPKKT_PSD_STEP_MAX_DIM) return true;
+    return false;
+}
 
 static int32_t psd_set_factors_impl(hipkkt_handle h, const double *Rinv_all, const double *lambda_all, bool dev) {
     HK_ENTER(h)
@@ -497,20 +511,23 @@ int32_t hipkkt_psd_scaling_enable(hipkkt_handle h, int32_t enable) {
 }
 
 // what hipkkt_psd_scaling_enable_large and hipkkt_step_default_start_enable_psd_large require: PSD step mode through
-// hipkkt_step_enable_psd_large (so the list of the large cones and their workspace exist, and no side exceeds 128)
-static bool psd_large_handle(hipkkt_solver *S, const char *who) {
+// hipkkt_step_enable_psd_large (so the list of the large cones and their workspace exist, and no side exceeds 128); `mixed`: Mixed step
+// mode through hipkkt_step_enable_mixed_large serves as well (the scaling; the start of a non-symmetric set stays with the caller)
+static bool psd_large_handle(hipkkt_solver *S, const char *who, bool mixed) {
     const ConeState &C = S->cones;
     if (C.step.mode == StepMode::Psd && C.step.psd_large_enabled) return true;
-    S->err = std::string(who) + ": needs a handle in PSD step mode through hipkkt_step_enable_psd_large first";
+    if (mixed && C.step.mode == StepMode::Mixed && C.step.mixed_large_enabled) return true;
+    S->err = std::string(who) + ": needs a handle in PSD step mode through hipkkt_step_enable_psd_large" +
+             (mixed ? " or in Mixed step mode through hipkkt_step_enable_mixed_large" : "") + " first";
     return false;
 }
 
-// hipkkt_psd_scaling_enable for a handle of hipkkt_step_enable_psd_large: the cones of step_psd_large.hip through scaling_psd_large.hip,
+// hipkkt_psd_scaling_enable for a handle of hipkkt_step_enable_psd_large / _mixed_large: the cones of step_psd_large.hip through scaling_psd_large.hip,
 // the others through scaling_psd.hip
 int32_t hipkkt_psd_scaling_enable_large(hipkkt_handle h, int32_t enable) {
     HK_ENTER(h)
     ConeState &C = S->cones;
-    if (!psd_large_handle(S, "psd_scaling_enable_large")) return HIPKKT_ERR_ARGUMENT;
+    if (!psd_large_handle(S, "psd_scaling_enable_large", true)) return HIPKKT_ERR_ARGUMENT;
     C.step.psd_scaling_large = enable != 0;
     C.step.scaled = false;      // as hipkkt_psd_scaling_enable
     C.step.have_step = false;
@@ -522,7 +539,7 @@ int32_t hipkkt_psd_scaling_enable_large(hipkkt_handle h, int32_t enable) {
 // the default start (start.hip) of a handle of hipkkt_step_enable_psd_large with a side above HIPKKT_PSD_STEP_MAX_DIM
 int32_t hipkkt_step_default_start_enable_psd_large(hipkkt_handle h, int32_t enable) {
     HK_ENTER(h)
-    if (!psd_large_handle(S, "step_default_start_enable_psd_large")) return HIPKKT_ERR_ARGUMENT;
+    if (!psd_large_handle(S, "step_default_start_enable_psd_large", false)) return HIPKKT_ERR_ARGUMENT;
     S->cones.step.start_psd_large = enable != 0;
     return HIPKKT_OK;
     HK_LEAVE

@@ -208,10 +208,15 @@ void launch_psd_large_nt_scaling(hipStream_t st, const PsdView &P, const double 
 // (hipkkt_step_enable_mixed).  launch_psd_barrier leaves [(0 - logdet(Z + a dZ)) | logdet(S + a dS)] per (cone, candidate) in slots =
 // psd_barrier_slots(work, nsoc, n3, ngp), 16 doubles per PSD cone of the work buffer of launch_step3_barrier; launch_psd_barrier_add,
 // behind launch_step3_barrier on the same stream, adds the cones' (0 - logdet_z) - logdet_s in PSD-cone order to out[2 j].  A shifted
-// point outside the cone gives -Inf (the reference subtracts typemax).
+// point outside the cone gives -Inf (the reference subtracts typemax).  launch_psd_barrier_large (hipkkt_step_enable_mixed_large),
+// behind launch_psd_barrier on the same stream, overwrites the slots of the cones of P.large (sides up to psd_step_large_max_dim(),
+// one 128 x 129 matrix in LDS; the same arithmetic -- applied to a side <= 64 the same bits), for which the first left the failure
+// arm; with P.large.nlarge == 0 it launches nothing.
 double *psd_barrier_slots(double *work, int nsoc, int n3, int ngp);
 void launch_psd_barrier(hipStream_t st, const PsdView &P, const double *z, const double *s, const double *dz, const double *ds,
                         const double *alphas, int nalpha, double *slots);
+void launch_psd_barrier_large(hipStream_t st, const PsdView &P, const double *z, const double *s, const double *dz, const double *ds,
+                              const double *alphas, int nalpha, double *slots);
 void launch_psd_barrier_add(hipStream_t st, int npsd, const double *slots, int nalpha, double *out);
 // start.hip: the default start of a symmetric cone set (solver.jl:383-405) on the tables above (P: its npsd and tab).
 // launch_start_identity writes the identity scaling's Hs values and sparse second-order terms into kval (psd_hs0 = first Hs entry per

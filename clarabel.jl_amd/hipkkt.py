@@ -53,7 +53,7 @@ SYMBOLS = [
     # the PSD step for sides 65 .. 128 (opt-in, added within ABI version 5)
     "hipkkt_step_enable_psd_large",
     # PSD triangle cones next to Exponential / Power / Generalized Power cones (opt-in, added within ABI version 5)
-    "hipkkt_step_enable_mixed",
+    "hipkkt_step_enable_mixed", "hipkkt_step_enable_mixed_large",
     # the Cholesky / SVD and the default start for PSD sides 65 .. 128 (opt-in, added within ABI version 5)
     "hipkkt_psd_scaling_enable_large", "hipkkt_step_default_start_enable_psd_large",
 ]
@@ -171,6 +171,7 @@ def lib():
     L.hipkkt_step_enable_psd.argtypes = [vp, i32]
     L.hipkkt_step_enable_psd_large.argtypes = [vp, i32]
     L.hipkkt_step_enable_mixed.argtypes = [vp, i32, f64, f64]
+    L.hipkkt_step_enable_mixed_large.argtypes = [vp, i32, f64, f64]
     L.hipkkt_psd_set_factors.argtypes = [vp, _f64p, _f64p]
     L.hipkkt_psd_set_factors_dev.argtypes = [vp, vp, vp]
     L.hipkkt_psd_scaling_enable.argtypes = [vp, i32]
@@ -772,6 +773,14 @@ class Handle:
         self._chk_step(self.L.hipkkt_step_enable_mixed(self.h, int(bool(enable)), float(linesearch_backtrack_step),
                                                        float(min_terminate_step_length)), "step_enable_mixed")
 
+    def step_enable_mixed_large(self, enable, linesearch_backtrack_step, min_terminate_step_length):
+        """step_enable_mixed with the side limit PSD_STEP_LARGE_MAX_DIM: PSD members of side 65 .. 128 step as after
+        step_enable_psd_large and their log-det barrier keeps one 128 x 129 matrix in LDS (same arithmetic).  psd_scaling_enable_large
+        is the scaling opt-in of such a handle; its default start stays with the caller.  ValueError when the registration does not
+        qualify; the handle stays as it was"""
+        self._chk_step(self.L.hipkkt_step_enable_mixed_large(self.h, int(bool(enable)), float(linesearch_backtrack_step),
+                                                             float(min_terminate_step_length)), "step_enable_mixed_large")
+
     def psd_set_factors(self, rinv, lam, dev=False):
         """stages the PSD cones' Rinv (n x n column-major each, concatenated like psd_R) and lambda (n each) for the next update_scaling;
         dev=True: rinv, lam are device pointers (not synchronised: they stay valid until the next synchronising call)"""
@@ -792,7 +801,7 @@ class Handle:
         self._chk_step(self.L.hipkkt_psd_scaling_enable(self.h, int(bool(enable))), "psd_scaling_enable")
 
     def psd_scaling_enable_large(self, enable):
-        """psd_scaling_enable for a handle after step_enable_psd_large(True) (ValueError otherwise): the cones of side 65 .. 128 get their
+        """psd_scaling_enable for a handle after step_enable_psd_large(True) or step_enable_mixed_large(True, ..) (ValueError otherwise): the cones of side 65 .. 128 get their
         (R, Rinv, lambda) from kernels with one matrix in LDS and the others in device memory (same arithmetic), the smaller ones from
         the kernel of psd_scaling_enable"""
         self._chk_step(self.L.hipkkt_psd_scaling_enable_large(self.h, int(bool(enable))), "psd_scaling_enable_large")

@@ -18,7 +18,7 @@ from .settings import Settings
 _DEBUG = os.environ.get("HIPKKT_DEBUG", "0") == "1"
 
 
-def cone_set_steps_on_device(cones, nonsymmetric=False, genpower=False, psd=False, psd_large=False, mixed=False) -> bool:
+def cone_set_steps_on_device(cones, nonsymmetric=False, genpower=False, psd=False, psd_large=False, mixed=False, mixed_large=False) -> bool:
     """the step entry points (hipkkt_cone_* / hipkkt_step_*) serve cone sets of ZeroCone, NonnegativeCone and SecondOrderCone only: a PSD
     cone's step length needs eigenvalue decompositions, the non-symmetric cones need backtracking and barriers.
     nonsymmetric=True: ExponentialCone and PowerCone members qualify as well (hipkkt_step_enable_cone3); Generalized Power and PSD
@@ -30,7 +30,9 @@ def cone_set_steps_on_device(cones, nonsymmetric=False, genpower=False, psd=Fals
     nothing.
     mixed=True (with nonsymmetric=True and psd=True): PSD triangle members of side at most hipkkt.PSD_STEP_MAX_DIM qualify next to
     Exponential / Power members, and next to Generalized Power members with genpower=True (hipkkt_step_enable_mixed); psd_large does not
-    widen that limit; alone it widens nothing"""
+    widen that limit; alone it widens nothing.
+    mixed_large=True (with mixed=True, nonsymmetric=True and psd=True): the side limit of such a set is hipkkt.PSD_STEP_LARGE_MAX_DIM
+    (hipkkt_step_enable_mixed_large); alone it widens nothing"""
     if not hasattr(cones, "kkt_cone_kinds"):
         return False
     kinds = cones.kkt_cone_kinds_ex()[0] if hasattr(cones, "kkt_cone_kinds_ex") else cones.kkt_cone_kinds()
@@ -44,7 +46,8 @@ def cone_set_steps_on_device(cones, nonsymmetric=False, genpower=False, psd=Fals
     if psd and bool(np.any(kinds == 3)) and (not has_nonsym or (mixed and nonsymmetric)):
         numel = np.asarray(cones.kkt_descriptors()[0])[kinds == 3]
         sides = ((np.sqrt(8.0 * numel + 1.0) - 1.0) / 2.0 + 0.5).astype(np.int64)
-        limit = hipkkt.PSD_STEP_LARGE_MAX_DIM if psd_large and not has_nonsym else hipkkt.PSD_STEP_MAX_DIM
+        large = mixed_large if has_nonsym else psd_large
+        limit = hipkkt.PSD_STEP_LARGE_MAX_DIM if large else hipkkt.PSD_STEP_MAX_DIM
         if bool(np.all(sides <= limit)):
             ok = ok | (kinds == 3)
     return kinds.size > 0 and bool(np.all(ok))
@@ -122,14 +125,21 @@ class HipKKTSolver:
         # ... and, opted in by Settings.device_step_mixed on top of device_step_nonsymmetric and device_step_psd, sets that hold PSD
         # triangle members (sides <= 64) next to Exponential / Power members, and next to Generalized Power members with
         # device_step_genpower (hipkkt_step_enable_mixed).  The PSD factors follow the protocol of steps_psd / scales_psd
+        # With Settings.device_step_mixed_large (and device_step_psd_large) on top, sides of 65 .. 128 qualify in such a set too
+        # (hipkkt_step_enable_mixed_large); its Cholesky / SVD follow device_scaling_psd_large as for steps_psd_large, its start stays
+        # the caller's unit initialisation
         self.steps_mixed = False
-        if not self._steps_on_device and getattr(settings, "device_step_mixed", False) \
-                and getattr(settings, "device_step_nonsymmetric", False) and getattr(settings, "device_step_psd", False) \
-                and self.scales_nonsymmetric and self._psd_cones \
-                and cone_set_steps_on_device(cones, nonsymmetric=True, genpower=bool(getattr(settings, "device_step_genpower", False)),
-                                             psd=True, mixed=True):
+        mixed_ok = not self._steps_on_device and getattr(settings, "device_step_mixed", False) \
+            and getattr(settings, "device_step_nonsymmetric", False) and getattr(settings, "device_step_psd", False) \
+            and self.scales_nonsymmetric and self._psd_cones
+        mixed_kw = dict(nonsymmetric=True, genpower=bool(getattr(settings, "device_step_genpower", False)), psd=True, mixed=True)
+        if mixed_ok and cone_set_steps_on_device(cones, **mixed_kw):
             self.h.step_enable_mixed(True, settings.linesearch_backtrack_step, settings.min_terminate_step_length)
             self._steps_on_device = self.steps_nonsymmetric = self.steps_psd = self.steps_mixed = True
+        elif mixed_ok and getattr(settings, "device_step_mixed_large", False) and getattr(settings, "device_step_psd_large", False) \
+                and cone_set_steps_on_device(cones, mixed_large=True, **mixed_kw):
+            self.h.step_enable_mixed_large(True, settings.linesearch_backtrack_step, settings.min_terminate_step_length)
+            self._steps_on_device = self.steps_nonsymmetric = self.steps_psd = self.steps_psd_large = self.steps_mixed = True
         if self.steps_psd:
             rows = [r for c, r in zip(cones.cones, cones.rng_cones) if hasattr(c, "RRt")]
             self._psd_rows = rows
@@ -150,7 +160,7 @@ class HipKKTSolver:
         # ... and whose default start the device serves when Settings.device_default_start_psd_large is set on top of
         # device_default_start (hipkkt_step_default_start_enable_psd_large)
         self.starts_psd_large = False
-        if self.steps_psd_large and getattr(settings, "device_default_start", False) \
+        if self.steps_psd_large and not self.steps_mixed and getattr(settings, "device_default_start", False) \
                 and getattr(settings, "device_default_start_psd_large", False):
             self.h.step_default_start_enable_psd_large(True)
             self.starts_psd_large = True

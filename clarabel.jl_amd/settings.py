@@ -100,4 +100,9 @@ class Settings:
     # unit initialisation stays on the host.  A PSD side above 64 in such a set keeps the host loop.  Needs device_step_nonsymmetric
     # and device_step_psd: the caller raises ValueError otherwise.
     device_step_mixed: bool = False
+    # device_step_mixed for a set with a PSD side of 65 .. 128 as well (hipkkt_step_enable_mixed_large: the larger cones' rows and step
+    # length through the kernels of device_step_psd_large, their log-det barrier with one 128 x 129 matrix in LDS).  The PSD factors
+    # follow device_scaling_psd + device_scaling_psd_large; the unit initialisation stays on the host; sides above 128 keep the host
+    # loop.  Needs device_step_mixed and device_step_psd_large: the caller raises ValueError otherwise.
+    device_step_mixed_large: bool = False
     extra: dict = field(default_factory=dict)

@@ -79,7 +79,8 @@ int32_t hipkkt_is_available(void);
  *    hipkkt_cone_set_identity_scaling / hipkkt_cone_margins / hipkkt_cone_shift_to_interior / hipkkt_step_default_start_dev;
  *    HIPKKT_PSD_STEP_LARGE_MAX_DIM / hipkkt_step_enable_psd_large;
  *    hipkkt_step_enable_mixed;
- *    hipkkt_psd_scaling_enable_large / hipkkt_step_default_start_enable_psd_large. */
+ *    hipkkt_psd_scaling_enable_large / hipkkt_step_default_start_enable_psd_large;
+ *    hipkkt_step_enable_mixed_large. */
 #define HIPKKT_ABI_VERSION 5
 int32_t hipkkt_abi_version(void);
 /* releases the process-wide cache of device memory blocks the library keeps between handles (not in the reference: an embedding
@@ -413,9 +414,22 @@ int32_t hipkkt_residuals_dev(hipkkt_handle h, const double *xzs_dev, double tau,
  *     (0 - logdet_z) - logdet_s, the terms added in PSD-cone order behind the other cones' sum.  As in the reference a shifted point
  *     outside a PSD cone therefore gives -Inf, not +Inf (`barrier -= typemax(T)`); in a solve the step length has bounded alpha inside.
  *     One workgroup per (cone, candidate, z | s), the matrix in LDS: hence the side limit.
- * A PSD side of 65 .. HIPKKT_PSD_STEP_LARGE_MAX_DIM next to a kind 4..6 cone keeps the host loop, and so does the default start of such
- * a set (the hipkkt_cone_set_identity_scaling group returns HIPKKT_ERR_ARGUMENT): a non-symmetric set starts from the caller's unit
- * initialisation.  Every other hipkkt_step_enable_* keeps refusing such a registration.
+ * A PSD side of 65 .. HIPKKT_PSD_STEP_LARGE_MAX_DIM next to a kind 4..6 cone keeps the host loop unless the opt-in of the next paragraph
+ * is used, and so does the default start of such a set (the hipkkt_cone_set_identity_scaling group returns HIPKKT_ERR_ARGUMENT): a
+ * non-symmetric set starts from the caller's unit initialisation.  Every other hipkkt_step_enable_* keeps refusing such a registration.
+ *
+ * Opt-in for PSDTriangleCone of side 65 .. HIPKKT_PSD_STEP_LARGE_MAX_DIM next to kinds 4..6: hipkkt_step_enable_mixed_large accepts what
+ * hipkkt_step_enable_mixed accepts with every PSD side <= HIPKKT_PSD_STEP_LARGE_MAX_DIM, and the same calls then serve all rows of the
+ * handle.  A cone of side <= HIPKKT_PSD_STEP_MAX_DIM and every other family are computed as after hipkkt_step_enable_mixed, bit for
+ * bit; a larger cone's rows and its step length by the kernels of hipkkt_step_enable_psd_large, bit for bit as on a handle without the
+ * kind 4..6 cones (mul_Hs!, coneops_psdtrianglecone.jl:201-213; step_length, :217-253).  Its barrier (compute_barrier / _logdet_barrier,
+ * coneops_psdtrianglecone.jl:256-290) is the computation of the paragraph above expression by expression -- the same load, the same
+ * right-looking Cholesky with every entry's subtractions in ascending column order, the same log sum -- by a second kernel behind
+ * the first on the same stream: one workgroup of 512 threads per (cone, candidate, z | s) with one 128 x 129 matrix in LDS (132 096
+ * bytes, one workgroup per CU); the same input gives the same bits whichever kernel computes a cone.  hipkkt_psd_scaling_enable
+ * returns HIPKKT_ERR_ARGUMENT on such a handle while the registration holds a side above HIPKKT_PSD_STEP_MAX_DIM
+ * (hipkkt_psd_scaling_enable_large is the call); hipkkt_step_default_start_enable_psd_large and the default-start group keep refusing
+ * it.  Sides above HIPKKT_PSD_STEP_LARGE_MAX_DIM keep the host loop.
  *
  * One operation each, host vectors of length m in cone order (the unit-tested surface):
  *   hipkkt_cone_affine_ds            ds = lambda o lambda                  coneops_nncone.jl affine_ds!, coneops_socone.jl:219-228
@@ -457,6 +471,14 @@ int32_t hipkkt_step_enable_psd_large(hipkkt_handle h, int32_t enable);
  * invalidation of the resident scaling are those of hipkkt_step_enable_cone3, the tables and factor buffers those of
  * hipkkt_step_enable_psd.  enable == 0 switches it off.  Every hipkkt_set_cone_types[_ex] clears it. */
 int32_t hipkkt_step_enable_mixed(hipkkt_handle h, int32_t enable, double linesearch_backtrack_step, double min_terminate_step_length);
+/* hipkkt_step_enable_mixed with the side limit HIPKKT_PSD_STEP_LARGE_MAX_DIM (compute_barrier of coneops_psdtrianglecone.jl:256-290 for
+ * the larger cones next to coneops_compositecone.jl:216-252): enable != 0 returns HIPKKT_ERR_ARGUMENT and leaves the handle as it was
+ * unless the last hipkkt_set_cone_types_ex names kinds {0, .., 6} only with at least one 3, at least one of 4 / 5 / 6 and every PSD
+ * side <= HIPKKT_PSD_STEP_LARGE_MAX_DIM, and the line-search parameters pass the checks of hipkkt_step_enable_cone3.  Enabling
+ * invalidates the resident scaling and allocates the larger cones' workspace, as hipkkt_step_enable_psd_large does.  enable == 0 does
+ * what hipkkt_step_enable_mixed(h, 0, ..) does.  Every hipkkt_set_cone_types[_ex] clears it. */
+int32_t hipkkt_step_enable_mixed_large(hipkkt_handle h, int32_t enable, double linesearch_backtrack_step,
+                                       double min_terminate_step_length);
 /* The factors of the PSD cones' scaling for the step (HIPKKT_ERR_ARGUMENT before hipkkt_step_enable_psd / _mixed): Rinv_all = the cones' Rinv, each
  * n x n column-major, concatenated like psd_R; lambda_all = the cones' lambda, n each, concatenated.  They are staged and consumed by
  * the next hipkkt_update_scaling[_ex][_dev]; on an enabled handle that call needs a non-NULL psd_R and factors staged since the last
@@ -485,9 +507,10 @@ int32_t hipkkt_psd_set_factors_dev(hipkkt_handle h, const double *Rinv_all, cons
  * factors the call does what it does without this enable.  Enabling or disabling invalidates the resident scaling; enable == 0
  * switches it off, and so do hipkkt_step_enable_psd and every hipkkt_set_cone_types[_ex]. */
 int32_t hipkkt_psd_scaling_enable(hipkkt_handle h, int32_t enable);
-/* hipkkt_psd_scaling_enable for a handle of hipkkt_step_enable_psd_large.  HIPKKT_ERR_ARGUMENT, and the handle as it was, unless the
- * handle is in PSD step mode through hipkkt_step_enable_psd_large (not after hipkkt_step_enable_psd or _mixed; a side above
- * HIPKKT_PSD_STEP_LARGE_MAX_DIM never gets that far).  Afterwards a hipkkt_update_scaling[_dev] with psd_R == NULL and no factors
+/* hipkkt_psd_scaling_enable for a handle of hipkkt_step_enable_psd_large or hipkkt_step_enable_mixed_large.  HIPKKT_ERR_ARGUMENT, and the
+ * handle as it was, unless the handle is in PSD step mode through hipkkt_step_enable_psd_large or in mixed step mode through
+ * hipkkt_step_enable_mixed_large (not after hipkkt_step_enable_psd or _mixed; a side above
+ * HIPKKT_PSD_STEP_LARGE_MAX_DIM never gets that far).  Afterwards a hipkkt_update_scaling[_ex][_dev] with psd_R == NULL and no factors
  * staged computes (R, Rinv, lambda) of every PSD cone of the set on the call's stream, with the call's single host synchronisation:
  * the cones hipkkt_step_enable_psd_large routes to its own kernels (side > HIPKKT_PSD_STEP_MAX_DIM) by the algorithm of
  * hipkkt_psd_scaling_enable operation for operation in another placement -- one workgroup of 512 threads per cone, one n x n matrix
@@ -497,7 +520,7 @@ int32_t hipkkt_psd_scaling_enable(hipkkt_handle h, int32_t enable);
  * Failures are those of hipkkt_psd_scaling_enable (*scaling_ok = 0 with HIPKKT_OK, NaN factors for that cone, none of its entries of
  * K written, the other cones served); hipkkt_psd_get_factors reads the result back.  With a non-NULL psd_R and staged factors the
  * call does what it does without this enable.  Enabling or disabling invalidates the resident scaling; enable == 0 switches it off,
- * and so do hipkkt_step_enable_psd[_large] and every hipkkt_set_cone_types[_ex]. */
+ * and so do hipkkt_step_enable_psd[_large], hipkkt_step_enable_mixed[_large] and every hipkkt_set_cone_types[_ex]. */
 int32_t hipkkt_psd_scaling_enable_large(hipkkt_handle h, int32_t enable);
 /* The resident factors of the last scaling of a handle in PSD or mixed step mode, whoever computed them (K.data.R, .Rinv, .lambda of
  * coneops_psdtrianglecone.jl:112-131): R and Rinv n x n column-major per cone, concatenated like psd_R, lambda n per cone.  Host
@@ -578,7 +601,8 @@ int32_t hipkkt_step_default_start_dev(hipkkt_handle h, double *xzs_dev, int32_t 
                                       int32_t ir_enable, double reltol, double abstol, int64_t max_iter, double stop_ratio,
                                       double *scal_out8, int64_t *ir_steps2);
 /* The default start for a handle of hipkkt_step_enable_psd_large with a side above HIPKKT_PSD_STEP_MAX_DIM.  HIPKKT_ERR_ARGUMENT, and
- * the handle as it was, unless the handle is in PSD step mode through hipkkt_step_enable_psd_large.  Afterwards the four calls above
+ * the handle as it was, unless the handle is in PSD step mode through hipkkt_step_enable_psd_large (a handle of
+ * hipkkt_step_enable_mixed_large is refused: a non-symmetric set starts from the caller's unit initialisation).  Afterwards the four calls above
  * serve the handle: the identity scaling does not depend on the side, the margins of a cone of side > HIPKKT_PSD_STEP_MAX_DIM come
  * from a second launch with one 128 x 129 matrix in LDS (the same sweeps: the same bits as the smaller cones' kernel on the same
  * matrix), the shift takes the larger side bound.  Without it they keep refusing such a handle.  enable == 0 switches it off, and so
@@ -634,7 +658,7 @@ int32_t hipkkt_get_counters(hipkkt_handle h, int64_t *out, int64_t cap);
  * and the panels per super-block of its solve sweeps, 0 = one hop per panel through that panel's inverse (k_front_fwd / k_front_bwd),
  * > 0 = products with the super-blocks' inverses (k_front_fwd_sb / k_front_bwd_sb), 23 the Newton steps of the last hipkkt_update_scaling_ex per
  * Power cone in cone order, 24 the PSD cones step_psd_large.hip serves on this handle, as indices into the registration's PSD cones,
- * read back from the device list -- empty unless hipkkt_step_enable_psd_large is in place, 25 the work matrices of those cones as the
+ * read back from the device list -- empty unless hipkkt_step_enable_psd_large / _mixed_large is in place, 25 the work matrices of those cones as the
  * last step operation left them, four of 128 x 128 doubles per served cone, each n x n column-major from its start); *len receives the length, nothing is copied
  * when cap is too small */
 int32_t hipkkt_debug_dump(hipkkt_handle h, int32_t what, double *out, int64_t cap, int64_t *len);

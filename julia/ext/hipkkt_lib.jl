@@ -150,6 +150,13 @@ function hip_step_enable_mixed!(handle::Ptr{Cvoid}, enable::Bool, backtrack_step
                backtrack_step, min_terminate_step_length)
     return hip_step_check(handle, rc, "hipkkt_step_enable_mixed")
 end
+# the same with PSD sides up to 128 (the larger cones through the kernels of hip_step_enable_psd_large!, their barrier with one matrix
+# in LDS); hip_psd_scaling_enable_large! is the scaling opt-in of such a handle, its start stays the unit initialisation
+function hip_step_enable_mixed_large!(handle::Ptr{Cvoid}, enable::Bool, backtrack_step::Float64, min_terminate_step_length::Float64)
+    rc = ccall((:hipkkt_step_enable_mixed_large, libhipkkt), Int32, (Ptr{Cvoid}, Int32, Float64, Float64), handle, enable ? 1 : 0,
+               backtrack_step, min_terminate_step_length)
+    return hip_step_check(handle, rc, "hipkkt_step_enable_mixed_large")
+end
 # Rinv_all: the cones' Rinv (n x n column-major each, concatenated like psd_R), λ_all: their λ; consumed by the next hip update_scaling
 function hip_psd_set_factors!(handle::Ptr{Cvoid}, Rinv_all::Vector{Float64}, λ_all::Vector{Float64})
     rc = ccall((:hipkkt_psd_set_factors, libhipkkt), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), handle, Rinv_all, λ_all)

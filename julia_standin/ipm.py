@@ -414,6 +414,10 @@ class Solver:
             raise ValueError("Settings.device_step_mixed needs device_step_nonsymmetric")
         if getattr(st, "device_step_mixed", False) and not getattr(st, "device_step_psd", False):
             raise ValueError("Settings.device_step_mixed needs device_step_psd")
+        if getattr(st, "device_step_mixed_large", False) and not getattr(st, "device_step_mixed", False):
+            raise ValueError("Settings.device_step_mixed_large needs device_step_mixed")
+        if getattr(st, "device_step_mixed_large", False) and not getattr(st, "device_step_psd_large", False):
+            raise ValueError("Settings.device_step_mixed_large needs device_step_psd_large")
         if getattr(st, "device_default_start", False) and not getattr(st, "device_step", False):
             raise ValueError("Settings.device_default_start needs device_step")
         self._device_step = bool(getattr(st, "device_step", False)) and hasattr(ks, "kktsolver_step_affine") and \

@@ -6,7 +6,7 @@ wall time per iteration and of the stand-in's timers, the bytes the Python bindi
 (clarabel.jl_amd/hipkkt.py TRAFFIC) and hipkkt_box_probe go into ONE JSON line on stdout.
 Symmetric configurations (3, 2a, psd) get one more path: the last one with device_default_start added (the default start on the
 device as well), so that default_start_ms and the bytes of a whole solve stand next to the same path without it in the same run.
-usage: step_path_compare.py [--cfgs 3,2a,exp_pow,genpow,psd,psd_large,mixed] [--repeats 5] [--one-solve CFG [--third] [--start] [--dual]]   (--one-solve: a single device_step solve, for a kernel trace; --dual: min_switch_step_length = 1, so that a
+usage: step_path_compare.py [--cfgs 3,2a,exp_pow,genpow,psd,psd_large,mixed,mixed_large] [--repeats 5] [--one-solve CFG [--third] [--start] [--dual]]   (--one-solve: a single device_step solve, for a kernel trace; --dual: min_switch_step_length = 1, so that a
 non-symmetric set runs the Dual strategy and its barrier search in every iteration)"""
 import argparse
 import json
@@ -36,15 +36,25 @@ CONFIGS = {"3": ("portfolio_socp", problems.portfolio_socp), "2a": ("random_spar
            # a third path with device_scaling_psd
            "mixed": ("mixed_psd_nonsym_4x20",
                      lambda: problems.mixed_psd_nonsym(n=80, psd_sides=[20] * 4, nexp=20, npow=10, ngenpow=0, nn=20, nzero=3, socdim=5,
-                                                       seed=5))}
+                                                       seed=5)),
+           # two PSD triangle cones of side 96 next to Exponential / Power cones: without device_step_mixed_large the set keeps the host
+           # loop; a third path with device_scaling_psd + device_scaling_psd_large.  (m = 9 430.  On the CPU oracle path: SOLVED in 12 iterations,
+           # objective 158.298465489, no barrier search; the host cone algebra on the HIP plugin and both device paths end the same
+           # way: profiles/step_path_compare_mixed_large.json)
+           "mixed_large": ("mixed_psd_nonsym_2x96",
+                           lambda: problems.mixed_psd_nonsym(n=80, psd_sides=[96] * 2, nexp=20, npow=10, ngenpow=0, nn=20, nzero=3,
+                                                             socdim=5, seed=5))}
 PARENT = dict(device_scaling=True, device_reduced=True, device_residuals=True)
 STEP_EXTRA = {"exp_pow": dict(device_step_nonsymmetric=True),
               "genpow": dict(device_step_nonsymmetric=True, device_step_genpower=True),
               "psd": dict(device_step_psd=True),
               "psd_large": dict(device_step_psd=True, device_step_psd_large=True),
-              "mixed": dict(device_step_nonsymmetric=True, device_step_psd=True, device_step_mixed=True)}      # what device_step needs on top, per configuration
+              "mixed": dict(device_step_nonsymmetric=True, device_step_psd=True, device_step_mixed=True),
+              "mixed_large": dict(device_step_nonsymmetric=True, device_step_psd=True, device_step_psd_large=True, device_step_mixed=True,
+                                  device_step_mixed_large=True)}      # what device_step needs on top, per configuration
 THIRD = {"psd": ("device_step_and_scaling", dict(device_scaling_psd=True)),
-         "mixed": ("device_step_and_scaling", dict(device_scaling_psd=True))}      # a further path on top of device_step, where there is one
+         "mixed": ("device_step_and_scaling", dict(device_scaling_psd=True)),
+         "mixed_large": ("device_step_and_scaling", dict(device_scaling_psd=True, device_scaling_psd_large=True))}      # a further path on top of device_step, where there is one
 START = ("3", "2a", "psd")      # symmetric cone sets: the last path once more with device_default_start
 # further paths of a configuration, each on top of the one before it: the Cholesky / SVD and the default start of PSD sides 65 .. 128
 MORE = {"psd_large": [("device_step_and_scaling_large", dict(device_scaling_psd=True, device_scaling_psd_large=True)),
@@ -85,7 +95,7 @@ def main():
     ap.add_argument("--cfgs", default="3,2a")
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--one-solve", default=None)
-    ap.add_argument("--third", action="store_true", help="--one-solve with the configuration's third path (psd, mixed: device_scaling_psd; psd_large: device_scaling_psd_large)")
+    ap.add_argument("--third", action="store_true", help="--one-solve with the configuration's third path (psd, mixed: device_scaling_psd; psd_large, mixed_large: device_scaling_psd_large)")
     ap.add_argument("--dual", action="store_true", help="--one-solve with min_switch_step_length = 1 (the Dual strategy throughout)")
     ap.add_argument("--start", action="store_true", help="--one-solve with device_default_start (symmetric configurations; psd_large: device_default_start_psd_large)")
     args = ap.parse_args()
